@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — agent-steps/s of the stepping engine at N = 16,384 TwoDBicycle (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" is one population tick (SocialForceIntersection.step, intersection.py:866-896) of the
 synthetic population of SURVEY.md §8(d): N agents uniform in a 200 m x 200 m square, random headings,
@@ -9,7 +9,15 @@ speeds in [3, 6] m/s, three destinations straight ahead.  For N > 1 the driver l
 torch.distributed.run (one rank per GPU); the population is index-sharded, N stays 16,384 ("strong").
 Rank 0 prints ONE JSON line.  The CPU oracle is used only for the `cpu_baseline` leg (N = 1, rank 0).
 
-What the line reports beside `value`:
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`, the workload (`config`),
+`preroll_ticks`, `healthy` (finite states, no status flags after the timed steps) and `build_id`.
+--dump-outputs DIR  after the timed steps, what a caller of the timed engine receives after its last step, as float64 .npy
+                    files: state.npy [N, n_states], forces.npy [N, 2] (total force of the last tick: Fx, Fy), dest_ptr.npy [N];
+                    rows.npy holds the indices of a fixed, seeded sample of the road users when all of them would exceed 64 MB.
+--full              also everything else below: kernel medians, roofline, window extents, the dispersed window, the
+                    far-field cull switched off (`every_pair`) and the CPU baseline (runs and read-backs of their own).
+
+What the line reports beside `value` (all but preroll_ticks only with --full):
   roofline      the dominant kernel (the all-pairs kernel) against the fp32 vector peak: 100 op-equivalents per pair
                  x the pairs the launch actually EVALUATES (counted on the device, csf_count_pairs:
                 pairs masked by the field of view are evaluated neither here nor by the reference) / the kernel's MEDIAN
@@ -138,6 +146,34 @@ def cpu_baseline(n, box, ticks):
     }
 
 
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, eng, lo, hi, dist, rank, world):
+    """--dump-outputs: what a caller of the timed engine receives after its last step (csf_get_tick: state, total forces,
+    destination pointers) as float64 DIR/<name>.npy; every rank's own rows [lo, hi) are gathered to rank 0.  Where all rows
+    would exceed DUMP_MAX_BYTES, a fixed sample of them (seed 0; their indices in rows.npy) is written instead."""
+    s, ptr, _, fx, fy, _ = eng.tick_snapshot(forces=True)
+    mine = (s[lo:hi], np.c_[fx, fy][lo:hi], ptr[lo:hi].astype(np.float64))
+    parts = [mine]
+    if dist is not None:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    if rank != 0:
+        return
+    arrays = {name: np.concatenate([p[k] for p in parts]) for k, name in enumerate(("state", "forces", "dest_ptr"))}
+    n = arrays["state"].shape[0]
+    row_bytes = sum(a.itemsize * (a.size // max(n, 1)) for a in arrays.values())
+    if n * row_bytes > DUMP_MAX_BYTES - 4096:                         # (4096: the .npy headers)
+        k = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -150,10 +186,16 @@ def main():
                     help="static-obstacle infrastructure (BASELINE config 5): the curve scenario tiled on a 100 m grid")
     ap.add_argument("--preroll", type=int, default=-1,
                     help="untimed ticks before the warm-up (reported as preroll_ticks); default: about 0.1 s of them")
-    ap.add_argument("--cpu-ticks", type=int, default=6, help="ticks of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-ticks", type=int, default=6, help="with --full: ticks of the CPU baseline sample (0 = skip)")
     ap.add_argument("--every-pair-steps", type=int, default=200,
-                    help="ticks of the secondary run with the far-field cull switched off (0 = skip)")
+                    help="with --full: ticks of the secondary run with the far-field cull switched off (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: kernel medians, roofline, window extents, dispersed, every_pair, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed engine's state, forces and destination pointers after its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
 
@@ -241,30 +283,32 @@ def main():
     # events costs the tick ~5 us (profiles/r4_v5_tick_sequence.json: 120.1 us per tick with every launch sampled, 114.6 with
     # none), so not every launch is sampled: every 16th tick in long runs (62 launches of the default 1 000 steps), every 4th tick
     # of the driver's 20-step command (five launches: their spread is 2 %).  (The event pool is created here, not in front of
-    # the timed region.)
+    # the timed region.)  Only --full samples them: a plain run times its ticks without the events.
     every = max(1, min(16, args.steps // 5))
     if os.environ.get("CSF_BENCH_SAMPLE_EVERY"):              # (measurement aid: what do the time stamps themselves cost?)
         every = int(os.environ["CSF_BENCH_SAMPLE_EVERY"])
-    eng.profile(every)
+    if args.full:
+        eng.profile(every)
     eng.step(first)
     fence()
     scratch.step(first, sync=True)
     # (the start of the window is read off the scratch engine, which is in the very state the timed engine is in: a read-back
     # right before the timed region lets the device fall idle for a millisecond, and the pair kernel then runs ~10 % slower
     # for the next 100 - 200 ticks)
-    win0 = window_state(scratch) if world == 1 else None
+    win0 = window_state(scratch) if world == 1 and args.full else None
     preroll = args.preroll
     if preroll < 0:
         t0 = time.perf_counter()
         scratch.step(4, sync=True)
         tick_s = (time.perf_counter() - t0) / 4
         preroll = int(min(1000, max(0, 0.1 / max(tick_s, 1e-6))))
-    eng.profile_kernels()                                     # (forget the time stamps of the first ticks)
+    if args.full:
+        eng.profile_kernels()                                 # (forget the time stamps of the first ticks)
     scratch.step(preroll + max(0, args.warmup - first), sync=True)
-    # the scratch engine has dispersed by now (tick ~900: what rounds 1 - 3 reported as the headline): K steps of it, timed
-    # the same way, go into the line as `dispersed` - and keep the device busy right up to the timed region
+    # the scratch engine has dispersed by now (tick ~900: what rounds 1 - 3 reported as the headline): with --full, K steps of it,
+    # timed the same way, go into the line as `dispersed` - and keep the device busy right up to the timed region
     dispersed = None
-    if world == 1 and not rehearse:
+    if world == 1 and not rehearse and args.full:
         d0 = int(scratch.tick)
         t0 = time.perf_counter()
         scratch.step(args.steps, sync=True)
@@ -279,10 +323,11 @@ def main():
     eng.step(args.steps)
     fence()
     dt = time.perf_counter() - t0
-    samples = eng.profile_samples()
-    stats = eng.profile_stats()                                # (median / min / max per kernel: before the reset below)
-    prof = eng.profile_kernels()
-    eng.profile(0)
+    if args.full:
+        samples = eng.profile_samples()
+        stats = eng.profile_stats()                            # (median / min / max per kernel: before the reset below)
+        prof = eng.profile_kernels()
+        eng.profile(0)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -292,28 +337,53 @@ def main():
     lo, hi = eng.shard_range()
     st = eng.state()[lo:hi]
     healthy = bool(np.isfinite(st).all() and (eng.status()[lo:hi] == 0).all())
-    work, kernel = eng.count_pairs(detail=True)     # one extra launch on the final snapshot, outside the timed region
-    evaluated = None if work is None else work["evaluated"]
-    win1 = window_state(eng) if world == 1 else None
-    # the per-agent launch beside the pair launch (include/csf.h: csf_chase_ticks): what the scratch engine measured on its warm-up
-    # ticks (16 ticks each way), and how many ticks of the timed engine took that order
-    cal = scratch.chase_calibration()
-    side_by_side = {"decided": {1: "side by side", -1: "in turn", 0: "not measured"}[cal[0]], "measured_us_per_tick": {"in_turn": cal[1][0], "side_by_side": cal[1][1]},
-                    "timed_engine": {"decided": eng.chase_calibration()[0], "ticks_side_by_side": int(eng.chase_ticks()), "ticks": int(eng.tick)}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, lo, hi, dist, rank, world)
+    if args.full:
+        work, kernel = eng.count_pairs(detail=True)     # one extra launch on the final snapshot, outside the timed region
+        evaluated = None if work is None else work["evaluated"]
+        win1 = window_state(eng) if world == 1 else None
+        # the per-agent launch beside the pair launch (include/csf.h: csf_chase_ticks): what the scratch engine measured on its
+        # warm-up ticks (16 ticks each way), and how many ticks of the timed engine took that order
+        cal = scratch.chase_calibration()
+        side_by_side = {"decided": {1: "side by side", -1: "in turn", 0: "not measured"}[cal[0]], "measured_us_per_tick": {"in_turn": cal[1][0], "side_by_side": cal[1][1]},
+                        "timed_engine": {"decided": eng.chase_calibration()[0], "ticks_side_by_side": int(eng.chase_ticks()), "ticks": int(eng.tick)}}
     scratch.close()
-    # every rank's own figures (kernel times incl. the all-gather, the stream order its communicator chose, the pairs one launch
-    # of its receiver block evaluates): a scaling curve then explains itself
-    order, cal = eng.comm_stream_order()
-    med = lambda k: (stats[k]["median"] if stats.get(k) else 0.0)   # noqa: E731  (microseconds; 0: not launched / not sampled)
-    mine = {"rank": rank, "receivers": [int(lo), int(hi)],
-            "kernels_us": {k: med(k) for k in prof}, "kernels_us_stats": stats,
-            "pairs_evaluated": evaluated, "comm_stream": order, "comm_calibration_us": cal}
-    ranks = [mine]
-    if dist is not None:
-        ranks = [None] * world
-        dist.all_gather_object(ranks, mine)
+    if args.full:
+        # every rank's own figures (kernel times incl. the all-gather, the stream order its communicator chose, the pairs one launch
+        # of its receiver block evaluates): a scaling curve then explains itself
+        order, cal = eng.comm_stream_order()
+        med = lambda k: (stats[k]["median"] if stats.get(k) else 0.0)   # noqa: E731  (microseconds; 0: not launched / not sampled)
+        mine = {"rank": rank, "receivers": [int(lo), int(hi)],
+                "kernels_us": {k: med(k) for k in prof}, "kernels_us_stats": stats,
+                "pairs_evaluated": evaluated, "comm_stream": order, "comm_calibration_us": cal}
+        ranks = [mine]
+        if dist is not None:
+            ranks = [None] * world
+            dist.all_gather_object(ranks, mine)
     if rank == 0:
         value = n * args.steps / dt
+        rfar = eng.far_radius()
+        far_note = ("every pair evaluated" if not np.isfinite(rfar) else
+                    f"batches of sources beyond {rfar:.1f} m skipped: together they add < 2^-24 f_0 to a receiver "
+                    f"(DESIGN.md D8; CSF_FAR_EPS=0 evaluates every pair)")
+        out = {
+            "metric": "agent-steps/sec at N=16k TwoDBicycle", "value": value, "unit": "agent-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "preroll_ticks": preroll,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": f"{n} {args.model} agents, uniform random in {box:g} m x {box:g} m, "
+                                   + ("every tracked pair evaluated" if not np.isfinite(rfar) else "all pairs within the 2^-24 far-field bound (every_pair: the literal sum)")
+                                   + ", t_s=0.01" + (", curve-scenario road tiled on a 100 m grid" if road else ""),
+                       "agents": n, "rider_model": args.model, "far_field": far_note,
+                       "road_vertices": 0 if road is None else int(road[1].shape[0]),
+                       "parallelism": f"index-sharded x{world}, RCCL all-gather of fp32 records per tick"
+                       if world > 1 else "single GPU"},
+            "healthy": healthy,
+            "build_id": build_id(),
+        }
+    if rank == 0 and args.full:
         n_loc = hi - lo
         # MEDIAN duration of each kernel over its sampled launches (round 6; the means stay beside them in `kernels_us_stats`:
         # one launch of ~40 that meets a clock step or a re-binning's tail moves a mean by per cents, a median not at all)
@@ -323,10 +393,6 @@ def main():
         pairs_all = float(n) * n_loc
         alg_bytes = 16.0 * n * n_loc + 8.0 * n_loc          # source records consumed + partial sums written
         traffic, traffic_src = measured_traffic(kernel) if (world == 1 and n == 16384 and args.model == "twod") else (None, None)
-        rfar = eng.far_radius()
-        far_note = ("every pair evaluated" if not np.isfinite(rfar) else
-                    f"batches of sources beyond {rfar:.1f} m skipped: together they add < 2^-24 f_0 to a receiver "
-                    f"(DESIGN.md D8; CSF_FAR_EPS=0 evaluates every pair)")
         roof = {"bound": "valu", "kernel": kernel, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "launch_us": pair_s * 1e6, "launch_us_is": "median of the sampled launches", "launch_us_mean": mean_s["pair"] * 1e6,
                 "launches_sampled": int(launches), "pairs_evaluated": evaluated,
@@ -347,21 +413,7 @@ def main():
             roof["hbm_frac"] = traffic / pair_s / 1e9 / HBM_PEAK_GBS
         if samples.size:
             roof["launch_us_min_med_max"] = [float(samples.min()), float(np.median(samples)), float(samples.max())]
-        out = {
-            "metric": "agent-steps/sec at N=16k TwoDBicycle", "value": value, "unit": "agent-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "preroll_ticks": preroll,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"{n} {args.model} agents, uniform random in {box:g} m x {box:g} m, "
-                                   + ("every tracked pair evaluated" if not np.isfinite(rfar) else "all pairs within the 2^-24 far-field bound (every_pair: the literal sum)")
-                                   + ", t_s=0.01" + (", curve-scenario road tiled on a 100 m grid" if road else ""),
-                       "agents": n, "rider_model": args.model, "far_field": far_note,
-                       "road_vertices": 0 if road is None else int(road[1].shape[0]),
-                       "parallelism": f"index-sharded x{world}, RCCL all-gather of fp32 records per tick"
-                       if world > 1 else "single GPU"},
-            "healthy": healthy,
-            "build_id": build_id(),
+        out.update({
             "ranks": ranks,
             "timed_window": {"start": win0, "end": win1},
             "per_agent_launch": side_by_side,
@@ -377,7 +429,7 @@ def main():
                             "pairs_per_s": pairs_all / pair_s if pair_s > 0 else None,
                             "note": "SURVEY.md 8(d): 16 B x N sources per receiver over ALL pairs, evaluated or masked; "
                                     "a rate, not a fraction of a peak (the stream never leaves LDS/L2)"},
-        }
+        })
         if world == 1 and not rehearse and np.isfinite(rfar) and args.every_pair_steps > 0:
             # the same population with the far-field cull off (reported beside the headline, never as `value`)
             # (timed like the headline: the read-backs above have let the clocks drop, so a scratch engine runs ~0.1 s first
@@ -397,6 +449,7 @@ def main():
                                  "note": "CSF_FAR_EPS=0: no batch is skipped for distance"}
         if world == 1 and args.cpu_ticks > 0 and args.model == "twod" and road is None:
             out["cpu_baseline"] = cpu_baseline(n, box, args.cpu_ticks)
+    if rank == 0:
         if real_stdout is not None:
             sys.stdout.flush()
             os.dup2(real_stdout, 1)

@@ -313,19 +313,18 @@ def test_whipple_carvallo_matrices_against_the_paper(golden):
 def test_balancingrider_pole_functions_against_the_reference_polemodel(golden):
     """parameters.py:1352-1411 -> controlbehavior.py PoleModel.get_component_mean_function: the straight lines over speed that
     give a rider's desired poles, computed by the host package's restatement (polemodel.py) from the reference's model files
-    where those are at hand (the build container), and its tabulated copy of them, against what the reference's own PoleModel
-    returned (make_golden_balancingrider.py executes the reference's controlbehavior.py)."""
+    (their copies under tests/golden/balancingriderparams), and its tabulated copy of them, against what the reference's own
+    PoleModel returned (make_golden_balancingrider.py executes the reference's controlbehavior.py)."""
     import os
 
     from cyclistsocialforce_amd import polemodel as pm
 
     g = golden("balancingrider")
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "balancingriderparams")
     for tag in ("BR0", "BR1"):
         name = f"{tag}_ImRe5GivenV_pole-model-params.yaml"
         np.testing.assert_allclose(pm.MEAN_FUNCTIONS[name], g[f"polefun_{tag}"], rtol=0, atol=1e-13)
-        path = os.path.join("/root/reference/src/cyclistsocialforce/data/balancingriderparams", name)
-        if os.path.exists(path):
-            np.testing.assert_allclose(pm.component_mean_functions(path), g[f"polefun_{tag}"], rtol=0, atol=1e-13)
+        np.testing.assert_allclose(pm.component_mean_functions(os.path.join(here, name)), g[f"polefun_{tag}"], rtol=0, atol=1e-13)
         for v, want in zip(g[f"poles_{tag}_v"], g[f"poles_{tag}"]):
             np.testing.assert_allclose(pm.poles_at(pm.MEAN_FUNCTIONS[name][0], v), want, rtol=0, atol=1e-12)
 

@@ -3,8 +3,8 @@
 rounding?  The fp64 CPU oracle is run twice, the second time from positions moved by N(0, 4e-6 m), and the distance
 between the two runs is printed every 100 ticks.  Output committed as profiles/r2_chaos_sensitivity.txt; it is why the
 full-length parity test re-anchors the oracle every 100 ticks (tests/test_gpu_large.py)."""
-import sys, time, numpy as np
-sys.path.insert(0,'/root/repo')
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from oracle import csf_oracle as orc
 n, box = 1024, 200.0

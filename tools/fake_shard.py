@@ -21,7 +21,7 @@ for shard in ("unsharded", "0/2", "0/4", "0/8"):
                 env[k] = v
             runs = []
             for _ in range(3):      # (a tick of 35 us is at the mercy of the host: 35 ... 55 us from run to run on one box, either way - the median of three)
-                out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "600", "--warmup", "30", "--cpu-ticks", "0",
+                out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "600", "--warmup", "30", "--cpu-ticks", "0",
                                       "--every-pair-steps", "0"], env=env, capture_output=True, text=True)
                 try:
                     runs.append(json.loads(out.stdout.strip().splitlines()[-1]))

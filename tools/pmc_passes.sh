@@ -3,6 +3,7 @@
 # run, with nothing but the counters, as MI355X_MICROARCH.md prescribes.
 #   tools/pmc_passes.sh NAME [bench.py arguments ...]      -> gpurun_out/pmc_NAME/{sq1,sq2,fetch,write,grbm}
 set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 NAME=${1:-r2}; shift || true
 ARGS=${@:-"--steps 20 --warmup 5"}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$NAME
@@ -11,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 run() { # name, counters...
   name=$1; shift
   case "$ARGS" in *--preroll*) PRE="";; *) PRE="--preroll 0";; esac
-  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS $PRE --cpu-ticks 0 --every-pair-steps 0 > $OUT/$name.log 2>&1
+  rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $ROOT/bench.py --full $ARGS $PRE --cpu-ticks 0 --every-pair-steps 0 > $OUT/$name.log 2>&1
   echo "pass $name done"
 }
 run sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU

@@ -1,6 +1,6 @@
 import time, sys, os
 import numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cyclistsocialforce_amd.vehicle import TwoDBicycle
 from cyclistsocialforce_amd.intersection import SocialForceIntersection
 a = TwoDBicycle((-6, 0, 0, 5, 0), id="a"); b = TwoDBicycle((15, -20, np.pi/2, 5, 0), id="b"); c = TwoDBicycle((13, -20, np.pi/2, 5, 0), id="c")

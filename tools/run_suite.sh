@@ -14,7 +14,7 @@ CSF_TEST_AUTO_VARIANT=1 timeout -k 10 900 python -m pytest tests -m gpu -q --tim
 rc2=$?
 tail -5 $OUT/pytest_auto_variant.log
 if [ $rc2 -gt 1 ]; then echo "pytest (own choice of kernels) rc=$rc2: no further GPU step"; exit $rc2; fi
-timeout -k 10 300 python bench.py --steps 1000 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err || exit 3
+timeout -k 10 300 python bench.py --full --steps 1000 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err || exit 3
 cat $OUT/bench.json
 [ $rc -ne 0 ] && exit $rc
 exit $rc2
