@@ -292,6 +292,14 @@ static int chase_alloc(csf_engine *e) {
         // nothing over (as csf_count_pairs's: partial sums and next tick's circles are written again by the tick's own launch)
         // and a kernel that asks for the per-agent kernels' bytes per lane, on the second stream
         if (e->d.n_live > 1 && e->d.hi > e->d.lo && !e->dirty_layout_for_warm()) {
+            // This launch writes the live partial sums, next tick's circles and the near-pair counter, and reads the records the
+            // per-agent kernel rewrites in place.  Where the upload did not run it (chase_shape was false then), it may come with
+            // hundreds of ticks queued on the main stream (chase_take: the measurement's first period starts at tick 256 or later of
+            // a long call), and nothing else orders the second stream behind them: so the second stream waits for everything
+            // enqueued on the main one, and the synchronisation below waits for those ticks as well.  No live tick can overlap it
+            // (once per engine, before the measurement's first event).
+            HIPCHK(e, hipEventRecord(e->ev_integ, e->main));
+            HIPCHK(e, hipStreamWaitEvent(e->comm, e->ev_integ, 0));
             Dev dw = e->d;
             dw.edge = nullptr;
             dw.pair_count = nullptr;
@@ -638,7 +646,15 @@ static int step_impl(csf_engine *e, int64_t n_ticks, bool want_snap, bool *snapp
     }
     for (int64_t t = 0; t < n_ticks; t++) {
         rc = enqueue_tick(e, n_ticks - t);
-        if (rc) return rc;
+        if (rc) {
+            // the streams meet on this way out too (every other entry point works on the main stream alone), best-effort: the
+            // message of the first error stays, and a join that fails is tried again by the next csf_step
+            if (e->chase_prev && hipEventRecord(e->ev_gather, e->comm) == hipSuccess && hipStreamWaitEvent(e->main, e->ev_gather, 0) == hipSuccess)
+                e->chase_prev = false;
+            (void)hipGetLastError();
+            if (e->cal_phase >= 1 && e->cal_phase <= 3) e->cal_phase = 0;
+            return rc;
+        }
     }
     if ((rc = chase_join(e))) return rc;                          // (every other entry point works on the main stream alone)
     if (e->cal_phase >= 1 && e->cal_phase <= 3) e->cal_phase = 0;  // (a measurement does not span calls)

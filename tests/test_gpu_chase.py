@@ -2,12 +2,24 @@
 wave of the per-agent kernel waits for the arrival counter of its 64 road users while the rest of the pair launch drains, on the engine's
 second stream.  The two orders must give the same states to the last bit (same kernels' arithmetic, same order of additions); the hand-over
 of undecidable pairs (intersection.py:690-745 decided in fp64 by the per-agent kernel) and the double-buffered records are what could
-break.  SocialForceIntersection.step: intersection.py:866-896."""
+break.  SocialForceIntersection.step: intersection.py:866-896.
+
+The side-by-side ticks are also held against the oracle directly - the forces the side-by-side tick itself wrote at the headline
+size, config 3 and PlanarPoint with priority to the right, trajectories of dense crowds with hand-overs across re-binnings - and the
+default path (CSF_CHASE=1: the engine measures which order is faster, behind a deep queue of ticks, and later engines take its
+decision over) is run in a fresh process, where nothing has measured yet: tests/chase_fresh_process.py, through
+test_the_default_path_in_a_fresh_process."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import csf_oracle as orc
-from test_gpu_parity import amd  # noqa: F401  (fixture)
+from conftest import shadow_run
+from test_gpu_parity import amd, synthetic_population  # noqa: F401  (amd: fixture)
 
 pytestmark = [pytest.mark.gpu]
 
@@ -126,3 +138,78 @@ def test_the_engine_measures_which_order_is_faster(amd, monkeypatch):
     c.step(40)
     assert c.chase_calibration() == (decided, [0.0, 0.0]) and (c.chase_ticks() >= 30) == (decided == 1)
     a.close(); b.close(); c.close()
+
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+@pytest.mark.parametrize("model", ["twod", "invpend", "planarpoint"])
+def test_the_default_path_in_a_fresh_process(model):
+    """CSF_CHASE=1 as a fresh process meets it (tests/chase_fresh_process.py, a process of its own per model: which order an engine takes
+    is decided once per process): the measuring engine's step(600) from tick 0 - the measurement begins behind ~250 queued ticks -
+    and an engine that takes the decision over (step(8), step(400): bench.py's timed engine), each to the last bit of an engine
+    with the launches in turn"""
+    out = subprocess.run([sys.executable, os.path.join(HERE, "chase_fresh_process.py"), model], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, f"the process ended with {out.returncode} (a negative code is a signal):\n{out.stderr[-3000:]}"
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    print(f"{model}: decided {res['decided']} ({res['us_per_tick']} us per tick in turn / side by side); B's step(600) returned after "
+          f"{res['b_step600_host_ms']:.1f} ms, the device needed {res['b_step600_device_after_ms']:.1f} ms more; side-by-side ticks "
+          f"B {res['b_chase_ticks_600']} -> {res['b_chase_ticks']}, C {res['c_chase_ticks']}")
+    assert res["failed"] == [], res
+
+
+def _start(model, n, box, seed=0):
+    x, y, psi, v, off, dq = synthetic_population(n, box, seed)
+    s0 = np.zeros((n, orc.N_STATES[orc.MODEL_IDS[model]])); s0[:, 0] = x; s0[:, 1] = y; s0[:, 2] = psi; s0[:, 3] = v
+    return s0, off, dq
+
+
+@pytest.mark.parametrize("model,n,box,rule", [("twod", 16384, 200.0, 0), ("invpend", 16384, 200.0, 0), ("planarpoint", 8192, 140.0, 1)])
+def test_side_by_side_ticks_vs_oracle(amd, monkeypatch, model, n, box, rule):
+    """the forces a side-by-side tick wrote (not calc_forces, which takes the launches in turn) against the oracle, which evaluates
+    every pair in fp64: the headline (BASELINE config 1), config 3 and PlanarPoint with priority to the right, six ticks from tick 0 -
+    the first may take the launches in turn, the rest run side by side.  The bounds of test_gpu_parity.py::test_full_size_ticks_vs_oracle."""
+    s0, off, dq = _start(model, n, box)
+    e = engine(amd, monkeypatch, 2, model, s0, off, dq, rule)
+    pop = orc.Population(orc.default_params(model, priority_rule=rule), s0, 5.0, off, dq)
+    c0 = e.chase_ticks()
+    e.step(6); pop.step(6)
+    took = e.chase_ticks() - c0
+    assert took >= 4, took                                      # (entered with >= 4 ticks left, no re-binning after: the last tick too)
+    got, ref = e.state(), pop.state()
+    moved = np.abs(ref[:, :2] - s0[:, :2]).max()
+    err = np.abs(got[:, :2] - ref[:, :2]).max()
+    fx, fy = e.forces(); ox, oy = pop.forces()
+    scale = np.hypot(ox, oy).max()
+    df = np.abs(np.c_[fx - ox, fy - oy]).max(axis=1)
+    print(f"{model} N={n}: {took} of 6 ticks side by side, max |dpos| {err:.3e} m (moved up to {moved:.3f} m); force error / max force: "
+          f"median {np.median(df) / scale:.2e}, 99.9 % {np.percentile(df, 99.9) / scale:.2e}, max {df.max() / scale:.2e} (receiver {int(df.argmax())})")
+    assert err < 1e-4 * moved
+    assert np.median(df) < 2e-6 * scale and np.percentile(df, 99.9) < 2e-5 * scale
+    assert df.max() < 1e-4 * scale                              # every receiver
+    assert (e.status() == 0).all() and e.near_dropped() == 0
+    e.close()
+
+
+@pytest.mark.parametrize("model,rule,hfov", [("twod", 0, 4.0), ("planarpoint", 1, 2.0)])
+def test_side_by_side_dense_crowds_vs_oracle(amd, monkeypatch, model, rule, hfov):
+    """4 096 road users in 45 m (near pairs, hand-overs of undecidable pairs) over 140 ticks across two re-binnings, the oracle shadowing
+    the engine in windows of 10 ticks (conftest.py: shadow_run - in a crowd this dense two free runs 1e-7 m apart meet a field-of-view
+    edge within a few ticks, so no per-tick force comparison here): every 9-tick call of a window runs side by side but for a
+    re-binning tick or a first tick behind the pushed anchor state.  Trajectories, destination pointers and navigation states."""
+    n, box, ticks = 4096, 45.0, 140
+    s0, off, dq = crowd(n, box, 11, orc.N_STATES[orc.MODEL_IDS[model]])
+    e = engine(amd, monkeypatch, 2, model, s0, off, dq, rule, hfov=hfov)
+    pop = orc.Population(orc.default_params(model, priority_rule=rule, hfov=hfov), s0, 5.0, off, dq)
+    worst, _, got, ref = shadow_run(e, pop, ticks, 10)
+    took = e.chase_ticks()
+    extent = max(np.ptp(ref[:, 0]), np.ptp(ref[:, 1]), 14.0)
+    print(f"{model} rule {rule}: {took} of {ticks} ticks side by side, worst window-end deviation {worst:.3e} m (extent {extent:.1f} m)")
+    assert took >= ticks // 2, took                              # (measured: 125 of 140 in both crowds)
+    assert worst < 1e-4 * extent
+    _, ptr, zn, _ = e.state(with_nav=True)
+    optr, ozn, _, _ = pop.nav()
+    np.testing.assert_array_equal(ptr, optr)
+    np.testing.assert_array_equal(np.asarray(zn).reshape(n, 3).astype(bool), ozn)
+    assert (e.status() == 0).all() and e.near_dropped() == 0
+    e.close()
