@@ -29,6 +29,7 @@ SYMBOLS = (
     "csf_update_nav_state", "csf_set_dest_pointer", "csf_set_incremental", "csf_set_script", "csf_near_dropped", "csf_comm_stream_order", "csf_small_ticks", "csf_step_get_tick",
     "csf_get_integrator_state", "csf_set_integrator_state", "csf_mid_ticks", "csf_holes_taken",
     "csf_create_v", "csf_params_size", "csf_profile_samples_of", "csf_chase_ticks", "csf_chase_calibration", "csf_replace_agents",
+    "csf_batch_join", "csf_batch_leave", "csf_step_batch", "csf_step_batch_get_tick", "csf_batch_ticks",
 )
 ABI_VERSION = 9
 
@@ -53,6 +54,13 @@ class Params(C.Structure):
         ("br_minv_steer", C.c_double * 2), ("br_yaw", C.c_double * 2), ("br_pole_fun", C.c_double * 10), ("br_gains", C.c_double * 5),
         ("model", C.c_int32), ("priority_rule", C.c_int32), ("traj_len", C.c_int32), ("br_mode", C.c_int32),
     ]
+
+
+class TickOut(C.Structure):
+    """csf_tick_out of include/csf.h: the outputs of csf_get_tick for one member of a batch (any may be NULL)."""
+
+    _fields_ = [("s_out", C.c_void_p), ("dest_ptr", C.c_void_p), ("znav", C.c_void_p), ("Fx", C.c_void_p), ("Fy", C.c_void_p),
+                ("tick", C.POINTER(C.c_int64))]
 
 
 class EngineError(RuntimeError):
@@ -146,6 +154,11 @@ def load():
     L.csf_chase_calibration.argtypes = [vp, C.POINTER(i32), dp]
     L.csf_get_integrator_state.argtypes = [vp, dp, dp, vp]
     L.csf_set_integrator_state.argtypes = [vp, i64, vp, dp, dp, vp]
+    L.csf_batch_join.argtypes = [C.POINTER(vp), i32]
+    L.csf_batch_leave.argtypes = [C.POINTER(vp), i32]
+    L.csf_step_batch.argtypes = [C.POINTER(vp), i32, i64]
+    L.csf_step_batch_get_tick.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(TickOut)]
+    L.csf_batch_ticks.argtypes = [vp, C.POINTER(i64)]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

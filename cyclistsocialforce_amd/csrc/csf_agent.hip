@@ -126,9 +126,11 @@ bool launch_agent_chase(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t 
 //                                                                         intersection.py:690-745, 814-843; vehicle.py:1560-1648
 //   the per-agent tick with that sum (agent_body<FUSED>)                  see the head of this file
 // No records are binned, nothing is noted or handed over: every yes / no is settled on the spot.
+// The body is shared by small_tick_kernel (one scene, its Dev in the kernarg segment) and small_batch_kernel (one scene per
+// workgroup, the Dev records in a table in global memory): `srv` is the LDS that stages the road, `snap` the packed read-back
+// behind the last tick (NULL: none).
 template <int MODEL>
-__global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n_ticks) {
-    const uint32_t ka_lines = kernarg_touch<(int)sizeof(Dev) + 4>();
+__device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks, double *const snap, float4 *const srv, const uint32_t ka_lines) {
     // Lane = (receiver, source group): with P the power of two that holds the road users, lane % P is the receiver and lane / P
     // one of 64 / P groups that share the sources between them (source j belongs to group j % G) - all 64 lanes work on the
     // pair term whatever the population, and the groups' sums meet in lanes 0 .. n - 1, which then tick their road user.
@@ -145,7 +147,6 @@ __global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n
     const PairConsts k = d.pc;
     const bool p2r = d.p.priority_rule == CSF_P2R;
     // road elements (intersection.py:226-242; the curve scenario's ~1 500 vertices): staged once per launch - they are static
-    __shared__ float4 srv[SMALL_ROAD_MAX];
     const int nvp = (int)d.nv_pad;
     for (int v = lane; v < nvp; v += WAVE) srv[v] = d.rv[v];
     for (int t = 0; t < n_ticks; t++) {
@@ -234,10 +235,10 @@ __global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n
         if (lane < n) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry);
     }
     // csf_step_get_tick: what snapshot_kernel would pack in a launch of its own (slots are the population order here)
-    if (d.snap != nullptr && lane < n) {
+    if (snap != nullptr && lane < n) {
         const int ns = d.ns;
-        for (int c = 0; c < ns; c++) d.snap[(int64_t)lane * ns + c] = d.s[(int64_t)c * cap + lane];
-        double *F = d.snap + (int64_t)n * ns;
+        for (int c = 0; c < ns; c++) snap[(int64_t)lane * ns + c] = d.s[(int64_t)c * cap + lane];
+        double *F = snap + (int64_t)n * ns;
         F[lane] = d.F[lane];
         F[n + lane] = d.F[cap + lane];
         int32_t *ptr = (int32_t *)(F + 2 * n);
@@ -248,6 +249,44 @@ __global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n
         zn[3 * lane + 1] = z == 1;
         zn[3 * lane + 2] = z == 2;
     }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n_ticks) {
+    const uint32_t ka_lines = kernarg_touch<(int)sizeof(Dev) + 4>();
+    __shared__ float4 srv[SMALL_ROAD_MAX];
+    small_tick_body<MODEL>(d, n_ticks, d.snap, srv, ka_lines);
+}
+
+// Many independent scenes of one vehicle class in one launch (csf_step_batch): workgroup b ticks the scene of table[b], all
+// n_ticks of the call.  The road is staged in dynamic LDS sized by the launch's largest nv_pad (none without roads), so that
+// registers and not an unused road buffer set how many of these waves a CU holds.  `pack`: write every member's read-back into
+// its Dev::snap behind the last tick (a per-call choice; the table changes only when a member's Dev does).
+template <int MODEL>
+__global__ __launch_bounds__(64) void small_batch_kernel(const Dev *__restrict__ table, const int count, const int n_ticks, const int pack) {
+    extern __shared__ float4 srv_dyn[];
+    if ((int)blockIdx.x >= count) return;
+    // (the record copied into the kernel, as the single-scene kernel has it in its kernarg segment: read through a reference to
+    // global memory, the compiler contracted a few fp64 chains of the PlanarPoint, PlanarBicycle and InvPendulum riders
+    // differently - 1 ulp, and the batch is no longer what csf_step on each member gives)
+    const Dev d = table[blockIdx.x];
+    small_tick_body<MODEL>(d, n_ticks, pack ? d.snap : nullptr, srv_dyn, 0u);
+}
+
+void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, int n_ticks, bool pack, hipStream_t st) {
+    if (n_ticks <= 0 || count <= 0) return;
+    const size_t lds = (size_t)max_nv_pad * sizeof(float4);
+    const int pk = pack ? 1 : 0;
+#define CSF_BATCH(MODEL) hipLaunchKernelGGL((small_batch_kernel<MODEL>), dim3((unsigned)count), dim3(64), lds, st, table, count, n_ticks, pk)
+    switch (model) {
+    case CSF_BICYCLE: CSF_BATCH(CSF_BICYCLE); break;
+    case CSF_TWOD: CSF_BATCH(CSF_TWOD); break;
+    case CSF_INVPEND: CSF_BATCH(CSF_INVPEND); break;
+    case CSF_PLANARBIKE: CSF_BATCH(CSF_PLANARBIKE); break;
+    case CSF_BALANCINGRIDER: CSF_BATCH(CSF_BALANCINGRIDER); break;
+    default: CSF_BATCH(CSF_PLANARPOINT); break;
+    }
+#undef CSF_BATCH
 }
 
 void launch_small_tick(const Dev &d, int n_ticks, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {

@@ -15,4 +15,5 @@
 #include "engine/tick.inc"   // one tick enqueued: two launches in turn, one launch (mid-size), side by side (large), one wave (a handful); csf_step, csf_sync
 #include "engine/abi_forces_readback.inc"   // C ABI: forces on their own, replay, read-backs, the single-function entry points
 #include "engine/abi_sharding.inc"   // C ABI: communicators, loopback groups
+#include "engine/abi_batch.inc"   // C ABI: batches of independent scenes (one launch per vehicle class for all one-wave members)
 #include "engine/abi_measurement.inc"   // C ABI: far-field radius, time stamps, counters

@@ -87,6 +87,7 @@ csf_engine *csf_create_v(const csf_params *params, size_t params_size, int32_t a
 int csf_destroy(csf_engine *e) try {
     if (!e) return CSF_OK;
     (void)hipSetDevice(e->device);
+    if (e->batch) (void)batch_dissolve(e);   // (the other members go on as single engines, each on its own stream again)
     if (e->main) (void)hipStreamSynchronize(e->main);
     if (e->comm) (void)hipStreamSynchronize(e->comm);
     if (e->time_pop && e->tp_calls > 0)

@@ -446,6 +446,12 @@ struct csf_engine {
     std::vector<csf_engine *> group;
     bool loopback = false;
 
+    // csf_batch_join: the batch this engine belongs to (shared by its members; engine/abi_batch.inc) and, while it does, the
+    // engine's own stream, kept for when it leaves (the members tick on the first member's)
+    std::shared_ptr<struct BatchState> batch;
+    std::shared_ptr<StreamHold> own_hold;
+    int64_t batch_ticks = 0;         // ticks run inside a batched launch (csf_batch_ticks)
+
     // profiling: a fixed pool of event slots, recycled in order (the oldest slot is resolved into the running sums
     // before it is reused, so stepping with profiling left on holds a bounded number of events)
     int profile = 0;             // 0 off, k > 0: time the kernels of every k-th tick
@@ -460,6 +466,9 @@ struct csf_engine {
     int64_t prof_ticks = 0;             // sampled ticks issued (the kernels beside the pair kernel are timed on every 8th)
     std::vector<float> prof_us[4];      // per sampled launch and kernel - pair, road, per-agent, all-gather - (at most PROF_KEEP of each)
 };
+
+// (engine/abi_batch.inc; csf_destroy dissolves the batch of the engine it destroys)
+static int batch_dissolve(csf_engine *e);
 
 // (defined with the side-by-side tick, used by upload_all)
 static bool chase_shape(const csf_engine *e);

@@ -394,6 +394,96 @@ class Engine:
         if sync:
             engines[0].sync()
 
+    # -- batches of independent scenes (include/csf.h: csf_batch_join) ------------------------------------------------
+    @staticmethod
+    def _batch_array(engines, what):
+        engines = list(engines)
+        if not engines:
+            raise ValueError(f"{what}: no engines")
+        for e in engines:
+            if not isinstance(e, Engine):
+                raise TypeError(f"{what}: every member must be an Engine")
+            if not e._h:
+                raise ValueError(f"{what}: an engine is closed")
+        if len({id(e) for e in engines}) != len(engines):
+            raise ValueError(f"{what}: an engine is listed twice")
+        return engines, (C.c_void_p * len(engines))(*[e._h for e in engines])
+
+    @staticmethod
+    def _batch_raise(lib, rc, engines):
+        msgs = [m for m in (lib.csf_last_error(e._h).decode() for e in engines) if m]
+        raise EngineError(f"[{rc}] " + "; ".join(dict.fromkeys(msgs)))
+
+    @staticmethod
+    def batch_join(engines):
+        """The engines - independent scenes on one device - become one batch: Engine.step_batch steps them together, every
+        member the one-wave tick takes in one launch per vehicle class.  Engine.batch_leave (or closing a member) dissolves it."""
+        engines, arr = Engine._batch_array(engines, "batch_join")
+        lib = _ffi.load()
+        rc = lib.csf_batch_join(arr, len(engines))
+        if rc != 0:
+            Engine._batch_raise(lib, rc, engines)
+
+    @staticmethod
+    def batch_leave(engines):
+        engines, arr = Engine._batch_array(engines, "batch_leave")
+        lib = _ffi.load()
+        rc = lib.csf_batch_leave(arr, len(engines))
+        if rc != 0:
+            Engine._batch_raise(lib, rc, engines)
+
+    @staticmethod
+    def step_batch(engines, n_ticks=1, sync=False):
+        """csf_step_batch: every member of the batch (the engines in join order) by n_ticks, bit for bit as Engine.step on each."""
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("step_batch: n_ticks must be an integer >= 0")
+        engines, arr = Engine._batch_array(engines, "step_batch")
+        lib = _ffi.load()
+        rc = lib.csf_step_batch(arr, len(engines), int(n_ticks))
+        if rc != 0:
+            Engine._batch_raise(lib, rc, engines)
+        if sync:
+            engines[0].sync()
+
+    @staticmethod
+    def step_batch_into(engines, n_ticks, outs):
+        """step_batch, then every member's read-back straight into the caller's arrays (csf_step_batch_get_tick): outs[i] is
+        (s [n, n_states] float64, ptr [n] int32, zn [n, 3] of one byte each, fx [n] float64, fy [n] float64) for member i, C-contiguous;
+        any of them may be None.  Returns the members' tick counts."""
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("step_batch_into: n_ticks must be an integer >= 0")
+        engines, arr = Engine._batch_array(engines, "step_batch_into")
+        outs = list(outs)
+        if len(outs) != len(engines):
+            raise ValueError("step_batch_into: one output tuple per engine")
+        tout = (_ffi.TickOut * len(engines))()
+        ticks = (C.c_int64 * len(engines))()
+        for i, (e, o) in enumerate(zip(engines, outs)):
+            n = e.n
+            s, ptr, zn, fx, fy = (tuple(o) + (None,) * 5)[:5]
+            checks = ((s, (n, e.ns), np.float64), (ptr, (n,), np.int32), (zn, (n, 3), None), (fx, (n,), np.float64), (fy, (n,), np.float64))
+            for a, shape, dt in checks:
+                if a is None:
+                    continue
+                if not isinstance(a, np.ndarray) or not a.flags.c_contiguous or a.shape != shape or (dt is not None and a.dtype != dt) \
+                        or (dt is None and a.dtype.itemsize != 1):
+                    raise ValueError("step_batch_into: s [n, n_states] float64, ptr [n] int32, zn [n, 3] of one byte each, fx / fy [n] "
+                                     "float64, C-contiguous")
+            t = tout[i]
+            t.s_out, t.dest_ptr, t.znav, t.Fx, t.Fy = [None if a is None else a.ctypes.data for a in (s, ptr, zn, fx, fy)]
+            t.tick = C.cast(C.byref(ticks, i * C.sizeof(C.c_int64)), C.POINTER(C.c_int64))
+        lib = _ffi.load()
+        rc = lib.csf_step_batch_get_tick(arr, len(engines), int(n_ticks), tout)
+        if rc != 0:
+            Engine._batch_raise(lib, rc, engines)
+        return list(ticks)
+
+    def batch_ticks(self):
+        """ticks this engine has run inside a batched launch (csf.h: csf_batch_ticks)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_batch_ticks(self._h, C.byref(n)))
+        return n.value
+
     def shard_range(self):
         lo, hi = C.c_int64(0), C.c_int64(0)
         self._ck(self._lib.csf_shard_range(self._h, C.byref(lo), C.byref(hi)))

@@ -638,6 +638,12 @@ class SocialForceIntersection:
             if forces:
                 self._fx[:n] = fx                                     # intersection.py:860-862
                 self._fy[:n] = fy
+        return self._book_pull(fx, fy, forces, advance)
+
+    def _book_pull(self, fx, fy, forces, advance):
+        """the host's per-tick bookkeeping behind a read-back into the bulk mirror (_pull; step_together): trajectory ring,
+        force logs, drawings, SUMO positions"""
+        n = len(self.vehicles)
         if forces:
             self._have_force = True
         if advance:
@@ -866,6 +872,17 @@ class SocialForceIntersection:
                 self._pull(forces=True, advance=int(n_ticks))
         self.hist_n_vecs.extend([self.n_bikes] * int(n_ticks))
 
+    def _batch_outputs(self):
+        """(engine, the bulk mirror's arrays for csf_step_batch_get_tick) when this intersection's tick can join a batched step,
+        else None: empty, custom force hooks, drawn poles or drawings on the first tick, a mirror narrower than the engine's state"""
+        if self.n_bikes <= 0 or self._hooked or (self.animate and self.is_first_step) or self._stochastic_riders():
+            return None
+        e = self._push_mutations()
+        n = len(self.vehicles)
+        if self._S.shape[1] != e.ns:
+            return None
+        return e, (self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n])
+
     def set_animated(self, animated):
         """intersection.py:899-915: switch every drawing between blitted (animated) and ordinary artists."""
         for v in self.vehicles:
@@ -875,3 +892,52 @@ class SocialForceIntersection:
     @property
     def engine(self):
         return self._engine_ready()
+
+
+def _batch_of(engines):
+    """the engines as ONE batch (Engine.batch_join), joined again when the set of engines changed - an intersection creates its
+    engine lazily, or a new one when its population's vehicle classes change"""
+    key = [id(e) for e in engines]
+    if getattr(engines[0], "_together", None) is not None and [id(e) for e in engines[0]._together] == key:
+        return
+    for e in engines:
+        old = getattr(e, "_together", None)
+        if old is None:
+            continue
+        try:
+            Engine.batch_leave(old)
+        except (_ffi.EngineError, ValueError):
+            pass                                        # (a member was destroyed: the batch is gone already)
+        for m in old:
+            m._together = None
+    Engine.batch_join(engines)
+    for e in engines:
+        e._together = list(engines)
+
+
+def step_together(intersections, n_ticks=1):
+    """Every SocialForceIntersection by n_ticks, exactly as `for ins in intersections: ins.step()` repeated n_ticks times would
+    leave them - vehicle.s, traj, trajF, F, znav, hist_n_vecs, drawings, SUMO positions - with the ticks of all their engines in
+    one csf_step_batch_get_tick per tick: the engines the one-wave tick takes run in one launch per vehicle class, and the host
+    waits once.  Intersections with custom force hooks or stochastic riders take their own .step() (they pass the host every tick
+    anyway); empty ones only count the tick.  The natural step_func of a Scenario over many junctions (SUMOScenario)."""
+    intersections = list(intersections)
+    for _ in range(int(n_ticks)):
+        joined = []
+        for ins in intersections:
+            got = ins._batch_outputs()
+            if got is None:
+                ins.step()
+            else:
+                joined.append((ins, got[0], got[1]))
+        if not joined:
+            continue
+        engines = [e for _, e, _ in joined]
+        _batch_of(engines)
+        Engine.step_batch_into(engines, 1, [o for _, _, o in joined])
+        for ins, _, (S, _, _, fx, fy) in joined:
+            ins.is_first_step = False
+            if ins._s_watched:
+                ins._shadow[:S.shape[0]] = S
+            ins._book_pull(fx, fy, True, 1)
+            ins.hist_n_vecs.append(ins.n_bikes)

@@ -285,6 +285,34 @@ int csf_shard_range(const csf_engine *e, int64_t *lo, int64_t *hi);
 int csf_comm_init_loopback(csf_engine *const *engines, int32_t world);
 int csf_step_group(csf_engine *const *engines, int32_t world, int64_t n_ticks);
 
+/* ---- batches of independent scenes -------------------------------------------------------------- */
+
+/* Many small, independent scenes stepped together (the junctions of a SUMO network, parameter sweeps): `count` engines on
+ * one device, each with its own population, road and parameters, become one batch.  They must be distinct, on one device,
+ * not sharded, not in a loopback group and not in another batch; otherwise the call is refused and nothing changes.  The
+ * members then share one HIP stream (each member's own stream is waited for first).  csf_step_batch steps every member by
+ * n_ticks: the members the one-wave tick takes (see csf_small_ticks) run in ONE launch per vehicle class present - one wave
+ * per scene, all ticks of the call - and every other member is stepped by csf_step in turn.  Bit for bit what csf_step on
+ * each member would give.  `engines` must be the batch in join order.  csf_batch_leave dissolves the batch, and so does
+ * csf_destroy of a member: the others go on as single engines, and csf_step_batch on them fails with CSF_E_STATE. */
+int csf_batch_join(csf_engine *const *engines, int32_t count);
+int csf_batch_leave(csf_engine *const *engines, int32_t count);
+int csf_step_batch(csf_engine *const *engines, int32_t count, int64_t n_ticks);
+/* the outputs of csf_get_tick for one member; any pointer may be NULL */
+typedef struct csf_tick_out {
+    double *s_out;
+    int32_t *dest_ptr;
+    uint8_t *znav;
+    double *Fx;
+    double *Fy;
+    int64_t *tick;
+} csf_tick_out;
+/* csf_step_batch, then the csf_get_tick outputs of every member (out[count]): the batched launch packs the read-back of its
+ * members behind their last tick, and the host waits once for all of them. */
+int csf_step_batch_get_tick(csf_engine *const *engines, int32_t count, int64_t n_ticks, const csf_tick_out *out);
+/* ticks this engine has run inside a batched launch (csf_small_ticks counts them too) */
+int csf_batch_ticks(const csf_engine *e, int64_t *n_ticks);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 /* HIP-event time of the pair kernel, measured on the stream it is launched on: enable with on = k > 0 to
