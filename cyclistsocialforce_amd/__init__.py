@@ -13,7 +13,11 @@ def __getattr__(name):
         from .intersection import step_together
 
         return step_together
+    if name == "advance_together":                       # ... by many ticks, with the trajectories of all of them
+        from .intersection import advance_together
+
+        return advance_together
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["step_together"]
+__all__ = ["step_together", "advance_together"]

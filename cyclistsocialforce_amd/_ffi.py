@@ -30,8 +30,10 @@ SYMBOLS = (
     "csf_get_integrator_state", "csf_set_integrator_state", "csf_mid_ticks", "csf_holes_taken",
     "csf_create_v", "csf_params_size", "csf_profile_samples_of", "csf_chase_ticks", "csf_chase_calibration", "csf_replace_agents",
     "csf_batch_join", "csf_batch_leave", "csf_step_batch", "csf_step_batch_get_tick", "csf_batch_ticks",
+    "csf_record", "csf_get_record", "csf_batch_get_record",
 )
 ABI_VERSION = 9
+REC_STATE, REC_FORCE = 1, 2
 
 
 class Params(C.Structure):
@@ -61,6 +63,12 @@ class TickOut(C.Structure):
 
     _fields_ = [("s_out", C.c_void_p), ("dest_ptr", C.c_void_p), ("znav", C.c_void_p), ("Fx", C.c_void_p), ("Fy", C.c_void_p),
                 ("tick", C.POINTER(C.c_int64))]
+
+
+class RecordOut(C.Structure):
+    """csf_record_out of include/csf.h: where the last samples of one member of a batch go (s and F NULL: the member is left out)."""
+
+    _fields_ = [("s", C.c_void_p), ("F", C.c_void_p), ("first_sample", C.POINTER(C.c_int64))]
 
 
 class EngineError(RuntimeError):
@@ -159,6 +167,10 @@ def load():
     L.csf_step_batch.argtypes = [C.POINTER(vp), i32, i64]
     L.csf_step_batch_get_tick.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(TickOut)]
     L.csf_batch_ticks.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_record"):                 # (CSF_LIB may name an older build for an A/B measurement: it lacks these three)
+        L.csf_record.argtypes = [vp, i32, i32, C.c_uint32]
+        L.csf_get_record.argtypes = [vp, i64, i64, dp, dp]
+        L.csf_batch_get_record.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(RecordOut)]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

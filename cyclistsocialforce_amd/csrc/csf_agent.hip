@@ -128,9 +128,11 @@ bool launch_agent_chase(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t 
 // No records are binned, nothing is noted or handed over: every yes / no is settled on the spot.
 // The body is shared by small_tick_kernel (one scene, its Dev in the kernarg segment) and small_batch_kernel (one scene per
 // workgroup, the Dev records in a table in global memory): `srv` is the LDS that stages the road, `snap` the packed read-back
-// behind the last tick (NULL: none).
+// behind the last tick (NULL: none), `tick0` the ticks the engine has done before this launch (what the samples of csf_record and
+// csf_enable_history are numbered from: sample k = state after tick (k + 1) * stride).
 template <int MODEL>
-__device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks, double *const snap, float4 *const srv, const uint32_t ka_lines) {
+__device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks, double *const snap, float4 *const srv, const uint32_t ka_lines,
+                                                const int64_t tick0) {
     // Lane = (receiver, source group): with P the power of two that holds the road users, lane % P is the receiver and lane / P
     // one of 64 / P groups that share the sources between them (source j belongs to group j % G) - all 64 lanes work on the
     // pair term whatever the population, and the groups' sums meet in lanes 0 .. n - 1, which then tick their road user.
@@ -149,7 +151,22 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
     // road elements (intersection.py:226-242; the curve scenario's ~1 500 vertices): staged once per launch - they are static
     const int nvp = (int)d.nv_pad;
     for (int v = lane; v < nvp; v += WAVE) srv[v] = d.rv[v];
+    // the recording (Dev::hist, hist_F): ticks until the next sampled one and its ring slot, divided out once per launch and
+    // counted on from there (uniform: scalar registers, nothing of it in the tick loop but a compare and an add)
+    int rec_wait = -1, rec_next = 0;
+    if (d.hist != nullptr) {
+        const int64_t rem = (tick0 + 1) % d.hist_stride;
+        rec_wait = rem == 0 ? 0 : (int)(d.hist_stride - rem);
+        rec_next = (int)(((tick0 + 1 + rec_wait) / d.hist_stride - 1) % d.hist_cap);
+    }
     for (int t = 0; t < n_ticks; t++) {
+        int rec_slot = -1;
+        if (rec_wait == 0) {
+            rec_slot = rec_next;
+            rec_next = rec_next + 1 == d.hist_cap ? 0 : rec_next + 1;
+            rec_wait = d.hist_stride;
+        }
+        if (rec_wait > 0) rec_wait--;
         // (own stores of the previous tick: the lanes of the first group wrote them, in this wave: program order)
         const double x = d.s[a], y = d.s[cap + a], psi = d.s[2 * cap + a];
         double sp, cp;
@@ -232,7 +249,7 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             if (lane < n) d.froad[lane] = make_float2(qx, qy);    // (agent_body reads it back: the same lane, program order)
         }
         __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
-        if (lane < n) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry);
+        if (lane < n) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
     }
     // csf_step_get_tick: what snapshot_kernel would pack in a launch of its own (slots are the population order here)
     if (snap != nullptr && lane < n) {
@@ -255,7 +272,7 @@ template <int MODEL>
 __global__ __launch_bounds__(64) void small_tick_kernel(const Dev d, const int n_ticks) {
     const uint32_t ka_lines = kernarg_touch<(int)sizeof(Dev) + 4>();
     __shared__ float4 srv[SMALL_ROAD_MAX];
-    small_tick_body<MODEL>(d, n_ticks, d.snap, srv, ka_lines);
+    small_tick_body<MODEL>(d, n_ticks, d.snap, srv, ka_lines, d.tick);
 }
 
 // Many independent scenes of one vehicle class in one launch (csf_step_batch): workgroup b ticks the scene of table[b], all
@@ -270,7 +287,10 @@ __global__ __launch_bounds__(64) void small_batch_kernel(const Dev *__restrict__
     // global memory, the compiler contracted a few fp64 chains of the PlanarPoint, PlanarBicycle and InvPendulum riders
     // differently - 1 ulp, and the batch is no longer what csf_step on each member gives)
     const Dev d = table[blockIdx.x];
-    small_tick_body<MODEL>(d, n_ticks, pack ? d.snap : nullptr, srv_dyn, 0u);
+    // (the table holds Dev::tick = 0: a recording member's count is a word of device memory, moved on here behind the last tick)
+    const int64_t tick0 = d.rec_tick != nullptr ? *d.rec_tick : 0;
+    small_tick_body<MODEL>(d, n_ticks, pack ? d.snap : nullptr, srv_dyn, 0u, tick0);
+    if (d.rec_tick != nullptr && threadIdx.x == 0) *d.rec_tick = tick0 + n_ticks;
 }
 
 void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, int n_ticks, bool pack, hipStream_t st) {
@@ -419,6 +439,44 @@ __global__ void snapshot_kernel(const Dev d, double *out) {
 void launch_snapshot(const Dev &d, double *out, hipStream_t st) {
     if (d.n_live <= 0) return;
     hipLaunchKernelGGL(snapshot_kernel, dim3((unsigned)((d.n_live + 255) / 256)), dim3(256), 0, st, d, out);
+}
+
+// The rings of csf_record / csf_enable_history -> one packed buffer: workgroup row y serves member y, its threads stride over
+// the member's samples [count][n][ns] and [count][n][2] in pairs of doubles (16-byte loads and stores; a ring slot is a whole
+// number of pairs unless n * ns is odd, then one double at a time).  Sample k of the output is ring slot (first + k) % cap.
+__device__ __forceinline__ void gather_ring(const double *__restrict__ ring, double *__restrict__ out, const int64_t row, const int cap,
+                                            const int first, const int count, const int64_t i0, const int64_t step) {
+    if ((row & 1) == 0) {
+        const int64_t rp = row >> 1, total = rp * count;
+        for (int64_t j = i0; j < total; j += step) {
+            const int64_t k = j / rp, r = j - k * rp;
+            const int64_t slot = (first + k) % cap;
+            ((double2 *)out)[j] = ((const double2 *)ring)[slot * rp + r];
+        }
+    } else {
+        const int64_t total = row * count;
+        for (int64_t j = i0; j < total; j += step) {
+            const int64_t k = j / row, r = j - k * row;
+            const int64_t slot = (first + k) % cap;
+            out[j] = ring[slot * row + r];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void record_gather_kernel(const RecDesc *__restrict__ desc, const int members, double *__restrict__ out) {
+    if ((int)blockIdx.y >= members) return;
+    const RecDesc m = desc[blockIdx.y];
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if (m.s != nullptr) gather_ring(m.s, out + m.s_off, (int64_t)m.n * m.ns, m.cap, m.first, m.count, i0, step);
+    if (m.F != nullptr) gather_ring(m.F, out + m.F_off, (int64_t)m.n * 2, m.cap, m.first, m.count, i0, step);
+}
+
+void launch_record_gather(const RecDesc *desc, int members, int64_t most_doubles, double *out, hipStream_t st) {
+    if (members <= 0 || most_doubles <= 0) return;
+    // (columns of workgroups: enough for the largest member at 4 pairs per thread, at most 256 - the threads stride over the rest)
+    const int64_t want = (most_doubles / 2 + 1023) / 1024;
+    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(want, 1), 256);
+    hipLaunchKernelGGL(record_gather_kernel, dim3(gx, (unsigned)members), dim3(256), 0, st, desc, members, out);
 }
 
 void launch_records(const Dev &d, hipStream_t st) {

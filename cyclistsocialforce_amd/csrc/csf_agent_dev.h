@@ -1000,7 +1000,8 @@ __device__ __forceinline__ void write_record(const Dev &d, const csf_params &p, 
 
 
 // One road user's tick.  FUSED (small_tick_kernel, below): the repulsive sum (frx, fry) comes from the caller - no pair kernel
-// has run, so there are no partial sums to read and no pairs handed over.
+// has run, so there are no partial sums to read and no pairs handed over - and so does the ring slot of this tick's recorded
+// sample (rec_slot, -1: none): many ticks run in one launch there, and Dev::tick is the launch's first.
 // MID (csf_mid.hip: the tick of a mid-size population in one launch, one workgroup per receiver group): 1 - this call is the
 // destination-force phase, run by the group's first wave WHILE the other waves form the pair sums (they may be setting
 // CSF_ST_EDGE in the status word: its bits go in with an atomic OR); 2 - this call is the rest, by the same wave behind the
@@ -1018,7 +1019,7 @@ __device__ __forceinline__ EdgeRec load_edge(const EdgeRec *p) {
 
 template <int MODEL, bool HET, bool FUSED, int MID = 0>
 __device__ __forceinline__ void agent_body(const Dev &d, const int phases, const int64_t a, uint64_t *const tr, const uint32_t ka_lines,
-                                           const double frx, const double fry) {
+                                           const double frx, const double fry, const int rec_slot = -1) {
     auto stamp = [&](int k) {
         if (tr != nullptr) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1264,9 +1265,14 @@ __device__ __forceinline__ void agent_body(const Dev &d, const int phases, const
             d.src64_w[2 * cap + a] = g.psi;
         }
         if (d.hist != nullptr) {
-            int64_t t1 = d.tick + 1;
-            if (t1 % d.hist_stride == 0) {
-                int64_t smp = (t1 / d.hist_stride - 1) % d.hist_cap;
+            // the ring slot of this tick's sample, -1: not a sampled tick.  The one-wave tick runs many ticks per launch (Dev::tick
+            // is the launch's first) and counts the slot itself; every other launch is one tick
+            int64_t smp = rec_slot;
+            if (!FUSED) {
+                const int64_t t1 = d.tick + 1;
+                smp = t1 % d.hist_stride == 0 ? (t1 / d.hist_stride - 1) % d.hist_cap : -1;
+            }
+            if (smp >= 0) {
                 double *o = d.hist + (smp * d.n + a) * d.ns;
                 o[0] = g.x;
                 o[1] = g.y;
@@ -1274,6 +1280,11 @@ __device__ __forceinline__ void agent_body(const Dev &d, const int phases, const
                 o[3] = g.v;
                 if (d.ns > 4) o[4] = g.delta;
                 if (d.ns > 5) o[5] = g.theta;
+                if ((HET || MODEL == CSF_BALANCINGRIDER) && d.ns > 6) {   // (the rates integrate() has just stored, this lane's own)
+                    o[6] = d.s[6 * cap + a];
+                    o[7] = d.s[7 * cap + a];
+                }
+                if (d.hist_F != nullptr) *(double2 *)(d.hist_F + (smp * d.n + a) * 2) = make_double2(Fx, Fy);   // (csf_record)
             }
         }
     }

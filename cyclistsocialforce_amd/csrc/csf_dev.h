@@ -259,6 +259,10 @@ struct Dev {
     int64_t replay_tick;        // the replay
     double *hist;      // opt-in history [hist_cap][n][ns]
     int32_t hist_stride, hist_cap;
+    // csf_record: the total force of every sampled tick beside its state, and the engine's tick counter in device memory - what
+    // small_batch_kernel numbers its samples from (the batch's table holds Dev::tick = 0) and moves on behind its last tick
+    double *hist_F;    // [hist_cap][n][2] (Fx, Fy), NULL: states only
+    int64_t *rec_tick; // [1] ticks done, as the batched launch sees them (engine/abi_batch.inc keeps it current); NULL: no csf_record
     unsigned long long *pair_count;  // csf_count_pairs: [4] pair evaluations, per-lane tests, full and partial evaluation passes of the launch (NULL: not counted)
     double *snap;      // csf_step_get_tick on the one-wave path: the packed read-back of csf_get_tick, written by the kernel behind its last
                        // tick (a mapped host buffer), else NULL
@@ -308,6 +312,18 @@ void launch_records(const Dev &d, hipStream_t st);  // rebuild fp32 records from
 // csf_get_tick: row-major state [n, ns], Fx [n], Fy [n] (doubles), destination pointers [n] (int32), navigation state
 // one-hot [n, 3] (bytes), packed behind each other in `out` (host-mapped)
 void launch_snapshot(const Dev &d, double *out, hipStream_t st);
+// csf_get_record, csf_batch_get_record, csf_get_history: samples of the rings of many engines, un-wrapped and packed into one
+// buffer.  One descriptor per engine (read by the kernel from mapped host memory: they change with every call); every offset and
+// every row of 16-byte accesses is even in doubles, where a row of doubles is odd (5 states, an odd population) they are single
+struct RecDesc {
+    const double *s;       // state ring [cap][n][ns], NULL: states not asked for
+    const double *F;       // force ring [cap][n][2], NULL: forces not asked for
+    int64_t s_off, F_off;  // where the member's samples go in the output, in doubles (both even)
+    int32_t n, ns, cap;    // road users, states of each, samples the rings hold
+    int32_t first, count;  // ring slot of the first sample asked for, samples asked for
+    int32_t pad;
+};
+void launch_record_gather(const RecDesc *desc, int members, int64_t most_doubles, double *out, hipStream_t st);
 // csf_bin.hip: spatial binning of the source records (Hilbert order) and per-batch bounding circles
 size_t bin_temp_bytes(int64_t n_pad);
 // class-segmented order: the runs of equal parameter set in the sorted order moved to batch-aligned places (csf_bin.hip)

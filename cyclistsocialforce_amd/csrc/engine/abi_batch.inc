@@ -6,8 +6,10 @@
 // (small_fused_ok) are stepped by small_batch_kernel instead - one launch per vehicle class present, workgroup b ticking the scene
 // of table[b] - and every other member by step_impl in turn.  The table holds the members' Dev records in device memory; it is
 // renewed in stream order, and only where a member's Dev changed since it was last copied (a host shadow, memcmp).  Per-call
-// values stay out of it: Dev::tick is read only by the history ring, which the one-wave tick excludes, and whether the read-back is
-// packed is a kernel argument.
+// values stay out of it: whether the read-back is packed is a kernel argument, and Dev::tick - what the samples of a recording
+// (csf_record) are numbered from - is 0 in the table: a recording member's count is a word of its own in device memory
+// (Dev::rec_tick) that the launch reads and moves on itself.  The host knows what the word holds (csf_engine::rec_tick_dev) and
+// writes it in stream order only where the engine has ticked outside the batched launch since.
 
 extern "C++" {
 
@@ -25,11 +27,14 @@ struct BatchState {
     std::vector<uint8_t> snapped;                // per member: its read-back is in its mapped snapshot buffer (1: packed by the
                                                  // batched launch, 2: by its own one-wave launch), 0: not
     std::vector<int32_t> slot_member;            // table slot -> member
+    RecGather rgather;                           // csf_batch_get_record
+    std::vector<RecAsk> asks;
     ~BatchState() {
         (void)hipSetDevice(device);
         if (copy_pending && copied) (void)hipEventSynchronize(copied);
         if (copied) (void)hipEventDestroy(copied);
         if (stage) (void)hipHostFree(stage);
+        rgather.release();
         table.release();
     }
 };
@@ -89,7 +94,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
         const csf_engine *e = b.members[(size_t)b.slot_member[j]];
         Dev dd;
         std::memcpy((void *)&dd, (const void *)&e->d, sizeof(Dev));
-        dd.tick = 0;                                              // (per call; read only by the history ring)
+        dd.tick = 0;                                              // (per call; a recording counts in Dev::rec_tick)
         dd.snap = (e->d.order == nullptr && e->snap_dev != nullptr && e->snap_bytes >= snap_need(e)) ? e->snap_dev : nullptr;
         const bool same = b.held[j] && std::memcmp((const void *)&b.shadow[j], (const void *)&dd, sizeof(Dev)) == 0;
         if (same) {
@@ -167,6 +172,13 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
         }
         cls_beg[7] = (int)b.slot_member.size();
         if ((rc = batch_table(b, e0->main))) return rc;
+        for (int32_t i : b.small) {                               // a recording member's tick word, where it is not current
+            csf_engine *e = engines[i];
+            if (e->d.rec_tick == nullptr || e->rec_tick_dev == e->d.tick) continue;
+            HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)e->d.rec_tick, (int)(uint32_t)((uint64_t)e->d.tick & 0xffffffffu), 1, e0->main));
+            HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)e->d.rec_tick + 1), (int)(uint32_t)((uint64_t)e->d.tick >> 32), 1, e0->main));
+            e->rec_tick_dev = e->d.tick;
+        }
         for (int64_t t = 0; t < n_ticks;) {                       // (launches of at most 2^16 ticks, as csf_step's)
             const int k = (int)std::min<int64_t>(n_ticks - t, 65536);
             const bool pack = want_snap && t + k == n_ticks;
@@ -183,6 +195,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
                 e->moves += k;
                 e->small_ticks += k;
                 e->batch_ticks += k;
+                if (e->d.rec_tick != nullptr) e->rec_tick_dev = e->d.tick;
             }
             t += k;
         }
@@ -256,6 +269,34 @@ int csf_step_batch(csf_engine *const *engines, int32_t count, int64_t n_ticks) t
 int csf_step_batch_get_tick(csf_engine *const *engines, int32_t count, int64_t n_ticks, const csf_tick_out *out) try {
     if (!out) return engines && count > 0 && engines[0] ? fail(engines[0], CSF_E_ARG, "csf_step_batch_get_tick: out is NULL") : CSF_E_ARG;
     return step_batch_impl(engines, count, n_ticks, out);
+} catch (...) { return csf_caught((engines && count > 0 ? engines[0] : nullptr)); }
+
+int csf_batch_get_record(csf_engine *const *engines, int32_t count, int64_t n_last, const csf_record_out *out) try {
+    int rc = batch_check(engines, count);
+    if (rc) return rc;
+    csf_engine *e0 = engines[0];
+    if (!out) return fail(e0, CSF_E_ARG, "csf_batch_get_record: out is NULL");
+    if (n_last < 0) return fail(e0, CSF_E_ARG, "csf_batch_get_record: n_last must be >= 0");
+    BatchState &b = *e0->batch;
+    b.asks.clear();
+    for (int32_t i = 0; i < count; i++) {        // every refusal before anything is written
+        csf_engine *e = engines[i];
+        const csf_record_out &o = out[i];
+        if (!o.s && !o.F) continue;
+        if (!e->d.hist) return fail(e, CSF_E_STATE, "member %d: history is not enabled (csf_record)", (int)i);
+        if (o.F && !e->d.hist_F) return fail(e, CSF_E_STATE, "member %d: forces are not recorded (csf_record with CSF_REC_FORCE)", (int)i);
+        const int64_t have = e->d.tick / e->d.hist_stride;
+        if (n_last > have || n_last > e->d.hist_cap)
+            return fail(e, CSF_E_ARG, "member %d: the last %lld samples are not in the ring (have %lld, capacity %d)", (int)i, (long long)n_last,
+                        (long long)have, e->d.hist_cap);
+        b.asks.push_back(RecAsk{e, have - n_last, n_last, o.s, o.F});
+    }
+    HIPCHK(e0, hipSetDevice(e0->device));
+    // (the members share one stream, and a member stepped in turn has joined its second stream back into it: stream order is enough)
+    if ((rc = record_gather(e0, b.rgather, e0->main, b.asks.data(), b.asks.size()))) return rc;
+    for (int32_t i = 0; i < count; i++)
+        if ((out[i].s || out[i].F) && out[i].first_sample) *out[i].first_sample = engines[i]->d.tick / engines[i]->d.hist_stride - n_last;
+    return CSF_OK;
 } catch (...) { return csf_caught((engines && count > 0 ? engines[0] : nullptr)); }
 
 int csf_batch_ticks(const csf_engine *e, int64_t *n_ticks) try {

@@ -86,6 +86,7 @@ int csf_replay_forces(csf_engine *e, int64_t n_ticks, const double *Fx, const do
     dd.F_rows = 2;                       // (the view holds Fx, Fy of one tick: the kernel clamps its row index - csf_dev.h)
     dd.replay_len = lengths ? lbuf.p : nullptr;
     dd.hist = (states_out && n_samples > 0) ? hbuf.p : nullptr;
+    dd.hist_F = nullptr;                 // (the engine's own recording does not see the replay)
     dd.hist_stride = stride;
     dd.hist_cap = (int32_t)std::max<int64_t>(n_samples, 1);
     std::vector<double> host((size_t)chunk * 2 * (size_t)cap, 0.0);
@@ -256,36 +257,131 @@ int csf_status(csf_engine *e, uint32_t *per_agent_flags) try {
     return rc;
 } catch (...) { return csf_caught(e); }
 
-int csf_enable_history(csf_engine *e, int32_t stride, int32_t capacity) try {
-    if (!e) return CSF_E_ARG;
-    if (stride < 1 || capacity < 1) return fail(e, CSF_E_ARG, "stride and capacity must be >= 1");
+// (re)allocates the rings; everything that can fail first, then the old rings go: a refused call changes nothing
+static int rings_setup(csf_engine *e, int32_t stride, int32_t capacity, bool forces, bool fast) {
     HIPCHK(e, hipSetDevice(e->device));
     int rc = csf_sync(e);
     if (rc) return rc;
     if ((rc = ensure_compact(e))) return rc;              // the ring is indexed by road user: slots == population order
-    HIPCHK(e, e->hist.alloc((size_t)capacity * (size_t)e->cap * (size_t)e->d.ns));
+    DevBuf<double> hs, hf;
+    DevBuf<int64_t> tk;
+    const size_t rows = (size_t)capacity * (size_t)e->cap;
+    hipError_t r = hs.alloc(rows * (size_t)e->d.ns);
+    if (r == hipSuccess && forces) r = hf.alloc(rows * 2);
+    if (r == hipSuccess && fast) r = tk.alloc(1);
+    if (r != hipSuccess) {
+        hs.release(); hf.release(); tk.release();
+        return fail(e, CSF_E_DEVICE, "no device memory for a ring of %d samples: %s", (int)capacity, hipGetErrorString(r));
+    }
+    std::swap(e->hist, hs); std::swap(e->hist_F, hf); std::swap(e->rec_tick, tk);
+    hs.release(); hf.release(); tk.release();
     e->d.hist = e->hist.p;
+    e->d.hist_F = e->hist_F.p;
+    e->d.rec_tick = e->rec_tick.p;
     e->d.hist_stride = stride;
     e->d.hist_cap = capacity;
+    e->rec_tick_dev = -1;
+    e->rec_fast = fast;
     return CSF_OK;
+}
+
+int csf_enable_history(csf_engine *e, int32_t stride, int32_t capacity) try {
+    if (!e) return CSF_E_ARG;
+    if (stride < 1 || capacity < 1) return fail(e, CSF_E_ARG, "stride and capacity must be >= 1");
+    return rings_setup(e, stride, capacity, false, false);
 } catch (...) { return csf_caught(e); }
+
+int csf_record(csf_engine *e, int32_t stride, int32_t capacity, uint32_t what) try {
+    if (!e) return CSF_E_ARG;
+    if (stride < 1 || capacity < 1) return fail(e, CSF_E_ARG, "stride and capacity must be >= 1");
+    if (what == 0 || (what & ~(CSF_REC_STATE | CSF_REC_FORCE)) != 0)
+        return fail(e, CSF_E_ARG, "csf_record: what must be CSF_REC_STATE, CSF_REC_FORCE or both (got 0x%x)", (unsigned)what);
+    return rings_setup(e, stride, capacity, (what & CSF_REC_FORCE) != 0, true);
+} catch (...) { return csf_caught(e); }
+
+extern "C++" {
+
+// samples [first, first + count) of one engine's rings, for the caller's arrays (either may be NULL)
+struct RecAsk {
+    csf_engine *e;
+    int64_t first, count;
+    double *s_out, *F_out;
+};
+
+// samples [first, first + count) are in the ring: the message of csf_get_history
+static int record_range(csf_engine *e, int64_t first, int64_t count) {
+    const int64_t have = e->d.tick / e->d.hist_stride;
+    if (first < 0 || count < 0 || first + count > have || have - first > e->d.hist_cap)
+        return fail(e, CSF_E_ARG, "samples [%lld, %lld) are not in the ring (have %lld, capacity %d)",
+                    (long long)first, (long long)(first + count), (long long)have, e->d.hist_cap);
+    return CSF_OK;
+}
+
+// One gather launch on `st` (the stream every engine asked about works on), one wait, then the packed buffer -> the callers' arrays.
+// The asks have been checked (record_range; rings present where an output is given).
+static int record_gather(csf_engine *e0, RecGather &g, hipStream_t st, const RecAsk *asks, size_t m) {
+    if (m == 0) return CSF_OK;
+    if (m > 65535) return fail(e0, CSF_E_ARG, "at most 65535 engines in one read-back of rings (%zu given)", m);
+    size_t total = 0;
+    int64_t most = 0;
+    for (size_t i = 0; i < m; i++) {
+        const RecAsk &a = asks[i];
+        const size_t n = (size_t)a.e->d.n, ns = (size_t)a.e->d.ns, c = (size_t)a.count;
+        if (a.s_out) total += (c * n * ns + 1) & ~(size_t)1, most = std::max<int64_t>(most, (int64_t)(c * n * ns));
+        if (a.F_out) total += c * n * 2, most = std::max<int64_t>(most, (int64_t)(c * n * 2));
+    }
+    if (total == 0) return CSF_OK;
+    HIPCHK(e0, g.reserve(m, total, st));
+    size_t at = 0;
+    for (size_t i = 0; i < m; i++) {
+        const RecAsk &a = asks[i];
+        const Dev &d = a.e->d;
+        const size_t n = (size_t)d.n, ns = (size_t)d.ns, c = (size_t)a.count;
+        RecDesc r{};
+        r.n = (int32_t)d.n, r.ns = d.ns, r.cap = d.hist_cap;
+        r.first = (int32_t)(a.first % d.hist_cap), r.count = (int32_t)a.count;
+        if (a.s_out && c * n > 0) r.s = d.hist, r.s_off = (int64_t)at, at += (c * n * ns + 1) & ~(size_t)1;
+        if (a.F_out && c * n > 0) r.F = d.hist_F, r.F_off = (int64_t)at, at += c * n * 2;
+        g.desc[i] = r;
+    }
+    launch_record_gather(g.desc_dev, (int)m, most, g.out_dev, st);
+    HIPCHK(e0, hipGetLastError());
+    HIPCHK(e0, hipStreamSynchronize(st));
+    for (size_t i = 0; i < m; i++) {
+        const RecAsk &a = asks[i];
+        const RecDesc &r = g.desc[i];
+        const size_t n = (size_t)r.n, c = (size_t)r.count;
+        if (r.s) std::memcpy(a.s_out, g.out + r.s_off, c * n * (size_t)r.ns * sizeof(double));
+        if (r.F) std::memcpy(a.F_out, g.out + r.F_off, c * n * 2 * sizeof(double));
+    }
+    return CSF_OK;
+}
+
+}  // extern "C++"
 
 int csf_get_history(csf_engine *e, int64_t first_sample, int64_t n_samples, double *out) try {
     if (!e) return CSF_E_ARG;
     if (!e->d.hist) return fail(e, CSF_E_STATE, "history is not enabled");
     if (!out || first_sample < 0 || n_samples < 0) return fail(e, CSF_E_ARG, "csf_get_history: bad arguments");
+    HIPCHK(e, hipSetDevice(e->device));
     int rc = csf_sync(e);
     if (rc) return rc;
-    const int64_t have = e->d.tick / e->d.hist_stride;
-    if (first_sample + n_samples > have || have - first_sample > e->d.hist_cap)
-        return fail(e, CSF_E_ARG, "samples [%lld, %lld) are not in the ring (have %lld, capacity %d)",
-                    (long long)first_sample, (long long)(first_sample + n_samples), (long long)have, e->d.hist_cap);
-    const size_t row = (size_t)e->d.n * (size_t)e->d.ns;
-    for (int64_t k = 0; k < n_samples; k++) {
-        int64_t slot = (first_sample + k) % e->d.hist_cap;
-        HIPCHK(e, hipMemcpy(out + (size_t)k * row, e->hist.p + (size_t)slot * row, row * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return CSF_OK;
+    if ((rc = record_range(e, first_sample, n_samples))) return rc;
+    const RecAsk ask{e, first_sample, n_samples, out, nullptr};
+    return record_gather(e, e->rgather, e->main, &ask, 1);
+} catch (...) { return csf_caught(e); }
+
+int csf_get_record(csf_engine *e, int64_t first_sample, int64_t n_samples, double *s_out, double *F_out) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->d.hist) return fail(e, CSF_E_STATE, "history is not enabled (csf_record)");
+    if ((!s_out && !F_out) || first_sample < 0 || n_samples < 0) return fail(e, CSF_E_ARG, "csf_get_record: bad arguments");
+    if (F_out && !e->d.hist_F) return fail(e, CSF_E_STATE, "forces are not recorded (csf_record with CSF_REC_FORCE)");
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = csf_sync(e);
+    if (rc) return rc;
+    if ((rc = record_range(e, first_sample, n_samples))) return rc;
+    const RecAsk ask{e, first_sample, n_samples, s_out, F_out};
+    return record_gather(e, e->rgather, e->main, &ask, 1);
 } catch (...) { return csf_caught(e); }
 
 int csf_pair_force(csf_engine *e, const double *src, int64_t m, const double *x, const double *y,

@@ -200,6 +200,43 @@ struct Knobs {
 
 }  // namespace
 
+// What the ring read-backs keep across calls (csf_get_record, csf_get_history: one per engine; csf_batch_get_record: one per
+// batch), grown geometrically like the packed snapshot's buffer: the descriptors the gather kernel reads and the buffer it packs
+// the samples into, both mapped host memory - the kernel's stores ARE the transfer, and the host waits once.
+struct RecGather {
+    RecDesc *desc = nullptr, *desc_dev = nullptr;
+    size_t desc_n = 0;
+    double *out = nullptr, *out_dev = nullptr;
+    size_t out_n = 0;               // doubles
+    hipError_t reserve(size_t members, size_t doubles, hipStream_t st) {
+        hipError_t r = hipSuccess;
+        if (members > desc_n) {
+            if (desc && (r = hipStreamSynchronize(st)) != hipSuccess) return r;
+            if (desc) (void)hipHostFree(desc);
+            desc = desc_dev = nullptr, desc_n = 0;
+            const size_t want = std::max<size_t>(2 * members, 16);
+            if ((r = hipHostMalloc((void **)&desc, want * sizeof(RecDesc), hipHostMallocMapped)) != hipSuccess) return r;
+            if ((r = hipHostGetDevicePointer((void **)&desc_dev, desc, 0)) != hipSuccess) return r;
+            desc_n = want;
+        }
+        if (doubles > out_n) {
+            if (out && (r = hipStreamSynchronize(st)) != hipSuccess) return r;
+            if (out) (void)hipHostFree(out);
+            out = out_dev = nullptr, out_n = 0;
+            const size_t want = std::max<size_t>(2 * doubles, 4096);
+            if ((r = hipHostMalloc((void **)&out, want * sizeof(double), hipHostMallocMapped)) != hipSuccess) return r;
+            if ((r = hipHostGetDevicePointer((void **)&out_dev, out, 0)) != hipSuccess) return r;
+            out_n = want;
+        }
+        return r;
+    }
+    void release() {
+        if (desc) (void)hipHostFree(desc);
+        if (out) (void)hipHostFree(out);
+        desc = desc_dev = nullptr, out = out_dev = nullptr, desc_n = out_n = 0;
+    }
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -318,6 +355,14 @@ struct csf_engine {
     bool device_ahead = false;             // ticks ran since the last download
 
     DevBuf<double> s, vdes, q, znp, hx, hy, lti, ppsi, F, hist;
+    // csf_record: the force ring beside `hist`, the tick counter the batched launch numbers its samples from (csf_dev.h:
+    // Dev::rec_tick) and the value that word holds once everything enqueued has run (-1: unknown, written before the next
+    // batched launch); rec_fast: this recording keeps the one-wave tick and the batched launch (csf_enable_history's does not)
+    DevBuf<double> hist_F;
+    DevBuf<int64_t> rec_tick;
+    int64_t rec_tick_dev = -1;
+    bool rec_fast = false;
+    RecGather rgather;
     DevBuf<int64_t> qbeg;
     DevBuf<int32_t> ptr, ti, dgood, qlen, order_dev;
     DevBuf<uint8_t> znav, zrid, alive;

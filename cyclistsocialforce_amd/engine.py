@@ -324,6 +324,58 @@ class Engine:
         self._ck(self._lib.csf_get_history(self._h, int(first), int(count), _ptr(out)))
         return out
 
+    def record(self, stride=1, capacity=3000, forces=True):
+        """csf_record: every `stride`-th tick's state - and total force - into device rings of `capacity` samples, written by
+        whatever kernel ticks the engine: unlike enable_history it keeps the one-wave tick and the batched launch."""
+        what = _ffi.REC_STATE | (_ffi.REC_FORCE if forces else 0)
+        self._ck(self._lib.csf_record(self._h, int(stride), int(capacity), what))
+        self._rec_forces = bool(forces)
+
+    def recorded(self, first, count):
+        """samples [first, first + count) of the recording: (S [count, n, n_states], F [count, n, 2] or None) - sample k is the
+        state after tick (k + 1) * stride and the total force of that tick; one gather launch and one wait (csf_get_record)"""
+        n = self.n
+        S = np.zeros((int(count), n, self.ns))
+        F = np.zeros((int(count), n, 2)) if getattr(self, "_rec_forces", False) else None
+        self._ck(self._lib.csf_get_record(self._h, int(first), int(count), _ptr(S), None if F is None else _ptr(F)))
+        return S, F
+
+    @staticmethod
+    def batch_recorded(engines, n_last, only=None):
+        """the last n_last samples of every recording member of a batch (the engines in join order): a list of (S, F, first) -
+        S [n_last, n, n_states], F [n_last, n, 2] (None without a force ring), first the index of S[0] - and None for members
+        that do not record (or are not in `only`, a collection of members to read).  One gather launch, one transfer and one wait
+        for the whole batch (csf_batch_get_record).  The arrays are the caller's: new ones whenever the set of engines, their
+        populations or n_last changed, else the previous call's, overwritten - the csf_record_out array is kept with them."""
+        engines, arr = Engine._batch_array(engines, "batch_recorded")
+        n_last = int(n_last)
+        if n_last < 0:
+            raise ValueError("batch_recorded: n_last must be >= 0")
+        pick = None if only is None else {id(e) for e in only}
+        key = (tuple(id(e) for e in engines), tuple(e.n for e in engines), n_last, None if pick is None else tuple(sorted(pick)))
+        cache = getattr(engines[0], "_rec_cache", None)
+        if cache is None or cache[0] != key:
+            outs = (_ffi.RecordOut * len(engines))()
+            firsts = (C.c_int64 * len(engines))()
+            res = []
+            for i, e in enumerate(engines):
+                if not hasattr(e, "_rec_forces") or (pick is not None and id(e) not in pick):
+                    res.append(None)
+                    continue
+                S = np.zeros((n_last, e.n, e.ns))
+                F = np.zeros((n_last, e.n, 2)) if e._rec_forces else None
+                outs[i].s = S.ctypes.data
+                outs[i].F = None if F is None else F.ctypes.data
+                outs[i].first_sample = C.cast(C.byref(firsts, i * C.sizeof(C.c_int64)), C.POINTER(C.c_int64))
+                res.append((S, F))
+            cache = engines[0]._rec_cache = (key, arr, outs, firsts, res)
+        _, arr, outs, firsts, res = cache
+        lib = _ffi.load()
+        rc = lib.csf_batch_get_record(arr, len(engines), n_last, outs)
+        if rc != 0:
+            Engine._batch_raise(lib, rc, engines)
+        return [None if r is None else (r[0], r[1], firsts[i]) for i, r in enumerate(res)]
+
     def pair_force(self, src, x, y, psi, apply_fov=False):
         src = _f64(src).reshape(4)
         x = _f64(x); y = _f64(y); psi = _f64(psi)

@@ -671,6 +671,45 @@ class SocialForceIntersection:
             self._pos_stale = True
         return fx, fy
 
+    def _book_block(self, S, F):
+        """_book_pull(fx, fy, True, 1) behind each of K consecutive ticks at once, from their recorded states S [K, n, n_states] and
+        total forces F [K, n, 2] (Engine.recorded / batch_recorded): the trajectory ring, trajF, the force log and vehicle.i move
+        as K read-backs would have moved them.  K may exceed the ring: only the last rows survive, as with K single ticks.  (The
+        bulk mirror itself - _S, _ptr, _zn, _fx, _fy - holds the last tick's values already; drawings and SUMO want every tick on
+        the host and do not come here: _dense_engine.)"""
+        n = len(self.vehicles)
+        K = int(S.shape[0])
+        if K == 0:
+            return
+        self._have_force = True
+        mag = F[:, :, 0] * F[:, :, 0]                                 # (_log_forces, tick by tick: the same two roundings and the root)
+        mag += F[:, :, 1] * F[:, :, 1]
+        np.sqrt(mag, out=mag)
+        for k in range(K):
+            self._flog.append(mag[k])
+            if len(self._flog) >= 4096:
+                self._fold_all_force_logs()
+        T = self._traj.shape[0]
+        k0 = max(0, K - T)                                            # (ticks before it are overwritten by later ones)
+        ti0 = self._ti[:n].copy()
+        steps = np.arange(k0 + 1, K + 1)
+        w = S.shape[2]
+        if n and (ti0 == ti0[0]).all():
+            self._traj[(ti0[0] + steps) % T, :n, :w] = S[k0:]         # the usual case: everyone joined at tick 0
+        elif n:
+            self._traj[(ti0[None, :] + steps[:, None]) % T, np.arange(n)[None, :], :w] = S[k0:]
+        self._ti[:n] = (ti0 + K) % T                                  # vehicle.py:1279-1282 (see DESIGN D5)
+        if self._drawn_stale:
+            self._drawn = [v for v in self.vehicles if v.drawing is not None or v.saveForces]
+            self._drawn_stale = False
+        for v in self._drawn:
+            if v.saveForces:
+                k = v._index
+                cols = (ti0[k] + steps) % T
+                v.trajF[0, cols] = F[k0:, k, 0]
+                v.trajF[1, cols] = F[k0:, k, 1]
+        self._pos_stale = True
+
     # vehicle.F: the per-tick magnitudes are logged as arrays and folded into a vehicle's list when it is read
     def _log_forces(self, fx, fy):
         mag = fx * fx                                                 # (np.hypot is three times the time of this at N = 16 384)
@@ -858,9 +897,45 @@ class SocialForceIntersection:
             self._pull(forces=True, advance=1, step=1)
         self.hist_n_vecs.append(self.n_bikes)
 
-    def step_n(self, n_ticks, pull=True):
-        """n_ticks ticks with no per-tick host work (the benchmark path).  `traj` receives only the final
-        state; enable the engine's device-side history for dense trajectories."""
+    def _dense_engine(self):
+        """the engine, recording (Engine.record: it keeps the one-wave tick and the batched launch), when n ticks of this
+        intersection can run in one call and be booked from the record afterwards; None when every tick has to pass the host:
+        empty, custom force hooks, drawn poles, drawings or `animate`, SUMO co-simulation, a mirror wider than the engine's state"""
+        if self.n_bikes <= 0 or self._hooked or self.animate or self.activate_sumo_cosimulation or self._stochastic_riders():
+            return None
+        if any(v.drawing is not None for v in self.vehicles):
+            return None
+        e = self._push_mutations()
+        if self._S.shape[1] != e.ns:
+            return None
+        if getattr(e, "_dense_for", None) != e.n:                     # (a new engine, or road users came or went: a ring of this layout)
+            e.record(stride=1, capacity=DENSE_CHUNK, forces=True)
+            e._dense_for = e.n
+        return e
+
+    def step_n(self, n_ticks, pull=True, dense=False):
+        """n_ticks ticks with no per-tick host work (the benchmark path).  `traj` receives only the final state, unless
+        `dense`: then the engine records every tick on the device (Engine.record), the ticks run in calls as long as its ring,
+        and vehicle.s, traj, trajF, F, znav, destpointer and hist_n_vecs are afterwards what n_ticks calls of step() leave."""
+        if dense:
+            left = int(n_ticks)
+            while left > 0:
+                e = self._dense_engine()
+                if e is None:
+                    self.step()
+                    left -= 1
+                    continue
+                k = min(left, DENSE_CHUNK)
+                n = len(self.vehicles)
+                tick = e.step_into(k, self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n])
+                S, F = e.recorded(tick - k, k)
+                self.is_first_step = False
+                if self._s_watched:
+                    self._shadow[:n] = self._S[:n]
+                self._book_block(S, F)
+                self.hist_n_vecs.extend([self.n_bikes] * k)
+                left -= k
+            return
         if self.n_bikes > 0 and (self._hooked or self._stochastic_riders()):   # (custom force hooks, drawn poles: every tick passes the host)
             for _ in range(int(n_ticks)):
                 self.step()
@@ -913,6 +988,47 @@ def _batch_of(engines):
     Engine.batch_join(engines)
     for e in engines:
         e._together = list(engines)
+
+
+DENSE_CHUNK = 512        # ticks per call of the dense paths = samples of the engines' rings (the bytes per member)
+
+
+def advance_together(intersections, n_ticks):
+    """step_together(intersections, n_ticks) - the same vehicle.s, traj, trajF, F, znav, destpointer, hist_n_vecs - with the
+    ticks in calls of up to DENSE_CHUNK: the engines record every tick on the device (Engine.record), a chunk is one
+    csf_step_batch_get_tick (one launch per vehicle class) and one csf_batch_get_record (one gather, one transfer, one wait), and
+    the host books the whole block at once (_book_block) - instead of a call, a wait and the host's bookkeeping per tick.
+    Intersections that need the host every tick (custom force hooks, stochastic riders, drawings or `animate`, SUMO
+    co-simulation) and empty ones take step_together's route inside the same call."""
+    intersections = list(intersections)
+    left = int(n_ticks)
+    while left > 0:
+        k = min(left, DENSE_CHUNK)
+        dense, rest = [], []
+        for ins in intersections:
+            e = ins._dense_engine()
+            if e is None:
+                rest.append(ins)
+            else:
+                dense.append((ins, e))
+        if rest:
+            step_together(rest, k)
+        if dense:
+            engines = [e for _, e in dense]
+            _batch_of(engines)
+            outs = []
+            for ins, _ in dense:
+                n = len(ins.vehicles)
+                outs.append((ins._S[:n], ins._ptr[:n], ins._zn[:n], ins._fx[:n], ins._fy[:n]))
+            Engine.step_batch_into(engines, k, outs)
+            for (ins, _), (S, F, _) in zip(dense, Engine.batch_recorded(engines, k)):
+                n = len(ins.vehicles)
+                ins.is_first_step = False
+                if ins._s_watched:
+                    ins._shadow[:n] = ins._S[:n]
+                ins._book_block(S, F)
+                ins.hist_n_vecs.extend([ins.n_bikes] * k)
+        left -= k
 
 
 def step_together(intersections, n_ticks=1):

@@ -234,6 +234,18 @@ int csf_status(csf_engine *e, uint32_t *per_agent_flags);
  * after tick (k+1)*stride) of all agents into out [n_samples, n_agents, n_states]. */
 int csf_enable_history(csf_engine *e, int32_t stride, int32_t capacity);
 int csf_get_history(csf_engine *e, int64_t first_sample, int64_t n_samples, double *out);
+/* An engine with csf_enable_history is ticked by the general path (two launches per tick, or one for a mid-size population), and
+ * inside a batch by csf_step in turn.  csf_record is the recording that keeps the fast paths: the same state ring (same layout,
+ * same sample numbering, csf_get_history reads it) and, with CSF_REC_FORCE, a second ring [capacity][n_agents][2] of the total
+ * force (Fx, Fy as csf_get_forces returns them after the sampled tick) - written by whatever kernel ticks the engine, the
+ * one-wave kernel and the batched launch of csf_step_batch included (see csf_small_ticks).  The state ring is always kept.
+ * Calling either again starts a new ring; the later call decides which path the engine takes.
+ * csf_get_record: samples [first_sample, first_sample + n_samples) as s_out [n_samples, n_agents, n_states] and F_out
+ * [n_samples, n_agents, 2]; one of the two may be NULL.  One gather launch and one wait, whatever n_samples is. */
+#define CSF_REC_STATE 1u
+#define CSF_REC_FORCE 2u
+int csf_record(csf_engine *e, int32_t stride, int32_t capacity, uint32_t what);
+int csf_get_record(csf_engine *e, int64_t first_sample, int64_t n_samples, double *s_out, double *F_out);
 
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
@@ -310,6 +322,17 @@ typedef struct csf_tick_out {
 /* csf_step_batch, then the csf_get_tick outputs of every member (out[count]): the batched launch packs the read-back of its
  * members behind their last tick, and the host waits once for all of them. */
 int csf_step_batch_get_tick(csf_engine *const *engines, int32_t count, int64_t n_ticks, const csf_tick_out *out);
+/* The last n_last samples of every member of a batch (in join order) whose out[i] names an output: s [n_last, n_agents, n_states],
+ * F [n_last, n_agents, 2] (either may be NULL; both NULL: the member is left out), first_sample (may be NULL) receives the index
+ * of the first sample returned.  A named member without a recording (csf_record; csf_enable_history for states), or with
+ * fewer than n_last samples in its ring, makes the call a refusal before anything is written.  One gather launch, one transfer
+ * and one wait for the whole batch. */
+typedef struct csf_record_out {
+    double *s;
+    double *F;
+    int64_t *first_sample;
+} csf_record_out;
+int csf_batch_get_record(csf_engine *const *engines, int32_t count, int64_t n_last, const csf_record_out *out);
 /* ticks this engine has run inside a batched launch (csf_small_ticks counts them too) */
 int csf_batch_ticks(const csf_engine *e, int64_t *n_ticks);
 
@@ -359,7 +382,7 @@ int csf_comm_stream_order(const csf_engine *e, int32_t *second_stream, double us
  * of the last csf_profile_read (0 for an unsharded engine) */
 int csf_profile_gather(const csf_engine *e, double *gather_ms);
 /* Ticks this engine has run in its one-wave kernel (ABI 6).  Up to 32 road users of one parameter set (any rider class; not
- * UncontrolledVehicle) - the reference's own scenarios, e.g. the three cyclists of scenarios/ - on one device, with no road or a small one (at most 2048 vertices), without history ring or profiling: csf_step(e, n) is then ONE
+ * UncontrolledVehicle) - the reference's own scenarios, e.g. the three cyclists of scenarios/ - on one device, with no road or a small one (at most 2048 vertices), without profiling and without the history ring of csf_enable_history (a recording by csf_record keeps this path): csf_step(e, n) is then ONE
  * launch of one wave for all n ticks (lane = road user; field-of-view decisions and np.sign(phi) on the fp64 difference of
  * the two positions, inside the band of fp32 rounding by the reference's own fp64 chain, intersection.py:690-745,
  * vehicle.py:1617-1625), instead of a pair launch and a per-agent launch per tick.  CSF_FUSED_SMALL=0 or a pinned CSF_PAIR_VARIANT keep the general path. */
