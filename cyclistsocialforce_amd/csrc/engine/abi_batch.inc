@@ -17,7 +17,7 @@ struct BatchState {
     int device = 0;
     std::vector<csf_engine *> members;           // join order
     DevBuf<Dev> table;                           // the one-wave members' Dev records, grouped by vehicle class
-    Dev *stage = nullptr;                        // pinned: what the copies into `table` read
+    HostBuf<Dev, false> stage;                   // what the copies into `table` read
     std::vector<Dev> shadow;                     // what `table` holds, slot by slot (valid where `held`)
     std::vector<uint8_t> held;
     hipEvent_t copied = nullptr;                 // recorded behind the last copy from `stage`
@@ -29,20 +29,12 @@ struct BatchState {
     std::vector<int32_t> slot_member;            // table slot -> member
     RecGather rgather;                           // csf_batch_get_record
     std::vector<RecAsk> asks;
-    ~BatchState() {
+    ~BatchState() {   // (the last copy from `stage` has ended before the members below go, `stage` among them)
         (void)hipSetDevice(device);
         if (copy_pending && copied) (void)hipEventSynchronize(copied);
         if (copied) (void)hipEventDestroy(copied);
-        if (stage) (void)hipHostFree(stage);
-        rgather.release();
-        table.release();
     }
 };
-
-// the bytes of a member's packed read-back (csf_get_tick: state rows, Fx, Fy, destination pointers, one-hot navigation state)
-static size_t snap_need(const csf_engine *e) {
-    return e->order.size() * ((size_t)(e->d.ns + 2) * sizeof(double) + sizeof(int32_t) + 3);
-}
 
 // Every member goes back to its own stream, and the batch's table, staging and event go with the last reference to it.
 static int batch_dissolve(csf_engine *e) {
@@ -84,7 +76,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
     bool waited = false;
     auto flush = [&](size_t end) -> int {
         if (end > run0) {
-            HIPCHK(b.members[0], hipMemcpyAsync(b.table.p + run0, b.stage + run0, (end - run0) * sizeof(Dev), hipMemcpyHostToDevice, st));
+            HIPCHK(b.members[0], hipMemcpyAsync(b.table.p + run0, b.stage.p + run0, (end - run0) * sizeof(Dev), hipMemcpyHostToDevice, st));
             runs++;
         }
         return CSF_OK;
@@ -95,7 +87,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
         Dev dd;
         std::memcpy((void *)&dd, (const void *)&e->d, sizeof(Dev));
         dd.tick = 0;                                              // (per call; a recording counts in Dev::rec_tick)
-        dd.snap = (e->d.order == nullptr && e->snap_dev != nullptr && e->snap_bytes >= snap_need(e)) ? e->snap_dev : nullptr;
+        dd.snap = (e->d.order == nullptr && e->snap.dev != nullptr && e->snap.n >= snap_need(e)) ? (double *)e->snap.dev : nullptr;
         const bool same = b.held[j] && std::memcmp((const void *)&b.shadow[j], (const void *)&dd, sizeof(Dev)) == 0;
         if (same) {
             if (in_run) {
@@ -110,7 +102,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
             b.copy_pending = false;
         }
         waited = true;
-        std::memcpy((void *)&b.stage[j], (const void *)&dd, sizeof(Dev));
+        std::memcpy((void *)&b.stage.p[j], (const void *)&dd, sizeof(Dev));
         std::memcpy((void *)&b.shadow[j], (const void *)&dd, sizeof(Dev));
         b.held[j] = 1;
         if (!in_run) run0 = j, in_run = true;
@@ -137,7 +129,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
     b.small.clear();
     b.rest.clear();
     b.snapped.assign((size_t)count, 0);
-    // per member, what step_impl does in front of its one-wave launch; the others are stepped by step_impl itself
+    // the members the one-wave launch takes get step_impl's prelude; the others are stepped by step_impl itself
     for (int32_t i = 0; i < count; i++) {
         csf_engine *e = engines[i];
         if ((rc = upload_all(e))) return rc;
@@ -150,11 +142,9 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
             b.rest.push_back(i);
             continue;
         }
-        if ((rc = set_fov_band(e))) return rc;
-        if (want_snap) {
-            if ((rc = sync_order(e))) return rc;
-            b.snapped[(size_t)i] = e->d.order == nullptr && snap_reserve(e, snap_need(e)) == CSF_OK;
-        }
+        bool pack = false;
+        if ((rc = small_prelude(e, want_snap, &pack))) return rc;
+        b.snapped[(size_t)i] = pack;
         b.small.push_back(i);
     }
     if (!b.small.empty()) {
@@ -179,8 +169,8 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
             HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)e->d.rec_tick + 1), (int)(uint32_t)((uint64_t)e->d.tick >> 32), 1, e0->main));
             e->rec_tick_dev = e->d.tick;
         }
-        for (int64_t t = 0; t < n_ticks;) {                       // (launches of at most 2^16 ticks, as csf_step's)
-            const int k = (int)std::min<int64_t>(n_ticks - t, 65536);
+        for (int64_t t = 0; t < n_ticks;) {
+            const int k = small_launch_ticks(n_ticks - t);
             const bool pack = want_snap && t + k == n_ticks;
             for (int m = 0; m < 7; m++) {
                 const int cnt = cls_beg[m + 1] - cls_beg[m];
@@ -188,15 +178,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
                 launch_small_batch(m, b.table.p + cls_beg[m], cnt, cls_nv[m], k, pack, e0->main);
                 HIPCHK(e0, hipGetLastError());
             }
-            for (int32_t i : b.small) {
-                csf_engine *e = engines[i];
-                e->mid_synced = false;
-                e->d.tick += k;
-                e->moves += k;
-                e->small_ticks += k;
-                e->batch_ticks += k;
-                if (e->d.rec_tick != nullptr) e->rec_tick_dev = e->d.tick;
-            }
+            for (int32_t i : b.small) small_ticked(engines[i], k, true);
             t += k;
         }
         for (int32_t i : b.small) engines[i]->device_ahead = true;
@@ -239,7 +221,7 @@ int csf_batch_join(csf_engine *const *engines, int32_t count) try {
     b->device = e0->device;
     b->members.assign(engines, engines + count);
     HIPCHK(e0, b->table.alloc((size_t)count));
-    HIPCHK(e0, hipHostMalloc((void **)&b->stage, (size_t)count * sizeof(Dev), hipHostMallocDefault));
+    HIPCHK(e0, b->stage.alloc((size_t)count));
     HIPCHK(e0, hipEventCreateWithFlags(&b->copied, hipEventDisableTiming));
     b->shadow.resize((size_t)count);
     b->held.assign((size_t)count, 0);

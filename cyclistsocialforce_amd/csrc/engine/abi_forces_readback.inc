@@ -119,9 +119,6 @@ int csf_replay_forces(csf_engine *e, int64_t n_ticks, const double *Fx, const do
     e->bounds_fresh = false;
     if (dd.hist)
         HIPCHK(e, hipMemcpy(states_out, hbuf.p, (size_t)n_samples * n * e->d.ns * sizeof(double), hipMemcpyDeviceToHost));
-    fbuf.release();
-    hbuf.release();
-    lbuf.release();
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 
@@ -170,31 +167,11 @@ static int get_F(csf_engine *e, int comp, double *out) {
     return read_rows(e, e->F.p + (size_t)comp * e->cap, 1, out, false);
 }
 
-static int snap_unpack(csf_engine *e, double *s_out, int32_t *dest_ptr, uint8_t *znav, double *Fx, double *Fy);
-
-int csf_get_tick(csf_engine *e, double *s_out, int32_t *dest_ptr, uint8_t *znav, double *Fx, double *Fy, int64_t *tick) try {
-    if (!e) return CSF_E_ARG;
-    HIPCHK(e, hipSetDevice(e->device));
-    int rc = upload_all(e);  // a never-stepped engine still answers from a consistent device copy
-    if (rc) return rc;
-    const int64_t n = (int64_t)e->order.size();
-    const int ns = e->d.ns;
-    if (tick) *tick = e->d.tick;
-    if (n == 0) return csf_sync(e);
-    if ((rc = sync_order(e))) return rc;
-    if ((rc = snap_reserve(e, (size_t)n * ((size_t)(ns + 2) * sizeof(double) + sizeof(int32_t) + 3)))) return rc;
-    launch_snapshot(e->d, e->snap_dev, e->main);
-    HIPCHK(e, hipGetLastError());
-    rc = csf_sync(e);
-    if (rc) return rc;
-    return snap_unpack(e, s_out, dest_ptr, znav, Fx, Fy);
-} catch (...) { return csf_caught(e); }
-
 // the packed read-back in the mapped host buffer -> the caller's arrays
 static int snap_unpack(csf_engine *e, double *s_out, int32_t *dest_ptr, uint8_t *znav, double *Fx, double *Fy) {
     const int64_t n = (int64_t)e->order.size();
     const int ns = e->d.ns;
-    const double *S = (const double *)e->snap_host;
+    const double *S = (const double *)e->snap.p;
     const double *F = S + (size_t)n * ns;
     const int32_t *P = (const int32_t *)(F + 2 * (size_t)n);
     const uint8_t *Z = (const uint8_t *)(P + n);
@@ -205,6 +182,22 @@ static int snap_unpack(csf_engine *e, double *s_out, int32_t *dest_ptr, uint8_t 
     if (znav) std::memcpy(znav, Z, (size_t)n * 3);
     return CSF_OK;
 }
+
+int csf_get_tick(csf_engine *e, double *s_out, int32_t *dest_ptr, uint8_t *znav, double *Fx, double *Fy, int64_t *tick) try {
+    if (!e) return CSF_E_ARG;
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = upload_all(e);  // a never-stepped engine still answers from a consistent device copy
+    if (rc) return rc;
+    if (tick) *tick = e->d.tick;
+    if (e->order.empty()) return csf_sync(e);
+    if ((rc = sync_order(e))) return rc;
+    if ((rc = snap_reserve(e))) return rc;
+    launch_snapshot(e->d, (double *)e->snap.dev, e->main);
+    HIPCHK(e, hipGetLastError());
+    rc = csf_sync(e);
+    if (rc) return rc;
+    return snap_unpack(e, s_out, dest_ptr, znav, Fx, Fy);
+} catch (...) { return csf_caught(e); }
 
 // csf_step(e, n_ticks) + csf_get_tick in one call: what a caller that looks at every tick does (SocialForceIntersection.step(),
 // intersection.py:866-896 - the host mirror refreshes vehicle.s, znav, force after each tick).  On the one-wave path the kernel
@@ -269,12 +262,9 @@ static int rings_setup(csf_engine *e, int32_t stride, int32_t capacity, bool for
     hipError_t r = hs.alloc(rows * (size_t)e->d.ns);
     if (r == hipSuccess && forces) r = hf.alloc(rows * 2);
     if (r == hipSuccess && fast) r = tk.alloc(1);
-    if (r != hipSuccess) {
-        hs.release(); hf.release(); tk.release();
+    if (r != hipSuccess)
         return fail(e, CSF_E_DEVICE, "no device memory for a ring of %d samples: %s", (int)capacity, hipGetErrorString(r));
-    }
-    std::swap(e->hist, hs); std::swap(e->hist_F, hf); std::swap(e->rec_tick, tk);
-    hs.release(); hf.release(); tk.release();
+    std::swap(e->hist, hs); std::swap(e->hist_F, hf); std::swap(e->rec_tick, tk);   // (the old rings go with hs, hf, tk)
     e->d.hist = e->hist.p;
     e->d.hist_F = e->hist_F.p;
     e->d.rec_tick = e->rec_tick.p;
@@ -342,17 +332,17 @@ static int record_gather(csf_engine *e0, RecGather &g, hipStream_t st, const Rec
         r.first = (int32_t)(a.first % d.hist_cap), r.count = (int32_t)a.count;
         if (a.s_out && c * n > 0) r.s = d.hist, r.s_off = (int64_t)at, at += (c * n * ns + 1) & ~(size_t)1;
         if (a.F_out && c * n > 0) r.F = d.hist_F, r.F_off = (int64_t)at, at += c * n * 2;
-        g.desc[i] = r;
+        g.desc.p[i] = r;
     }
-    launch_record_gather(g.desc_dev, (int)m, most, g.out_dev, st);
+    launch_record_gather(g.desc.dev, (int)m, most, g.out.dev, st);
     HIPCHK(e0, hipGetLastError());
     HIPCHK(e0, hipStreamSynchronize(st));
     for (size_t i = 0; i < m; i++) {
         const RecAsk &a = asks[i];
-        const RecDesc &r = g.desc[i];
+        const RecDesc &r = g.desc.p[i];
         const size_t n = (size_t)r.n, c = (size_t)r.count;
-        if (r.s) std::memcpy(a.s_out, g.out + r.s_off, c * n * (size_t)r.ns * sizeof(double));
-        if (r.F) std::memcpy(a.F_out, g.out + r.F_off, c * n * 2 * sizeof(double));
+        if (r.s) std::memcpy(a.s_out, g.out.p + r.s_off, c * n * (size_t)r.ns * sizeof(double));
+        if (r.F) std::memcpy(a.F_out, g.out.p + r.F_off, c * n * 2 * sizeof(double));
     }
     return CSF_OK;
 }

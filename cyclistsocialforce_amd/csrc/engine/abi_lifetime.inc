@@ -64,6 +64,7 @@ csf_engine *csf_create(const csf_params *params, int64_t n_capacity, int32_t dev
         if (hi < lo && hipStreamCreateWithPriority(&e->comm, hipStreamNonBlocking, hi) != hipSuccess) e->comm = nullptr;
         (void)hipGetLastError();
         if (!e->comm && hipStreamCreateWithFlags(&e->comm, hipStreamNonBlocking) != hipSuccess) return bail("stream");
+        e->comm_hold.s = e->comm;
     }
     if (hipEventCreateWithFlags(&e->ev_integ, hipEventDisableTiming) != hipSuccess) return bail("event");
     if (hipEventCreateWithFlags(&e->ev_gather, hipEventDisableTiming) != hipSuccess) return bail("event");
@@ -106,7 +107,6 @@ int csf_destroy(csf_engine *e) try {
                 fclose(f);
             }
         }
-        e->chase_clock.release();
     }
     if (e->atrace.p) {  // CSF_TRACE_AGENT=<file>: the stamps of the last per-agent launch
         std::vector<uint64_t> h(e->atrace.n);
@@ -116,7 +116,6 @@ int csf_destroy(csf_engine *e) try {
                 fclose(f);
             }
         }
-        e->atrace.release();
     }
     if (e->trace.p) {  // CSF_TRACE_BLOCKS=<file>: workgroup timeline of the last pair-kernel launch
         std::vector<uint64_t> h(e->trace_words);
@@ -126,7 +125,6 @@ int csf_destroy(csf_engine *e) try {
                 fclose(f);
             }
         }
-        e->trace.release();
     }
     if (e->nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(e->nccl);
     for (auto &sl : e->prof_pool)
@@ -136,31 +134,13 @@ int csf_destroy(csf_engine *e) try {
         if (ev) (void)hipEventDestroy(ev);
     if (e->ev_integ) (void)hipEventDestroy(e->ev_integ);
     if (e->ev_gather) (void)hipEventDestroy(e->ev_gather);
-    e->s.release(); e->vdes.release(); e->q.release(); e->znp.release(); e->hx.release(); e->hy.release();
-    e->rec_alt.release(); e->recg_alt.release(); e->rec2_alt.release(); e->src64_a.release(); e->src64_b.release();
-    e->recs_alt.release(); e->chase_misc.release(); e->part4.release();
-    if (e->chase_err_host) (void)hipHostFree(e->chase_err_host);
-    e->lti.release(); e->ppsi.release(); e->script.release(); e->sbeg.release(); e->slen.release(); e->F.release(); e->hist.release(); e->hist_F.release(); e->rec_tick.release(); e->rgather.release(); e->qbeg.release(); e->qlen.release(); e->alive.release(); e->order_dev.release();
-    e->ptr.release(); e->ti.release(); e->dgood.release(); e->znav.release(); e->zrid.release();
-    e->status.release(); e->rec.release(); e->rv.release(); e->rvo.release(); e->rg_v.release(); e->rg_start.release(); e->rg_c.release(); e->kat4.release(); e->rec2.release(); e->recs2.release();
-    e->part.release(); e->froad.release(); e->kat2.release(); e->bnd.release(); e->bnd2.release(); e->rorg.release(); e->reclo.release(); e->xbuf.release(); e->segtab.release(); e->tcirc.release(); e->clist.release(); e->ccount.release(); e->far_stat.release(); e->edge.release(); e->edge_n.release(); e->edge_head.release(); e->perm.release(); e->pos.release(); e->recs.release(); e->recg.release(); e->recb.release(); e->borg.release();
-    e->ticket.release(); e->scratch_u8.release(); e->scratch_i32.release(); e->scratch_f64.release(); e->scratch_cnt.release();
-    e->ptab.release(); e->pctab.release(); e->pbtab.release(); e->cls.release();
-    e->sort_vals.release(); e->rlist.release(); e->sort_keys.release(); e->sort_keys_out.release(); e->sort_tmp.release();
-    if (e->snap_host) (void)hipHostFree(e->snap_host);
-    if (e->bound_pin) (void)hipHostFree(e->bound_pin);
-    if (e->holes.pos) (void)hipHostFree(e->holes.pos);
-    if (e->holes.bnd) (void)hipHostFree(e->holes.bnd);
     if (e->holes.ev) (void)hipEventDestroy(e->holes.ev);
-    for (auto &sl : e->pinned) {
-        if (sl.host) (void)hipHostFree(sl.host);
+    for (auto &sl : e->pinned)
         if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    if (e->comm) (void)hipStreamDestroy(e->comm);
     for (csf_engine *m : e->group)          // the others of a loopback group lose this member: no group any more (csf_step_group says so)
         if (m != e) m->group.clear();
-    e->main = nullptr;
-    e->main_hold.reset();                   // (the stream itself goes with its last holder; this engine's events went above)
+    // every buffer of the engine goes with it, ahead of its streams (the order of csf_engine's members); the main stream itself
+    // goes with its last holder
     delete e;
     return CSF_OK;
 } catch (...) { return csf_caught(nullptr); }   // (the engine may be gone by now: the sentence goes where csf_last_error(NULL) finds it)

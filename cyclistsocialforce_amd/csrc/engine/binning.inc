@@ -17,29 +17,17 @@ static int holes_request(csf_engine *e) {
     e->pop_calls_in_period = false;
     if (!traffic && e->knobs.hole_lazy) return CSF_OK;
     const size_t np = (size_t)d.n_pad, nb = np / 64;
-    if (h.pos_n < np) {
-        if (h.pos) HIPCHK(e, hipHostFree(h.pos));
-        h.pos = nullptr;
-        HIPCHK(e, hipHostMalloc((void **)&h.pos, np * sizeof(int32_t), hipHostMallocMapped));
-        HIPCHK(e, hipHostGetDevicePointer((void **)&h.pos_dev, h.pos, 0));
-        h.pos_n = np;
-    }
-    if (h.bnd_n < nb) {
-        if (h.bnd) HIPCHK(e, hipHostFree(h.bnd));
-        h.bnd = nullptr;
-        HIPCHK(e, hipHostMalloc((void **)&h.bnd, nb * sizeof(float4), hipHostMallocMapped));
-        HIPCHK(e, hipHostGetDevicePointer((void **)&h.bnd_dev, h.bnd, 0));
-        h.bnd_n = nb;
-    }
+    if (h.pos.n < np) HIPCHK(e, h.pos.alloc(np));     // (the last read-back has landed, or nobody will look at it: no wait)
+    if (h.bnd.n < nb) HIPCHK(e, h.bnd.alloc(nb));
     if (!h.ev) HIPCHK(e, hipEventCreateWithFlags(&h.ev, hipEventDisableTiming));
     // (a KERNEL writes them into mapped host memory: two hipMemcpyAsync to the host in the middle of a run cost the tick loop far more
     // than their 7 us on the device - 2.6 us per tick at the headline with a re-binning every 64 ticks, profiles/r6_hole_readback_ab.txt)
     if (e->knobs.hole_export_kernel) {
-        launch_export_places(d, h.pos_dev, h.bnd_dev, (int64_t)np, (int64_t)nb, e->main);
+        launch_export_places(d, h.pos.dev, h.bnd.dev, (int64_t)np, (int64_t)nb, e->main);
         HIPCHK(e, hipGetLastError());
     } else {
-        HIPCHK(e, hipMemcpyAsync(h.pos, d.pos, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->main));
-        HIPCHK(e, hipMemcpyAsync(h.bnd, d.bnd, nb * sizeof(float4), hipMemcpyDeviceToHost, e->main));
+        HIPCHK(e, hipMemcpyAsync(h.pos.p, d.pos, np * sizeof(int32_t), hipMemcpyDeviceToHost, e->main));
+        HIPCHK(e, hipMemcpyAsync(h.bnd.p, d.bnd, nb * sizeof(float4), hipMemcpyDeviceToHost, e->main));
     }
     HIPCHK(e, hipEventRecord(h.ev, e->main));
     h.places = (e->live_at_rebin + 63) / 64 * 64;
@@ -56,8 +44,8 @@ static bool holes_ready(csf_engine *e) {
     if (hipEventSynchronize(h.ev) != hipSuccess) return h.pending = false;
     h.pending = false;
     const int64_t nb = h.places / 64;
-    h.hpos.assign(h.pos, h.pos + h.pos_n);
-    h.hbnd.assign(h.bnd, h.bnd + h.bnd_n);
+    h.hpos.assign(h.pos.p, h.pos.p + h.pos.n);
+    h.hbnd.assign(h.bnd.p, h.bnd.p + h.bnd.n);
     std::vector<float> radii;
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
     for (int64_t b = 0; b < nb; b++) {
@@ -321,10 +309,9 @@ int rebin(csf_engine *e) {
                 // (into the pinned buffer csf_create made for the coordinate bound - cap >= 64 doubles; the stream is waited for
                 // right below, so the two uses cannot meet: a runtime's first copy into PAGEABLE memory cost 9 ms in mid-run)
                 unsigned st[2] = {0u, 0u};
-                if (!e->bound_pin) HIPCHK(e, hipHostMalloc((void **)&e->bound_pin, 2 * (size_t)e->cap * sizeof(double), hipHostMallocDefault));
-                HIPCHK(e, hipMemcpyAsync(e->bound_pin, e->far_stat.p, sizeof st, hipMemcpyDeviceToHost, e->main));
+                HIPCHK(e, hipMemcpyAsync(e->bound_pin.p, e->far_stat.p, sizeof st, hipMemcpyDeviceToHost, e->main));
                 HIPCHK(e, hipStreamSynchronize(e->main));
-                std::memcpy(st, e->bound_pin, sizeof st);
+                std::memcpy(st, e->bound_pin.p, sizeof st);
                 float tail;
                 std::memcpy(&tail, &st[1], sizeof tail);
                 const double eps = e->knobs.far_eps, met = std::min<double>((double)st[0], (double)d.n) + (double)TAIL_SLOTS;   // (+ arrivals until then)

@@ -183,10 +183,10 @@ int set_fov_band(csf_engine *e) {
     if (e->bound_stale) {   // (single device: every slot's state is here)
         // (through a pinned buffer: the first copy into pageable memory of a process costs ~9 ms - the runtime sets its staging
         // path up - and a population that is only ever stepped met it here, in the middle of a run: tick 4 096 of config 2)
-        if (!e->bound_pin) HIPCHK(e, hipHostMalloc((void **)&e->bound_pin, 2 * (size_t)e->cap * sizeof(double), hipHostMallocDefault));   // (csf_create made it)
-        HIPCHK(e, hipMemcpyAsync(e->bound_pin, e->s.p, 2 * (size_t)e->cap * sizeof(double), hipMemcpyDeviceToHost, e->main));
+        // (csf_create made it: alloc_all)
+        HIPCHK(e, hipMemcpyAsync(e->bound_pin.p, e->s.p, 2 * (size_t)e->cap * sizeof(double), hipMemcpyDeviceToHost, e->main));
         HIPCHK(e, hipStreamSynchronize(e->main));
-        const double *xy = e->bound_pin;
+        const double *xy = e->bound_pin.p;
         double cb = e->coord_bound0;
         for (int32_t a : e->order) {
             const double bx = std::fabs(xy[(size_t)a] - d.ox), by = std::fabs(xy[(size_t)e->cap + (size_t)a] - d.oy);

@@ -92,7 +92,6 @@ static int gather_population(csf_engine *e) {
         hipError_t r1 = hipStreamSynchronize(m->main);
         if (sr == hipSuccess) sr = r1;
     }
-    for (auto &b : stage) b.release();
     if (rc) return rc;
     HIPCHK(e, sr);
     for (csf_engine *m : mem) m->state_all_current = true;

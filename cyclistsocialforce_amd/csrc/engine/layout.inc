@@ -85,7 +85,7 @@ int alloc_all(csf_engine *e) {
     HIPCHK(e, e->edge_n.alloc(2));
     HIPCHK(e, e->edge_head.alloc(cap));
     e->sidx.assign(cap, csf_engine::SlotIdx());
-    if (!e->bound_pin) HIPCHK(e, hipHostMalloc((void **)&e->bound_pin, 2 * (size_t)cap * sizeof(double), hipHostMallocDefault));
+    HIPCHK(e, e->bound_pin.alloc(2 * cap));
     e->dev_alive.assign(cap, 0);
     Dev &d = e->d;
     d.cap = (int64_t)cap;

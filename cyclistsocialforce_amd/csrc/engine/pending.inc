@@ -16,13 +16,7 @@ int stage_acquire(csf_engine *e, size_t bytes, csf_engine::PinnedSlot **out) {
         HIPCHK(e, hipEventSynchronize(sl.done));
         sl.busy = false;
     }
-    if (bytes > sl.bytes) {
-        if (sl.host) HIPCHK(e, hipHostFree(sl.host));
-        sl.host = nullptr;
-        sl.bytes = std::max<size_t>(2 * bytes, 1 << 16);
-        HIPCHK(e, hipHostMalloc(&sl.host, sl.bytes, hipHostMallocMapped));
-        HIPCHK(e, hipHostGetDevicePointer(&sl.dev, sl.host, 0));
-    }
+    if (bytes > sl.buf.n) HIPCHK(e, sl.buf.alloc(std::max<size_t>(2 * bytes, 1 << 16)));   // (not busy: nothing reads it any more)
     if (!sl.done) HIPCHK(e, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     *out = &sl;
     return CSF_OK;
@@ -54,7 +48,7 @@ int flush_pending(csf_engine *e) {
     csf_engine::PinnedSlot *pin = nullptr;
     int rc = stage_acquire(e, (size_t)h.off_rows + b_rows, &pin);
     if (rc) return rc;
-    char *base = (char *)pin->host;
+    char *base = pin->buf.p;
     memcpy(base, &h, sizeof h);
     if (b_ret) memcpy(base + h.off_retire, pd.retire.data(), b_ret);
     if (b_sp) memcpy(base + h.off_spawn, pd.spawn.data(), b_sp);
@@ -70,7 +64,7 @@ int flush_pending(csf_engine *e) {
         b1 = (int)((e->live_at_rebin + e->tail_used + 63) / 64);
         if (b1 - b0 > 32 || (int64_t)b1 * 64 > d.n_src) circles_here = false, b0 = b1 = 0;
     }
-    launch_patch(d, h, pin->dev, e->ticket.p, b0, b1, h.n_retire + h.n_spawn + h.n_requeue + 3 * h.n_rows, e->main);
+    launch_patch(d, h, pin->buf.dev, e->ticket.p, b0, b1, h.n_retire + h.n_spawn + h.n_requeue + 3 * h.n_rows, e->main);
     e->tail_flushed = e->tail_used;
     e->pend_inplace = false;
     // The class-segmented order has no tail for arrivals: an arrival belongs into its set's run, which only a re-binning

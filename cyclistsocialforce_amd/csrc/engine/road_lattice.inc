@@ -85,8 +85,6 @@ int build_road_grid(csf_engine *e, const double box[4]) {
         HIPCHK(e, hipStreamSynchronize(e->main));
         std::vector<double> sm((size_t)ncell * 128);
         HIPCHK(e, hipMemcpy(sm.data(), dsm.p, sm.size() * sizeof(double), hipMemcpyDeviceToHost));
-        dvc.release();
-        dsm.release();
         // c_ab = k_a k_b (2/8)^2 sum_ij f(x_i, y_j) cos(a pi (i + 1/2) / 8) cos(b pi (j + 1/2) / 8), k_0 = 1/2
         double cs[RG_NODES][RG_NODES];
         for (int a = 0; a < RG_NODES; a++)

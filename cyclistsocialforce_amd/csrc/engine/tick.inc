@@ -47,17 +47,6 @@ static void launch_pair_all(csf_engine *e, const Dev &base, hipEvent_t t0 = null
 // all-gather of the records (in place: what arrives is what was there), 8 + 32 times in stream order and 8 + 32 times with
 // the collective on the second stream behind an event and a small kernel of the next tick in front of the wait.  The two
 // times are max-reduced over the ranks, so that every rank keeps the same order.
-static int calibrate_comm_stream_body(csf_engine *e);
-
-// (the flag is set only when the measurement went through: after an error the order is the plain one - collective in stream
-// order - and the next csf_step tries again)
-int calibrate_comm_stream(csf_engine *e) {
-    const int rc = calibrate_comm_stream_body(e);
-    if (rc) e->comm_second = false;
-    else e->comm_calibrated = true;
-    return rc;
-}
-
 static int calibrate_comm_stream_body(csf_engine *e) {
     if (!e->nccl || e->loopback) {
         e->comm_second = e->knobs.comm_second > 0;
@@ -72,7 +61,6 @@ static int calibrate_comm_stream_body(csf_engine *e) {
         NCCLCHK(e, g_rccl.AllReduce(t.p, t.p, 2, ncclFloat32, ncclMax, e->nccl, e->main));
         HIPCHK(e, hipStreamSynchronize(e->main));
         HIPCHK(e, hipMemcpy(v, t.p, sizeof v, hipMemcpyDeviceToHost));
-        t.release();
         if (v[0] != -v[1]) return fail(e, CSF_E_STATE, "CSF_COMM_STREAM differs between the ranks of this communicator: set it on all of them or on none");
     }
     if (e->knobs.comm_second >= 0) {
@@ -127,12 +115,20 @@ static int calibrate_comm_stream_body(csf_engine *e) {
         NCCLCHK(e, g_rccl.AllReduce(t.p, t.p, 2, ncclFloat32, ncclMax, e->nccl, e->main));
         HIPCHK(e, hipStreamSynchronize(e->main));
         HIPCHK(e, hipMemcpy(us, t.p, sizeof us, hipMemcpyDeviceToHost));
-        t.release();
     }
     e->comm_cal_us[0] = us[0];
     e->comm_cal_us[1] = us[1];
     e->comm_second = us[1] < us[0];
     return CSF_OK;
+}
+
+// (the flag is set only when the measurement went through: after an error the order is the plain one - collective in stream
+// order - and the next csf_step tries again)
+int calibrate_comm_stream(csf_engine *e) {
+    const int rc = calibrate_comm_stream_body(e);
+    if (rc) e->comm_second = false;
+    else e->comm_calibrated = true;
+    return rc;
 }
 
 // ---- mid-size populations: the whole tick in one launch (csf_mid.hip) --------------------------------------------------
@@ -155,7 +151,6 @@ static bool mid_fused_ok(const csf_engine *e) {
            d.src_beg == 0 && d.n_src / 64 * 8 <= 384;                  // (csf_mid.hip: MID_ITEMS_MAX items of the largest group)
 }
 
-// the other halves of the double buffers <- this tick's records (sentinels of free and padding slots included) and state
 // the second halves of the double buffers (allocations synchronise: never inside something that is being timed)
 static int alt_alloc(csf_engine *e) {
     const size_t nrec = e->rec.n;
@@ -176,18 +171,51 @@ static int alt_alloc(csf_engine *e) {
     return CSF_OK;
 }
 
+// The halves of the double buffers that the engine's Dev does not read this tick - a one-launch or side-by-side tick writes next
+// tick's records there -, and the fp64 snapshots of (x, y, psi): `cur` holds the state of the tick's start, `nxt` takes its end.
+struct OtherHalves {
+    float4 *rec, *recg, *recs;
+    float2 *rec2;
+    double *cur, *nxt;
+};
+
+static OtherHalves other_halves(const csf_engine *e) {
+    const Dev &d = e->d;
+    return {d.rec == e->rec.p ? e->rec_alt.p : e->rec.p,     d.recg == e->recg.p ? e->recg_alt.p : e->recg.p,
+            d.recs == e->recs.p ? e->recs_alt.p : e->recs.p, d.rec2 == e->rec2.p ? e->rec2_alt.p : e->rec2.p,
+            e->mid_cur_is_a ? e->src64_a.p : e->src64_b.p,   e->mid_cur_is_a ? e->src64_b.p : e->src64_a.p};
+}
+
+// a launch's view writes them (with_recs: the binned copy too - the side-by-side tick; the one-launch tick keeps none)
+static void write_other_halves(Dev &dd, const OtherHalves &o, bool with_recs) {
+    dd.rec_w = o.rec;
+    dd.recg_w = o.recg;
+    dd.rec2_w = o.rec2;
+    if (with_recs) dd.recs_w = o.recs;
+    dd.src64 = o.cur;
+    dd.src64_w = o.nxt;
+}
+
+// the halves trade places: what the launch wrote is what every later launch reads
+static void trade_halves(csf_engine *e, const OtherHalves &o, bool with_recs) {
+    Dev &d = e->d;
+    d.rec = d.rec_w = o.rec;
+    d.recg = d.recg_w = o.recg;
+    d.rec2 = d.rec2_w = o.rec2;
+    if (with_recs) d.recs = d.recs_w = o.recs;
+    e->mid_cur_is_a = !e->mid_cur_is_a;
+}
+
+// the other halves <- this tick's records (sentinels of free and padding slots included) and state
 static int mid_sync(csf_engine *e, unsigned *through = nullptr) {
     Dev &d = e->d;
     {
         int rca = alt_alloc(e);
         if (rca) return rca;
     }
-    float4 *rec_o = d.rec == e->rec.p ? e->rec_alt.p : e->rec.p, *recg_o = d.recg == e->recg.p ? e->recg_alt.p : e->recg.p;
-    float4 *recs_o = d.recs == e->recs.p ? e->recs_alt.p : e->recs.p;
-    float2 *rec2_o = d.rec2 == e->rec2.p ? e->rec2_alt.p : e->rec2.p;
-    double *cur = e->mid_cur_is_a ? e->src64_a.p : e->src64_b.p;
+    const OtherHalves o = other_halves(e);
     // (one launch: six copy / fill calls cost a launch and its gap each, once per re-binning)
-    launch_chase_sync(d, rec_o, recg_o, recs_o, rec2_o, cur, (int64_t)std::min((size_t)d.n_pad, e->recg.n), through, e->main);
+    launch_chase_sync(d, o.rec, o.recg, o.recs, o.rec2, o.cur, (int64_t)std::min((size_t)d.n_pad, e->recg.n), through, e->main);
     HIPCHK(e, hipGetLastError());
     if (through == nullptr) e->chase_resume = false;              // (the one-launch tick's call: the gate's counter is as it was)
     e->mid_synced = true;
@@ -201,15 +229,9 @@ static int enqueue_mid_tick(csf_engine *e) {
     if ((rc = set_fov_band(e))) return rc;
     if (!e->mid_synced && (rc = mid_sync(e))) return rc;
     if (d.nv > 0) launch_road(d, e->main);
-    float4 *rec_o = d.rec == e->rec.p ? e->rec_alt.p : e->rec.p, *recg_o = d.recg == e->recg.p ? e->recg_alt.p : e->recg.p;
-    float2 *rec2_o = d.rec2 == e->rec2.p ? e->rec2_alt.p : e->rec2.p;
-    double *cur = e->mid_cur_is_a ? e->src64_a.p : e->src64_b.p, *nxt = e->mid_cur_is_a ? e->src64_b.p : e->src64_a.p;
+    const OtherHalves o = other_halves(e);
     Dev dd = d;
-    dd.rec_w = rec_o;
-    dd.recg_w = recg_o;
-    dd.rec2_w = rec2_o;
-    dd.src64 = cur;
-    dd.src64_w = nxt;
+    write_other_halves(dd, o, false);                             // (this tick writes no binned copy)
     // road users per workgroup: about one workgroup (of eight waves, at the per-agent code's 255 registers a CU holds one) per CU
     int G = e->knobs.mid_group;
     if (G != 4 && G != 8 && G != 16 && G != 32) {
@@ -220,11 +242,7 @@ static int enqueue_mid_tick(csf_engine *e) {
     // (nothing has traded places yet: a refused launch leaves the engine where it was)
     if (!launch_mid_tick(dd, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, G);
     HIPCHK(e, hipGetLastError());
-    // the halves trade places: what the launch wrote is what every later launch reads
-    d.rec = d.rec_w = rec_o;
-    d.recg = d.recg_w = recg_o;
-    d.rec2 = d.rec2_w = rec2_o;
-    e->mid_cur_is_a = !e->mid_cur_is_a;
+    trade_halves(e, o, false);
     bounds_after_pair(e, true);
     e->moves++;
     e->mid_ticks++;
@@ -253,25 +271,28 @@ static bool chase_shape(const csf_engine *e) {
            !d.recv_binned && e->world == 1 && !e->nccl && !e->loopback && d.nv == 0 && d.hist == nullptr && e->comm != nullptr;   // (CSF_FAKE_SHARD: a rank's block of receivers, for tools/fake_shard.py)
 }
 
-// everything but "no re-binning this tick"
+// ... and what does: everything but "no re-binning this tick".  The receiver range is asked about here only: chase_shape says yes
+// to a rank's block whatever CSF_FAKE_SHARD is (the upload then makes the path's buffers, which harms nobody), a tick takes a
+// partial block only under CSF_FAKE_SHARD.
 static bool chase_eligible(const csf_engine *e, int64_t ticks_left) {
     const Dev &d = e->d;
-    if (e->knobs.chase == 0) return false;
-    const int m = d.p.model;
-    if (m != CSF_TWOD && m != CSF_INVPEND && m != CSF_PLANARPOINT) return false;
-    const bool rebin_now = false;
-    return e->classes.size() == 1 && d.n_classes == 1 && d.pair_variant == 0 && d.classify && d.recs_valid && !d.recv_binned && d.dyn_recv &&
-           (d.rpb == 32 || d.rpb == 16 || d.rpb == 8) && d.n_split <= 16 && d.part_base == 0 && e->world == 1 && !e->nccl && !e->loopback &&
-           d.nv == 0 && d.hist == nullptr && d.pair_count == nullptr && e->segs.empty() && e->state_all_current &&   // (wave traces allowed: tools/chase_timeline.py)
-           e->pend.empty() && !rebin_now && !e->bound_stale && e->bounds_fresh && d.n_live > 1 && d.hi > d.lo && (d.lo & 63) == 0 && d.replay_len == nullptr &&
-           ((d.lo == 0 && d.hi == d.n) || e->knobs.fake_world > 1) &&
-           e->comm != nullptr && (e->chase_prev || ticks_left >= 4);
+    return chase_shape(e) && d.n_classes == 1 && d.recs_valid && d.dyn_recv && (d.rpb == 32 || d.rpb == 16 || d.rpb == 8) && d.n_split <= 16 &&
+           d.part_base == 0 && d.pair_count == nullptr && e->segs.empty() && e->state_all_current &&   // (wave traces allowed: tools/chase_timeline.py)
+           e->pend.empty() && !e->bound_stale && e->bounds_fresh && d.n_live > 1 && d.hi > d.lo && (d.lo & 63) == 0 && d.replay_len == nullptr &&
+           ((d.lo == 0 && d.hi == d.n) || e->knobs.fake_world > 1) && (e->chase_prev || ticks_left >= 4);
 }
 
 static bool chase_ok(const csf_engine *e, int64_t ticks_left) { return !rebin_due(e) && chase_eligible(e, ticks_left); }
 
-static int chase_join(csf_engine *e);
-static int alt_alloc(csf_engine *e);
+// the two streams meet: whatever follows runs on the main stream alone
+static int chase_join(csf_engine *e) {
+    if (!e->chase_prev) return CSF_OK;
+    // (one event: the main stream behind the second; the second stream is put behind the main one when the path is entered again)
+    HIPCHK(e, hipEventRecord(e->ev_gather, e->comm));
+    HIPCHK(e, hipStreamWaitEvent(e->main, e->ev_gather, 0));
+    e->chase_prev = false;
+    return CSF_OK;
+}
 
 // what the side-by-side tick needs beside the engine's arrays (allocations synchronise: before a measurement, not inside it)
 static int chase_alloc(csf_engine *e) {
@@ -282,10 +303,9 @@ static int chase_alloc(csf_engine *e) {
         // is first asked for - a hundred microseconds and more each, which would land in the first side-by-side tick (and, for a
         // caller who times twenty ticks, in the figure)
         HIPCHK(e, hipMemsetAsync(e->chase_misc.p, 0, 64 * sizeof(unsigned), e->comm));
-        if (!e->chase_err_host) {   // (the word a wait that gives up sets: mapped host memory, so that csf_sync need not copy anything)
-            HIPCHK(e, hipHostMalloc((void **)&e->chase_err_host, 64, hipHostMallocMapped));
-            std::memset(e->chase_err_host, 0, 64);
-            HIPCHK(e, hipHostGetDevicePointer((void **)&e->chase_err_dev, e->chase_err_host, 0));
+        if (!e->chase_err.p) {   // (the word a wait that gives up sets: mapped host memory, so that csf_sync need not copy anything)
+            HIPCHK(e, e->chase_err.alloc(16));
+            std::memset(e->chase_err.p, 0, 64);
         }
         preload_chase_kernels();
         // ... and a queue gets its scratch memory when a kernel that spills is first dispatched on it: one pair launch that hands
@@ -395,16 +415,6 @@ static bool chase_take(csf_engine *e, int64_t ticks_left) {
     return false;
 }
 
-// the two streams meet: whatever follows runs on the main stream alone
-static int chase_join(csf_engine *e) {
-    if (!e->chase_prev) return CSF_OK;
-    // (one event: the main stream behind the second; the second stream is put behind the main one when the path is entered again)
-    HIPCHK(e, hipEventRecord(e->ev_gather, e->comm));
-    HIPCHK(e, hipStreamWaitEvent(e->main, e->ev_gather, 0));
-    e->chase_prev = false;
-    return CSF_OK;
-}
-
 static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engine::ProfSlot *po) {
     Dev &d = e->d;
     int rc;
@@ -425,21 +435,13 @@ static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engin
         HIPCHK(e, hipStreamWaitEvent(e->comm, e->ev_integ, 0));
     }
     hipStream_t P = e->chase_parity ? e->comm : e->main, Q = e->chase_parity ? e->main : e->comm;
-    float4 *rec_o = d.rec == e->rec.p ? e->rec_alt.p : e->rec.p, *recg_o = d.recg == e->recg.p ? e->recg_alt.p : e->recg.p;
-    float4 *recs_o = d.recs == e->recs.p ? e->recs_alt.p : e->recs.p;
-    float2 *rec2_o = d.rec2 == e->rec2.p ? e->rec2_alt.p : e->rec2.p;
-    double *cur = e->mid_cur_is_a ? e->src64_a.p : e->src64_b.p, *nxt = e->mid_cur_is_a ? e->src64_b.p : e->src64_a.p;
+    const OtherHalves o = other_halves(e);
     const int64_t groups = (d.hi - d.lo + d.rpb - 1) / d.rpb, wgs = groups * d.n_split;
     e->chase_round++;
     Dev dd = d;
-    dd.rec_w = rec_o;
-    dd.recg_w = recg_o;
-    dd.rec2_w = rec2_o;
-    dd.recs_w = recs_o;
-    dd.src64 = cur;
-    dd.src64_w = nxt;
+    write_other_halves(dd, o, true);
     dd.chase_misc = e->chase_misc.p;
-    dd.chase_err = e->chase_err_dev;
+    dd.chase_err = e->chase_err.dev;
     dd.chase_round = e->chase_round;
     dd.part4 = e->part4.p;
     dd.chase_tag = (uint32_t)(e->chase_ticks + 1) | 0x40000000u;   // (never 0, never a tag an older granule carries)
@@ -465,12 +467,7 @@ static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engin
         return fail(e, CSF_E_STATE, "the per-agent kernel beside the pair launch is not built for vehicle class %d", (int)d.p.model);
     if (po) po->agent = true;
     HIPCHK(e, hipGetLastError());
-    // the halves trade places: what the launch wrote is what every later launch reads
-    d.rec = d.rec_w = rec_o;
-    d.recg = d.recg_w = recg_o;
-    d.rec2 = d.rec2_w = rec2_o;
-    d.recs = d.recs_w = recs_o;
-    e->mid_cur_is_a = !e->mid_cur_is_a;
+    trade_halves(e, o, true);
     e->chase_parity ^= 1;
     e->chase_prev = true;
     e->chase_ticks++;
@@ -590,20 +587,41 @@ static bool small_fused_ok(const csf_engine *e) {
            d.atrace == nullptr && d.lo == 0 && d.hi == d.n && e->pend.empty() && !e->dirty;
 }
 
-// the mapped host buffer of the packed read-back (csf_get_tick, csf_step_get_tick), large enough for the population
-static int snap_reserve(csf_engine *e, size_t need) {
-    if (need <= e->snap_bytes) return CSF_OK;
-    if (e->snap_host) {
-        HIPCHK(e, hipStreamSynchronize(e->main));
-        HIPCHK(e, hipHostFree(e->snap_host));
-        e->snap_host = nullptr;
-        e->snap_bytes = 0;
-    }
-    const size_t want = std::max<size_t>(need * 2, 4096);
-    HIPCHK(e, hipHostMalloc(&e->snap_host, want, hipHostMallocMapped));
-    HIPCHK(e, hipHostGetDevicePointer((void **)&e->snap_dev, e->snap_host, 0));
-    e->snap_bytes = want;
+// the bytes of the packed read-back (csf_get_tick: state rows, Fx, Fy, destination pointers, one-hot navigation state)
+static size_t snap_need(const csf_engine *e) {
+    return e->order.size() * ((size_t)(e->d.ns + 2) * sizeof(double) + sizeof(int32_t) + 3);
+}
+
+// ... and its mapped host buffer (csf_get_tick, csf_step_get_tick, csf_step_batch_get_tick), large enough for the population
+static int snap_reserve(csf_engine *e) {
+    HIPCHK(e, e->snap.reserve(snap_need(e), e->main, 4096));
     return CSF_OK;
+}
+
+// In front of a launch of one-wave ticks (small_fused_ok holds): the bands of the fp32 decisions (tracked_precise, side_undecided)
+// and, for a read-back, its buffer.  *pack: the kernel may pack the read-back itself behind its last tick - slots are the
+// population order and the buffer is there.
+static int small_prelude(csf_engine *e, bool want_snap, bool *pack) {
+    *pack = false;
+    int rc = set_fov_band(e);
+    if (rc || !want_snap) return rc;
+    if ((rc = sync_order(e))) return rc;
+    *pack = e->d.order == nullptr && snap_reserve(e) == CSF_OK;
+    return CSF_OK;
+}
+
+// one launch takes at most 2^16 ticks: a second or less
+static int small_launch_ticks(int64_t ticks_left) { return (int)std::min<int64_t>(ticks_left, 65536); }
+
+// behind a launch of k one-wave ticks (batched: small_batch_kernel's, which also moved a recording member's tick word on)
+static void small_ticked(csf_engine *e, int64_t k, bool batched) {
+    e->mid_synced = false;
+    e->d.tick += k;
+    e->moves += k;
+    e->small_ticks += k;
+    if (!batched) return;
+    e->batch_ticks += k;
+    if (e->d.rec_tick != nullptr) e->rec_tick_dev = e->d.tick;
 }
 
 static int step_impl(csf_engine *e, int64_t n_ticks, bool want_snap, bool *snapped) {
@@ -621,24 +639,15 @@ static int step_impl(csf_engine *e, int64_t n_ticks, bool want_snap, bool *snapp
     }
     if (n_ticks > 0 && !e->comm_calibrated && (rc = calibrate_comm_stream(e))) return rc;
     if (n_ticks > 0 && small_fused_ok(e)) {
-        if ((rc = set_fov_band(e))) return rc;                 // (the bands of the fp32 decisions: tracked_precise, side_undecided)
-        // csf_step_get_tick: the kernel packs the read-back itself behind its last tick, when slots are the population order
-        bool snap = false;
-        if (want_snap) {
-            if ((rc = sync_order(e))) return rc;
-            const size_t n = e->order.size();
-            snap = e->d.order == nullptr && snap_reserve(e, n * ((size_t)(e->d.ns + 2) * sizeof(double) + sizeof(int32_t) + 3)) == CSF_OK;
-        }
-        for (int64_t t = 0; t < n_ticks;) {                    // (launches of at most 2^16 ticks: a second or less each)
-            const int k = (int)std::min<int64_t>(n_ticks - t, 65536);
+        bool snap = false;                                     // csf_step_get_tick: the kernel packs the read-back
+        if ((rc = small_prelude(e, want_snap, &snap))) return rc;
+        for (int64_t t = 0; t < n_ticks;) {
+            const int k = small_launch_ticks(n_ticks - t);
             Dev dd = e->d;
-            dd.snap = (snap && t + k == n_ticks) ? e->snap_dev : nullptr;
+            dd.snap = (snap && t + k == n_ticks) ? (double *)e->snap.dev : nullptr;
             launch_small_tick(dd, k, e->main);
-            e->mid_synced = false;
             HIPCHK(e, hipGetLastError());
-            e->d.tick += k;
-            e->moves += k;
-            e->small_ticks += k;
+            small_ticked(e, k, false);
             t += k;
         }
         e->device_ahead = true;
@@ -681,7 +690,7 @@ int csf_sync(csf_engine *e) try {
     chase_cal_resolve(e, true);
     // did a wait of the side-by-side tick give up? (csf_dev.h: CHASE_SPIN_LIMIT - it never has.)  The kernels set a word of mapped host
     // memory: read here behind the streams' end, no copy (a 4-byte hipMemcpyAsync + wait per csf_sync was ~20 us of every timed call)
-    if (e->chase_err_host && *(volatile unsigned *)e->chase_err_host != 0)
+    if (e->chase_err.p && *(volatile unsigned *)e->chase_err.p != 0)
         return fail(e, CSF_E_DEVICE, "a wait of the per-agent kernel beside the pair launch gave up: the states since are not a simulation (CSF_CHASE=0 takes the two launches in turn)");
     return CSF_OK;
 } catch (...) { return csf_caught(e); }

@@ -17,7 +17,9 @@
 #include <memory>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "csf_dev.h"
@@ -79,10 +81,20 @@ struct Rccl {
 bool g_poison = false;
 constexpr size_t POISON_GUARD = 1 << 16;
 
+// Device memory that belongs to its holder: freed when the holder goes, moved but never copied.
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) release(), p = o.p, n = o.n, o.p = nullptr, o.n = 0;
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t alloc(size_t count) {
         release();
         n = count;
@@ -104,12 +116,49 @@ struct DevBuf {
     }
     // grow-only scratch: contents undefined
     hipError_t reserve(size_t count) { return count <= n ? hipSuccess : alloc(count); }
-    void release() {
+    void release() {   // (the result is ignored: this runs in destructors, and leaves no error behind for the next call to find)
         if (p) (void)hipFree(p);
         p = nullptr;
         n = 0;
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf<char>>::value && !std::is_copy_assignable<DevBuf<char>>::value, "a DevBuf has one owner");
+
+// The same for pinned host memory.  Mapped (the default): `dev` is the address a kernel reaches the buffer by - its stores ARE
+// the transfer.  Contents are undefined after alloc and reserve.
+template <class T, bool Mapped = true>
+struct HostBuf {
+    T *p = nullptr, *dev = nullptr;
+    size_t n = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { release(); }
+    hipError_t alloc(size_t count) {
+        release();
+        if (count == 0) return hipSuccess;
+        hipError_t e = hipHostMalloc((void **)&p, count * sizeof(T), Mapped ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e == hipSuccess && Mapped) e = hipHostGetDevicePointer((void **)&dev, p, 0);
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    // grow-only; a kernel on `st` may still write the old buffer: wait for it before the buffer goes.  floor == 0: exactly `need`
+    // elements, else max(2 * need, floor)
+    hipError_t reserve(size_t need, hipStream_t st, size_t floor = 0) {
+        if (need <= n) return hipSuccess;
+        if (p) {
+            hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return e;
+        }
+        return alloc(floor ? std::max(2 * need, floor) : need);
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+        n = 0;
+    }
+};
+static_assert(!std::is_copy_constructible<HostBuf<char>>::value && !std::is_copy_assignable<HostBuf<char>>::value, "a HostBuf has one owner");
 
 // Measurement and test knobs.  Read from the environment ONCE per engine, in csf_create: nothing on the tick path or in
 // a re-binning calls getenv.
@@ -204,36 +253,11 @@ struct Knobs {
 // batch), grown geometrically like the packed snapshot's buffer: the descriptors the gather kernel reads and the buffer it packs
 // the samples into, both mapped host memory - the kernel's stores ARE the transfer, and the host waits once.
 struct RecGather {
-    RecDesc *desc = nullptr, *desc_dev = nullptr;
-    size_t desc_n = 0;
-    double *out = nullptr, *out_dev = nullptr;
-    size_t out_n = 0;               // doubles
+    HostBuf<RecDesc> desc;
+    HostBuf<double> out;
     hipError_t reserve(size_t members, size_t doubles, hipStream_t st) {
-        hipError_t r = hipSuccess;
-        if (members > desc_n) {
-            if (desc && (r = hipStreamSynchronize(st)) != hipSuccess) return r;
-            if (desc) (void)hipHostFree(desc);
-            desc = desc_dev = nullptr, desc_n = 0;
-            const size_t want = std::max<size_t>(2 * members, 16);
-            if ((r = hipHostMalloc((void **)&desc, want * sizeof(RecDesc), hipHostMallocMapped)) != hipSuccess) return r;
-            if ((r = hipHostGetDevicePointer((void **)&desc_dev, desc, 0)) != hipSuccess) return r;
-            desc_n = want;
-        }
-        if (doubles > out_n) {
-            if (out && (r = hipStreamSynchronize(st)) != hipSuccess) return r;
-            if (out) (void)hipHostFree(out);
-            out = out_dev = nullptr, out_n = 0;
-            const size_t want = std::max<size_t>(2 * doubles, 4096);
-            if ((r = hipHostMalloc((void **)&out, want * sizeof(double), hipHostMallocMapped)) != hipSuccess) return r;
-            if ((r = hipHostGetDevicePointer((void **)&out_dev, out, 0)) != hipSuccess) return r;
-            out_n = want;
-        }
-        return r;
-    }
-    void release() {
-        if (desc) (void)hipHostFree(desc);
-        if (out) (void)hipHostFree(out);
-        desc = desc_dev = nullptr, out = out_dev = nullptr, desc_n = out_n = 0;
+        hipError_t r = desc.reserve(members, st, 16);
+        return r != hipSuccess ? r : out.reserve(doubles, st, 4096);
     }
 };
 
@@ -241,6 +265,20 @@ struct csf_engine {
     Dev d{};
     Knobs knobs;
     int device = 0;
+    // The streams are declared ahead of every buffer: members go in reverse order, so the buffers are freed while the streams exist.
+    hipStream_t main = nullptr, comm = nullptr;
+    // The members of a loopback group share ONE main stream (ticks and exchanges in order).  It belongs to all of them: the
+    // handle lives as long as any member does, whichever is destroyed first (until round 5 it was the first member's, the
+    // others were told when that one went - unless another member had gone before and cleared the lists through which they
+    // would have been told: a dangling handle, which hipStreamSynchronize happened to tolerate and hipStreamQuery did not)
+    struct StreamHold {
+        hipStream_t s = nullptr;
+        ~StreamHold() {
+            if (s) (void)hipStreamDestroy(s);
+        }
+    };
+    std::shared_ptr<StreamHold> main_hold;
+    StreamHold comm_hold;                // (the second stream is the engine's own)
     // parameter sets (csf_set_param_classes): classes[0] is d.p; h_cls[slot] the set of a road user
     std::vector<csf_params> classes;
     std::vector<double> class_kappa;     // far_kappa of every set (the grid search is done once per table)
@@ -266,18 +304,6 @@ struct csf_engine {
     bool classes_dirty = true;
     int64_t cap = 0;        // slots: the caller's capacity + head room for arrivals between two re-binnings (csf_create)
     int64_t cap_user = 0;   // road users the caller may have at once
-    hipStream_t main = nullptr, comm = nullptr;
-    // The members of a loopback group share ONE main stream (ticks and exchanges in order).  It belongs to all of them: the
-    // handle lives as long as any member does, whichever is destroyed first (until round 5 it was the first member's, the
-    // others were told when that one went - unless another member had gone before and cleared the lists through which they
-    // would have been told: a dangling handle, which hipStreamSynchronize happened to tolerate and hipStreamQuery did not)
-    struct StreamHold {
-        hipStream_t s = nullptr;
-        ~StreamHold() {
-            if (s) (void)hipStreamDestroy(s);
-        }
-    };
-    std::shared_ptr<StreamHold> main_hold;
     hipEvent_t ev_integ = nullptr, ev_gather = nullptr;
     std::string err;
 
@@ -310,13 +336,10 @@ struct csf_engine {
     // host needs for that it reads back once per re-binning, without waiting: the place of every slot and the circles (85 KB at
     // N = 16 384).  The holes are kept in a lattice over the scene by the centre of their batch.
     struct HoleIndex {
-        int32_t *pos = nullptr;                     // pinned: slot -> place at the last re-binning
-        float4 *bnd = nullptr;                      // pinned: circle of every batch then (scene coordinates)
-        int32_t *pos_dev = nullptr;                 // the same two buffers as the device sees them (mapped)
-        float4 *bnd_dev = nullptr;
+        HostBuf<int32_t> pos;                       // slot -> place at the last re-binning
+        HostBuf<float4> bnd;                        // circle of every batch then (scene coordinates)
         std::vector<int32_t> hpos;                  // ... copied to ordinary memory when they have landed (the lookups
         std::vector<float4> hbnd;                   //     per arrival and departure are the host's hot loop under traffic)
-        size_t pos_n = 0, bnd_n = 0;
         hipEvent_t ev = nullptr;
         bool pending = false, ready = false;        // the read-back is under way / the lattice is built
         int64_t places = 0;                         // places that held road users at the re-binning
@@ -384,8 +407,7 @@ struct csf_engine {
     std::vector<SlotIdx> sidx;
     std::vector<uint8_t> dev_alive;        // [cap] what d.alive holds on the device (as of the last flush or upload)
     struct PinnedSlot {
-        void *host = nullptr, *dev = nullptr;
-        size_t bytes = 0;
+        HostBuf<char> buf;
         hipEvent_t done = nullptr;
         bool busy = false;
     };
@@ -406,7 +428,7 @@ struct csf_engine {
     // meet before anything else runs), ticks since the counters were cleared, which stream the next pair launch goes to
     DevBuf<float4> recs_alt;
     DevBuf<unsigned> chase_misc;
-    unsigned *chase_err_host = nullptr, *chase_err_dev = nullptr;   // a wait gave up: one word of mapped host memory (csf_sync)
+    HostBuf<unsigned> chase_err;        // a wait gave up: one word of mapped host memory (csf_sync)
     DevBuf<float4> part4;               // the partial sums of a side-by-side tick as tagged 16-byte granules (csf_dev.h: part4)
     DevBuf<unsigned long long> chase_clock;   // CSF_CHASE_CLOCK=<file>: stamps of the last 64 side-by-side ticks, written at csf_destroy
     bool dirty_layout_for_warm() const { return dirty || !segs.empty() || classes.size() != 1; }   // (the warm pair launch of chase_alloc takes the plain single-set launch)
@@ -456,7 +478,7 @@ struct csf_engine {
     // largest |coordinate| relative to the scene origin at the last upload (road users, prescribed trajectories, arrivals
     // since), and the integration steps since - nobody moves farther than t_s * v_max per step
     double coord_bound0 = 0.0;
-    double *bound_pin = nullptr;     // pinned: where the positions land when that bound is measured again (set_fov_band)
+    HostBuf<double, false> bound_pin;   // where the positions land when that bound is measured again (set_fov_band)
     int64_t moves = 0;
     int64_t small_ticks = 0;         // ticks run by the one-wave kernel (csf_small_ticks)
     int64_t slab_rewrites = 0;       // compact_slab calls (upload_queues sizes the slab by them)
@@ -468,9 +490,7 @@ struct csf_engine {
     double far_kappa = 0.0;   // lower bound of the field's decay rate (far_kappa())
     double last_gather_ms = 0.0;  // all-gather time accumulated by the last csf_profile_read
     bool ev_gather_recorded = false;
-    void *snap_host = nullptr;  // csf_get_tick: pinned, device-mapped staging buffer
-    double *snap_dev = nullptr;
-    size_t snap_bytes = 0;
+    HostBuf<char> snap;       // csf_get_tick: the packed read-back (snap_need bytes), written by the kernels themselves
     DevBuf<uint64_t> trace;   // CSF_TRACE_BLOCKS (measurement aid)
     DevBuf<uint64_t> atrace;  // CSF_TRACE_AGENT (measurement aid)
     size_t trace_words = 0;

@@ -217,6 +217,22 @@ class Engine:
         return fx, fy
 
     # -- read-back --------------------------------------------------------------------------
+    def _readback_arrays(self):
+        """fresh arrays of one read-back: s [n, n_states], ptr [n] int32, zn [n, 3] one-hot uint8, fx [n], fy [n]"""
+        n = self.n
+        return np.zeros((n, self.ns)), np.zeros(n, dtype=np.int32), np.zeros((n, 3), dtype=np.uint8), np.zeros(n), np.zeros(n)
+
+    def _readback_ptrs(self, what, arrays):
+        """the addresses of a caller's read-back arrays (s, ptr, zn, fx, fy; None where an array is None), checked"""
+        n = self.n
+        shapes = (((n, self.ns), np.float64), ((n,), np.int32), ((n, 3), None), ((n,), np.float64), ((n,), np.float64))
+        for a, (shape, dt) in zip(arrays, shapes):
+            if a is not None and not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.shape == shape
+                                      and (a.dtype == dt if dt is not None else a.dtype.itemsize == 1)):
+                raise ValueError(f"{what}: s [n, n_states] float64, ptr [n] int32, zn [n, 3] of one byte each, fx / fy [n] "
+                                 "float64, C-contiguous")
+        return [None if a is None else a.ctypes.data for a in arrays]
+
     def state(self, with_nav=False):
         """[n, n_states] state (and destination pointers, one-hot navigation state, tick count): one packed transfer
         (csf_get_tick; csf_get_state copies component by component)"""
@@ -225,13 +241,10 @@ class Engine:
 
     def state_by_component(self, with_nav=False):
         """the same through csf_get_state"""
-        n = self.n
-        s = np.zeros((n, self.ns))
+        s, ptr, zn, _, _ = self._readback_arrays()
         if not with_nav:
             self._ck(self._lib.csf_get_state(self._h, _ptr(s), None, None, None))
             return s
-        ptr = np.zeros(n, dtype=np.int32)
-        zn = np.zeros((n, 3), dtype=np.uint8)
         tick = C.c_int64(0)
         self._ck(self._lib.csf_get_state(self._h, _ptr(s), _ptr(ptr), _ptr(zn), C.byref(tick)))
         return s, ptr, zn.astype(bool), tick.value
@@ -239,41 +252,31 @@ class Engine:
     def tick_snapshot(self, forces=True):
         """state [n, n_states], destination pointers, one-hot navigation state, total forces and the tick count in one
         device-to-host transfer (csf_get_tick)"""
-        n = self.n
-        s = np.zeros((n, self.ns))
-        ptr = np.zeros(n, dtype=np.int32)
-        zn = np.zeros((n, 3), dtype=np.uint8)
-        fx = np.zeros(n) if forces else None
-        fy = np.zeros(n) if forces else None
+        s, ptr, zn, fx, fy = self._readback_arrays()
         tick = C.c_int64(0)
-        self._ck(self._lib.csf_get_tick(self._h, _ptr(s), _ptr(ptr), _ptr(zn), None if fx is None else _ptr(fx),
-                                        None if fy is None else _ptr(fy), C.byref(tick)))
-        return s, ptr, zn.astype(bool), fx, fy, tick.value
+        self._ck(self._lib.csf_get_tick(self._h, _ptr(s), _ptr(ptr), _ptr(zn), _ptr(fx) if forces else None,
+                                        _ptr(fy) if forces else None, C.byref(tick)))
+        return s, ptr, zn.astype(bool), (fx if forces else None), (fy if forces else None), tick.value
 
     def step_snapshot(self, n_ticks=1, forces=True, reuse=False):
         """step(n_ticks) and tick_snapshot() in one call (csf_step_get_tick): a handful of road users then cost one launch and
         one wait per call.  reuse: the arrays returned are the engine's own buffers, overwritten by the next call (the host
         mirror copies them into its bulk arrays at once) - at three road users the allocations are a fifth of the call."""
-        n = self.n
         if reuse:
-            key = (n, self.ns)
+            key = (self.n, self.ns)
             if getattr(self, "_snap_key", None) != key:
-                bufs = (np.zeros((n, self.ns)), np.zeros(n, dtype=np.int32), np.zeros((n, 3), dtype=np.uint8), np.zeros(n), np.zeros(n))
+                bufs = self._readback_arrays()
                 self._snap_key, self._snap_bufs, self._snap_ptrs, self._snap_tick = key, bufs, [_ptr(b) for b in bufs], C.c_int64(0)
             s, ptr, zn, fx, fy = self._snap_bufs
             p = self._snap_ptrs
             self._ck(self._lib.csf_step_get_tick(self._h, int(n_ticks), p[0], p[1], p[2], p[3] if forces else None,
                                                  p[4] if forces else None, C.byref(self._snap_tick)))
             return s, ptr, zn, (fx if forces else None), (fy if forces else None), self._snap_tick.value
-        s = np.zeros((n, self.ns))
-        ptr = np.zeros(n, dtype=np.int32)
-        zn = np.zeros((n, 3), dtype=np.uint8)
-        fx = np.zeros(n) if forces else None
-        fy = np.zeros(n) if forces else None
+        s, ptr, zn, fx, fy = self._readback_arrays()
         tick = C.c_int64(0)
-        self._ck(self._lib.csf_step_get_tick(self._h, int(n_ticks), _ptr(s), _ptr(ptr), _ptr(zn), None if fx is None else _ptr(fx),
-                                             None if fy is None else _ptr(fy), C.byref(tick)))
-        return s, ptr, zn.astype(bool), fx, fy, tick.value
+        self._ck(self._lib.csf_step_get_tick(self._h, int(n_ticks), _ptr(s), _ptr(ptr), _ptr(zn), _ptr(fx) if forces else None,
+                                             _ptr(fy) if forces else None, C.byref(tick)))
+        return s, ptr, zn.astype(bool), (fx if forces else None), (fy if forces else None), tick.value
 
     def step_into(self, n_ticks, s, ptr, zn, fx=None, fy=None):
         """step_snapshot straight into the caller's arrays: s [n, n_states] float64, ptr [n] int32, zn [n, 3] bool or uint8
@@ -281,14 +284,8 @@ class Engine:
         n = self.n
         key = (s.ctypes.data, ptr.ctypes.data, zn.ctypes.data, 0 if fx is None else fx.ctypes.data, 0 if fy is None else fy.ctypes.data, n)
         if getattr(self, "_into_key", None) != key:
-            if not (s.flags.c_contiguous and ptr.flags.c_contiguous and zn.flags.c_contiguous and s.shape == (n, self.ns) and s.dtype == np.float64
-                    and ptr.shape == (n,) and ptr.dtype == np.int32 and zn.shape == (n, 3) and zn.dtype.itemsize == 1):
-                raise ValueError("step_into: s [n, n_states] float64, ptr [n] int32, zn [n, 3] of one byte each, C-contiguous")
-            for f in (fx, fy):
-                if f is not None and not (f.flags.c_contiguous and f.shape == (n,) and f.dtype == np.float64):
-                    raise ValueError("step_into: fx, fy [n] float64, C-contiguous")
+            self._into_ptrs = self._readback_ptrs("step_into", (s, ptr, zn, fx, fy))
             self._into_key = key
-            self._into_ptrs = [_ptr(s), _ptr(ptr), _ptr(zn), None if fx is None else _ptr(fx), None if fy is None else _ptr(fy)]
             self._into_tick = C.c_int64(0)
         p = self._into_ptrs
         self._ck(self._lib.csf_step_get_tick(self._h, int(n_ticks), p[0], p[1], p[2], p[3], p[4], C.byref(self._into_tick)))
@@ -370,10 +367,7 @@ class Engine:
                 res.append((S, F))
             cache = engines[0]._rec_cache = (key, arr, outs, firsts, res)
         _, arr, outs, firsts, res = cache
-        lib = _ffi.load()
-        rc = lib.csf_batch_get_record(arr, len(engines), n_last, outs)
-        if rc != 0:
-            Engine._batch_raise(lib, rc, engines)
+        Engine._group_call("csf_batch_get_record", engines, arr, n_last, outs)
         return [None if r is None else (r[0], r[1], firsts[i]) for i, r in enumerate(res)]
 
     def pair_force(self, src, x, y, psi, apply_fov=False):
@@ -427,22 +421,26 @@ class Engine:
         self._ck(self._lib.csf_comm_init(self._h, buf, int(rank), int(world)))
 
     @staticmethod
+    def _group_call(symbol, engines, arr, *args, every_message=False):
+        """an entry point that takes an array of handles; a refusal raises with the members' messages - every member's, or
+        (batches) the distinct non-empty ones"""
+        lib = _ffi.load()
+        rc = getattr(lib, symbol)(arr, len(engines), *args)
+        if rc != 0:
+            msgs = [lib.csf_last_error(e._h).decode() for e in engines]
+            raise EngineError(f"[{rc}] " + "; ".join(msgs if every_message else dict.fromkeys(m for m in msgs if m)))
+
+    @staticmethod
     def loopback_group(engines):
         """One-device rehearsal of the sharded path (include/csf.h: csf_comm_init_loopback): the engines, all holding the
         same population, become ranks 0 .. len-1; step them together with Engine.step_group."""
-        lib = _ffi.load()
         arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
-        rc = lib.csf_comm_init_loopback(arr, len(engines))
-        if rc != 0:
-            raise EngineError(f"[{rc}] " + "; ".join(lib.csf_last_error(e._h).decode() for e in engines))
+        Engine._group_call("csf_comm_init_loopback", engines, arr, every_message=True)
 
     @staticmethod
     def step_group(engines, n_ticks=1, sync=False):
-        lib = _ffi.load()
         arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
-        rc = lib.csf_step_group(arr, len(engines), int(n_ticks))
-        if rc != 0:
-            raise EngineError(f"[{rc}] " + "; ".join(lib.csf_last_error(e._h).decode() for e in engines))
+        Engine._group_call("csf_step_group", engines, arr, int(n_ticks), every_message=True)
         if sync:
             engines[0].sync()
 
@@ -462,27 +460,16 @@ class Engine:
         return engines, (C.c_void_p * len(engines))(*[e._h for e in engines])
 
     @staticmethod
-    def _batch_raise(lib, rc, engines):
-        msgs = [m for m in (lib.csf_last_error(e._h).decode() for e in engines) if m]
-        raise EngineError(f"[{rc}] " + "; ".join(dict.fromkeys(msgs)))
-
-    @staticmethod
     def batch_join(engines):
         """The engines - independent scenes on one device - become one batch: Engine.step_batch steps them together, every
         member the one-wave tick takes in one launch per vehicle class.  Engine.batch_leave (or closing a member) dissolves it."""
         engines, arr = Engine._batch_array(engines, "batch_join")
-        lib = _ffi.load()
-        rc = lib.csf_batch_join(arr, len(engines))
-        if rc != 0:
-            Engine._batch_raise(lib, rc, engines)
+        Engine._group_call("csf_batch_join", engines, arr)
 
     @staticmethod
     def batch_leave(engines):
         engines, arr = Engine._batch_array(engines, "batch_leave")
-        lib = _ffi.load()
-        rc = lib.csf_batch_leave(arr, len(engines))
-        if rc != 0:
-            Engine._batch_raise(lib, rc, engines)
+        Engine._group_call("csf_batch_leave", engines, arr)
 
     @staticmethod
     def step_batch(engines, n_ticks=1, sync=False):
@@ -490,10 +477,7 @@ class Engine:
         if int(n_ticks) != n_ticks or n_ticks < 0:
             raise ValueError("step_batch: n_ticks must be an integer >= 0")
         engines, arr = Engine._batch_array(engines, "step_batch")
-        lib = _ffi.load()
-        rc = lib.csf_step_batch(arr, len(engines), int(n_ticks))
-        if rc != 0:
-            Engine._batch_raise(lib, rc, engines)
+        Engine._group_call("csf_step_batch", engines, arr, int(n_ticks))
         if sync:
             engines[0].sync()
 
@@ -511,23 +495,10 @@ class Engine:
         tout = (_ffi.TickOut * len(engines))()
         ticks = (C.c_int64 * len(engines))()
         for i, (e, o) in enumerate(zip(engines, outs)):
-            n = e.n
-            s, ptr, zn, fx, fy = (tuple(o) + (None,) * 5)[:5]
-            checks = ((s, (n, e.ns), np.float64), (ptr, (n,), np.int32), (zn, (n, 3), None), (fx, (n,), np.float64), (fy, (n,), np.float64))
-            for a, shape, dt in checks:
-                if a is None:
-                    continue
-                if not isinstance(a, np.ndarray) or not a.flags.c_contiguous or a.shape != shape or (dt is not None and a.dtype != dt) \
-                        or (dt is None and a.dtype.itemsize != 1):
-                    raise ValueError("step_batch_into: s [n, n_states] float64, ptr [n] int32, zn [n, 3] of one byte each, fx / fy [n] "
-                                     "float64, C-contiguous")
             t = tout[i]
-            t.s_out, t.dest_ptr, t.znav, t.Fx, t.Fy = [None if a is None else a.ctypes.data for a in (s, ptr, zn, fx, fy)]
+            t.s_out, t.dest_ptr, t.znav, t.Fx, t.Fy = e._readback_ptrs("step_batch_into", (tuple(o) + (None,) * 5)[:5])
             t.tick = C.cast(C.byref(ticks, i * C.sizeof(C.c_int64)), C.POINTER(C.c_int64))
-        lib = _ffi.load()
-        rc = lib.csf_step_batch_get_tick(arr, len(engines), int(n_ticks), tout)
-        if rc != 0:
-            Engine._batch_raise(lib, rc, engines)
+        Engine._group_call("csf_step_batch_get_tick", engines, arr, int(n_ticks), tout)
         return list(ticks)
 
     def batch_ticks(self):

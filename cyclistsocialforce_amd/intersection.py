@@ -617,17 +617,23 @@ class SocialForceIntersection:
             self._road_sig = sig
         return e
 
+    def _live(self):
+        """the bulk mirror's rows of the live road users (state, destination pointers, navigation state, Fx, Fy): one contiguous
+        block of each, what a read-back straight into the mirror writes"""
+        n = len(self.vehicles)
+        return self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n]
+
     def _pull(self, forces=True, advance=1, step=0):
         """One read-back of the device's view into the bulk mirror (vehicle.s, znav, traj are views of it); step: that many
         ticks first, in the same call (csf_step_get_tick)."""
         e = self._engine
         n = len(self.vehicles)
         if step and self._S.shape[1] == e.ns:
-            # straight into the bulk mirror: the rows of the live road users are one contiguous block of it
-            fx, fy = (self._fx[:n], self._fy[:n]) if forces else (None, None)
-            e.step_into(step, self._S[:n], self._ptr[:n], self._zn[:n], fx, fy)
-            if self._s_watched:
-                self._shadow[:n] = self._S[:n]
+            S, ptr, zn, fx, fy = self._live()
+            if not forces:
+                fx = fy = None
+            e.step_into(step, S, ptr, zn, fx, fy)
+            return self._booked_pull(fx, fy, forces, advance)
         else:
             s, ptr, zn, fx, fy, _ = e.step_snapshot(step, forces=forces, reuse=True) if step else e.tick_snapshot(forces=forces)
             self._S[:n, : s.shape[1]] = s
@@ -639,6 +645,20 @@ class SocialForceIntersection:
                 self._fx[:n] = fx                                     # intersection.py:860-862
                 self._fy[:n] = fy
         return self._book_pull(fx, fy, forces, advance)
+
+    def _booked_pull(self, fx, fy, forces, advance):
+        """_book_pull behind a read-back that went straight into the live rows (_pull, step_together): the watched shadow first"""
+        if self._s_watched:
+            n = len(self.vehicles)
+            self._shadow[:n] = self._S[:n]
+        return self._book_pull(fx, fy, forces, advance)
+
+    def _drawn_now(self):
+        """the vehicles with a drawing or saveForces (the only per-tick Python loop), listed anew when the population changed"""
+        if self._drawn_stale:
+            self._drawn = [v for v in self.vehicles if v.drawing is not None or v.saveForces]
+            self._drawn_stale = False
+        return self._drawn
 
     def _book_pull(self, fx, fy, forces, advance):
         """the host's per-tick bookkeeping behind a read-back into the bulk mirror (_pull; step_together): trajectory ring,
@@ -655,10 +675,7 @@ class SocialForceIntersection:
                 self._traj[ti[0], :n] = self._S[:n]                   # the usual case: everyone joined at tick 0
             else:
                 self._traj[ti, np.arange(n)] = self._S[:n]
-            if self._drawn_stale:
-                self._drawn = [v for v in self.vehicles if v.drawing is not None or v.saveForces]
-                self._drawn_stale = False
-            for v in self._drawn:
+            for v in self._drawn_now():
                 k = v._index
                 Fx, Fy = (fx[k], fy[k]) if forces else (0.0, 0.0)
                 if v.saveForces:
@@ -699,16 +716,23 @@ class SocialForceIntersection:
         elif n:
             self._traj[(ti0[None, :] + steps[:, None]) % T, np.arange(n)[None, :], :w] = S[k0:]
         self._ti[:n] = (ti0 + K) % T                                  # vehicle.py:1279-1282 (see DESIGN D5)
-        if self._drawn_stale:
-            self._drawn = [v for v in self.vehicles if v.drawing is not None or v.saveForces]
-            self._drawn_stale = False
-        for v in self._drawn:
+        for v in self._drawn_now():
             if v.saveForces:
                 k = v._index
                 cols = (ti0[k] + steps) % T
                 v.trajF[0, cols] = F[k0:, k, 0]
                 v.trajF[1, cols] = F[k0:, k, 1]
         self._pos_stale = True
+
+    def _booked_block(self, S, F):
+        """behind a chunk of recorded ticks whose last read-back went straight into the live rows (step_n(dense=True),
+        advance_together): what that many calls of step() leave on the host"""
+        self.is_first_step = False
+        if self._s_watched:
+            n = len(self.vehicles)
+            self._shadow[:n] = self._S[:n]
+        self._book_block(S, F)
+        self.hist_n_vecs.extend([self.n_bikes] * int(S.shape[0]))
 
     # vehicle.F: the per-tick magnitudes are logged as arrays and folded into a vehicle's list when it is read
     def _log_forces(self, fx, fy):
@@ -926,14 +950,8 @@ class SocialForceIntersection:
                     left -= 1
                     continue
                 k = min(left, DENSE_CHUNK)
-                n = len(self.vehicles)
-                tick = e.step_into(k, self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n])
-                S, F = e.recorded(tick - k, k)
-                self.is_first_step = False
-                if self._s_watched:
-                    self._shadow[:n] = self._S[:n]
-                self._book_block(S, F)
-                self.hist_n_vecs.extend([self.n_bikes] * k)
+                tick = e.step_into(k, *self._live())
+                self._booked_block(*e.recorded(tick - k, k))
                 left -= k
             return
         if self.n_bikes > 0 and (self._hooked or self._stochastic_riders()):   # (custom force hooks, drawn poles: every tick passes the host)
@@ -953,10 +971,9 @@ class SocialForceIntersection:
         if self.n_bikes <= 0 or self._hooked or (self.animate and self.is_first_step) or self._stochastic_riders():
             return None
         e = self._push_mutations()
-        n = len(self.vehicles)
         if self._S.shape[1] != e.ns:
             return None
-        return e, (self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n])
+        return e, self._live()
 
     def set_animated(self, animated):
         """intersection.py:899-915: switch every drawing between blitted (animated) and ordinary artists."""
@@ -1016,18 +1033,9 @@ def advance_together(intersections, n_ticks):
         if dense:
             engines = [e for _, e in dense]
             _batch_of(engines)
-            outs = []
-            for ins, _ in dense:
-                n = len(ins.vehicles)
-                outs.append((ins._S[:n], ins._ptr[:n], ins._zn[:n], ins._fx[:n], ins._fy[:n]))
-            Engine.step_batch_into(engines, k, outs)
+            Engine.step_batch_into(engines, k, [ins._live() for ins, _ in dense])
             for (ins, _), (S, F, _) in zip(dense, Engine.batch_recorded(engines, k)):
-                n = len(ins.vehicles)
-                ins.is_first_step = False
-                if ins._s_watched:
-                    ins._shadow[:n] = ins._S[:n]
-                ins._book_block(S, F)
-                ins.hist_n_vecs.extend([ins.n_bikes] * k)
+                ins._booked_block(S, F)
         left -= k
 
 
@@ -1051,9 +1059,7 @@ def step_together(intersections, n_ticks=1):
         engines = [e for _, e, _ in joined]
         _batch_of(engines)
         Engine.step_batch_into(engines, 1, [o for _, _, o in joined])
-        for ins, _, (S, _, _, fx, fy) in joined:
+        for ins, _, (_, _, _, fx, fy) in joined:
             ins.is_first_step = False
-            if ins._s_watched:
-                ins._shadow[:S.shape[0]] = S
-            ins._book_pull(fx, fy, True, 1)
+            ins._booked_pull(fx, fy, True, 1)
             ins.hist_n_vecs.append(ins.n_bikes)
