@@ -30,6 +30,7 @@ SYMBOLS = (
     "csf_get_integrator_state", "csf_set_integrator_state", "csf_mid_ticks", "csf_holes_taken",
     "csf_create_v", "csf_params_size", "csf_profile_samples_of", "csf_chase_ticks", "csf_chase_calibration", "csf_replace_agents",
     "csf_batch_join", "csf_batch_leave", "csf_step_batch", "csf_step_batch_get_tick", "csf_batch_ticks",
+    "csf_batch_mid_ticks", "csf_batch_launches",
     "csf_record", "csf_get_record", "csf_batch_get_record",
 )
 ABI_VERSION = 9
@@ -167,6 +168,9 @@ def load():
     L.csf_step_batch.argtypes = [C.POINTER(vp), i32, i64]
     L.csf_step_batch_get_tick.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(TickOut)]
     L.csf_batch_ticks.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_batch_mid_ticks"):        # (the same: an older build lacks these two)
+        L.csf_batch_mid_ticks.argtypes = [vp, C.POINTER(i64)]
+        L.csf_batch_launches.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "csf_record"):                 # (CSF_LIB may name an older build for an A/B measurement: it lacks these three)
         L.csf_record.argtypes = [vp, i32, i32, C.c_uint32]
         L.csf_get_record.argtypes = [vp, i64, i64, dp, dp]

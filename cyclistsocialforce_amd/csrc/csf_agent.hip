@@ -499,6 +499,27 @@ __global__ void chase_sync_kernel(const Dev d, float4 *rec_o, float4 *recg_o, fl
     if (through != nullptr && i == 0) *through = 0u;
 }
 
+// csf_step_batch: the same for every mid-size member of the table whose tick record asks (MID_DUE_SYNC), grid y = table slot.  The
+// records of such a member are not binned (no copy in binned order to keep), and nobody waits at a gate.
+__global__ void mid_sync_batch_kernel(const Dev *__restrict__ table, const MidTick *__restrict__ ticks) {
+    const MidTick t = ticks[blockIdx.y];
+    if (!(t.flags & MID_DUE_SYNC)) return;
+    Dev d = table[blockIdx.y];
+    mid_compose(d, t);                                            // (rec ...: this tick's halves, rec_w ...: the others)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n_pad) {
+        d.rec_w[i] = d.rec[i];
+        if (i < t.nrecg) d.recg_w[i] = d.recg[i];
+        if (d.has_bike) d.rec2_w[i] = d.rec2[i];
+    }
+    if (i < 3 * d.cap) const_cast<double *>(d.src64)[i] = d.s[i];
+}
+
+void launch_mid_batch_sync(const Dev *table, const MidTick *ticks, int slots, int64_t max_elems, hipStream_t st) {
+    if (slots <= 0 || max_elems <= 0) return;
+    hipLaunchKernelGGL(mid_sync_batch_kernel, dim3((unsigned)((max_elems + 255) / 256), (unsigned)slots), dim3(256), 0, st, table, ticks);
+}
+
 void launch_chase_sync(const Dev &d, float4 *rec_o, float4 *recg_o, float4 *recs_o, float2 *rec2_o, double *cur, int64_t nrecg, unsigned *through,
                        hipStream_t st) {
     const int64_t n = std::max<int64_t>(d.n_pad, 3 * d.cap);

@@ -109,8 +109,19 @@ __global__ void sorted_copy_kernel(const Dev d) {
 //     origin) is exact, the sum rounds once);
 //   * pos[], the copy of the records in binned order and scene coordinates, the batch's bounding circle.
 // Sentinel records stay as they are (the padding slot of the class-segmented order sits in many places at once).
-__global__ __launch_bounds__(256) void rebase_kernel(const Dev d) {
-    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+// csf_step_batch: the two kernels above for every member of the table whose tick record asks (MID_DUE_REBIN), grid y = table slot.
+// The member's Dev is copied into the kernel and composed with its tick record, as mid_batch_kernel does it.
+__global__ void identity_perm_batch_kernel(const Dev *__restrict__ table, const MidTick *__restrict__ ticks) {
+    const MidTick t = ticks[blockIdx.y];
+    if (!(t.flags & MID_DUE_REBIN)) return;
+    const int64_t n_pad = table[blockIdx.y].n_pad;
+    int32_t *const perm = table[blockIdx.y].perm;
+    const int64_t a = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a < n_pad) perm[a] = (int32_t)a;
+}
+
+template <class D>
+__device__ __forceinline__ void rebase_body(const D &d, const int64_t b) {
     if (b * 64 >= d.n_pad) return;
     const int lane = threadIdx.x & 63;
     const int64_t p = b * 64 + lane;
@@ -163,6 +174,16 @@ __global__ __launch_bounds__(256) void rebase_kernel(const Dev d) {
     if (real) d.recg[a] = q;
     if (d.has_bike) d.recs2[p] = d.rec2[a];
     if (lane == 0) d.bnd[b] = box_circle(x0, x1, y0, y1, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void rebase_kernel(const Dev d) { rebase_body(d, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)); }
+
+__global__ __launch_bounds__(256) void rebase_batch_kernel(const Dev *__restrict__ table, const MidTick *__restrict__ ticks) {
+    const MidTick t = ticks[blockIdx.y];
+    if (!(t.flags & MID_DUE_REBIN)) return;
+    Dev d = table[blockIdx.y];
+    mid_compose(d, t);
+    rebase_body(d, (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
 __global__ __launch_bounds__(256) void bounds_kernel(const Dev d) {
@@ -344,6 +365,12 @@ void launch_rebase(const Dev &d, hipStream_t st) {
     if (d.n_pad <= 0) return;
     const int64_t batches = d.n_pad / 64;
     hipLaunchKernelGGL(rebase_kernel, dim3((unsigned)((batches + 3) / 4)), dim3(256), 0, st, d);
+}
+
+void launch_mid_batch_rebin(const Dev *table, const MidTick *ticks, int slots, int64_t max_n_pad, hipStream_t st) {
+    if (slots <= 0 || max_n_pad <= 0) return;
+    hipLaunchKernelGGL(identity_perm_batch_kernel, dim3((unsigned)((max_n_pad + 255) / 256), (unsigned)slots), dim3(256), 0, st, table, ticks);
+    hipLaunchKernelGGL(rebase_batch_kernel, dim3((unsigned)((max_n_pad / 64 + 3) / 4), (unsigned)slots), dim3(256), 0, st, table, ticks);
 }
 
 void launch_bounds(const Dev &d, hipStream_t st) {

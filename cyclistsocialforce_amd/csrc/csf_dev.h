@@ -307,6 +307,36 @@ void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, 
 // csf_mid.hip: one tick of a mid-size population (plain pair sums + per-agent tick) in one launch; d.rec_w / recg_w / rec2_w /
 // src64_w point at the halves of the double buffers this tick does not read, d.mid_group = slots per workgroup
 bool launch_mid_tick(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_step_batch, mid-size members (csf_mid.hip: mid_batch_kernel): what changes in a member's Dev from tick to tick, 48 bytes
+// where the Dev is 1.3 KB.  The batch's table holds the rest - the halves of the double buffers by name, rec / recg / rec2 / src64 the
+// engine's first halves and rec_w / recg_w / rec2_w / src64_w its second - and the kernels compose the tick's Dev from the two.
+struct MidTick {
+    int64_t tick;            // Dev::tick
+    uint32_t edge_stamp;     // Dev::edge_stamp
+    uint32_t flags;          // MID_SWAP_*: this tick READS the second half; MID_DUE_*: the periodic work of this tick (the batched
+                             // launches in front of it: mid_batch_rebin, mid_batch_sync)
+    float fovA, fovB, sideA, sideB, fovT0, fovT1;   // the rounding bands of the tick (csf_engine.hip: set_fov_band)
+    int32_t nrecg;           // MID_DUE_SYNC: elements of recg that the other half takes
+    int32_t pad;
+};
+constexpr uint32_t MID_SWAP_REC = 1, MID_SWAP_RECG = 2, MID_SWAP_REC2 = 4, MID_SWAP_SRC64 = 8, MID_DUE_REBIN = 256, MID_DUE_SYNC = 512;
+__host__ __device__ __forceinline__ void mid_compose(Dev &d, const MidTick &t) {
+    if (t.flags & MID_SWAP_REC) { float4 *x = d.rec; d.rec = d.rec_w; d.rec_w = x; }
+    if (t.flags & MID_SWAP_RECG) { float4 *x = d.recg; d.recg = d.recg_w; d.recg_w = x; }
+    if (t.flags & MID_SWAP_REC2) { float2 *x = d.rec2; d.rec2 = d.rec2_w; d.rec2_w = x; }
+    if (t.flags & MID_SWAP_SRC64) { double *x = const_cast<double *>(d.src64); d.src64 = d.src64_w; d.src64_w = x; }
+    d.tick = t.tick;
+    d.edge_stamp = t.edge_stamp;
+    d.pc.fovA = t.fovA, d.pc.fovB = t.fovB, d.pc.sideA = t.sideA, d.pc.sideB = t.sideB, d.pc.fovT0 = t.fovT0, d.pc.fovT1 = t.fovT1;
+}
+bool mid_shape_ok(const Dev &d);   // launch_mid_tick / mid_batch_kernel take this population in groups of d.mid_group
+// one tick of the `n_groups` groups listed in `groups` (table slot, group within the member), all of vehicle class `model` and one priority rule
+void launch_mid_batch(int model, bool p2r, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st);
+// the periodic work of the members whose MidTick says so, one launch each whatever their number (grid y = table slot; the x
+// extents are the largest member's): the plain order and every record re-expressed (launch_identity_perm + launch_rebase: two
+// launches), the other halves made equal (launch_chase_sync without the binned copy)
+void launch_mid_batch_rebin(const Dev *table, const MidTick *ticks, int slots, int64_t max_n_pad, hipStream_t st);
+void launch_mid_batch_sync(const Dev *table, const MidTick *ticks, int slots, int64_t max_elems, hipStream_t st);
 const char *pair_kernel_name(const Dev &d);           // the kernel launch_pair() takes for this engine
 void launch_records(const Dev &d, hipStream_t st);  // rebuild fp32 records from the fp64 state
 // csf_get_tick: row-major state [n, ns], Fx [n], Fy [n] (doubles), destination pointers [n] (int32), navigation state

@@ -10,6 +10,22 @@
 // (csf_record) are numbered from - is 0 in the table: a recording member's count is a word of its own in device memory
 // (Dev::rec_tick) that the launch reads and moves on itself.  The host knows what the word holds (csf_engine::rec_tick_dev) and
 // writes it in stream order only where the engine has ticked outside the batched launch since.
+//
+// Mid-size members - those the one-launch tick takes (tick.inc: mid_fused_ok), without a road (the road term is a launch of its
+// own per tick: such members stay in turn), without wave traces, with nothing pending, and at least two of them - are stepped
+// together too: tick by tick, one launch of mid_batch_kernel (csf_mid.hip) per vehicle class and priority rule present.  Their
+// Dev differs on every tick (the halves of the double buffers trade places, tick, stamp, rounding bands), so a second table holds
+// each member's Dev in a form that does not (mid_canon), renewed like the first one, and the kernel composes the tick's Dev from
+// it and the member's MidTick (csf_dev.h: 48 bytes).  The host knows these records in advance: it writes them for a STRETCH of
+// ticks - up to MID_STRETCH, ending in front of the next tick on which some member re-bins or measures its coordinate bound
+// again - into pinned staging, copies them in one go and enqueues the stretch's launches.  Per tick that is O(members) host
+// work and 48 bytes per member.  The periodic work of the stretch's first tick - the re-binning on the plain order, the copy into
+// the other halves - runs for all members that are due in one launch each (csf_bin.hip: rebase_batch_kernel ...); its host side
+// stays per member (binning.inc: rebin).  A member that stops qualifying behind a re-binning finishes the call in turn.
+// The host books the ticks of a stretch (halves traded, counters, tick) BEFORE the stretch is enqueued.  An error return in
+// between - a failed HIP call - therefore leaves the mid-size members of the batch ahead of the device by up to a stretch: such
+// an error is not a refusal, and the members' states are not a simulation after it; they are to be uploaded again (csf_push_state)
+// or destroyed.
 
 extern "C++" {
 
@@ -27,14 +43,42 @@ struct BatchState {
     std::vector<uint8_t> snapped;                // per member: its read-back is in its mapped snapshot buffer (1: packed by the
                                                  // batched launch, 2: by its own one-wave launch), 0: not
     std::vector<int32_t> slot_member;            // table slot -> member
+    // mid-size members: their Dev records in canonical form (table slot = place in `mid` at the call's start), the workgroups of a
+    // tick (slot, group within the member) sorted by launch, the tick records of a stretch
+    std::vector<int32_t> mid;                    // members the batched one-launch tick takes, by launch (class, priority rule)
+    std::vector<uint8_t> mid_out;                // per slot: the member left the batched tick in mid-call
+    DevBuf<Dev> mtable;
+    HostBuf<Dev, false> mstage;
+    std::vector<Dev> mshadow;
+    std::vector<uint8_t> mheld;
+    hipEvent_t mcopied = nullptr;
+    bool mcopy_pending = false;
+    DevBuf<int2> mgroups;
+    HostBuf<int2, false> mgroups_stage;
+    std::vector<int2> mgroups_now, mgroups_dev;  // what this call wants / what the device holds
+    struct MidLaunch { int model, p2r, beg, end; };
+    std::vector<MidLaunch> mlaunch;
+    DevBuf<MidTick> mticks;                      // [MID_STRETCH][members]
+    HostBuf<MidTick, false> mticks_stage;        // two of them, used in turn
+    hipEvent_t mticked[2] = {nullptr, nullptr};
+    bool mticked_pending[2] = {false, false};
+    unsigned mstretch = 0;
+    int64_t launches = 0;                        // csf_batch_launches
     RecGather rgather;                           // csf_batch_get_record
     std::vector<RecAsk> asks;
     ~BatchState() {   // (the last copy from `stage` has ended before the members below go, `stage` among them)
         (void)hipSetDevice(device);
         if (copy_pending && copied) (void)hipEventSynchronize(copied);
         if (copied) (void)hipEventDestroy(copied);
+        if (mcopy_pending && mcopied) (void)hipEventSynchronize(mcopied);
+        if (mcopied) (void)hipEventDestroy(mcopied);
+        for (int h = 0; h < 2; h++) {
+            if (mticked_pending[h] && mticked[h]) (void)hipEventSynchronize(mticked[h]);
+            if (mticked[h]) (void)hipEventDestroy(mticked[h]);
+        }
     }
 };
+constexpr int MID_STRETCH = 64;   // ticks whose records one copy carries at most (CSF_REBIN_TICKS' default: a stretch per re-binning)
 
 // Every member goes back to its own stream, and the batch's table, staging and event go with the last reference to it.
 static int batch_dissolve(csf_engine *e) {
@@ -78,6 +122,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
         if (end > run0) {
             HIPCHK(b.members[0], hipMemcpyAsync(b.table.p + run0, b.stage.p + run0, (end - run0) * sizeof(Dev), hipMemcpyHostToDevice, st));
             runs++;
+            b.launches++;
         }
         return CSF_OK;
     };
@@ -118,6 +163,267 @@ static int batch_table(BatchState &b, hipStream_t st) {
     return CSF_OK;
 }
 
+// ---- mid-size members ---------------------------------------------------------------------------------------------------------
+// could the batched one-launch tick take this member (behind upload_all and the calibration)?
+static bool batch_mid_ok(const csf_engine *e) {
+    return e->knobs.batch_mid != 0 && mid_fused_ok(e) && e->d.nv == 0 && e->d.atrace == nullptr && e->pend.empty() && !e->dirty;
+}
+
+// A member's Dev as the table holds it: what enqueue_mid_tick's launch sees, but for what changes from tick to tick - the halves
+// by name, not by role; tick, stamp and bands zero (csf_dev.h: mid_compose puts them in) - and the flags that say which halves
+// this tick reads.
+static uint32_t mid_canon(const csf_engine *e, Dev &dd) {
+    std::memcpy((void *)&dd, (const void *)&e->d, sizeof(Dev));
+    uint32_t fl = 0;
+    if (e->d.rec != e->rec.p) fl |= MID_SWAP_REC;
+    if (e->d.recg != e->recg.p) fl |= MID_SWAP_RECG;
+    if (e->d.rec2 != e->rec2.p) fl |= MID_SWAP_REC2;
+    if (!e->mid_cur_is_a) fl |= MID_SWAP_SRC64;
+    dd.rec = e->rec.p, dd.rec_w = e->rec_alt.p;
+    dd.recg = e->recg.p, dd.recg_w = e->recg_alt.p;
+    dd.rec2 = e->rec2.p, dd.rec2_w = e->rec2_alt.p;
+    dd.src64 = e->src64_a.p, dd.src64_w = e->src64_b.p;
+    dd.mid_group = mid_group_for(e);
+    dd.tick = 0;
+    dd.edge_stamp = 0;
+    dd.pc.fovA = dd.pc.fovB = dd.pc.sideA = dd.pc.sideB = dd.pc.fovT0 = dd.pc.fovT1 = 0.0f;
+    return fl;
+}
+
+// the table's slot j <- member's Dev where it changed (one copy per slot: members change one at a time, at their re-binnings)
+static int mid_table_slot(BatchState &b, size_t j, const Dev &dd, bool *waited, bool *copied) {
+    if (b.mheld[j] && std::memcmp((const void *)&b.mshadow[j], (const void *)&dd, sizeof(Dev)) == 0) return CSF_OK;
+    if (!*waited && b.mcopy_pending) {                            // (an earlier copy may still read the staging memory)
+        HIPCHK(b.members[0], hipEventSynchronize(b.mcopied));
+        b.mcopy_pending = false;
+    }
+    *waited = true;
+    std::memcpy((void *)&b.mstage.p[j], (const void *)&dd, sizeof(Dev));
+    std::memcpy((void *)&b.mshadow[j], (const void *)&dd, sizeof(Dev));
+    b.mheld[j] = 1;
+    *copied = true;
+    return CSF_OK;
+}
+
+// ... and the copies: one per run of changed slots
+static int mid_table_flush(BatchState &b, const std::vector<uint8_t> &changed, hipStream_t st) {
+    const size_t k = changed.size();
+    bool any = false;
+    for (size_t j = 0; j < k;) {
+        if (!changed[j]) {
+            j++;
+            continue;
+        }
+        size_t end = j;
+        while (end < k && changed[end]) end++;
+        HIPCHK(b.members[0], hipMemcpyAsync(b.mtable.p + j, b.mstage.p + j, (end - j) * sizeof(Dev), hipMemcpyHostToDevice, st));
+        b.launches++;
+        any = true;
+        j = end;
+    }
+    if (any) {
+        HIPCHK(b.members[0], hipEventRecord(b.mcopied, st));
+        b.mcopy_pending = true;
+    }
+    return CSF_OK;
+}
+
+// the workgroups of a tick, launch by launch: (slot, group) of every group of every member that is still in; copied where the
+// list differs from what the device holds
+static int mid_groups(BatchState &b, csf_engine *const *engines, hipStream_t st) {
+    csf_engine *e0 = b.members[0];
+    b.mgroups_now.clear();
+    b.mlaunch.clear();
+    for (size_t j = 0; j < b.mid.size(); j++) {
+        if (b.mid_out[j]) continue;
+        const csf_engine *e = engines[b.mid[j]];
+        const int model = e->d.p.model, p2r = e->d.p.priority_rule == CSF_P2R ? 1 : 0;
+        if (b.mlaunch.empty() || b.mlaunch.back().model != model || b.mlaunch.back().p2r != p2r)
+            b.mlaunch.push_back({model, p2r, (int)b.mgroups_now.size(), (int)b.mgroups_now.size()});
+        const int G = mid_group_for(e), groups = (int)((e->d.hi - e->d.lo + G - 1) / G);
+        for (int g = 0; g < groups; g++) b.mgroups_now.push_back(make_int2((int)j, g));
+        b.mlaunch.back().end = (int)b.mgroups_now.size();
+    }
+    const size_t n = b.mgroups_now.size();
+    if (n == b.mgroups_dev.size() && (n == 0 || std::memcmp(b.mgroups_now.data(), b.mgroups_dev.data(), n * sizeof(int2)) == 0)) return CSF_OK;
+    if (b.mgroups.n < n || b.mgroups_stage.n < n) {              // (allocations synchronise: membership changed)
+        HIPCHK(e0, hipStreamSynchronize(st));
+        HIPCHK(e0, b.mgroups.alloc(2 * n));
+        HIPCHK(e0, b.mgroups_stage.alloc(2 * n));
+    } else {
+        HIPCHK(e0, hipStreamSynchronize(st));                     // (the last copy from the staging memory; once per change of membership)
+    }
+    std::memcpy(b.mgroups_stage.p, b.mgroups_now.data(), n * sizeof(int2));
+    HIPCHK(e0, hipMemcpyAsync(b.mgroups.p, b.mgroups_stage.p, n * sizeof(int2), hipMemcpyHostToDevice, st));
+    b.launches++;
+    b.mgroups_dev = b.mgroups_now;
+    return CSF_OK;
+}
+
+// a member that the batched tick no longer takes (behind mid_prelude: this tick's bounds are in place): what was deferred is
+// enqueued for it alone, and it finishes the call in turn
+static int mid_leave(csf_engine *e, int64_t ticks_left) {
+    e->mid_defer = false;
+    if (e->mid_deferred & MID_DUE_REBIN) {
+        launch_identity_perm(e->d, e->main);
+        launch_rebase(e->d, e->main);
+    }
+    if (e->mid_deferred & MID_DUE_SYNC) e->mid_synced = false;
+    e->mid_deferred = 0;
+    int rc = enqueue_two_launch_tick(e, true);
+    for (int64_t t = 1; t < ticks_left && !rc; t++) rc = enqueue_tick(e, ticks_left - t);
+    if (!rc) rc = chase_join(e);
+    if (e->cal_phase >= 1 && e->cal_phase <= 3) e->cal_phase = 0;  // (as step_impl: a measurement does not span calls)
+    e->device_ahead = true;                                        // (it has ticked, whatever the batch does with the others)
+    return rc;
+}
+
+// n_ticks ticks of the members in b.mid (at least two; batch_mid_ok held for each when the call began)
+static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_ticks) {
+    csf_engine *e0 = b.members[0];
+    hipStream_t st = e0->main;
+    const size_t k = b.mid.size(), cap = b.members.size();
+    int rc;
+    // everything that allocates (and so synchronises) in front of the tick loop
+    if (b.mtable.n < cap) {
+        HIPCHK(e0, b.mtable.alloc(cap));
+        HIPCHK(e0, b.mstage.alloc(cap));
+        HIPCHK(e0, b.mticks.alloc(cap * MID_STRETCH));
+        HIPCHK(e0, b.mticks_stage.alloc(2 * cap * MID_STRETCH));
+        HIPCHK(e0, hipEventCreateWithFlags(&b.mcopied, hipEventDisableTiming));
+        for (hipEvent_t &ev : b.mticked) HIPCHK(e0, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        b.mshadow.resize(cap);
+        b.mheld.assign(cap, 0);
+    }
+    for (int32_t i : b.mid) {
+        csf_engine *e = engines[i];
+        if ((rc = chase_join(e))) return rc;
+        if ((rc = alt_alloc(e))) return rc;
+    }
+    // by launch: vehicle class, then priority rule; join order within
+    std::stable_sort(b.mid.begin(), b.mid.end(), [&](int32_t x, int32_t y) {
+        const Dev &dx = engines[x]->d, &dy = engines[y]->d;
+        const int px = dx.p.priority_rule == CSF_P2R, py = dy.p.priority_rule == CSF_P2R;
+        return dx.p.model != dy.p.model ? dx.p.model < dy.p.model : px < py;
+    });
+    b.mid_out.assign(k, 0);
+    struct Defer {   // (the members go back to enqueueing their own periodic launches on every way out)
+        BatchState &b;
+        csf_engine *const *engines;
+        ~Defer() {
+            for (int32_t i : b.mid) engines[i]->mid_defer = false;
+        }
+    } guard{b, engines};
+    for (int32_t i : b.mid) engines[i]->mid_defer = true, engines[i]->mid_deferred = 0;
+    bool regroup = true;
+    std::vector<uint8_t> changed(k, 0);
+    std::vector<OtherHalves> halves(k);
+    for (int64_t t = 0; t < n_ticks;) {
+        // the stretch's first tick: whatever is periodic - re-binning, a coordinate bound measured again, halves made equal
+        std::fill(changed.begin(), changed.end(), 0);
+        const unsigned h = b.mstretch++ & 1u;
+        if (b.mticked_pending[h]) {                               // (the copy of the stretch before last read this staging half)
+            HIPCHK(e0, hipEventSynchronize(b.mticked[h]));
+            b.mticked_pending[h] = false;
+        }
+        MidTick *const stage = b.mticks_stage.p + (size_t)h * cap * MID_STRETCH;
+        bool waited = false;
+        uint32_t due = 0;
+        int64_t max_n_pad = 0, max_sync = 0;
+        size_t in = 0;
+        auto tick_of = [&](size_t j, int64_t row, bool head) -> int {
+            csf_engine *e = engines[b.mid[j]];
+            bool take = false;
+            int rc2 = mid_prelude(e, &take);
+            if (rc2) return rc2;
+            Dev dd;
+            uint32_t fl = 0;
+            if (take) {
+                fl = mid_canon(e, dd);
+                take = mid_shape_ok(dd);
+            }
+            if (!take && !head) return fail(e, CSF_E_STATE, "a member of the batched one-launch tick changed inside a stretch of ticks");
+            if (!take) {                                          // (only ever on a stretch's first tick: nothing else changes a Dev)
+                b.mid_out[j] = 1;
+                regroup = true;
+                stage[(size_t)row * k + j] = MidTick{};
+                return mid_leave(e, n_ticks - t);
+            }
+            if (!head && std::memcmp((const void *)&b.mshadow[j], (const void *)&dd, sizeof(Dev)) != 0)
+                return fail(e, CSF_E_STATE, "a member of the batched one-launch tick changed inside a stretch of ticks");
+            if (head) {
+                bool cp = false;
+                if ((rc2 = mid_table_slot(b, j, dd, &waited, &cp))) return rc2;
+                changed[j] = cp;
+            }
+            MidTick &m = stage[(size_t)row * k + j];
+            m.tick = e->d.tick;
+            m.edge_stamp = e->d.edge_stamp;
+            m.flags = fl | e->mid_deferred;
+            const PairConsts &pc = e->d.pc;
+            m.fovA = pc.fovA, m.fovB = pc.fovB, m.sideA = pc.sideA, m.sideB = pc.sideB, m.fovT0 = pc.fovT0, m.fovT1 = pc.fovT1;
+            m.nrecg = (int32_t)std::min((size_t)e->d.n_pad, e->recg.n);
+            m.pad = 0;
+            if (e->mid_deferred) {
+                due |= e->mid_deferred;
+                max_n_pad = std::max(max_n_pad, e->d.n_pad);
+                max_sync = std::max(max_sync, std::max<int64_t>(e->d.n_pad, 3 * e->d.cap));
+                e->mid_deferred = 0;
+            }
+            mid_ticked(e, other_halves(e), true);
+            e->device_ahead = true;
+            return CSF_OK;
+        };
+        for (size_t j = 0; j < k; j++) {
+            if (b.mid_out[j]) {                                   // (its slot asks for nothing)
+                stage[j] = MidTick{};
+                continue;
+            }
+            if ((rc = tick_of(j, 0, true))) return rc;
+            if (!b.mid_out[j]) in++;
+        }
+        if (in == 0) return CSF_OK;                               // (every member left: each has finished the call in turn)
+        // ... and the ticks behind it, up to the next one on which a member has periodic work
+        int64_t T = 1;
+        for (; T < MID_STRETCH && t + T < n_ticks; T++) {
+            bool quiet = true;
+            for (size_t j = 0; j < k && quiet; j++) {
+                if (b.mid_out[j]) continue;
+                const csf_engine *e = engines[b.mid[j]];
+                quiet = !rebin_due(e) && e->mid_synced && !e->bound_stale;
+            }
+            if (!quiet) break;
+            for (size_t j = 0; j < k; j++) {
+                if (b.mid_out[j]) continue;
+                if ((rc = tick_of(j, T, false))) return rc;
+            }
+        }
+        if ((rc = mid_table_flush(b, changed, st))) return rc;
+        if (regroup && (rc = mid_groups(b, engines, st))) return rc;
+        regroup = false;
+        HIPCHK(e0, hipMemcpyAsync(b.mticks.p, stage, (size_t)T * k * sizeof(MidTick), hipMemcpyHostToDevice, st));
+        HIPCHK(e0, hipEventRecord(b.mticked[h], st));
+        b.mticked_pending[h] = true;
+        b.launches++;
+        if (due & MID_DUE_REBIN) {
+            launch_mid_batch_rebin(b.mtable.p, b.mticks.p, (int)k, max_n_pad, st);
+            b.launches += 2;
+        }
+        if (due & MID_DUE_SYNC) {
+            launch_mid_batch_sync(b.mtable.p, b.mticks.p, (int)k, max_sync, st);
+            b.launches++;
+        }
+        for (int64_t r = 0; r < T; r++)
+            for (const BatchState::MidLaunch &l : b.mlaunch) {
+                launch_mid_batch(l.model, l.p2r != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
+                b.launches++;
+            }
+        HIPCHK(e0, hipGetLastError());
+        t += T;
+    }
+    return CSF_OK;
+}
+
 static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_ticks, const csf_tick_out *out) {
     int rc = batch_check(engines, count);
     if (rc) return rc;
@@ -128,6 +434,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
     const bool want_snap = out != nullptr;
     b.small.clear();
     b.rest.clear();
+    b.mid.clear();
     b.snapped.assign((size_t)count, 0);
     // the members the one-wave launch takes get step_impl's prelude; the others are stepped by step_impl itself
     for (int32_t i = 0; i < count; i++) {
@@ -136,6 +443,11 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
         const bool take = n_ticks > 0 && !e->order.empty() && (e->comm_calibrated || (rc = calibrate_comm_stream(e)) == CSF_OK) && small_fused_ok(e);
         if (rc) return rc;
         if (!take) {
+            // (small_fused_ok is false, so the calibration ran - or failed - above, where n_ticks > 0 and the member has road users)
+            if (n_ticks > 0 && !e->order.empty() && e->comm_calibrated && batch_mid_ok(e)) {
+                b.mid.push_back(i);
+                continue;
+            }
             bool snapped = false;
             if ((rc = step_impl(e, n_ticks, want_snap, &snapped))) return rc;
             b.snapped[(size_t)i] = snapped ? 2 : 0;
@@ -147,6 +459,14 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
         b.snapped[(size_t)i] = pack;
         b.small.push_back(i);
     }
+    if (b.mid.size() == 1) {                                      // a single mid-size member: stepped as it is alone
+        bool snapped = false;
+        if ((rc = step_impl(engines[b.mid[0]], n_ticks, want_snap, &snapped))) return rc;
+        b.snapped[(size_t)b.mid[0]] = snapped ? 2 : 0;
+        b.rest.push_back(b.mid[0]);
+        b.mid.clear();
+    }
+    if (b.mid.size() >= 2 && (rc = step_batch_mid(b, engines, n_ticks))) return rc;
     if (!b.small.empty()) {
         // table slots: the one-wave members by vehicle class, in join order within a class - one launch per class
         b.slot_member.clear();
@@ -168,6 +488,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
             HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)e->d.rec_tick, (int)(uint32_t)((uint64_t)e->d.tick & 0xffffffffu), 1, e0->main));
             HIPCHK(e, hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)e->d.rec_tick + 1), (int)(uint32_t)((uint64_t)e->d.tick >> 32), 1, e0->main));
             e->rec_tick_dev = e->d.tick;
+            b.launches += 2;
         }
         for (int64_t t = 0; t < n_ticks;) {
             const int k = small_launch_ticks(n_ticks - t);
@@ -176,6 +497,7 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
                 const int cnt = cls_beg[m + 1] - cls_beg[m];
                 if (cnt == 0) continue;
                 launch_small_batch(m, b.table.p + cls_beg[m], cnt, cls_nv[m], k, pack, e0->main);
+                b.launches++;
                 HIPCHK(e0, hipGetLastError());
             }
             for (int32_t i : b.small) small_ticked(engines[i], k, true);
@@ -284,5 +606,18 @@ int csf_batch_get_record(csf_engine *const *engines, int32_t count, int64_t n_la
 int csf_batch_ticks(const csf_engine *e, int64_t *n_ticks) try {
     if (!e || !n_ticks) return CSF_E_ARG;
     *n_ticks = e->batch_ticks;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_batch_mid_ticks(const csf_engine *e, int64_t *n_ticks) try {
+    if (!e || !n_ticks) return CSF_E_ARG;
+    *n_ticks = e->batch_mid_ticks;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_batch_launches(const csf_engine *e, int64_t *n_launches) try {
+    if (!e || !n_launches) return CSF_E_ARG;
+    if (!e->batch) return CSF_E_STATE;           // (not a member; no message is written: the call changes nothing)
+    *n_launches = e->batch->launches;
     return CSF_OK;
 } catch (...) { return csf_caught(e); }

@@ -223,6 +223,9 @@ int rebin(csf_engine *e) {
     d.classify = binned;
     update_far_radius(e);
     const bool track = binned && !seg && e->world <= 1 && !e->loopback;
+    // (a mid-size member of a batch on the plain order: the batch runs the two launches for all members that are due - abi_batch.inc)
+    const bool defer = e->mid_defer && !seg && !binned;
+    if (defer) e->mid_deferred |= MID_DUE_REBIN;
     if (seg) {
         Dev ds = d;
         ds.perm = e->rlist.p;                                        // the sorted slots, before the runs are moved apart
@@ -232,7 +235,7 @@ int rebin(csf_engine *e) {
     } else if (binned) {
         int rc = launch_rebin(d, e->sort_keys.p, e->sort_keys_out.p, e->sort_vals.p, e->sort_tmp.p, e->sort_tmp.n, e->main);
         if (rc != 0) return fail(e, CSF_E_DEVICE, "radix sort of the record bins failed (%d)", rc);
-    } else {
+    } else if (!defer) {
         launch_identity_perm(d, e->main);
     }
     // Every precise record gets a new origin - where the road user is now - and is re-expressed relative to it; pos[],
@@ -241,7 +244,7 @@ int rebin(csf_engine *e) {
     // pair launch of a sharded run (enqueue_tick).
     d.recs_valid = binned;
     d.rebase_from_state = e->state_all_current;
-    launch_rebase(d, e->main);
+    if (!defer) launch_rebase(d, e->main);
     {   // receivers in binned order + far-tile skipping, where there are enough tiles for it to pay.  A rank that owns
         // an index block [lo, hi) takes ITS receivers in binned order: their positions, sorted
         const int ov = e->knobs.recv_binned;

@@ -222,31 +222,61 @@ static int mid_sync(csf_engine *e, unsigned *through = nullptr) {
     return CSF_OK;
 }
 
-// (behind bounds_before_pair - the re-binning: new origins of the precise records, and a new d.n_src, which the gate reads)
-static int enqueue_mid_tick(csf_engine *e) {
-    Dev &d = e->d;
+// The one-launch tick in three parts, which csf_step (below) and the mid-size members of a batch (abi_batch.inc) both run: what
+// comes in front of the launch, the launch's view of the engine, and the book-keeping behind it.
+//
+// In front: the re-binning where it is due (new origins of the precise records, and a new d.n_src, which the gate reads: *take
+// false - the bounds are in place, the caller carries on with two launches), the rounding bands, the other halves made equal.
+// With csf_engine::mid_defer the launches of a re-binning on the plain order and of the copy are noted in mid_deferred instead.
+static int mid_prelude(csf_engine *e, bool *take) {
+    *take = false;
     int rc;
+    if ((rc = bounds_before_pair(e))) return rc;
+    if (!mid_fused_ok(e)) return CSF_OK;
     if ((rc = set_fov_band(e))) return rc;
-    if (!e->mid_synced && (rc = mid_sync(e))) return rc;
-    if (d.nv > 0) launch_road(d, e->main);
-    const OtherHalves o = other_halves(e);
-    Dev dd = d;
-    write_other_halves(dd, o, false);                             // (this tick writes no binned copy)
-    // road users per workgroup: about one workgroup (of eight waves, at the per-agent code's 255 registers a CU holds one) per CU
+    if (!e->mid_synced) {
+        if (e->mid_defer && !e->d.recs_valid && e->rec_alt.n >= e->rec.n) {
+            e->mid_deferred |= MID_DUE_SYNC;
+            e->chase_resume = false;
+            e->mid_synced = true;
+        } else if ((rc = mid_sync(e))) return rc;
+    }
+    *take = true;
+    return CSF_OK;
+}
+
+// road users per workgroup: about one workgroup (of eight waves, at the per-agent code's 255 registers a CU holds one) per CU
+static int mid_group_for(const csf_engine *e) {
     int G = e->knobs.mid_group;
     if (G != 4 && G != 8 && G != 16 && G != 32) {
         G = 4;
-        while (G < 32 && (d.hi - d.lo + G - 1) / G > 256) G *= 2;
+        while (G < 32 && (e->d.hi - e->d.lo + G - 1) / G > 256) G *= 2;
     }
-    dd.mid_group = G;
-    // (nothing has traded places yet: a refused launch leaves the engine where it was)
-    if (!launch_mid_tick(dd, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, G);
-    HIPCHK(e, hipGetLastError());
+    return G;
+}
+
+// behind the launch: the halves trade places, the counters move on
+static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched) {
     trade_halves(e, o, false);
     bounds_after_pair(e, true);
     e->moves++;
     e->mid_ticks++;
-    d.tick++;
+    if (batched) e->batch_mid_ticks++;
+    e->d.tick++;
+}
+
+// (behind mid_prelude)
+static int enqueue_mid_tick(csf_engine *e) {
+    Dev &d = e->d;
+    if (d.nv > 0) launch_road(d, e->main);
+    const OtherHalves o = other_halves(e);
+    Dev dd = d;
+    write_other_halves(dd, o, false);                             // (this tick writes no binned copy)
+    dd.mid_group = mid_group_for(e);
+    // (nothing has traded places yet: a refused launch leaves the engine where it was)
+    if (!launch_mid_tick(dd, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, dd.mid_group);
+    HIPCHK(e, hipGetLastError());
+    mid_ticked(e, o, false);
     return CSF_OK;
 }
 
@@ -478,8 +508,9 @@ static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engin
 
 //   main:  agent(DEST) - wait(ev_gather) - bounds - pair - road - agent(COMBINE|INTEGRATE) - record(ev_integ)
 //   comm:  wait(ev_integ) - all-gather(records) - record(ev_gather)
+static int enqueue_two_launch_tick(csf_engine *e, bool bounds_done);
+
 static int enqueue_tick(csf_engine *e, int64_t ticks_left = 1) {
-    Dev &d = e->d;
     if (chase_take(e, ticks_left)) {                              // the per-agent launch beside the pair launch (large populations)
         int rcp = CSF_OK;
         csf_engine::ProfSlot *ps = prof_slot(e, &rcp);
@@ -492,13 +523,20 @@ static int enqueue_tick(csf_engine *e, int64_t ticks_left = 1) {
     }
     bool bounds_done = false;
     if (mid_fused_ok(e)) {
-        // the re-binning inside may move d.n_src past what the one-launch tick takes: ask again behind it, and carry on with
-        // two launches (the bounds are in place) rather than lose the tick
-        int rcb = bounds_before_pair(e);
+        // the re-binning inside may move d.n_src past what the one-launch tick takes: mid_prelude asks again behind it, and the
+        // tick carries on with two launches (the bounds are in place) rather than be lost
+        bool take = false;
+        int rcb = mid_prelude(e, &take);
         if (rcb) return rcb;
         bounds_done = true;
-        if (mid_fused_ok(e)) return enqueue_mid_tick(e);
+        if (take) return enqueue_mid_tick(e);
     }
+    return enqueue_two_launch_tick(e, bounds_done);
+}
+
+// the pair launch and the per-agent launch in turn (bounds_done: bounds_before_pair has run for this tick)
+static int enqueue_two_launch_tick(csf_engine *e, bool bounds_done) {
+    Dev &d = e->d;
     e->mid_synced = false;
     const bool sharded = e->world > 1 || e->nccl != nullptr || e->loopback;  // a 1-rank communicator rehearses the sharded path
     int rc = CSF_OK;

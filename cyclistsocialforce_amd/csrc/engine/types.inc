@@ -174,6 +174,7 @@ struct Knobs {
     int pair_variant = -1;                    // CSF_PAIR_VARIANT (-1: by population size)
     int64_t rebin_ticks = 64;                 // CSF_REBIN_TICKS: ticks between two re-binnings (1 .. 120; the tests that step 40 - 48 ticks "across a re-binning" pin 32)
     int fused_mid = 1;                        // CSF_FUSED_MID=0: mid-size populations take a pair launch and a per-agent launch per tick (csf_mid.hip: one launch)
+    int batch_mid = 1;                        // CSF_BATCH_MID=0: the mid-size members of a batch are stepped in turn (engine/abi_batch.inc)
     int mid_below = 0;                        // CSF_MID_BELOW: ... for populations smaller than this (0: by vehicle class, mid_below_for)
     int mid_group = 0;                        // CSF_MID_GROUP: road users per workgroup of it, 4 / 8 / 16 / 32 (0: about one workgroup per CU)
     int chase = 1;                            // CSF_CHASE: 0 the per-agent launch behind the pair launch, 2 beside it (enqueue_chase_tick), 1 [default] whichever the engine measures faster on its first stretch of eligible ticks
@@ -226,6 +227,7 @@ struct Knobs {
         fused_small = geti("CSF_FUSED_SMALL", 1);
         fused_mid = geti("CSF_FUSED_MID", 1);
         mid_below = geti("CSF_MID_BELOW", 0);
+        batch_mid = geti("CSF_BATCH_MID", 1);
         mid_group = geti("CSF_MID_GROUP", 0);
         rebin_ticks = std::max(1, std::min(120, geti("CSF_REBIN_TICKS", 64)));
         segments = geti("CSF_SEGMENTS", -1);
@@ -515,7 +517,13 @@ struct csf_engine {
     // engine's own stream, kept for when it leaves (the members tick on the first member's)
     std::shared_ptr<struct BatchState> batch;
     std::shared_ptr<StreamHold> own_hold;
-    int64_t batch_ticks = 0;         // ticks run inside a batched launch (csf_batch_ticks)
+    int64_t batch_ticks = 0;         // ticks run inside a batched ONE-WAVE launch (csf_batch_ticks)
+    int64_t batch_mid_ticks = 0;     // ticks run inside a batched one-launch tick (csf_batch_mid_ticks; mid_ticks counts them too)
+    // csf_step_batch, mid-size members: the launches of a re-binning on the plain order (identity order, records re-expressed) and
+    // the copy into the other halves are not enqueued by rebin / mid_prelude but noted here (MID_DUE_*): the batch runs them for
+    // all its members that are due in one launch each
+    bool mid_defer = false;
+    uint32_t mid_deferred = 0;
 
     // profiling: a fixed pool of event slots, recycled in order (the oldest slot is resolved into the running sums
     // before it is reused, so stepping with profiling left on holds a bounded number of events)

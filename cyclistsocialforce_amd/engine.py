@@ -507,6 +507,18 @@ class Engine:
         self._ck(self._lib.csf_batch_ticks(self._h, C.byref(n)))
         return n.value
 
+    def batch_mid_ticks(self):
+        """ticks this engine has run inside a batched one-launch tick of mid-size members (csf.h: csf_batch_mid_ticks)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_batch_mid_ticks(self._h, C.byref(n)))
+        return n.value
+
+    def batch_launches(self):
+        """launches and copies enqueued for the batched members of this engine's batch since the join (csf.h: csf_batch_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_batch_launches(self._h, C.byref(n)))
+        return n.value
+
     def shard_range(self):
         lo, hi = C.c_int64(0), C.c_int64(0)
         self._ck(self._lib.csf_shard_range(self._h, C.byref(lo), C.byref(hi)))

@@ -304,7 +304,11 @@ int csf_step_group(csf_engine *const *engines, int32_t world, int64_t n_ticks);
  * not sharded, not in a loopback group and not in another batch; otherwise the call is refused and nothing changes.  The
  * members then share one HIP stream (each member's own stream is waited for first).  csf_step_batch steps every member by
  * n_ticks: the members the one-wave tick takes (see csf_small_ticks) run in ONE launch per vehicle class present - one wave
- * per scene, all ticks of the call - and every other member is stepped by csf_step in turn.  Bit for bit what csf_step on
+ * per scene, all ticks of the call -; the members the one-launch tick takes (see csf_mid_ticks: 33 ... 2 175 road users of one
+ * parameter set), where the batch has at least two of them, run tick by tick in ONE launch per vehicle class and priority rule
+ * present; every other member is stepped by csf_step in turn - among them a mid-size member with road edges (its road term is
+ * a launch of its own per tick), with several parameter sets, a BalancingRider or UncontrolledVehicle population above 32 road
+ * users, and a single mid-size member.  CSF_BATCH_MID=0 steps the mid-size members in turn as well.  Bit for bit what csf_step on
  * each member would give.  `engines` must be the batch in join order.  csf_batch_leave dissolves the batch, and so does
  * csf_destroy of a member: the others go on as single engines, and csf_step_batch on them fails with CSF_E_STATE. */
 int csf_batch_join(csf_engine *const *engines, int32_t count);
@@ -333,8 +337,14 @@ typedef struct csf_record_out {
     int64_t *first_sample;
 } csf_record_out;
 int csf_batch_get_record(csf_engine *const *engines, int32_t count, int64_t n_last, const csf_record_out *out);
-/* ticks this engine has run inside a batched launch (csf_small_ticks counts them too) */
+/* ticks this engine has run inside a batched ONE-WAVE launch (csf_small_ticks counts them too) */
 int csf_batch_ticks(const csf_engine *e, int64_t *n_ticks);
+/* ticks this engine has run inside a batched one-launch tick of mid-size members (csf_mid_ticks counts them too) */
+int csf_batch_mid_ticks(const csf_engine *e, int64_t *n_ticks);
+/* kernel launches and copy commands that csf_step_batch / csf_step_batch_get_tick have enqueued for the batched members - one-wave
+ * and mid-size - of this engine's batch since csf_batch_join; what csf_step enqueues for the members stepped in turn is not
+ * counted.  CSF_E_STATE: the engine is in no batch. */
+int csf_batch_launches(const csf_engine *e, int64_t *n_launches);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 

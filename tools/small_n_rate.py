@@ -15,8 +15,9 @@ from cyclistsocialforce_amd import parameters  # noqa: E402
 from cyclistsocialforce_amd.engine import Engine  # noqa: E402
 
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
+SIZES = tuple(int(v) for v in sys.argv[2].split(",")) if len(sys.argv) > 2 else (3, 128, 1024)   # (second argument: the sizes)
 for model in ("bicycle", "twod", "invpend", "planarpoint"):
-    for n in (3, 128, 1024):
+    for n in SIZES:
         box = max(10.0, float(np.sqrt(n / 0.41)))
         s0, off, dq = synthetic_population(n, box, reach=tuple(50.0 * k for k in range(1, 14)))
         if model == "invpend":
