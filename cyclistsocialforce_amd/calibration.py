@@ -1,0 +1,407 @@
+"""Calibration of rider-model parameters against recorded trajectories (the reference's calibration.py).
+
+The names and signatures are the reference's: `calc_sse_timesteps`, `calc_maesse_samples`, `CalibrationData`,
+`DownhillSimplexCalibration` (constructor, `_update_params_args_dict`, `simulate_single`, `run`, `test`, `param_args_opt`).
+What differs is where the work is done: the data set is loaded onto the device once (`Engine.calib_load`), and an evaluation of
+the objective is one kernel launch for ALL sequences and up to 256 candidate parameter sets (`Engine.calib_eval`); with one of the
+two error functions above the error is summed on the device, so no trajectory is copied back.  On top of the reference's
+interface: `evaluate` (many parameter vectors -> their errors, one launch) and `run_many` (independent downhill-simplex runs in
+lockstep, every iteration of all of them one launch).
+
+Two things are not the reference's:
+  * a simulated sample is the state AFTER each tick, compared with the objective row of that tick (what the reference's `test`
+    extracts: traj[:, 1 : i + 1]); the reference's `simulate_single` returns traj[:, :n], which leads with the start state;
+  * `CalibrationData` is built from plain arrays (the reference's builds on the `trajdatamanager` package).
+"""
+import numpy as np
+
+from .engine import Engine
+
+TRAJ_ROWS = 6  # rows of vehicle.traj an objective can name: x, y, psi, v, delta, theta (calibration.py:352-357)
+
+
+# --------------------------------------------------------------------------- error functions
+def calc_sse_timesteps(outputs, objectives):
+    """Sum of squared errors over all time steps of all samples (calibration.py:27-50)."""
+    return sum(float(np.square(np.asarray(out) - np.asarray(obj)).sum()) for out, obj in zip(outputs, objectives))
+
+
+def calc_maesse_samples(outputs, objectives):
+    """Sum over the samples of the squared mean absolute error of each (calibration.py:53-77)."""
+    per_sample = [np.abs(np.asarray(out) - np.asarray(obj)).mean() for out, obj in zip(outputs, objectives)]
+    return float(np.square(per_sample).sum()) if per_sample else 0
+
+
+def objective_function_wrapper(params_vals, calibration):
+    """The objective with the signature scipy's optimisers want (calibration.py:80-105)."""
+    return float(calibration.evaluate(np.asarray(params_vals, dtype=float)[None, :])[0])
+
+
+def _indicators(ind, name, n):
+    """boolean indicator array of length n from booleans or 0 / 1 integers (utils.validate_boolean_indicators)"""
+    a = np.asarray(ind)
+    if a.shape != (n,):
+        raise ValueError(f"{name} must have {n} entries, one per feature (got shape {a.shape})")
+    if a.dtype != bool:
+        if not np.all((a == 0) | (a == 1)):
+            raise ValueError(f"{name} must hold booleans or 0 / 1")
+        a = a.astype(bool)
+    return a
+
+
+# --------------------------------------------------------------------------- data
+class Track:
+    """One time series: data [n_t, n_features] and the keys of its columns; track["x"] is a column."""
+
+    def __init__(self, data, data_feature_keys):
+        self.data = np.asarray(data, dtype=float)
+        self.data_feature_keys = list(data_feature_keys)
+        if self.data.ndim != 2 or self.data.shape[1] != len(self.data_feature_keys):
+            raise ValueError("a track is [n_t, n_features] with one key per feature")
+
+    def __getitem__(self, key):
+        return self.data[:, self.data_feature_keys.index(key)]
+
+
+class CalibrationData:
+    """A collection of tracks, each one sample of the data set (calibration.py:111-240).
+
+    tracks: a list of [n_t, n_features] arrays (then `feature_keys` names their columns) or of Track objects.  Iterating yields
+    (s0, input_data, objective_data) per track as calibration.py:165-208: the start state (x, y, psi, v, delta, theta - the last two
+    0 where the tracks lack them) and rows 1 .. of the input and objective columns."""
+
+    def __init__(self, tracks, objective_features, input_features, feature_keys=None):
+        self.tracks = [t if isinstance(t, Track) else Track(t, feature_keys if feature_keys is not None else ()) for t in tracks]
+        if not self.tracks:
+            raise ValueError("no tracks")
+        nf = self.tracks[0].data.shape[1]
+        if any(t.data.shape[1] != nf for t in self.tracks):
+            raise ValueError("the tracks of a data set share their features")
+        self.objective_features = _indicators(objective_features, "objective_features", nf)
+        self.input_features = _indicators(input_features, "input_features", nf)
+
+    def __len__(self):
+        return len(self.tracks)
+
+    def __iter__(self):
+        self._i_iter = 0
+        return self
+
+    def __next__(self):
+        if self._i_iter >= len(self.tracks):
+            raise StopIteration
+        trk = self.tracks[self._i_iter]
+        self._i_iter += 1
+        s0 = np.zeros(TRAJ_ROWS)
+        for k, key in enumerate(("x", "y", "psi", "v")):
+            s0[k] = trk[key][0]
+        if "delta" in trk.data_feature_keys:
+            s0[4] = trk["delta"][0]
+        if "theta" in trk.data_feature_keys:
+            s0[5] = trk["theta"][0]
+        return s0, trk.data[1:, self.input_features], trk.data[1:, self.objective_features]
+
+    def partition(self, n_seq, shares, random_seed=None):
+        """n_seq random subsets holding the given shares of the tracks (a seeded NumPy permutation; the last takes the rest)."""
+        shares = np.asarray(shares, dtype=float)
+        if shares.shape != (n_seq,) or abs(shares.sum() - 1.0) > 1e-9 or np.any(shares < 0):
+            raise ValueError("shares: n_seq non-negative numbers that sum to 1")
+        n = len(self.tracks)
+        perm = np.random.default_rng(random_seed).permutation(n)
+        cuts = np.floor(np.cumsum(shares)[:-1] * n + 1e-9).astype(int)
+        return [CalibrationData([self.tracks[i] for i in part], self.objective_features, self.input_features)
+                for part in np.split(perm, cuts)]
+
+
+# --------------------------------------------------------------------------- downhill simplex, ask / tell
+class NelderMead:
+    """scipy.optimize.fmin's downhill simplex (Nelder and Mead 1965) turned inside out: `ask()` names the points whose values the
+    next decision needs, `tell(values)` takes them.  Rules, arithmetic and order of operations are fmin's - initial simplex 5 % /
+    0.00025, reflection 1, expansion 2, contraction 0.5, shrink 0.5, xtol = ftol = 1e-4 - so the simplices are the same to the
+    last bit.  An iteration asks for reflection, expansion and both contractions at once (one launch for the caller) and uses
+    what the rule needs; a shrink asks once more.  `maxiter` must be given: fmin then limits no function calls, and neither does this
+    class (without it fmin also caps the CALLS at 200 per parameter, counted along its own sequence of evaluations - not restated)."""
+
+    def __init__(self, x0, xtol=1e-4, ftol=1e-4, maxiter=None):
+        if maxiter is None:
+            raise ValueError("NelderMead: maxiter must be given (see the class docstring)")
+        x0 = np.atleast_1d(np.asarray(x0, dtype=float)).flatten()
+        self.N = N = len(x0)
+        self.xtol, self.ftol = xtol, ftol
+        self.maxiter = maxiter
+        sim = np.empty((N + 1, N), dtype=x0.dtype)
+        sim[0] = x0
+        for k in range(N):
+            y = np.array(x0, copy=True)
+            y[k] = (1 + 0.05) * y[k] if y[k] != 0 else 0.00025
+            sim[k + 1] = y
+        self.sim = sim
+        self.fsim = np.full((N + 1,), np.inf, dtype=float)
+        self.iterations = 0
+        self.state = "init"
+
+    @property
+    def done(self):
+        return self.state == "done"
+
+    @property
+    def x(self):
+        return self.sim[0]
+
+    @property
+    def fun(self):
+        return np.min(self.fsim)
+
+    def _sort(self):
+        ind = np.argsort(self.fsim)
+        self.sim = np.take(self.sim, ind, 0)
+        self.fsim = np.take(self.fsim, ind, 0)
+
+    def _next(self):
+        sim, fsim = self.sim, self.fsim
+        if not self.iterations < self.maxiter or (np.max(np.ravel(np.abs(sim[1:] - sim[0]))) <= self.xtol
+                                                 and np.max(np.abs(fsim[0] - fsim[1:])) <= self.ftol):
+            self.state = "done"
+            return
+        rho, chi, psi = 1, 2, 0.5
+        xbar = np.add.reduce(sim[:-1], 0) / self.N
+        self._cand = np.array([(1 + rho) * xbar - rho * sim[-1], (1 + rho * chi) * xbar - rho * chi * sim[-1],
+                               (1 + psi * rho) * xbar - psi * rho * sim[-1], (1 - psi) * xbar + psi * sim[-1]])
+        self.state = "iter"
+
+    def ask(self):
+        if self.state == "init":
+            return self.sim.copy()
+        if self.state == "iter":
+            return self._cand.copy()
+        if self.state == "shrink":
+            return self.sim[1:].copy()
+        return np.empty((0, self.N))
+
+    def tell(self, f):
+        f = np.asarray(f, dtype=float)
+        sim, fsim = self.sim, self.fsim
+        if self.state == "init":
+            fsim[:] = f
+            self._sort()
+            self._sort()
+            self.iterations = 1
+            self._next()
+            return
+        if self.state == "shrink":
+            fsim[1:] = f
+        elif self.state == "iter":
+            (xr, xe, xc, xcc), (fxr, fxe, fxc, fxcc) = self._cand, f
+            doshrink = False
+            if fxr < fsim[0]:
+                if fxe < fxr:
+                    sim[-1], fsim[-1] = xe, fxe
+                else:
+                    sim[-1], fsim[-1] = xr, fxr
+            elif fxr < fsim[-2]:
+                sim[-1], fsim[-1] = xr, fxr
+            elif fxr < fsim[-1]:
+                if fxc <= fxr:
+                    sim[-1], fsim[-1] = xc, fxc
+                else:
+                    doshrink = True
+            else:
+                if fxcc < fsim[-1]:
+                    sim[-1], fsim[-1] = xcc, fxcc
+                else:
+                    doshrink = True
+            if doshrink:
+                for j in range(1, self.N + 1):
+                    sim[j] = sim[0] + 0.5 * (sim[j] - sim[0])
+                self.state = "shrink"
+                return
+        else:
+            raise RuntimeError("tell() on a finished run")
+        self.iterations += 1
+        self._sort()
+        self._next()
+
+
+def minimize_many(func_many, guesses, xtol=1e-4, ftol=1e-4, maxiter=None):
+    """Independent downhill-simplex runs in lockstep: func_many([m, N] points) -> [m] values is called once per round with what
+    every live run asks for.  Returns a list of (xopt, fopt, iterations), what scipy.optimize.fmin returns for each guess."""
+    runs = [NelderMead(g, xtol=xtol, ftol=ftol, maxiter=maxiter) for g in guesses]
+    while True:
+        asks = [(r, r.ask()) for r in runs if not r.done]
+        if not asks:
+            break
+        vals = np.asarray(func_many(np.concatenate([a for _, a in asks], axis=0)), dtype=float)
+        at = 0
+        for r, a in asks:
+            r.tell(vals[at:at + len(a)])
+            at += len(a)
+    return [(r.x.copy(), float(r.fun), r.iterations) for r in runs]
+
+
+# --------------------------------------------------------------------------- the calibration
+class ReplayedVehicle:
+    """What simulate_single(return_vehicles=True) hands back per sample: `traj` [6, n + 1] (column 0: the start state, column
+    i: the state after tick i; rows the vehicle class lacks stay 0), `i` = n ticks, `s` the last state."""
+
+    def __init__(self, traj, vid):
+        self.traj = traj
+        self.i = traj.shape[1] - 1
+        self.s = traj[:, -1].copy()
+        self.id = vid
+
+
+class DownhillSimplexCalibration:
+    """Fit parameters of a vehicle class to recorded trajectories by downhill simplex (calibration.py:243-526).  Arguments as the
+    reference's; `device` and `max_sets` (parameter sets per launch, at most 256) are this package's."""
+
+    def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
+                 fix_speed=True, maxiter=100, params_auxfuncs=None, params_auxfuncsargs=None, verbose=True, device=0, max_sets=256):
+        n_keys = len(params_keys)
+        if params_auxfuncs is None:
+            if params_auxfuncsargs is not None:
+                raise ValueError("params_auxfuncsargs without params_auxfuncs")
+        else:
+            params_auxfuncs = list(params_auxfuncs)
+            params_auxfuncsargs = [{} for _ in params_auxfuncs] if params_auxfuncsargs is None else list(params_auxfuncsargs)
+            for name, lst in (("params_auxfuncs", params_auxfuncs), ("params_auxfuncsargs", params_auxfuncsargs)):
+                if len(lst) != n_keys:
+                    raise ValueError(f"{name} has {len(lst)} entries, params_keys names {n_keys} parameters")
+        self.vehicle_type, self.params_keys = vehicle_type, params_keys
+        self.params_auxfuncs, self.params_auxfuncsargs = params_auxfuncs, params_auxfuncsargs
+        self.train_data, self.test_data = train_data, test_data
+        self.objective_features_traj = _indicators(objective_features_traj, "objective_features_traj", TRAJ_ROWS)
+        self.error_func, self.fix_speed, self.maxiter, self.verbose = error_func, fix_speed, maxiter, verbose
+        self.param_args_opt = None
+        self.device, self.max_sets = device, int(max_sets)
+        self._sets = {}
+
+    def close(self):
+        for ds in self._sets.values():
+            ds["engine"].close()
+        self._sets = {}
+
+    def _update_params_args_dict(self, params_vals):
+        """the optimiser's vector -> keyword arguments of the vehicle class's parameter object: value k belongs to params_keys[k],
+        or, with auxiliary functions, key k gets params_auxfuncs[k](params_vals, **params_auxfuncsargs[k])"""
+        if self.params_auxfuncs is None:
+            return dict(zip(self.params_keys, params_vals))
+        return {key: fn(params_vals, **kw) for key, fn, kw in zip(self.params_keys, self.params_auxfuncs, self.params_auxfuncsargs)}
+
+    def _pod(self, params_args):
+        return self.vehicle_type.PARAMS_TYPE(**params_args).to_pod(self.vehicle_type.MODEL)
+
+    def _dataset(self, test=False):
+        """the engine that holds the training (test) data, loaded on first use"""
+        ds = self._sets.get(bool(test))
+        if ds is not None:
+            return ds
+        data = self.test_data if test else self.train_data
+        samples = [(s0, np.asarray(i, dtype=float), np.asarray(o, dtype=float)) for s0, i, o in data]
+        feat = np.flatnonzero(self.objective_features_traj).astype(np.int32)
+        n_seq = len(samples)
+        lens = np.array([i.shape[0] for _, i, _ in samples], dtype=np.int32)
+        T = int(lens.max())
+        Fx, Fy, obj = np.zeros((T, n_seq)), np.zeros((T, n_seq)), np.zeros((T, n_seq, feat.size))
+        s0s = np.zeros((n_seq, 8))
+        for k, (s0, inp, o) in enumerate(samples):
+            if o.shape != (lens[k], feat.size):
+                raise ValueError(f"sample {k}: the objective has shape {o.shape}, objective_features_traj selects {feat.size} rows of vehicle.traj")
+            Fx[: lens[k], k], Fy[: lens[k], k], obj[: lens[k], k] = inp[:, 0], inp[:, 1], o
+            s0s[k, :TRAJ_ROWS] = s0
+        sets = max(1, min(self.max_sets, 256))
+        engine = Engine(self._pod({}), sets * n_seq, device=self.device)
+        engine.calib_load(s0s, Fx, Fy, obj, feat, lengths=lens, max_sets=sets)
+        ds = dict(engine=engine, lens=lens, feat=feat, n_seq=n_seq, sets=sets, s0=s0s, objectives=[o for _, _, o in samples])
+        self._sets[bool(test)] = ds
+        return ds
+
+    def _trajs(self, ds, states, k):
+        """the samples of parameter set k from the states of one evaluation: [len, n_feat] each (rows the class lacks: 0)"""
+        ns = states.shape[2]
+        out = []
+        for q in range(ds["n_seq"]):
+            tr = np.zeros((ds["lens"][q], ds["feat"].size))
+            for c, f in enumerate(ds["feat"]):
+                if f < ns:
+                    tr[:, c] = states[: ds["lens"][q], k * ds["n_seq"] + q, f]
+            out.append(tr)
+        return out
+
+    def evaluate(self, params_vals, test=False):
+        """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them.  With calc_sse_timesteps or
+        calc_maesse_samples the error is formed from the sums the device returns; another error_func gets the trajectories."""
+        vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
+        ds = self._dataset(test)
+        pods = [self._pod(self._update_params_args_dict(v)) for v in vals]
+        err = np.zeros(len(pods))
+        for at in range(0, len(pods), ds["sets"]):
+            chunk = pods[at:at + ds["sets"]]
+            if self.error_func is calc_sse_timesteps:
+                err[at:at + len(chunk)] = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed)[:, :, 0].sum(axis=1)
+            elif self.error_func is calc_maesse_samples:
+                sums = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed)
+                with np.errstate(invalid="ignore", divide="ignore"):   # (an empty sample: nan, as np.mean gives)
+                    err[at:at + len(chunk)] = ((sums[:, :, 1] / (ds["lens"] * float(ds["feat"].size))[None, :]) ** 2).sum(axis=1)
+            else:
+                _, states = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed, states=True)
+                for k in range(len(chunk)):
+                    err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
+        return err
+
+    def simulate_single(self, params_args, return_vehicles=False, test=False):
+        """One parameter set on every sample of the training (test) data (calibration.py:397-470): the samples' trajectories
+        [n, n_feat] - the state after each tick - or, with return_vehicles, ReplayedVehicle objects; and the objectives."""
+        ds = self._dataset(test)
+        _, states = ds["engine"].calib_eval([self._pod(params_args)], fix_speed=self.fix_speed, states=True)
+        if not return_vehicles:
+            return self._trajs(ds, states, 0), list(ds["objectives"])
+        ns = states.shape[2]
+        vehicles = []
+        for q in range(ds["n_seq"]):
+            n = int(ds["lens"][q])
+            traj = np.zeros((TRAJ_ROWS, n + 1))
+            traj[:, 0] = ds["s0"][q, :TRAJ_ROWS]
+            traj[: min(ns, TRAJ_ROWS), 1:] = states[:n, q, :TRAJ_ROWS].T
+            vehicles.append(ReplayedVehicle(traj, self.vehicle_type.__name__))
+        return vehicles, list(ds["objectives"])
+
+    def run(self, params_vals_guess):
+        """The calibration by scipy.optimize.fmin, as the reference runs it (calibration.py:472-526): returns fmin's full output
+        with the samples replayed at the optimum appended."""
+        from scipy.optimize import fmin
+
+        if self.verbose:
+            print(f"Calibrating {self.vehicle_type.__name__} ...")
+        results = list(fmin(objective_function_wrapper, params_vals_guess, (self,), full_output=True, maxiter=self.maxiter,
+                            disp=bool(self.verbose)))
+        param_args = self._update_params_args_dict(results[0])
+        if self.verbose:
+            for key in param_args.keys():
+                print(f"         {key}: {param_args[key]}")
+        results.append(self.simulate_single(param_args, return_vehicles=True))
+        self.param_args_opt = param_args
+        return results
+
+    def run_many(self, guesses):
+        """Independent calibrations from several guesses, in lockstep: every iteration of all live runs is one launch (a shrink one
+        more).  Returns a list of (xopt, fopt, iterations) - per guess what `run` finds from it - and keeps the best in
+        param_args_opt."""
+        res = minimize_many(self.evaluate, [np.asarray(g, dtype=float) for g in guesses], maxiter=self.maxiter)
+        best = min(res, key=lambda r: r[1])
+        self.param_args_opt = self._update_params_args_dict(best[0])
+        return res
+
+    def test(self, param_args_opt=None, plot_results=False, color="blue", axes=None, name=None, plot_inref=True):
+        """Error of a parameter set - by default the one `run` / `run_many` found - on the TEST data; returns (error, vehicles).
+        The plotting arguments of the reference's signature are accepted; plotting itself is not part of this package."""
+        if plot_results:
+            raise NotImplementedError("DownhillSimplexCalibration.test: plotting is not provided; plot the returned vehicles' traj")
+        args = self.param_args_opt if param_args_opt is None else param_args_opt
+        if args is None:
+            raise RuntimeError("no parameters to test: call run() or run_many() first, or pass param_args_opt")
+        vehicles, objectives = self.simulate_single(args, test=True, return_vehicles=True)
+        rows = self.objective_features_traj
+        error = self.error_func([v.traj[rows, 1: v.i + 1].T for v in vehicles], objectives)
+        if self.verbose:
+            print(f"test error on {len(vehicles)} samples: {error:.6g}")
+        return error, vehicles

@@ -16,4 +16,5 @@
 #include "engine/abi_forces_readback.inc"   // C ABI: forces on their own, replay, read-backs, the single-function entry points
 #include "engine/abi_sharding.inc"   // C ABI: communicators, loopback groups
 #include "engine/abi_batch.inc"   // C ABI: batches of independent scenes (one launch per vehicle class for all one-wave members)
+#include "engine/abi_calib.inc"   // C ABI: calibration - a resident data set, many parameter sets evaluated per launch (csf_calib.hip)
 #include "engine/abi_measurement.inc"   // C ABI: far-field radius, time stamps, counters

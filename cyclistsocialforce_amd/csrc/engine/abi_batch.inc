@@ -533,6 +533,7 @@ int csf_batch_join(csf_engine *const *engines, int32_t count) try {
             if (engines[q] == e) return fail(e, CSF_E_ARG, "engine listed twice");
         if (e->device != engines[0]->device) return fail(e, CSF_E_ARG, "the members of a batch are on one device");
         if (e->batch) return fail(e, CSF_E_STATE, "engine already belongs to a batch");
+        if (int crc = calib_refuses(e, "csf_batch_join")) return crc;
         if (e->loopback) return fail(e, CSF_E_STATE, "members of a loopback group cannot join a batch");
         if (e->nccl || e->world > 1) return fail(e, CSF_E_STATE, "a sharded engine cannot join a batch");
     }

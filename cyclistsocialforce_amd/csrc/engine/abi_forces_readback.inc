@@ -3,6 +3,7 @@
 
 int csf_calc_forces(csf_engine *e) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_calc_forces")) return crc;
     HIPCHK(e, hipSetDevice(e->device));
     int rc = upload_all(e);
     if (rc) return rc;
@@ -27,6 +28,7 @@ int csf_calc_forces(csf_engine *e) try {
 
 int csf_apply_forces(csf_engine *e, const double *Fx, const double *Fy) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_apply_forces")) return crc;
     if (!Fx || !Fy) return fail(e, CSF_E_ARG, "csf_apply_forces: NULL force array");
     HIPCHK(e, hipSetDevice(e->device));
     if (e->world > 1) return fail(e, CSF_E_STATE, "csf_apply_forces is a single-device entry point");
@@ -58,6 +60,7 @@ int csf_apply_forces(csf_engine *e, const double *Fx, const double *Fy) try {
 int csf_replay_forces(csf_engine *e, int64_t n_ticks, const double *Fx, const double *Fy, const int32_t *lengths,
                       int32_t fix_speed, int32_t stride, double *states_out) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_replay_forces")) return crc;
     if (n_ticks < 0 || stride < 1 || (n_ticks > 0 && (!Fx || !Fy))) return fail(e, CSF_E_ARG, "csf_replay_forces: bad arguments");
     if (e->world > 1) return fail(e, CSF_E_STATE, "csf_replay_forces is a single-device entry point");
     if (lengths)
@@ -125,6 +128,7 @@ int csf_replay_forces(csf_engine *e, int64_t n_ticks, const double *Fx, const do
 int csf_dest_force(csf_engine *e, double *Fx, double *Fy) try {
     if (!e) return CSF_E_ARG;
     if (!Fx || !Fy) return fail(e, CSF_E_ARG, "csf_dest_force: NULL output");
+    if (int crc = calib_refuses(e, "csf_dest_force")) return crc;
     HIPCHK(e, hipSetDevice(e->device));
     int rc = upload_all(e);
     if (rc) return rc;
@@ -252,6 +256,7 @@ int csf_status(csf_engine *e, uint32_t *per_agent_flags) try {
 
 // (re)allocates the rings; everything that can fail first, then the old rings go: a refused call changes nothing
 static int rings_setup(csf_engine *e, int32_t stride, int32_t capacity, bool forces, bool fast) {
+    if (int crc = calib_refuses(e, "csf_record / csf_enable_history")) return crc;
     HIPCHK(e, hipSetDevice(e->device));
     int rc = csf_sync(e);
     if (rc) return rc;
@@ -428,6 +433,7 @@ int csf_untracked(csf_engine *e, uint8_t *out) try {
 
 static int nav_kat(csf_engine *e, int64_t n, const int32_t *idx, int what, const int32_t *stop, double *vd, double *ddest) {
     if (n < 0 || (n > 0 && !idx)) return fail(e, CSF_E_ARG, "bad agent list");
+    if (int crc = calib_refuses(e, "csf_update_destination / csf_update_nav_state")) return crc;
     for (int64_t k = 0; k < n; k++)
         if (idx[k] < 0 || idx[k] >= (int64_t)e->order.size()) return fail(e, CSF_E_ARG, "agent index %d out of range", idx[k]);
     HIPCHK(e, hipSetDevice(e->device));

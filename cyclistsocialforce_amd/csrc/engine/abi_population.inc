@@ -33,6 +33,7 @@ static void side_state(csf_engine *e, size_t a, const csf_params &p) {
 // over them (csf_replace_agents)
 static int add_agents_impl(csf_engine *e, int64_t n, const double *s0, const double *v_desired, const int64_t *q_off, const double *q_rows) {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_add_agents")) return crc;
     if (n < 0 || (n > 0 && (!s0 || !v_desired))) return fail(e, CSF_E_ARG, "csf_add_agents: bad arguments");
     int64_t q_total = 0;
     if (q_off != nullptr) {
@@ -190,6 +191,7 @@ int csf_remove_agents(csf_engine *e, int64_t n, const int32_t *idx);
 int csf_replace_agents(csf_engine *e, int64_t n_leave, const int32_t *idx_leave, int64_t n_arrive, const double *s0, const double *v_desired,
                        const int64_t *q_offsets, const double *q_rows) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_replace_agents")) return crc;
     if (n_leave < 0 || n_arrive < 0 || (n_arrive > 0 && (!q_offsets || !q_rows))) return fail(e, CSF_E_ARG, "csf_replace_agents: bad arguments");
     if ((int64_t)e->order.size() - n_leave + n_arrive > e->cap_user) return fail(e, CSF_E_CAPACITY, "capacity %lld exceeded", (long long)e->cap_user);
     int rc = n_leave > 0 ? csf_remove_agents(e, n_leave, idx_leave) : CSF_OK;
@@ -199,6 +201,7 @@ int csf_replace_agents(csf_engine *e, int64_t n_leave, const int32_t *idx_leave,
 
 int csf_remove_agents(csf_engine *e, int64_t n, const int32_t *idx) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_remove_agents")) return crc;
     if (n < 0 || (n > 0 && !idx)) return fail(e, CSF_E_ARG, "csf_remove_agents: bad arguments");
     HIPCHK(e, hipSetDevice(e->device));
     const int64_t pop = (int64_t)e->order.size();
@@ -318,7 +321,7 @@ int csf_set_dest_queue(csf_engine *e, int64_t n, const int32_t *agent, const int
         if (rc) return rc;
     }
     if (!patch) {
-        int rc = prepare_mutation(e);
+        int rc = prepare_mutation(e, true);                // (a loaded calibration engine takes a route for its vehicles: abi_calib.inc)
         if (rc) return rc;
     }
     for (int64_t k = 0; k < n; k++) {
@@ -382,12 +385,14 @@ int csf_set_road_vertices(csf_engine *e, int32_t n_edges, const int64_t *offsets
 
 int csf_set_incremental(csf_engine *e, int32_t on) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_set_incremental")) return crc;
     e->incremental = on != 0;
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 
 int csf_set_params(csf_engine *e, const csf_params *params) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_set_params")) return crc;
     int rc = check_params(e, params);
     if (rc) return rc;
     if (params->model != e->d.p.model) return fail(e, CSF_E_ARG, "the model of an engine cannot change");
@@ -400,6 +405,7 @@ int csf_set_params(csf_engine *e, const csf_params *params) try {
 
 int csf_set_param_classes(csf_engine *e, int32_t n_classes, const csf_params *classes) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_set_param_classes")) return crc;
     if (n_classes < 1 || n_classes > 256 || !classes) return fail(e, CSF_E_ARG, "csf_set_param_classes: 1 to 256 parameter sets");
     for (int32_t c = 0; c < n_classes; c++) {
         int rc = check_params(e, classes + c);
@@ -430,6 +436,7 @@ int csf_set_param_classes(csf_engine *e, int32_t n_classes, const csf_params *cl
 
 int csf_set_agent_class(csf_engine *e, int64_t n, const int32_t *idx, const int32_t *cls) try {
     if (!e) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_set_agent_class")) return crc;
     if (n < 0 || (n > 0 && (!idx || !cls))) return fail(e, CSF_E_ARG, "csf_set_agent_class: bad arguments");
     const int64_t pop = (int64_t)e->order.size();
     for (int64_t k = 0; k < n; k++) {
@@ -462,6 +469,7 @@ int csf_set_agent_class(csf_engine *e, int64_t n, const int32_t *idx, const int3
 int csf_set_priority_rule(csf_engine *e, int32_t rule) try {
     if (!e) return CSF_E_ARG;
     if (rule < 0 || rule > 1) return fail(e, CSF_E_ARG, "unknown priority rule %d", rule);
+    if (int crc = calib_refuses(e, "csf_set_priority_rule")) return crc;
     e->d.p.priority_rule = rule;
     derive_consts(e);
     return CSF_OK;
@@ -470,6 +478,7 @@ int csf_set_priority_rule(csf_engine *e, int32_t rule) try {
 int csf_set_v_desired(csf_engine *e, int64_t n, const int32_t *idx, const double *v_desired) try {
     if (!e) return CSF_E_ARG;
     if (n < 0 || (n > 0 && (!idx || !v_desired))) return fail(e, CSF_E_ARG, "csf_set_v_desired: bad arguments");
+    if (int crc = calib_refuses(e, "csf_set_v_desired")) return crc;
     for (int64_t k = 0; k < n; k++)
         if (idx[k] < 0 || idx[k] >= (int64_t)e->order.size()) return fail(e, CSF_E_ARG, "agent index %d out of range", idx[k]);
     HIPCHK(e, hipSetDevice(e->device));

@@ -17,6 +17,7 @@ int csf_comm_init(csf_engine *e, const uint8_t id[CSF_UNIQUE_ID_BYTES], int32_t 
     if (world < 1 || rank < 0 || rank >= world) return fail(e, CSF_E_ARG, "bad rank %d / world %d", rank, world);
     if (world > 64) return fail(e, CSF_E_ARG, "world > 64 is not supported");
     if (e->nccl) return fail(e, CSF_E_STATE, "communicator already initialised");
+    if (int crc = calib_refuses(e, "csf_comm_init")) return crc;
     if (e->batch) return fail(e, CSF_E_STATE, "engine belongs to a batch (csf_batch_leave first)");
     if (!id && world > 1) return fail(e, CSF_E_ARG, "unique id is NULL");       // (before anything changes: a refused call leaves the engine as it was)
     if (id && !g_rccl.load()) return fail(e, CSF_E_COMM, "%s", g_rccl.err.c_str());
@@ -48,6 +49,7 @@ int csf_comm_init_loopback(csf_engine *const *engines, int32_t world) try {
         csf_engine *e = engines[r];
         if (!e) return CSF_E_ARG;
         if (e->nccl || e->loopback || e->world > 1) return fail(e, CSF_E_STATE, "engine already belongs to a communicator");
+        if (int crc = calib_refuses(e, "csf_comm_init_loopback")) return crc;
         if (e->batch) return fail(e, CSF_E_STATE, "engine belongs to a batch (csf_batch_leave first)");
         if (e->device != engines[0]->device || e->order.size() != engines[0]->order.size() || e->d.p.model != engines[0]->d.p.model)
             return fail(e, CSF_E_ARG, "loopback members hold the same population on the same device");

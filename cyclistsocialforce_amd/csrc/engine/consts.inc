@@ -14,6 +14,12 @@ int fail(csf_engine *e, int code, const char *fmt, ...) {
     return code;
 }
 
+// an engine that holds a calibration data set (csf_calib_load) is evaluated, read, given destination queues and cleared - nothing else
+int calib_refuses(csf_engine *e, const char *what) {
+    if (!e || !e->calib) return CSF_OK;
+    return fail(e, CSF_E_STATE, "%s: the engine holds a calibration data set (csf_calib_clear first)", what);
+}
+
 constexpr int64_t MAX_QUEUE_ROWS = 1 << 24;   // destinations of ONE road user (row numbers are 32-bit; a route has a few dozen)
 
 // Every extern "C" entry point is a function-try-block that ends here: no C++ exception (a std::bad_alloc of the host mirror's

@@ -98,10 +98,12 @@ static int gather_population(csf_engine *e) {
     return CSF_OK;
 }
 
-int prepare_mutation(csf_engine *e) {
+// calib_ok: the caller is one of the calls a loaded calibration engine takes (csf_set_dest_queue)
+int prepare_mutation(csf_engine *e, bool calib_ok = false) {
     // a rank integrates only its own block: its fp64 copy of the other blocks goes stale with the first tick, and an
     // upload would rebuild their records from it - so the blocks are gathered first (gather_population)
     int rc;
+    if (!calib_ok && (rc = calib_refuses(e, "a change of the population"))) return rc;
     if ((e->world > 1 || e->loopback || e->nccl) && e->device_ahead) {
         if ((rc = flush_pending(e))) return rc;
         if ((rc = gather_population(e))) return rc;

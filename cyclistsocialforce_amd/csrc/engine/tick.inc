@@ -666,6 +666,7 @@ static int step_impl(csf_engine *e, int64_t n_ticks, bool want_snap, bool *snapp
     if (snapped) *snapped = false;
     if (!e) return CSF_E_ARG;
     if (n_ticks < 0) return fail(e, CSF_E_ARG, "n_ticks must be >= 0");
+    if (int crc = calib_refuses(e, "csf_step")) return crc;
     HIPCHK(e, hipSetDevice(e->device));
     if (e->loopback) return fail(e, CSF_E_STATE, "members of a loopback group are stepped with csf_step_group");
     if (e->world > 1 && !e->nccl) return fail(e, CSF_E_STATE, "csf_comm_init must run before csf_step when world > 1");

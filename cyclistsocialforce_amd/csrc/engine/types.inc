@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "csf_dev.h"
+#include "csf_calib.h"
 
 using namespace csf;
 
@@ -517,6 +518,10 @@ struct csf_engine {
     // engine's own stream, kept for when it leaves (the members tick on the first member's)
     std::shared_ptr<struct BatchState> batch;
     std::shared_ptr<StreamHold> own_hold;
+    // csf_calib_load: the resident calibration data set and the reset image (engine/abi_calib.inc); while it is there the engine
+    // takes csf_calib_eval, csf_calib_clear, csf_set_dest_queue (a route for its vehicles) and the read-backs, and refuses everything
+    // that steps it, changes its population, parameters or recording, or writes navigation state (calib_refuses)
+    std::shared_ptr<struct CalibState> calib;
     int64_t batch_ticks = 0;         // ticks run inside a batched ONE-WAVE launch (csf_batch_ticks)
     int64_t batch_mid_ticks = 0;     // ticks run inside a batched one-launch tick (csf_batch_mid_ticks; mid_ticks counts them too)
     // csf_step_batch, mid-size members: the launches of a re-binning on the plain order (identity order, records re-expressed) and

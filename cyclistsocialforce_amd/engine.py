@@ -210,6 +210,56 @@ class Engine:
                                              int(bool(fix_speed)), int(stride), None if out is None else _ptr(out)))
         return out
 
+    # -- calibration (include/csf.h: csf_calib_load ...; cyclistsocialforce_amd.calibration drives it) ---------------------------
+    def calib_load(self, s0, Fx, Fy, objective, feat, lengths=None, max_sets=256):
+        """Make this EMPTY engine hold a calibration data set: start states s0 [n_seq, >= n_states], recorded forces Fx, Fy
+        [T, n_seq], the objective [T, n_seq, n_feat] and the rows of vehicle.traj (0 .. 5) its columns are compared with;
+        lengths [n_seq]: ticks of every sequence (default: T).  capacity >= max_sets * n_seq."""
+        s0 = np.asarray(s0, dtype=np.float64)
+        if s0.ndim != 2 or s0.shape[1] < self.ns:
+            raise ValueError(f"s0 must be [n_seq, >={self.ns}]")
+        s0 = _f64(s0[:, : self.ns])
+        n_seq = s0.shape[0]
+        Fx, Fy = _f64(Fx), _f64(Fy)
+        if Fx.ndim != 2 or Fx.shape != Fy.shape or Fx.shape[1] != n_seq:
+            raise ValueError("Fx, Fy must be [n_ticks, n_seq]")
+        T = Fx.shape[0]
+        feat = np.ascontiguousarray(feat, dtype=np.int32).reshape(-1)
+        obj = _f64(objective)
+        if obj.shape != (T, n_seq, feat.size):
+            raise ValueError("objective must be [n_ticks, n_seq, n_feat]")
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        if ln is not None and ln.shape != (n_seq,):
+            raise ValueError("lengths must have one entry per sequence")
+        self._ck(self._lib.csf_calib_load(self._h, n_seq, T, _ptr(s0), _ptr(Fx), _ptr(Fy), None if ln is None else _ptr(ln),
+                                          _ptr(obj), feat.size, _ptr(feat), int(max_sets)))
+        self._calib = (n_seq, T)
+
+    def calib_eval(self, pods, fix_speed=True, states=False, stride=1):
+        """Evaluate the parameter sets `pods` (a sequence of csf_params) on the loaded data set in one launch: sums
+        [n_sets, n_seq, 2] = (sum d^2, sum |d|) per set and sequence, and with states=True the trajectories
+        [T // stride, n_sets * n_seq, n_states] as well (slot = set * n_seq + seq)."""
+        if getattr(self, "_calib", None) is None:
+            raise EngineError("calib_eval: no calibration data set (calib_load first)")
+        n_seq, T = self._calib
+        pods = list(pods)
+        tab = (Params * len(pods))(*pods)
+        sums = np.zeros((len(pods), n_seq, 2))
+        out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * n_seq, self.ns)) if states else None
+        self._ck(self._lib.csf_calib_eval(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION, int(bool(fix_speed)),
+                                          _ptr(sums), int(stride), None if out is None else _ptr(out)))
+        return (sums, out) if states else sums
+
+    def calib_clear(self):
+        self._ck(self._lib.csf_calib_clear(self._h))
+        self._calib = None
+
+    def calib_launches(self):
+        """kernel launches of calib_eval since calib_load: one per call"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_calib_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def dest_force(self):
         fx = np.zeros(self.n)
         fy = np.zeros(self.n)

@@ -429,6 +429,36 @@ int csf_holes_taken(const csf_engine *e, int64_t *n);
 int csf_step_get_tick(csf_engine *e, int64_t n_ticks, double *s_out, int32_t *dest_ptr, uint8_t *znav, double *Fx, double *Fy,
                       int64_t *tick);
 
+/* Calibration on the device (calibration.py:243-526).  The optimiser of the reference calls its objective
+ * hundreds of times; each call replays every recorded sequence with one candidate parameter set (:438-460) and sums an error over
+ * the trajectories (:27-77).  csf_calib_load makes an EMPTY engine (capacity >= max_sets * n_seq, max_sets <= 256; one parameter
+ * set, no road, no recording; not a member of a batch or of a communicator; not an UncontrolledVehicle's) hold a data set: n_seq
+ * sequences of up to n_ticks ticks - their start states s0 [n_seq][n_states], the recorded forces Fx, Fy [n_ticks][n_seq], the
+ * ticks of each (lengths [n_seq], 0 .. n_ticks; NULL: all of them), the objective [n_ticks][n_seq][n_feat] and the rows of
+ * vehicle.traj its columns are compared with (feat [n_feat], 0 .. 5 = x, y, psi, v, delta, theta; a row the vehicle class does not have
+ * compares 0, as the reference's traj holds 0 there).  It creates max_sets * n_seq road users - slot set * n_seq + seq - and keeps an
+ * image of what csf_add_agents made of them.
+ * csf_calib_eval evaluates n_sets <= max_sets candidate sets (checked as csf_create_v checks: params_size, abi_version; all of the
+ * engine's vehicle class, t_s and traj_len) in ONE launch: every (set, sequence) starts from the image - an evaluation does not
+ * depend on the one before -, replays its sequence through the per-agent tick of csf_replay_forces (fix_speed: calibration.py:455-458)
+ * and sums, in fp64 and tick order, d = state after tick t - objective[t] over the features (no angle wrap): sums_out
+ * [n_sets][n_seq][2] = (sum d^2, sum |d|).  calc_sse_timesteps is the sum of the first over the sequences, calc_maesse_samples the sum of
+ * (second / (length * n_feat))^2.  states_out (may be NULL): [n_ticks / stride][n_sets * n_seq][n_states], the state after every
+ * stride-th tick; a sequence that has ended keeps its last state.  Launches and copies per call do not depend on n_ticks, n_sets or
+ * n_seq (csf_calib_launches counts the launches).  While the data set is held the engine refuses csf_step and every call that changes
+ * the population or its parameters (CSF_E_STATE); the read-backs show the end of the last evaluation.  csf_set_dest_queue alone stays open
+ * (on the device path and through the host mirror alike): a
+ * fresh reference vehicle's only destination is its start (vehicle.py:183-185), and the Bicycle / TwoD / walking InvPendulum controllers
+ * scale the desired speed within 3 m of the last destination (vehicle.py:1226-1232) - a data set recorded on a route is replayed with
+ * that route's queue (no tick of a replay moves the queue pointer; the queue is not part of the image).  csf_calib_clear drops the
+ * data set and empties the engine.  A refused call changes nothing. */
+int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *s0, const double *Fx, const double *Fy, const int32_t *lengths,
+                   const double *objective, int32_t n_feat, const int32_t *feat, int32_t max_sets);
+int csf_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version, int32_t fix_speed,
+                   double *sums_out, int32_t stride, double *states_out);
+int csf_calib_launches(const csf_engine *e, int64_t *n_launches);
+int csf_calib_clear(csf_engine *e);
+
 /* Far-field radius of the pair kernel (metres; +inf when the cull is off).  The repulsive field of
  * vehicle.py:1560-1648 decays at least like f_0 exp(-kappa rho); sources beyond
  * R = ln(n / eps) / kappa together add less than eps * f_0 (eps = 2^-24 unless the environment variable
