@@ -405,3 +405,193 @@ class DownhillSimplexCalibration:
         if self.verbose:
             print(f"test error on {len(vehicles)} samples: {error:.6g}")
         return error, vehicles
+
+
+# --------------------------------------------------------------------------- interaction parameters, closed loop
+class SceneData:
+    """One recorded scene of up to 32 road users that interact (plain arrays): start states s0 [n, >= 4] (x, y, psi, v, ...),
+    desired speeds v_desired [n] (or a scalar), the riders' destination queues in CSR form (dest_offsets [n + 1], dest_xyz_stop
+    [rows, 3] = (x, y, stop); at least one row each), the recorded trajectory traj [n_t, n, n_cols] - row t the state AFTER tick
+    t + 1, columns the rows of vehicle.traj (x, y, psi, v, delta, theta) as far as they were recorded - and its length in ticks
+    (default: n_t)."""
+
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None):
+        self.s0 = np.asarray(s0, dtype=float)
+        if self.s0.ndim != 2 or self.s0.shape[1] < 4 or not 1 <= self.s0.shape[0] <= 32:
+            raise ValueError("a scene has 1 .. 32 road users: s0 is [n, >= 4]")
+        n = self.s0.shape[0]
+        try:
+            self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (n,)))
+        except ValueError:
+            raise ValueError("v_desired: one desired speed per road user, or a scalar") from None
+        self.dest_offsets = np.asarray(dest_offsets, dtype=np.int64)
+        self.dest_xyz_stop = np.asarray(dest_xyz_stop, dtype=float).reshape(-1, 3)
+        off = self.dest_offsets
+        if off.shape != (n + 1,) or off[0] != 0 or off[-1] != self.dest_xyz_stop.shape[0] or np.any(np.diff(off) < 1):
+            raise ValueError("dest_offsets is [n + 1], starts at 0, ends at the rows of dest_xyz_stop, and gives every road user a row")
+        self.traj = np.asarray(traj, dtype=float)
+        if self.traj.ndim != 3 or self.traj.shape[1] != n or not 1 <= self.traj.shape[2] <= TRAJ_ROWS:
+            raise ValueError(f"traj is [n_t, n, 1 .. {TRAJ_ROWS}]: the state of every road user after every tick")
+        self.length = self.traj.shape[0] if length is None else int(length)
+        if not 0 <= self.length <= self.traj.shape[0]:
+            raise ValueError("length: 0 .. the rows of traj")
+
+    @property
+    def n(self):
+        return self.s0.shape[0]
+
+
+def _riders_then_scenes(per_rider, roff):
+    """[k, R] per-rider figures -> [k, n_scn]: the riders of a scene added in rider order (the order of the sum is fixed)"""
+    out = np.zeros((per_rider.shape[0], len(roff) - 1))
+    for q in range(len(roff) - 1):
+        for r in range(roff[q], roff[q + 1]):
+            out[:, q] += per_rider[:, r]
+    return out
+
+
+def _scenes_in_order(per_scene):
+    acc = np.zeros(per_scene.shape[0])
+    for q in range(per_scene.shape[1]):
+        acc += per_scene[:, q]
+    return acc
+
+
+class InteractionCalibration:
+    """Fit parameters that act BETWEEN road users - the social-force field f_0, sigma_0..3, e_0, e_1, hfov, p_0, p_decay, the priority
+    rule - to recorded scenes by downhill simplex.  A replay of recorded forces (DownhillSimplexCalibration) couples no two vehicles;
+    here every candidate set simulates every scene with its road users together, on the device: the scenes are loaded once
+    (`Engine.scene_calib_load`) and an evaluation of the objective is one launch for all scenes and up to `max_sets` (at most 256)
+    candidate sets (`Engine.scene_calib_eval`).  With calc_sse_timesteps or calc_maesse_samples the error is formed from the
+    per-rider sums the device returns - the riders of a scene added in rider order, then the scenes in scene order; a sample of
+    calc_maesse_samples is a scene - and another error_func gets the trajectories, [length, n_riders, n_feat] per scene.
+
+    train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
+
+    def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
+                 max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine):
+        self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
+        self.train_data, self.test_data = list(train_data), list(test_data)
+        for d in self.train_data + self.test_data:
+            if not isinstance(d, SceneData):
+                raise TypeError("train_data and test_data are lists of SceneData")
+        if not self.train_data:
+            raise ValueError("no scenes to train on")
+        self.objective_features_traj = _indicators(objective_features_traj, "objective_features_traj", TRAJ_ROWS)
+        if not self.objective_features_traj.any():
+            raise ValueError("objective_features_traj selects no row of vehicle.traj")
+        self.error_func, self.maxiter, self.xtol, self.ftol, self.verbose = error_func, maxiter, xtol, ftol, verbose
+        self.device, self.max_sets = device, max(1, min(int(max_sets), 256))
+        self.param_args_opt = None
+        self._factory = engine_factory
+        self._sets = {}
+
+    def close(self):
+        for ds in self._sets.values():
+            ds["engine"].close()
+        self._sets = {}
+
+    def _update_params_args_dict(self, params_vals):
+        return dict(zip(self.params_keys, params_vals))
+
+    def _pod(self, params_args):
+        return self.vehicle_type.PARAMS_TYPE(**params_args).to_pod(self.vehicle_type.MODEL)
+
+    def _dataset(self, test=False):
+        """the engine that holds the training (test) scenes, loaded on first use"""
+        ds = self._sets.get(bool(test))
+        if ds is not None:
+            return ds
+        data = self.test_data if test else self.train_data
+        if not data:
+            raise ValueError("no test scenes")
+        feat = np.flatnonzero(self.objective_features_traj).astype(np.int32)
+        nr = np.array([d.n for d in data], dtype=np.int32)
+        roff = np.r_[0, np.cumsum(nr)].astype(np.int64)
+        R, T = int(roff[-1]), max(1, max(d.traj.shape[0] for d in data))
+        lens = np.array([d.length for d in data], dtype=np.int32)
+        s0, vd, obj = np.zeros((R, 8)), np.zeros(R), np.zeros((T, R, feat.size))
+        off, rows = [0], []
+        for q, d in enumerate(data):
+            if feat.max() >= d.traj.shape[2]:
+                raise ValueError(f"scene {q}: objective_features_traj names row {int(feat.max())} of vehicle.traj, the recorded trajectory has {d.traj.shape[2]}")
+            sl = slice(roff[q], roff[q + 1])
+            s0[sl, : min(d.s0.shape[1], 8)] = d.s0[:, :8]
+            vd[sl] = d.v_desired
+            obj[: d.traj.shape[0], sl] = d.traj[:, :, feat]
+            off.extend((d.dest_offsets[1:] + len(rows)).tolist())
+            rows.extend(d.dest_xyz_stop.tolist())
+        engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
+        engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
+                                max_sets=self.max_sets)
+        ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets,
+                  objectives=[d.traj[: d.length][:, :, feat] for d in data])
+        self._sets[bool(test)] = ds
+        return ds
+
+    def _trajs(self, ds, states, k):
+        """the scenes of parameter set k from the states of one evaluation: [length, n_riders, n_feat] each (rows the class lacks: 0)"""
+        ns, out = states.shape[2], []
+        for q, ln in enumerate(ds["lens"]):
+            tr = np.zeros((ln, ds["nr"][q], ds["feat"].size))
+            for c, f in enumerate(ds["feat"]):
+                if f < ns:
+                    tr[:, :, c] = states[:ln, k * ds["R"] + ds["roff"][q]: k * ds["R"] + ds["roff"][q + 1], f]
+            out.append(tr)
+        return out
+
+    def evaluate(self, params_vals, test=False):
+        """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them."""
+        vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
+        ds = self._dataset(test)
+        pods = [self._pod(self._update_params_args_dict(v)) for v in vals]
+        err = np.zeros(len(pods))
+        for at in range(0, len(pods), ds["sets"]):
+            chunk = pods[at:at + ds["sets"]]
+            if self.error_func is calc_sse_timesteps:
+                sums = ds["engine"].scene_calib_eval(chunk)
+                err[at:at + len(chunk)] = _scenes_in_order(_riders_then_scenes(sums[:, :, 0], ds["roff"]))
+            elif self.error_func is calc_maesse_samples:
+                sums = ds["engine"].scene_calib_eval(chunk)
+                with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
+                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["lens"] * ds["nr"] * float(ds["feat"].size))[None, :]
+                err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
+            else:
+                _, states = ds["engine"].scene_calib_eval(chunk, states=True)
+                for k in range(len(chunk)):
+                    err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
+        return err
+
+    def simulate(self, params_vals, test=False):
+        """The trajectories of one parameter vector on the training (test) scenes: ([length, n_riders, n_feat] per scene - the state
+        after each tick -, the objectives)."""
+        ds = self._dataset(test)
+        _, states = ds["engine"].scene_calib_eval([self._pod(self._update_params_args_dict(np.asarray(params_vals, dtype=float)))], states=True)
+        return self._trajs(ds, states, 0), list(ds["objectives"])
+
+    def run(self, params_vals_guess):
+        """The calibration by scipy.optimize.fmin, as DownhillSimplexCalibration.run: fmin's full output with the scenes simulated
+        at the optimum appended."""
+        from scipy.optimize import fmin
+
+        results = list(fmin(objective_function_wrapper, params_vals_guess, (self,), xtol=self.xtol, ftol=self.ftol, full_output=True,
+                            maxiter=self.maxiter, disp=bool(self.verbose)))
+        self.param_args_opt = self._update_params_args_dict(results[0])
+        results.append(self.simulate(results[0]))
+        return results
+
+    def run_many(self, guesses):
+        """Independent calibrations from several guesses, in lockstep (minimize_many): every iteration of all live runs is one launch.
+        Returns a list of (xopt, fopt, iterations) - per guess what `run` finds from it - and keeps the best in param_args_opt."""
+        res = minimize_many(self.evaluate, [np.asarray(g, dtype=float) for g in guesses], xtol=self.xtol, ftol=self.ftol, maxiter=self.maxiter)
+        best = min(res, key=lambda r: r[1])
+        self.param_args_opt = self._update_params_args_dict(best[0])
+        return res
+
+    def test(self, params_vals=None):
+        """Error of a parameter vector - by default the one `run` / `run_many` found - on the TEST scenes."""
+        if params_vals is None:
+            if self.param_args_opt is None:
+                raise RuntimeError("no parameters to test: call run() or run_many() first, or pass params_vals")
+            params_vals = [self.param_args_opt[k] for k in self.params_keys]
+        return float(self.evaluate([params_vals], test=True)[0])

@@ -1,0 +1,47 @@
+// csf_scene.h — what the closed-loop calibration kernel (csf_scene.hip: scene_eval_kernel) is handed beside the table of Dev views,
+// shared with the host side (engine/abi_scene.inc).
+#pragma once
+#include "csf_calib.h"
+
+namespace csf {
+
+// One candidate parameter set of a call, as the one-wave tick reads it from Dev: the set, what derive_pair_consts / the rounding
+// bands make of it, and the PlanarBicycle step matrices (derive_planarbike).  The host composes n_sets of them per call.
+struct SceneSet {
+    csf_params p;
+    PairConsts pc;
+    double pb[7];
+    double pad;
+};
+
+// The data set of csf_scene_calib_load, resident on the device, and the reset image.  The image is indexed by RIDER (0 .. R - 1,
+// the scenes one after the other): every set starts every scene from the same state, so one copy of what csf_add_agents made of
+// the first set's slots serves all of them.  It holds every per-slot array that a closed-loop tick (agent_body<.., FUSED = true>
+// under small_tick_body) writes and a later tick reads:
+//   s [STATE_ROWS], lti [5], ppsi, ti, status      as csf_calib.h
+//   ptr, znav, znp [3]                             the destination pointer, the navigation state and its latched parameters
+//   hx0, hy0                                       row 0 of the short position ring - the only row a tick reads before a tick of
+//                                                  the same evaluation has written it (ti starts at 0: load_ring, twod_dest)
+// zrid and dgood follow from the image's state and the limits of the evaluation's own set (vehicle.py:1732-1736).  The force
+// rows are written before they are read in every tick; they are cleared so that the read-backs of a scene of length 0 show
+// nothing of the evaluation before.  The fp32 records are written and never read by the one-wave tick.
+struct SceneDev {
+    const double *obj;           // [n_ticks][R][n_feat]
+    const int32_t *len;          // [n_scn] ticks of every scene (0 .. n_ticks)
+    const int32_t *roff;         // [n_scn + 1] first rider of every scene
+    int32_t n_scn, n_ticks, n_feat, R;
+    int32_t feat[CALIB_MAX_FEAT];
+    int64_t img_cap;             // stride of the image's rows
+    const double *img_s, *img_lti, *img_ppsi, *img_znp, *img_hx0, *img_hy0;
+    const int32_t *img_ti, *img_ptr;
+    const uint32_t *img_status;
+    const uint8_t *img_znav;
+    double2 *sums;               // [n_sets][R] (sum d^2, sum |d|) per rider: mapped host memory
+    double *states;              // [n_ticks / stride][n_sets * R][ns], NULL: none
+    int32_t stride, n_samples, n_sets, pad;
+};
+
+// One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].
+void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st);
+
+}  // namespace csf

@@ -1,0 +1,128 @@
+// csf_scene.hip — calibration of the interaction parameters on the device: many parameter sets x many closed-loop scenes in ONE
+// launch, the error against the recorded trajectories summed here.
+//
+// csf_calib.hip replays recorded forces: no two vehicles are coupled, and the social-force field (f_0, sigma_0..3, e_0, e_1, hfov,
+// p_0, p_decay, the priority rule) never acts.  Here the riders of a scene are simulated together by the one-wave tick
+// (csf_small_body.inc), workgroup = (candidate set, scene):
+//
+//   b = set * n_scn + scene            table[b] is the Dev view of the scene's slot block (slot = set * R + rider, pointers shifted
+//                                      to the block, n = the scene's riders); p / pc / pb come from the call's table of sets
+//   before tick 0                      the block becomes the fresh vehicles of the scene, from the image (csf_scene.h)
+//   t = 0 .. len[scene] - 1            one closed-loop tick; then, per rider, d = state - objective[t][rider][f] over the
+//                                      objective's features, sum d^2 and sum |d| in fp64, tick order, features in column order
+//   at the end                         (sum d^2, sum |d|) -> sums[set * R + rider] in mapped host memory; the host adds the riders
+//                                      of a scene in rider order (no reduction across lanes: the order of the sum is fixed)
+//
+// The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
+// chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
+#include "csf_agent_dev.h"
+#include "csf_field.h"
+#include "csf_scene.h"
+
+namespace csf {
+
+#include "csf_small_body.inc"
+
+// behind every tick: lane = rider of the scene, its error terms and, on a sampled tick, its state
+struct SceneHook {
+    const SceneDev &c;
+    const int64_t rider;          // set * R + first rider of the scene + lane: row of sums and of a sample
+    const double *obj;            // objective of this lane's rider at tick 0
+    double *smp;                  // where this lane's next sample goes (NULL: none)
+    int wait;                     // ticks until the next sampled one
+    int taken = 0;                // samples written
+    double sse = 0.0, sae = 0.0;
+    __device__ __forceinline__ SceneHook(const SceneDev &c_, int64_t rider_, const double *obj_, double *smp_)
+        : c(c_), rider(rider_), obj(obj_), smp(smp_), wait(c_.stride - 1) {}
+    __device__ __forceinline__ void sample(const Dev &d, int lane) {
+        for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
+        smp += (int64_t)c.n_sets * c.R * d.ns;
+        taken++;
+    }
+    __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
+        if (lane >= n) return;
+        const double *o = obj + (int64_t)t * c.R * c.n_feat;
+        for (int k = 0; k < c.n_feat; k++) {
+            const int f = c.feat[k];
+            // (a row the class does not have stays zero in the reference's traj: vehicle.py:158-160)
+            const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
+            const double e = sv - o[k];                       // a plain difference, no angle wrap: calibration.py:49, 76
+            sse += e * e;
+            sae += fabs(e);
+        }
+        if (smp != nullptr) {
+            if (wait == 0) {
+                sample(d, lane);
+                wait = c.stride;
+            }
+            wait--;
+        }
+    }
+};
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
+    extern __shared__ float4 srv_none[];                      // (no road: small_tick_body stages nothing)
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * c.n_scn) return;
+    const int set = b / c.n_scn, scn = b - set * c.n_scn;
+    Dev d = table[b];
+    {
+        const SceneSet ss = sets[set];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;
+    const int64_t cap = d.cap, first = c.roff[scn];
+    const int len = c.len[scn];
+    if (lane < n) {   // Vehicle.__init__ for this rider (vehicle.py:64-204, 1728-1736): see patch_kernel's spawn
+        const int64_t a = lane, r = first + lane, ic = c.img_cap;
+#pragma unroll
+        for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
+        d.ppsi[a] = c.img_ppsi[r];
+        d.ti[a] = c.img_ti[r];
+        d.status[a] = c.img_status[r];
+        d.ptr[a] = c.img_ptr[r];
+        d.znav[a] = c.img_znav[r];
+        d.hx[a] = c.img_hx0[r];
+        d.hy[a] = c.img_hy0[r];
+        const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
+        d.zrid[a] = v < d.p.v_max_walk ? 0 : 1;
+        d.dgood[a] = (-d.p.delta_max_walk < delta && d.p.delta_max_walk > delta) ? 1 : 0;
+    }
+    // (the restored block is read by every lane of this wave in the first tick: the wave's own stores, program order - as from
+    // tick to tick in small_tick_body)
+    const int64_t rider = (int64_t)set * c.R + first + lane;
+    SceneHook hook(c, rider, c.obj + (first + lane) * c.n_feat, c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr);
+    small_tick_body<MODEL>(d, len, nullptr, srv_none, 0u, 0, hook);
+    if (lane >= n) return;
+    c.sums[rider] = make_double2(hook.sse, hook.sae);
+    // an ended (or empty) scene keeps its last state in every later sample
+    if (hook.smp != nullptr)
+        while (hook.taken < c.n_samples) hook.sample(d, lane);
+}
+
+void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st) {
+    const int count = c.n_sets * c.n_scn;
+    if (count <= 0) return;
+#define CSF_SCENE(MODEL) hipLaunchKernelGGL((scene_eval_kernel<MODEL>), dim3((unsigned)count), dim3(64), 0, st, table, sets, c)
+    switch (model) {
+    case CSF_BICYCLE: CSF_SCENE(CSF_BICYCLE); break;
+    case CSF_TWOD: CSF_SCENE(CSF_TWOD); break;
+    case CSF_INVPEND: CSF_SCENE(CSF_INVPEND); break;
+    case CSF_PLANARBIKE: CSF_SCENE(CSF_PLANARBIKE); break;
+    case CSF_BALANCINGRIDER: CSF_SCENE(CSF_BALANCINGRIDER); break;
+    default: CSF_SCENE(CSF_PLANARPOINT); break;
+    }
+#undef CSF_SCENE
+}
+
+}  // namespace csf

@@ -1,0 +1,168 @@
+// csf_small_body.inc - the one-wave tick of a handful of road users (DESIGN.md 4.6): included by csf_agent.hip (small_tick_kernel,
+// small_batch_kernel) and by csf_scene.hip (scene_eval_kernel) inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
+// include and not a __device__ function of a translation unit of its own, as csf_mid_body.inc is (DESIGN.md 4.6d): the kernels of
+// csf_agent.hip keep the instruction stream they had when the body stood in that file.
+//
+// HOOK: what a caller does behind every tick - hook(d, t, lane, n) is called by all 64 lanes once the tick's stores are issued
+// (lanes 0 .. n - 1 have just written their road user's state: their own stores, program order).  NoTickHook is empty and
+// compiles to nothing; csf_scene.hip sums an error there.
+struct NoTickHook {
+    __device__ __forceinline__ void operator()(const Dev &, int, int, int) {}
+};
+
+// ---- a handful of road users: the whole tick in one wave, any number of ticks in one launch ---------------------------------
+// The reference's own scenarios (three cyclists at a crossing, scenarios/*.py; BASELINE config 1) are latency, not work: a pair
+// launch and a per-agent launch of 5 - 6 us each, nearly all of it launch, teardown and first round trips (DESIGN 4.3).  Up to
+// SMALL_MAX road users of one class (not the UncontrolledVehicle's) are ticked by ONE wave instead - lane = road user - with nothing between the
+// phases but the wave's own program order, and csf_step(n) is one launch for all n ticks:
+//   snapshot (x, y, psi) of every road user, staged in LDS                intersection.py:660-677
+//   every source j of the lane's group in turn: receiver - source formed in fp64; the field of view and
+//   np.sign(phi) decided in fp32 on that difference with the band of ITS rounding (csf_field.h: tracked_precise,
+//   side_undecided - the predicates of the pair kernels' exact path) and, inside the band, as the reference decides them -
+//   fp64 atan2 -> limitAngle -> angleDifference (csf_dev.h: untracked_exact_xy), acos -> limitAngle -> sign
+//   (sign_phi_exact); the field in fp32, summed in fp64 (per group in source order, the groups pairwise)
+//                                                                         intersection.py:690-745, 814-843; vehicle.py:1560-1648
+//   the per-agent tick with that sum (agent_body<FUSED>)                  see the head of this file
+// No records are binned, nothing is noted or handed over: every yes / no is settled on the spot.
+// The body is shared by small_tick_kernel (one scene, its Dev in the kernarg segment) and small_batch_kernel (one scene per
+// workgroup, the Dev records in a table in global memory): `srv` is the LDS that stages the road, `snap` the packed read-back
+// behind the last tick (NULL: none), `tick0` the ticks the engine has done before this launch (what the samples of csf_record and
+// csf_enable_history are numbered from: sample k = state after tick (k + 1) * stride).
+template <int MODEL, class HOOK>
+__device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks, double *const snap, float4 *const srv, const uint32_t ka_lines,
+                                                const int64_t tick0, HOOK &hook) {
+    // Lane = (receiver, source group): with P the power of two that holds the road users, lane % P is the receiver and lane / P
+    // one of 64 / P groups that share the sources between them (source j belongs to group j % G) - all 64 lanes work on the
+    // pair term whatever the population, and the groups' sums meet in lanes 0 .. n - 1, which then tick their road user.
+    __shared__ double sx[SMALL_MAX], sy[SMALL_MAX], spsi[SMALL_MAX], scs[SMALL_MAX], ssn[SMALL_MAX];
+    __shared__ float2 se[MODEL == CSF_BICYCLE ? SMALL_MAX : 1];   // Bicycle field: (e, 1 / sqrt(1 - e^2)) of every source (vehicle.py:1062-1064)
+    const int lane = (int)threadIdx.x;
+    const int n = (int)d.n;
+    int P = 1;
+    while (P < n) P <<= 1;
+    const int G = WAVE / P, i = lane & (P - 1), grp = lane / P;
+    const int64_t cap = d.cap;
+    const bool live = i < n;
+    const int64_t a = live ? i : 0;
+    const PairConsts k = d.pc;
+    const bool p2r = d.p.priority_rule == CSF_P2R;
+    // road elements (intersection.py:226-242; the curve scenario's ~1 500 vertices): staged once per launch - they are static
+    const int nvp = (int)d.nv_pad;
+    for (int v = lane; v < nvp; v += WAVE) srv[v] = d.rv[v];
+    // the recording (Dev::hist, hist_F): ticks until the next sampled one and its ring slot, divided out once per launch and
+    // counted on from there (uniform: scalar registers, nothing of it in the tick loop but a compare and an add)
+    int rec_wait = -1, rec_next = 0;
+    if (d.hist != nullptr) {
+        const int64_t rem = (tick0 + 1) % d.hist_stride;
+        rec_wait = rem == 0 ? 0 : (int)(d.hist_stride - rem);
+        rec_next = (int)(((tick0 + 1 + rec_wait) / d.hist_stride - 1) % d.hist_cap);
+    }
+    for (int t = 0; t < n_ticks; t++) {
+        int rec_slot = -1;
+        if (rec_wait == 0) {
+            rec_slot = rec_next;
+            rec_next = rec_next + 1 == d.hist_cap ? 0 : rec_next + 1;
+            rec_wait = d.hist_stride;
+        }
+        if (rec_wait > 0) rec_wait--;
+        // (own stores of the previous tick: the lanes of the first group wrote them, in this wave: program order)
+        const double x = d.s[a], y = d.s[cap + a], psi = d.s[2 * cap + a];
+        double sp, cp;
+        sincos(psi, &sp, &cp);
+        if (lane < n) sx[lane] = x, sy[lane] = y, spsi[lane] = psi, scs[lane] = cp, ssn[lane] = sp;
+        if (MODEL == CSF_BICYCLE && lane < n) {                    // (what write_record keeps in rec2 for the pair kernels)
+            const double v = d.s[3 * cap + a];
+            const double e = v > 0.0 ? fmin(pow(v / d.p.v_max_riding[1], 0.1), 0.7) : 0.0;
+            se[lane] = make_float2((float)e, (float)(1.0 / sqrt(1.0 - e * e)));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const Recv r{0.f, 0.f, (float)cp, (float)sp};
+        double rx = 0.0, ry = 0.0;
+        for (int j = grp; j < n; j += G) {                         // (lanes of one group: the same j)
+            const double xs = sx[j], ys = sy[j], ps = spsi[j];
+            const double ex = x - xs, ey = y - ys;                 // vehicle.py:1615-1616
+            // the receiver itself and a road user on the very same spot (D2) add nothing
+            if (!live || j == i || (ex == 0.0 && ey == 0.0)) continue;
+            const float dx = (float)ex, dy = (float)ey, r2 = fmaxf(dx * dx + dy * dy, 1e-30f);
+            const float4 q = make_float4(0.f, 0.f, (float)scs[j], (float)ssn[j]);
+            bool edge;
+            bool seen = p2r ? tracked_precise<true>(k, k.chs, r, dx, dy, r2, edge) : tracked_precise<false>(k, k.chs, r, dx, dy, r2, edge);
+            if (edge) seen = !untracked_exact_xy(xs, ys, x, y, psi, d.p.hfov, p2r);   // (one pair in a million)
+            if (!seen) continue;
+            int sg = 1;
+            float F, gx, gy;
+            if (MODEL == CSF_BICYCLE) {                             // vehicle.py:1054-1147: no jump at phi = 0
+                field_bicycle(k, q, se[j], dx, dy, r2, F, gx, gy);
+            } else {
+                float sgf = 0.0f;                                   // 0: the sign of the fp32 sine
+                if (side_undecided(k, q, dx, dy, r2)) {
+                    sg = sign_phi_exact(xs, ys, ps, x, y);
+                    sgf = sg < 0 ? -1.0f : 1.0f;
+                }
+                field_twod(k, r, q, dx, dy, r2, F, gx, gy, sgf);
+            }
+            double wx = (double)(F * gx), wy = (double)(F * gy);
+            if (sg == 0) {                                          // phi = 0 exactly: no tangential part, |F| = P along the line
+                const double Pm = sqrt(wx * wx + wy * wy), il = 1.0 / sqrt(ex * ex + ey * ey);
+                wx = Pm * ex * il;
+                wy = Pm * ey * il;
+            }
+            rx += wx;
+            ry += wy;
+        }
+        // the groups' sums of a receiver, added pairwise in a fixed order: every lane of it ends with the total
+        for (int o = P; o < WAVE; o <<= 1) {
+            rx += __shfl_xor(rx, o, WAVE);
+            ry += __shfl_xor(ry, o, WAVE);
+        }
+        if (nvp > 0) {
+            // vertices as offsets from the origin of their tile of 1 024 (csf_dev.h: rv, rvo): the receiver's offset from it is formed
+            // in fp64; the sum as road_kernel forms it (fp32, r^-(sigma+1) as a power of rsq(r^2) where every edge shares an integer sigma)
+            float qx = 0.f, qy = 0.f;
+            const double bx = x - d.ox, by = y - d.oy;
+            for (int base = 0; base < nvp; base += 1024) {
+                const float2 ot = d.rvo[base >> 10];
+                const float rxo = (float)(bx - (double)ot.x), ryo = (float)(by - (double)ot.y);
+                const int cnt = nvp - base < 1024 ? nvp - base : 1024;
+                for (int u = grp; u < cnt; u += G) {
+                    const float4 v = srv[base + u];                // (x, y, -F0, -(sigma + 1) / 2); padding has F0 = 0
+                    const float ex = v.x - rxo, ey = v.y - ryo, r2 = ex * ex + ey * ey;
+                    float m;
+                    if (d.road_np) {
+                        const float inv = fminf(fast_rsq(r2), 1e6f), i2 = inv * inv;   // r = 0: finite, times ex = ey = 0
+                        m = d.road_np == 2 ? i2 : d.road_np == 3 ? i2 * inv : d.road_np == 4 ? i2 * i2 : d.road_np == 5 ? i2 * i2 * inv : i2 * i2 * i2;
+                    } else {
+                        m = fast_exp2(fminf(v.w * fast_log2(r2), 120.f));
+                    }
+                    m *= v.z;
+                    qx = m * ex + qx;
+                    qy = m * ey + qy;
+                }
+            }
+            for (int o = P; o < WAVE; o <<= 1) {
+                qx += __shfl_xor(qx, o, WAVE);
+                qy += __shfl_xor(qy, o, WAVE);
+            }
+            if (lane < n) d.froad[lane] = make_float2(qx, qy);    // (agent_body reads it back: the same lane, program order)
+        }
+        __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
+        if (lane < n) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+        hook(d, t, lane, n);
+    }
+    // csf_step_get_tick: what snapshot_kernel would pack in a launch of its own (slots are the population order here)
+    if (snap != nullptr && lane < n) {
+        const int ns = d.ns;
+        for (int c = 0; c < ns; c++) snap[(int64_t)lane * ns + c] = d.s[(int64_t)c * cap + lane];
+        double *F = snap + (int64_t)n * ns;
+        F[lane] = d.F[lane];
+        F[n + lane] = d.F[cap + lane];
+        int32_t *ptr = (int32_t *)(F + 2 * n);
+        ptr[lane] = d.ptr[lane];
+        uint8_t *zn = (uint8_t *)(ptr + n);
+        const int z = d.znav[lane] & 3;
+        zn[3 * lane + 0] = z == 0;
+        zn[3 * lane + 1] = z == 1;
+        zn[3 * lane + 2] = z == 2;
+    }
+}

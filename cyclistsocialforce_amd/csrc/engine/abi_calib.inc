@@ -36,6 +36,7 @@ int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *
     if (n_seq < 1 || n_ticks < 1 || n_ticks > 2000000000 || n_feat < 1 || n_feat > CALIB_MAX_FEAT || max_sets < 1 || max_sets > 256)
         return fail(e, CSF_E_ARG, "csf_calib_load: n_seq >= 1, 1 <= n_ticks <= 2e9, 1 <= n_feat <= %d, 1 <= max_sets <= 256", CALIB_MAX_FEAT);
     if (e->calib) return fail(e, CSF_E_STATE, "csf_calib_load: the engine holds a calibration data set already (csf_calib_clear first)");
+    if (int crc = calib_refuses(e, "csf_calib_load")) return crc;      // (a closed-loop data set: engine/abi_scene.inc)
     if (!e->order.empty()) return fail(e, CSF_E_STATE, "csf_calib_load: the engine is not empty (%lld road users)", (long long)e->order.size());
     if (e->batch) return fail(e, CSF_E_STATE, "csf_calib_load: the engine belongs to a batch (csf_batch_leave first)");
     if (e->loopback) return fail(e, CSF_E_STATE, "csf_calib_load: the engine is a member of a loopback group");

@@ -291,6 +291,7 @@ int csf_remove_agents(csf_engine *e, int64_t n, const int32_t *idx) try {
 int csf_set_dest_queue(csf_engine *e, int64_t n, const int32_t *agent, const int64_t *offsets,
                        const double *xyz_stop, int32_t reset) try {
     if (!e) return CSF_E_ARG;
+    if (e->scene_calib) return calib_refuses(e, "csf_set_dest_queue");   // (the queues are part of that data set, the pointers of its image)
     if (n < 0 || (n > 0 && (!agent || !offsets || !xyz_stop))) return fail(e, CSF_E_ARG, "csf_set_dest_queue: bad arguments");
     const int64_t pop = (int64_t)e->order.size();
     // rows the slab must take: every listed queue is written out whole, as it will be after ITS entry of the call (a

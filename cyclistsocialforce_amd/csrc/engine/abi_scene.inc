@@ -1,0 +1,265 @@
+// engine/abi_scene.inc - C ABI: calibration on closed-loop scenes.  A data set of small scenes resident on the device, workgroup = (parameter set, scene), the error against the recorded trajectories summed in the launch.
+// (a section of csf_engine.hip: included there, in this order; not a translation unit of its own)
+//
+// csf_calib_eval (engine/abi_calib.inc) replays recorded forces, which couples no two vehicles: the parameters of the social-force
+// field cannot be fitted with it.  Here every candidate set simulates every scene of the data set with its riders together - the
+// one-wave tick of csf_step for up to 32 road users (csf_small_body.inc) - and the kernel sums the error against the recorded
+// trajectories per rider (csf_scene.hip: scene_eval_kernel).  One copy of the call's table of sets, one launch, one wait per call.
+
+extern "C++" {
+
+struct SceneCalibState {
+    int32_t n_scn = 0, n_feat = 0, max_sets = 0, R = 0;
+    int64_t n_ticks = 0;
+    int32_t feat[CALIB_MAX_FEAT] = {0, 0, 0, 0, 0, 0};
+    double coord_bound = 0.0;                // largest |coordinate| of a start position, relative to the scene origin
+    DevBuf<double> obj, img_s, img_lti, img_ppsi, img_znp, img_hx0, img_hy0, states;
+    DevBuf<int32_t> len, roff, img_ti, img_ptr;
+    DevBuf<uint32_t> img_status;
+    DevBuf<uint8_t> img_znav;
+    DevBuf<Dev> table;                       // [max_sets][n_scn] the views of the slot blocks, built once
+    DevBuf<SceneSet> sets;                   // [max_sets] the call's candidate sets ...
+    HostBuf<SceneSet, false> sets_pin;       // ... and where the host composes them: one copy per call
+    HostBuf<double2> sums;                   // [max_sets * R] written by the kernel (mapped)
+    int64_t launches = 0;                    // csf_scene_calib_launches
+};
+
+}  // extern "C++"
+
+int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks, const double *s0, const double *v_desired,
+                         const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
+                         int32_t n_feat, const int32_t *feat, int32_t max_sets) try {
+    if (!e) return CSF_E_ARG;
+    if (!n_riders || !s0 || !v_desired || !dest_offsets || !dest_xyz_stop || !objective || !feat) return fail(e, CSF_E_ARG, "csf_scene_calib_load: NULL array");
+    if (n_scn < 1 || n_scn > (1 << 20) || n_ticks < 1 || n_ticks > 2000000000 || n_feat < 1 || n_feat > CALIB_MAX_FEAT || max_sets < 1 || max_sets > 256)
+        return fail(e, CSF_E_ARG, "csf_scene_calib_load: 1 <= n_scn <= 2^20, 1 <= n_ticks <= 2e9, 1 <= n_feat <= %d, 1 <= max_sets <= 256", CALIB_MAX_FEAT);
+    if (e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine holds a closed-loop data set already (csf_scene_calib_clear first)");
+    if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine holds a calibration data set (csf_calib_clear first)");
+    if (!e->order.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine is not empty (%lld road users)", (long long)e->order.size());
+    if (e->batch) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine belongs to a batch (csf_batch_leave first)");
+    if (e->loopback) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine is a member of a loopback group");
+    if (e->world > 1 || e->nccl) return fail(e, CSF_E_STATE, "csf_scene_calib_load: a sharded engine holds no scenes");
+    if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has a road (scenes with roads are not evaluated)");
+    if (e->d.hist != nullptr) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine records (csf_record / csf_enable_history); an evaluation writes its own samples");
+    if (e->classes.size() != 1) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has %d parameter sets; the candidates of an evaluation replace ONE", (int)e->classes.size());
+    if (e->d.p.model == CSF_UNCONTROLLED) return fail(e, CSF_E_ARG, "csf_scene_calib_load: an UncontrolledVehicle follows its trajectory whatever the field");
+    int64_t R64 = 0;
+    for (int32_t q = 0; q < n_scn; q++) {
+        if (n_riders[q] < 1 || n_riders[q] > SMALL_MAX) return fail(e, CSF_E_ARG, "csf_scene_calib_load: scene %d has %d road users (1 .. %d)", (int)q, (int)n_riders[q], SMALL_MAX);
+        R64 += n_riders[q];
+    }
+    const int64_t n = (int64_t)max_sets * R64;
+    if (n > e->cap_user) return fail(e, CSF_E_CAPACITY, "csf_scene_calib_load: max_sets x riders = %lld road users, capacity %lld", (long long)n, (long long)e->cap_user);
+    const int32_t R = (int32_t)R64;
+    for (int32_t q = 0; lengths && q < n_scn; q++)
+        if (lengths[q] < 0 || lengths[q] > n_ticks) return fail(e, CSF_E_ARG, "csf_scene_calib_load: lengths[%d] = %d outside 0 .. %lld", (int)q, (int)lengths[q], (long long)n_ticks);
+    for (int32_t k = 0; k < n_feat; k++)
+        if (feat[k] < 0 || feat[k] >= CALIB_MAX_FEAT) return fail(e, CSF_E_ARG, "csf_scene_calib_load: feature %d names no row of vehicle.traj (0 .. %d)", (int)feat[k], CALIB_MAX_FEAT - 1);
+    for (int32_t r = 0; r < R; r++) {
+        const int64_t rows = dest_offsets[r + 1] - dest_offsets[r];
+        if (dest_offsets[r] < 0 || rows < 1 || rows > MAX_QUEUE_ROWS) return fail(e, CSF_E_ARG, "csf_scene_calib_load: the destination queue of rider %d has %lld rows (1 .. %lld)", (int)r, (long long)rows, (long long)MAX_QUEUE_ROWS);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    // everything that can fail first: a refused call changes nothing
+    auto cs = std::make_shared<SceneCalibState>();
+    cs->n_scn = n_scn, cs->n_feat = n_feat, cs->max_sets = max_sets, cs->n_ticks = n_ticks, cs->R = R;
+    for (int32_t k = 0; k < n_feat; k++) cs->feat[k] = feat[k];
+    const size_t Rs = (size_t)R, tn = (size_t)n_ticks * Rs * (size_t)n_feat, views = (size_t)max_sets * (size_t)n_scn;
+    hipError_t r = cs->obj.alloc(tn);
+    if (r == hipSuccess) r = cs->img_s.alloc(STATE_ROWS * Rs);
+    if (r == hipSuccess) r = cs->img_lti.alloc(5 * Rs);
+    if (r == hipSuccess) r = cs->img_ppsi.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_znp.alloc(3 * Rs);
+    if (r == hipSuccess) r = cs->img_hx0.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_hy0.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_ti.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_ptr.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_status.alloc(Rs);
+    if (r == hipSuccess) r = cs->img_znav.alloc(Rs);
+    if (r == hipSuccess) r = cs->len.alloc((size_t)n_scn);
+    if (r == hipSuccess) r = cs->roff.alloc((size_t)n_scn + 1);
+    if (r == hipSuccess) r = cs->table.alloc(views);
+    if (r == hipSuccess) r = cs->sets.alloc((size_t)max_sets);
+    if (r == hipSuccess) r = cs->sets_pin.alloc((size_t)max_sets);
+    if (r == hipSuccess) r = cs->sums.alloc((size_t)n);
+    if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_load: no memory for the data set: %s", hipGetErrorString(r));
+    std::memset(cs->sets_pin.p, 0, (size_t)max_sets * sizeof(SceneSet));
+    std::vector<int32_t> ls((size_t)n_scn), ro((size_t)n_scn + 1, 0);
+    for (int32_t q = 0; q < n_scn; q++) ls[(size_t)q] = lengths ? lengths[q] : (int32_t)n_ticks, ro[(size_t)q + 1] = ro[(size_t)q] + n_riders[q];
+    HIPCHK(e, hipMemcpy(cs->obj.p, objective, tn * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(cs->len.p, ls.data(), ls.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(cs->roff.p, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the max_sets x R vehicles, slot set * R + rider: every set starts every scene from the scene's start states, with its queues
+    const int ns = e->d.ns;
+    const int64_t q0 = dest_offsets[0], q_rows = dest_offsets[R] - q0;
+    std::vector<double> s_all((size_t)n * (size_t)ns), vd((size_t)n), rows_all((size_t)max_sets * (size_t)q_rows * 3);
+    std::vector<int64_t> off_all((size_t)n + 1);
+    for (int32_t k = 0; k < max_sets; k++) {
+        std::memcpy(&s_all[(size_t)k * Rs * (size_t)ns], s0, Rs * (size_t)ns * sizeof(double));
+        std::memcpy(&vd[(size_t)k * Rs], v_desired, Rs * sizeof(double));
+        std::memcpy(&rows_all[(size_t)k * (size_t)q_rows * 3], dest_xyz_stop + 3 * q0, (size_t)q_rows * 3 * sizeof(double));
+        for (int32_t i = 0; i < R; i++) off_all[(size_t)k * Rs + (size_t)i] = (int64_t)k * q_rows + (dest_offsets[i] - q0);
+    }
+    off_all[(size_t)n] = (int64_t)max_sets * q_rows;
+    int rc = add_agents_impl(e, n, s_all.data(), vd.data(), off_all.data(), rows_all.data());
+    auto undo = [&](int code) {       // (the engine was empty: what has been added goes again)
+        std::vector<int32_t> all((size_t)e->order.size());
+        for (size_t i = 0; i < all.size(); i++) all[i] = (int32_t)i;
+        const std::string msg = e->err;
+        if (!all.empty()) (void)csf_remove_agents(e, (int64_t)all.size(), all.data());
+        e->err = msg;
+        return code;
+    };
+    if (rc) return rc;
+    if ((rc = upload_all(e))) return undo(rc);
+    if ((rc = ensure_compact(e))) return undo(rc);             // slot == place in the population order: slot a is (a / R, a % R)
+    // the image: what csf_add_agents made of the first set's slots (the stream is idle: upload_all has waited)
+    const size_t cap = (size_t)e->cap;
+    hipError_t c = hipStreamSynchronize(e->main);
+    for (size_t k = 0; c == hipSuccess && k < STATE_ROWS; k++) c = hipMemcpy(cs->img_s.p + k * Rs, e->s.p + k * cap, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+    for (size_t k = 0; c == hipSuccess && k < 5; k++) c = hipMemcpy(cs->img_lti.p + k * Rs, e->lti.p + k * cap, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+    for (size_t k = 0; c == hipSuccess && k < 3; k++) c = hipMemcpy(cs->img_znp.p + k * Rs, e->znp.p + k * cap, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_ppsi.p, e->ppsi.p, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_hx0.p, e->hx.p, Rs * sizeof(double), hipMemcpyDeviceToDevice);      // (row 0 of the ring: csf_scene.h)
+    if (c == hipSuccess) c = hipMemcpy(cs->img_hy0.p, e->hy.p, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_ti.p, e->ti.p, Rs * sizeof(int32_t), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_ptr.p, e->ptr.p, Rs * sizeof(int32_t), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_status.p, e->status.p, Rs * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+    if (c == hipSuccess) c = hipMemcpy(cs->img_znav.p, e->znav.p, Rs, hipMemcpyDeviceToDevice);
+    if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "csf_scene_calib_load: the reset image: %s", hipGetErrorString(c)));
+    // the views: the engine's Dev with every per-slot array shifted to the block of (set, scene) and the population the scene's.  What
+    // the one-wave tick does not touch - the binned order, the exchange records, the rings of a recording - is switched off.
+    {
+        const Dev &d0 = e->d;
+        std::vector<Dev> tab(views, d0);
+        for (int32_t k = 0; k < max_sets; k++)
+            for (int32_t q = 0; q < n_scn; q++) {
+                Dev &v = tab[(size_t)k * (size_t)n_scn + (size_t)q];
+                const int64_t b = (int64_t)k * R + ro[(size_t)q];
+                v.n = v.n_live = v.hi = n_riders[q];
+                v.lo = 0;
+                v.n_classes = 1;
+                v.s = d0.s + b, v.vdes = d0.vdes + b, v.qbeg = d0.qbeg + b, v.qlen = d0.qlen + b, v.ptr = d0.ptr + b, v.znav = d0.znav + b;
+                v.znp = d0.znp + b, v.ti = d0.ti + b, v.hx = d0.hx + b, v.hy = d0.hy + b, v.lti = d0.lti + b, v.zrid = d0.zrid + b;
+                v.dgood = d0.dgood + b, v.ppsi = d0.ppsi + b, v.F = d0.F + b, v.status = d0.status + b, v.froad = d0.froad + b;
+                v.alive = d0.alive + b;
+                v.rorg = d0.rorg + b;
+                v.rec = v.rec_w = d0.rec + b;
+                v.recg = v.recg_w = d0.recg + b;
+                v.rec2 = v.rec2_w = d0.rec2 ? d0.rec2 + b : nullptr;
+                v.F_rows = 6;
+                v.recs_valid = 0, v.recv_binned = 0, v.keep_lo = 0, v.classify = 0;
+                v.xbuf = nullptr, v.src64_w = nullptr, v.order = nullptr;
+                v.nv = v.nv_pad = 0;
+                v.replay_len = nullptr, v.replay_tick = 0, v.tick = 0;
+                v.hist = nullptr, v.hist_F = nullptr, v.rec_tick = nullptr, v.hist_stride = 1, v.hist_cap = 1;
+                v.snap = nullptr, v.atrace = nullptr, v.trace = nullptr, v.pair_count = nullptr;
+            }
+        c = hipMemcpy(cs->table.p, tab.data(), views * sizeof(Dev), hipMemcpyHostToDevice);
+        if (c == hipSuccess) c = hipDeviceSynchronize();
+        if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "csf_scene_calib_load: the table of views: %s", hipGetErrorString(c)));
+        double cb = 0.0;
+        for (int32_t i = 0; i < R; i++) cb = std::max({cb, std::fabs(s0[(size_t)i * ns] - d0.ox), std::fabs(s0[(size_t)i * ns + 1] - d0.oy)});
+        cs->coord_bound = cb;
+    }
+    e->scene_calib = std::move(cs);
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version, double *sums_out,
+                         int32_t stride, double *states_out) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_eval: no closed-loop data set (csf_scene_calib_load first)");
+    // before anything is read from `params` (csf_create_v)
+    if (params_size != sizeof(csf_params) || abi_version != CSF_ABI_VERSION)
+        return fail(e, CSF_E_ABI, "csf_scene_calib_eval: the caller's csf_params has %zu bytes and ABI %d, this library's has %zu bytes and ABI %d",
+                    params_size, (int)abi_version, sizeof(csf_params), (int)CSF_ABI_VERSION);
+    SceneCalibState &cs = *e->scene_calib;
+    if (!params || !sums_out) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: NULL array");
+    if (n_sets < 1 || n_sets > cs.max_sets) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: %d parameter sets, the data set was loaded for 1 .. %d", (int)n_sets, (int)cs.max_sets);
+    if (stride < 1) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: stride must be >= 1");
+    for (int32_t k = 0; k < n_sets; k++) {
+        int rc = check_params(e, params + k);
+        if (rc) return rc;
+        if (params[k].model != e->d.p.model) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d is of vehicle class %d, the data set was loaded for class %d", (int)k, (int)params[k].model, (int)e->d.p.model);
+        if (params[k].t_s != e->d.p.t_s || params[k].traj_len != e->d.p.traj_len)
+            return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d: t_s and traj_len are the engine's (parameters.py:516-528)", (int)k);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = upload_all(e);
+    if (rc) return rc;
+    const int64_t n = (int64_t)n_sets * cs.R;
+    const int64_t n_samples = states_out ? cs.n_ticks / stride : 0;
+    const size_t n_states = (size_t)n_samples * (size_t)n * (size_t)e->d.ns;
+    if (n_states > cs.states.n) {
+        HIPCHK(e, hipStreamSynchronize(e->main));
+        HIPCHK(e, cs.states.alloc(n_states));
+    }
+    // the table of this call, composed in pinned memory (the last call has been waited for).  The bands of the fp32 field-of-view
+    // and side decisions (consts.inc: fov_band_consts) are those of the largest coordinate any rider can reach in n_ticks from the
+    // start of its scene with the set's speed clamp: conservative for every tick, and inside a band the kernel decides by the
+    // reference's fp64 chain, so its width changes no result.
+    for (int32_t k = 0; k < n_sets; k++) {
+        SceneSet &ss = cs.sets_pin.p[k];
+        std::memset(&ss, 0, sizeof ss);
+        ss.p = params[k];
+        // (derive_consts without update_far_radius: rfar, reach and tA0 .. tB1 stay 0.  They are the cull of the pair kernels
+        // (csf_field.h: keep_x2) and depend on the population size, which differs from scene to scene; the one-wave tick culls
+        // nothing and reads none of them.  A tick that does must get them per (set, scene), not from this record.)
+        derive_pair_consts(ss.p, ss.pc, e->knobs.rnear);
+        if (ss.p.model == CSF_PLANARBIKE) derive_planarbike(ss.p, ss.pb);
+        const double vmax = std::max({std::fabs(ss.p.v_max_riding[0]), std::fabs(ss.p.v_max_riding[1]), std::fabs(ss.p.v_max_walk)});
+        const double step = ss.p.t_s * vmax * 1.01 + 1e-4;
+        fov_band_consts(e->knobs, step, cs.coord_bound + step * (double)(cs.n_ticks + 2) + 1.0, ss.pc);
+    }
+    SceneDev c{};
+    c.obj = cs.obj.p, c.len = cs.len.p, c.roff = cs.roff.p;
+    c.n_scn = cs.n_scn, c.n_ticks = (int32_t)cs.n_ticks, c.n_feat = cs.n_feat, c.R = cs.R;
+    for (int k = 0; k < CALIB_MAX_FEAT; k++) c.feat[k] = cs.feat[k];
+    c.img_cap = cs.R;
+    c.img_s = cs.img_s.p, c.img_lti = cs.img_lti.p, c.img_ppsi = cs.img_ppsi.p, c.img_znp = cs.img_znp.p, c.img_hx0 = cs.img_hx0.p, c.img_hy0 = cs.img_hy0.p;
+    c.img_ti = cs.img_ti.p, c.img_ptr = cs.img_ptr.p, c.img_status = cs.img_status.p, c.img_znav = cs.img_znav.p;
+    c.sums = cs.sums.dev;
+    c.states = n_states > 0 ? cs.states.p : nullptr;
+    c.stride = states_out ? stride : 1;
+    c.n_samples = (int32_t)n_samples;
+    c.n_sets = n_sets;
+    HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
+    launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
+    HIPCHK(e, hipGetLastError());
+    cs.launches++;
+    if (n_states > 0) HIPCHK(e, hipMemcpyAsync(states_out, cs.states.p, n_states * sizeof(double), hipMemcpyDeviceToHost, e->main));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    std::memcpy(sums_out, cs.sums.p, (size_t)n * sizeof(double2));
+    // the slots hold the end of this evaluation (the read-backs show it); nothing of it enters the next one
+    e->device_ahead = true;
+    e->mid_synced = false;
+    e->bounds_fresh = false;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_launches(const csf_engine *e, int64_t *n_launches) try {
+    if (!e || !n_launches) return CSF_E_ARG;
+    if (!e->scene_calib) return CSF_E_STATE;       // (no data set; no message is written: the call changes nothing)
+    *n_launches = e->scene_calib->launches;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_clear(csf_engine *e) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_clear: no closed-loop data set");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // The removal goes through the host mirror, which closes the holes (compact_host): patched on the device it would leave
+    // max_sets x R dead slots behind, and a small population added next would find d.n > n_live and miss the one-wave tick.
+    // What can fail - the download into the mirror - comes first, with the data set still held: a refused call changes nothing.
+    int rc = prepare_mutation(e, true);
+    if (rc) return rc;
+    std::vector<int32_t> all(e->order.size());
+    for (size_t i = 0; i < all.size(); i++) all[i] = (int32_t)i;
+    std::shared_ptr<SceneCalibState> cs = std::move(e->scene_calib);   // (csf_remove_agents takes the engine again)
+    e->scene_calib.reset();
+    rc = all.empty() ? CSF_OK : csf_remove_agents(e, (int64_t)all.size(), all.data());
+    if (rc) e->scene_calib = std::move(cs);                            // (refused before it touched the mirror: the data set stays)
+    return rc;                                                         // the buffers go with cs
+} catch (...) { return csf_caught(e); }

@@ -14,9 +14,10 @@ int fail(csf_engine *e, int code, const char *fmt, ...) {
     return code;
 }
 
-// an engine that holds a calibration data set (csf_calib_load) is evaluated, read, given destination queues and cleared - nothing else
+// an engine that holds a calibration data set (csf_calib_load, csf_scene_calib_load) is evaluated, read, given destination queues and cleared - nothing else
 int calib_refuses(csf_engine *e, const char *what) {
-    if (!e || !e->calib) return CSF_OK;
+    if (!e || (!e->calib && !e->scene_calib)) return CSF_OK;
+    if (e->scene_calib) return fail(e, CSF_E_STATE, "%s: the engine holds a closed-loop calibration data set (csf_scene_calib_clear first)", what);
     return fail(e, CSF_E_STATE, "%s: the engine holds a calibration data set (csf_calib_clear first)", what);
 }
 
@@ -183,9 +184,34 @@ void update_far_radius(csf_engine *e) {   // depends on the parameters and on th
 // with cos(hfov / 2): off by < 3 eps_p / rho + 8 u (the rsq included); twice that is its band, and that of sin(bearing).
 // A pair formed from the precise records (offsets of at most a few metres from origins whose difference is exact) has
 // eps_p = u * (largest offset), and its band is evaluated with rho itself: 24 eps_p rho + 36 u r2; 6 eps_p + 10 u rho.
+// the bands themselves, for positions whose coordinates stay below cmax and road users that move at most `step` per tick
+void fov_band_consts(const Knobs &kn, double step, double cmax, PairConsts &k) {
+    const double u = 5.9604644775390625e-8;
+    const double eps_p = u * cmax * 1.01 + 4 * u;
+    // (full circle: chs = 4, g > 3 r2 - never inside a band that small)
+    const double sc = kn.fov_band;
+    k.fovA = (float)(sc * (36 * u + 1.5 * eps_p));
+    k.fovB = (float)(sc * 96 * eps_p);
+    k.sideA = (float)(sc * 0.625 * u);
+    k.sideB = (float)(sc * (6 * eps_p + 40 * u));
+    k.fovT0 = (float)(sc * 16 * u);
+    k.fovT1 = (float)(sc * 6 * eps_p);
+    // whole batches are classified against the field-of-view cone with a margin of 1e-4 in the cosine (csf_pair.hip:
+    // classify_batch): the bearing of a source nearer than 2.9 u (coordinates) / 5e-5 is not known that well in fp32, so a
+    // batch whose circle comes closer goes to the per-lane test
+    k.clsk = (float)(2.9 * u * 1.01 / 5e-5);
+    // offsets: a quarter-metre grid of origins + what a road user covers between two re-binnings (REBIN_TICKS steps + a few;
+    // arrivals take their position as their origin)
+    const double off = 0.25 + step * (double)(kn.rebin_ticks + 8);
+    const double eps_o = u * off * 1.5;
+    k.fovP1 = (float)(sc * 24 * eps_o);
+    k.fovP2 = (float)(sc * 36 * u);
+    k.sideP0 = (float)(sc * 6 * eps_o);
+    k.sideP1 = (float)(sc * 10 * u);
+}
+
 int set_fov_band(csf_engine *e) {
     Dev &d = e->d;
-    const double u = 5.9604644775390625e-8;
     if (e->bound_stale) {   // (single device: every slot's state is here)
         // (through a pinned buffer: the first copy into pageable memory of a process costs ~9 ms - the runtime sets its staging
         // path up - and a population that is only ever stepped met it here, in the middle of a run: tick 4 096 of config 2)
@@ -212,28 +238,8 @@ int set_fov_band(csf_engine *e) {
     // (a tighter one - far-field radius + the extent of a group and of a batch - would need the circles, which only the
     // device knows; the band only decides how many pairs take the exact path, a few per thousand receivers either way)
     if (d.recv_binned) cmax *= 2.0;
-    const double eps_p = u * cmax * 1.01 + 4 * u;
-    // (full circle: chs = 4, g > 3 r2 - never inside a band that small)
     PairConsts &k = d.pc;
-    const double sc = e->knobs.fov_band;
-    k.fovA = (float)(sc * (36 * u + 1.5 * eps_p));
-    k.fovB = (float)(sc * 96 * eps_p);
-    k.sideA = (float)(sc * 0.625 * u);
-    k.sideB = (float)(sc * (6 * eps_p + 40 * u));
-    k.fovT0 = (float)(sc * 16 * u);
-    k.fovT1 = (float)(sc * 6 * eps_p);
-    // whole batches are classified against the field-of-view cone with a margin of 1e-4 in the cosine (csf_pair.hip:
-    // classify_batch): the bearing of a source nearer than 2.9 u (coordinates) / 5e-5 is not known that well in fp32, so a
-    // batch whose circle comes closer goes to the per-lane test
-    k.clsk = (float)(2.9 * u * 1.01 / 5e-5);
-    // offsets: a quarter-metre grid of origins + what a road user covers between two re-binnings (REBIN_TICKS steps + a few;
-    // arrivals take their position as their origin)
-    const double off = 0.25 + step * (double)(e->knobs.rebin_ticks + 8);
-    const double eps_o = u * off * 1.5;
-    k.fovP1 = (float)(sc * 24 * eps_o);
-    k.fovP2 = (float)(sc * 36 * u);
-    k.sideP0 = (float)(sc * 6 * eps_o);
-    k.sideP1 = (float)(sc * 10 * u);
+    fov_band_consts(e->knobs, step, cmax, k);
     for (csf_engine::Segment &sg : e->segs) {
         sg.pc.fovA = k.fovA, sg.pc.fovB = k.fovB, sg.pc.sideA = k.sideA, sg.pc.sideB = k.sideB;
         sg.pc.fovT0 = k.fovT0, sg.pc.fovT1 = k.fovT1, sg.pc.clsk = k.clsk;

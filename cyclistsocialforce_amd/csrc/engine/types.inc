@@ -24,6 +24,7 @@
 
 #include "csf_dev.h"
 #include "csf_calib.h"
+#include "csf_scene.h"
 
 using namespace csf;
 
@@ -522,6 +523,9 @@ struct csf_engine {
     // takes csf_calib_eval, csf_calib_clear, csf_set_dest_queue (a route for its vehicles) and the read-backs, and refuses everything
     // that steps it, changes its population, parameters or recording, or writes navigation state (calib_refuses)
     std::shared_ptr<struct CalibState> calib;
+    // csf_scene_calib_load: the same for closed-loop scenes (engine/abi_scene.inc); such an engine takes csf_scene_calib_eval,
+    // csf_scene_calib_clear and the read-backs
+    std::shared_ptr<struct SceneCalibState> scene_calib;
     int64_t batch_ticks = 0;         // ticks run inside a batched ONE-WAVE launch (csf_batch_ticks)
     int64_t batch_mid_ticks = 0;     // ticks run inside a batched one-launch tick (csf_batch_mid_ticks; mid_ticks counts them too)
     // csf_step_batch, mid-size members: the launches of a re-binning on the plain order (identity order, records re-expressed) and

@@ -260,6 +260,62 @@ class Engine:
         self._ck(self._lib.csf_calib_launches(self._h, C.byref(n)))
         return int(n.value)
 
+    # -- calibration on closed-loop scenes (include/csf.h: csf_scene_calib_load ...; calibration.InteractionCalibration drives it) --
+    def scene_calib_load(self, n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths=None, max_sets=256):
+        """Make this EMPTY engine hold a data set of closed-loop scenes: n_riders [n_scn] road users per scene (1 .. 32, R their
+        sum), start states s0 [R, >= n_states], v_desired [R] (or a scalar), the riders' destination queues in CSR form
+        (dest_offsets [R + 1], dest_xyz_stop [rows, 3]), the objective [T, R, n_feat] and the rows of vehicle.traj (0 .. 5) its
+        columns are compared with; lengths [n_scn]: ticks of every scene (default: T).  capacity >= max_sets * R."""
+        nr = np.ascontiguousarray(n_riders, dtype=np.int32).reshape(-1)
+        if nr.size < 1:
+            raise ValueError("n_riders must name at least one scene")
+        R = int(nr.sum())
+        s0 = np.asarray(s0, dtype=np.float64)
+        if s0.ndim != 2 or s0.shape[0] != R or s0.shape[1] < self.ns:
+            raise ValueError(f"s0 must be [sum(n_riders), >={self.ns}]")
+        s0 = _f64(s0[:, : self.ns])
+        vd = _f64(np.broadcast_to(np.asarray(v_desired, dtype=np.float64), (R,)))
+        off = np.ascontiguousarray(dest_offsets, dtype=np.int64)
+        xyz = _f64(dest_xyz_stop).reshape(-1, 3)
+        if off.shape != (R + 1,) or off[0] < 0 or off[-1] > xyz.shape[0] or np.any(np.diff(off) < 1):
+            raise ValueError("dest_offsets must be [sum(n_riders) + 1], ascending, with at least one row of dest_xyz_stop per rider")
+        feat = np.ascontiguousarray(feat, dtype=np.int32).reshape(-1)
+        obj = _f64(objective)
+        if obj.ndim != 3 or obj.shape[1:] != (R, feat.size) or obj.shape[0] < 1:
+            raise ValueError("objective must be [n_ticks, sum(n_riders), n_feat]")
+        T = obj.shape[0]
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        if ln is not None and ln.shape != (nr.size,):
+            raise ValueError("lengths must have one entry per scene")
+        self._ck(self._lib.csf_scene_calib_load(self._h, nr.size, _ptr(nr), T, _ptr(s0), _ptr(vd), _ptr(off), _ptr(xyz),
+                                                None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat), int(max_sets)))
+        self._scene_calib = (R, T)
+
+    def scene_calib_eval(self, pods, states=False, stride=1):
+        """Evaluate the parameter sets `pods` (a sequence of csf_params) on the loaded scenes in one launch: sums [n_sets, R, 2] =
+        (sum d^2, sum |d|) per set and RIDER (the riders of a scene are added by the caller, in rider order), and with states=True
+        the trajectories [T // stride, n_sets * R, n_states] as well (slot = set * R + rider)."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_eval: no closed-loop data set (scene_calib_load first)")
+        R, T = self._scene_calib
+        pods = list(pods)
+        tab = (Params * len(pods))(*pods)
+        sums = np.zeros((len(pods), R, 2))
+        out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * R, self.ns)) if states else None
+        self._ck(self._lib.csf_scene_calib_eval(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION, _ptr(sums), int(stride),
+                                                None if out is None else _ptr(out)))
+        return (sums, out) if states else sums
+
+    def scene_calib_clear(self):
+        self._ck(self._lib.csf_scene_calib_clear(self._h))
+        self._scene_calib = None
+
+    def scene_calib_launches(self):
+        """kernel launches of scene_calib_eval since scene_calib_load: one per call"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_scene_calib_launches(self._h, C.byref(n)))
+        return int(n.value)
+
     def dest_force(self):
         fx = np.zeros(self.n)
         fy = np.zeros(self.n)

@@ -459,6 +459,43 @@ int csf_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size
 int csf_calib_launches(const csf_engine *e, int64_t *n_launches);
 int csf_calib_clear(csf_engine *e);
 
+/* Calibration of the interaction parameters on closed-loop scenes.  A replay of recorded forces (above) couples
+ * no two vehicles, so the parameters of the social-force field - f_0, sigma_0..3, e_0, e_1, hfov, p_0, p_decay, the priority rule - act
+ * only when the riders of a scene are simulated together.  csf_scene_calib_load makes an EMPTY engine (one parameter set, no road, no
+ * recording; not a member of a batch or of a communicator; not an UncontrolledVehicle's) hold a data set of n_scn scenes: scene q has
+ * n_riders[q] road users (1 .. 32) of the engine's class, R = sum n_riders; per rider the start state s0 [R][n_states], v_desired [R] and a
+ * destination queue in CSR form as csf_set_dest_queue takes it with reset = 1 (dest_offsets [R + 1], dest_xyz_stop rows of (x, y, stop); at
+ * least one row each); per scene its ticks (lengths [n_scn], 0 .. n_ticks; NULL: all of them); the objective [n_ticks][R][n_feat] and the rows
+ * of vehicle.traj its columns are compared with (feat [n_feat], 0 .. 5 = x, y, psi, v, delta, theta; a row the vehicle class does not have
+ * compares 0).  The engine's capacity must be >= max_sets * R, max_sets <= 256.  It creates the max_sets * R road users - slot set * R +
+ * rider, the scenes of a set one after the other - and keeps an image of every per-slot array that a closed-loop tick writes and a later
+ * tick reads: the state, the integrator's side-state, ring column and status as csf_calib_load does, and with them the destination pointer,
+ * the navigation state and its latched parameters, and the row of the short position ring that the spline planner reads first.
+ * csf_scene_calib_eval evaluates n_sets <= max_sets candidate sets (checked as csf_create_v checks: params_size, abi_version; all of the
+ * engine's vehicle class, t_s and traj_len; the priority rule is the set's own) in ONE launch, one workgroup of one wave per (set, scene):
+ * it restores its scene from the image, runs the one-wave tick of csf_step (csf_small_ticks) for lengths[scene] ticks and adds after every
+ * tick, per rider, in fp64 and tick order, d = state after tick t - objective[t][rider][f] over the features (no angle wrap): sums_out
+ * [n_sets][R][2] = (sum d^2, sum |d|) PER RIDER - the caller adds the riders of a scene in rider order, so the order of every sum is fixed.
+ * calc_sse_timesteps is the sum of the first over all riders; calc_maesse_samples the sum over the scenes of (sum of the second over the
+ * scene's riders / (length * n_riders * n_feat))^2.  states_out (may be NULL): [n_ticks / stride][n_sets * R][n_states], the state after every
+ * stride-th tick (stride >= 1); a scene that has ended keeps its last state.  An evaluation does not depend on the one before, on the place
+ * of a set in the call or on the other sets in it; launches and copies per call do not depend on n_ticks, n_sets or the scenes
+ * (csf_scene_calib_launches counts the launches).  While the data set is held the engine refuses csf_step and every call that changes the
+ * population, its queues, its parameters or its recording, and csf_calib_load (CSF_E_STATE; csf_scene_calib_load refuses an engine that holds
+ * the data set of csf_calib_load likewise); the read-backs show the end of the last evaluation.  csf_scene_calib_clear drops the data set and
+ * empties the engine - through the host mirror, so that no dead slot stays behind and a small population added next takes the one-wave
+ * tick of csf_step again.  A refused call changes nothing. */
+int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks,
+                         const double *s0, const double *v_desired,
+                         const int64_t *dest_offsets, const double *dest_xyz_stop,
+                         const int32_t *lengths, const double *objective,
+                         int32_t n_feat, const int32_t *feat, int32_t max_sets);
+int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params,
+                         size_t params_size, int32_t abi_version,
+                         double *sums_out, int32_t stride, double *states_out);
+int csf_scene_calib_launches(const csf_engine *e, int64_t *n_launches);
+int csf_scene_calib_clear(csf_engine *e);
+
 /* Far-field radius of the pair kernel (metres; +inf when the cull is off).  The repulsive field of
  * vehicle.py:1560-1648 decays at least like f_0 exp(-kappa rho); sources beyond
  * R = ln(n / eps) / kappa together add less than eps * f_0 (eps = 2^-24 unless the environment variable

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Time of ONE evaluation of a closed-loop calibration objective for n_sets candidate parameter sets (GPU box): (b)
+csf_scene_calib_eval - the scenes resident, workgroup = (set, scene), the error summed in the launch - against (a) what a caller
+had before: one engine per (set, scene) in a batch, every call their start states pushed back (csf_push_state, destination
+pointers rewound), step_batch with csf_record, batch_recorded, and the NumPy error on the trajectories.  (The baseline's reset
+leaves the latched navigation state and the integrators' side-state where the last call ended - it does less than a full reset
+and is timed as it is.)  16 scenes of 3 - 8 riders x 1 000 ticks, TwoDBicycle and InvPendulumBicycle, n_sets in 1, 4, 16, 64, 256
+(the baseline holds n_sets x 16 engines - 4 096 at 256 sets; --base-max caps it where that is too many for a box); the two paths
+alternate window by window in one process, after one warm-up call of each.  One JSON line per cell, printed and appended to --out
+as soon as the cell is done: medians of the windows with min / max, milliseconds per evaluation of all n_sets.
+
+    python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.environ.pop("CSF_PAIR_VARIANT", None)
+from cyclistsocialforce_amd import _ffi, parameters  # noqa: E402
+from cyclistsocialforce_amd.engine import Engine  # noqa: E402
+
+
+def scene(model, n, seed, box=14.0):
+    rng = np.random.default_rng(seed)
+    s0 = np.zeros((n, _ffi.N_STATES[parameters.default_pod(model).model]))
+    s0[:, 0], s0[:, 1] = rng.uniform(0, box, n), rng.uniform(0, box, n)
+    s0[:, 2], s0[:, 3] = rng.uniform(-np.pi, np.pi, n), rng.uniform(3, 6, n)
+    reach = np.array([8.0, 25.0, 60.0, 61.0])
+    dq = np.zeros((n, 5, 3))
+    dq[:, 0, :2] = s0[:, :2]
+    dq[:, 1:, 0] = s0[:, 0:1] + reach[None, :] * np.cos(s0[:, 2:3])
+    dq[:, 1:, 1] = s0[:, 1:2] + reach[None, :] * np.sin(s0[:, 2:3])
+    dq[:, 4, 2] = 1.0
+    return s0, np.arange(n + 1) * 5, dq.reshape(-1, 3)
+
+
+def pod_sets(base, n):
+    out = []
+    for k in range(n):
+        p = _ffi.Params.from_buffer_copy(base)
+        p.f_0 = base.f_0 * (1.0 + 0.002 * k)
+        p.p_0 = base.p_0 * (1.0 + 0.002 * k)
+        out.append(p)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", default="1,4,16,64,256")
+    ap.add_argument("--scenes", type=int, default=16)
+    ap.add_argument("--ticks", type=int, default=1000)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--base-max", type=int, default=256)
+    ap.add_argument("--models", default="twod,invpend")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    feat = np.array([0, 1], dtype=np.int32)
+    if a.out:
+        open(a.out, "w").close()
+    for model in a.models.split(","):
+        base = parameters.default_pod(model)
+        per = [scene(model, 3 + q % 6, 50 + q) for q in range(a.scenes)]
+        nr = np.array([s.shape[0] for s, _, _ in per], dtype=np.int32)
+        roff = np.r_[0, np.cumsum(nr)]
+        R = int(roff[-1])
+        s0 = np.concatenate([s for s, _, _ in per])
+        rows = np.concatenate([d for _, _, d in per])
+        off = np.r_[0, np.cumsum(np.concatenate([np.diff(o) for _, o, _ in per]))]
+        obj = np.random.default_rng(1).normal(size=(a.ticks, R, feat.size))
+        for n_sets in [int(x) for x in a.sets.split(",")]:
+            sets = pod_sets(base, n_sets)
+            e = Engine(base, n_sets * R)
+            e.scene_calib_load(nr, s0, 5.0, off, rows, obj, feat, max_sets=n_sets)
+            twins = []
+            if n_sets <= a.base_max:
+                for pod in sets:
+                    for s, o, d in per:
+                        t = Engine(pod, s.shape[0])
+                        t.add_agents(s, 5.0)
+                        t.set_dest_queue(np.arange(s.shape[0]), o, d, reset=True)
+                        t.record(stride=1, capacity=a.ticks, forces=False)
+                        twins.append(t)
+                Engine.batch_join(twins)
+
+            def new():
+                return e.scene_calib_eval(sets)[:, :, 0].sum(axis=1)
+
+            def old():
+                err = np.zeros(n_sets)
+                for i, t in enumerate(twins):
+                    s = per[i % a.scenes][0]
+                    t.push_state(np.arange(s.shape[0]), s)
+                    t.set_dest_pointer(np.arange(s.shape[0]), 0)
+                Engine.step_batch(twins, a.ticks)
+                for i, (S, _, _) in enumerate(Engine.batch_recorded(twins, a.ticks)):
+                    q = i % a.scenes
+                    err[i // a.scenes] += float(np.square(S[:, :, feat] - obj[:, roff[q]: roff[q + 1]]).sum())
+                return err
+
+            first_new = new()
+            # (the first baseline call starts from fresh engines: there the two legs do the same job and their errors agree)
+            first_gap = float(np.abs(old() / first_new - 1.0).max()) if twins else None
+            t_new, t_old = [], []
+            for _ in range(a.windows):
+                t0 = time.perf_counter(); new(); t_new.append((time.perf_counter() - t0) * 1e3)
+                if twins:
+                    t0 = time.perf_counter(); old(); t_old.append((time.perf_counter() - t0) * 1e3)
+            line = dict(model=model, n_sets=n_sets, scenes=a.scenes, riders=R, ticks=a.ticks, windows=a.windows, first_call_rel_gap=first_gap,
+                        new_ms=dict(median=float(np.median(t_new)), min=min(t_new), max=max(t_new)),
+                        base_ms=dict(median=float(np.median(t_old)), min=min(t_old), max=max(t_old)) if t_old else None)
+            print(json.dumps(line), flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(json.dumps(line) + "\n")
+            for t in twins:
+                t.close()
+            e.close()
+
+
+if __name__ == "__main__":
+    main()
