@@ -34,6 +34,7 @@ SYMBOLS = (
     "csf_record", "csf_get_record", "csf_batch_get_record",
     "csf_calib_load", "csf_calib_eval", "csf_calib_launches", "csf_calib_clear",
     "csf_scene_calib_load", "csf_scene_calib_eval", "csf_scene_calib_launches", "csf_scene_calib_clear",
+    "csf_scene_calib_replay",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -187,6 +188,8 @@ def load():
         L.csf_scene_calib_eval.argtypes = [vp, i32, C.POINTER(Params), C.c_size_t, i32, dp, i32, dp]
         L.csf_scene_calib_launches.argtypes = [vp, C.POINTER(i64)]
         L.csf_scene_calib_clear.argtypes = [vp]
+    if hasattr(L, "csf_scene_calib_replay"):     # (the same)
+        L.csf_scene_calib_replay.argtypes = [vp, vp, dp]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

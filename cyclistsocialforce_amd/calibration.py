@@ -413,9 +413,15 @@ class SceneData:
     desired speeds v_desired [n] (or a scalar), the riders' destination queues in CSR form (dest_offsets [n + 1], dest_xyz_stop
     [rows, 3] = (x, y, stop); at least one row each), the recorded trajectory traj [n_t, n, n_cols] - row t the state AFTER tick
     t + 1, columns the rows of vehicle.traj (x, y, psi, v, delta, theta) as far as they were recorded - and its length in ticks
-    (default: n_t)."""
+    (default: n_t).
 
-    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None):
+    replayed [n] (bool, default: nobody) marks road users that FOLLOW THEIR RECORDING: they are not simulated with the candidate
+    parameters but put on traj[t, i, :4] = (x, y, psi, v) after every tick, act on the others as sources of the field only and
+    add nothing to the error - the others of an ego evaluation (`ego_split`), or a road user of another class.  Such a road
+    user needs finite columns 0 .. 3 of traj over all `length` rows; its destination queue may be left out (no row between its
+    two offsets): it gets the single row a fresh vehicle has, its own start (vehicle.py:183-185)."""
+
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None):
         self.s0 = np.asarray(s0, dtype=float)
         if self.s0.ndim != 2 or self.s0.shape[1] < 4 or not 1 <= self.s0.shape[0] <= 32:
             raise ValueError("a scene has 1 .. 32 road users: s0 is [n, >= 4]")
@@ -424,21 +430,48 @@ class SceneData:
             self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (n,)))
         except ValueError:
             raise ValueError("v_desired: one desired speed per road user, or a scalar") from None
+        if replayed is None:
+            self.replayed = np.zeros(n, dtype=bool)
+        else:
+            self.replayed = np.array(replayed, dtype=bool)
+            if self.replayed.shape != (n,):
+                raise ValueError("replayed: one flag per road user")
         self.dest_offsets = np.asarray(dest_offsets, dtype=np.int64)
         self.dest_xyz_stop = np.asarray(dest_xyz_stop, dtype=float).reshape(-1, 3)
         off = self.dest_offsets
-        if off.shape != (n + 1,) or off[0] != 0 or off[-1] != self.dest_xyz_stop.shape[0] or np.any(np.diff(off) < 1):
-            raise ValueError("dest_offsets is [n + 1], starts at 0, ends at the rows of dest_xyz_stop, and gives every road user a row")
+        if off.shape != (n + 1,) or off[0] != 0 or off[-1] != self.dest_xyz_stop.shape[0] or np.any(np.diff(off) < 0) \
+                or np.any((np.diff(off) < 1) & ~self.replayed):
+            raise ValueError("dest_offsets is [n + 1], starts at 0, ends at the rows of dest_xyz_stop, and gives every simulated road user a row")
+        if np.any(np.diff(off) < 1):                              # a replayed road user without a queue: its own start, no stop
+            rows, new = [], [0]
+            for i in range(n):
+                own = self.dest_xyz_stop[off[i]: off[i + 1]]
+                rows.append(own if own.shape[0] else np.array([[self.s0[i, 0], self.s0[i, 1], 0.0]]))
+                new.append(new[-1] + rows[-1].shape[0])
+            self.dest_offsets, self.dest_xyz_stop = np.array(new, dtype=np.int64), np.concatenate(rows)
         self.traj = np.asarray(traj, dtype=float)
         if self.traj.ndim != 3 or self.traj.shape[1] != n or not 1 <= self.traj.shape[2] <= TRAJ_ROWS:
             raise ValueError(f"traj is [n_t, n, 1 .. {TRAJ_ROWS}]: the state of every road user after every tick")
         self.length = self.traj.shape[0] if length is None else int(length)
         if not 0 <= self.length <= self.traj.shape[0]:
             raise ValueError("length: 0 .. the rows of traj")
+        if self.replayed.any() and (self.traj.shape[2] < 4 or not np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()):
+            raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over all `length` rows")
 
     @property
     def n(self):
         return self.s0.shape[0]
+
+    def ego_split(self):
+        """The leave-one-out scenes of this scene, one per simulated road user: scene i simulates that road user alone and replays
+        all others from the recording (road users that are replayed here stay so).  Host only.  s0, the queues and traj are
+        shared with this scene, not copied; every scene has a mask of its own."""
+        out = []
+        for i in np.flatnonzero(~self.replayed):
+            mask = np.ones(self.n, dtype=bool)
+            mask[i] = False
+            out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask))
+        return out
 
 
 def _riders_then_scenes(per_rider, roff):
@@ -465,6 +498,10 @@ class InteractionCalibration:
     candidate sets (`Engine.scene_calib_eval`).  With calc_sse_timesteps or calc_maesse_samples the error is formed from the
     per-rider sums the device returns - the riders of a scene added in rider order, then the scenes in scene order; a sample of
     calc_maesse_samples is a scene - and another error_func gets the trajectories, [length, n_riders, n_feat] per scene.
+
+    Road users a scene marks as replayed (`SceneData(replayed=...)`, `SceneData.ego_split`) follow their recording on the device
+    (`Engine.scene_calib_replay`) and are no part of the error: calc_sse_timesteps sums the simulated riders, calc_maesse_samples
+    divides a scene's sum by length x simulated riders x n_feat, another error_func and `simulate` get the simulated riders only.
 
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
@@ -512,7 +549,10 @@ class InteractionCalibration:
         lens = np.array([d.length for d in data], dtype=np.int32)
         s0, vd, obj = np.zeros((R, 8)), np.zeros(R), np.zeros((T, R, feat.size))
         off, rows = [0], []
+        rep = np.concatenate([d.replayed for d in data])
         for q, d in enumerate(data):
+            if d.replayed.all():
+                raise ValueError(f"scene {q}: every road user is replayed - there is nothing to fit")
             if feat.max() >= d.traj.shape[2]:
                 raise ValueError(f"scene {q}: objective_features_traj names row {int(feat.max())} of vehicle.traj, the recorded trajectory has {d.traj.shape[2]}")
             sl = slice(roff[q], roff[q + 1])
@@ -524,20 +564,31 @@ class InteractionCalibration:
         engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
         engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
                                 max_sets=self.max_sets)
-        ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets,
-                  objectives=[d.traj[: d.length][:, :, feat] for d in data])
+        if rep.any():                                            # the recorded (x, y, psi, v) of the replayed riders, in rider order
+            rec = np.zeros((T, int(rep.sum()), 4))
+            at = 0
+            for d in data:
+                k = int(d.replayed.sum())
+                if k:
+                    rec[: d.traj.shape[0], at: at + k] = d.traj[:, d.replayed, :4]
+                at += k
+            engine.scene_calib_replay(rep, rec)
+        ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets, sim=[~d.replayed for d in data],
+                  nsim=np.array([int((~d.replayed).sum()) for d in data]),
+                  objectives=[d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data])
         self._sets[bool(test)] = ds
         return ds
 
     def _trajs(self, ds, states, k):
-        """the scenes of parameter set k from the states of one evaluation: [length, n_riders, n_feat] each (rows the class lacks: 0)"""
+        """the scenes of parameter set k from the states of one evaluation: [length, simulated riders, n_feat] each (rows the class
+        lacks: 0)"""
         ns, out = states.shape[2], []
         for q, ln in enumerate(ds["lens"]):
             tr = np.zeros((ln, ds["nr"][q], ds["feat"].size))
             for c, f in enumerate(ds["feat"]):
                 if f < ns:
                     tr[:, :, c] = states[:ln, k * ds["R"] + ds["roff"][q]: k * ds["R"] + ds["roff"][q + 1], f]
-            out.append(tr)
+            out.append(tr if ds["sim"][q].all() else tr[:, ds["sim"][q]])
         return out
 
     def evaluate(self, params_vals, test=False):
@@ -554,7 +605,7 @@ class InteractionCalibration:
             elif self.error_func is calc_maesse_samples:
                 sums = ds["engine"].scene_calib_eval(chunk)
                 with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
-                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["lens"] * ds["nr"] * float(ds["feat"].size))[None, :]
+                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["lens"] * ds["nsim"] * float(ds["feat"].size))[None, :]
                 err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
             else:
                 _, states = ds["engine"].scene_calib_eval(chunk, states=True)
@@ -563,8 +614,8 @@ class InteractionCalibration:
         return err
 
     def simulate(self, params_vals, test=False):
-        """The trajectories of one parameter vector on the training (test) scenes: ([length, n_riders, n_feat] per scene - the state
-        after each tick -, the objectives)."""
+        """The trajectories of one parameter vector on the training (test) scenes: ([length, simulated riders, n_feat] per scene -
+        the state after each tick -, the objectives)."""
         ds = self._dataset(test)
         _, states = ds["engine"].scene_calib_eval([self._pod(self._update_params_args_dict(np.asarray(params_vals, dtype=float)))], states=True)
         return self._trajs(ds, states, 0), list(ds["objectives"])

@@ -38,7 +38,11 @@ struct SceneDev {
     const uint8_t *img_znav;
     double2 *sums;               // [n_sets][R] (sum d^2, sum |d|) per rider: mapped host memory
     double *states;              // [n_ticks / stride][n_sets * R][ns], NULL: none
-    int32_t stride, n_samples, n_sets, pad;
+    int32_t stride, n_samples, n_sets, n_rep;
+    // Riders that follow their recording (csf_scene_calib_replay): they are put on their recorded (x, y, psi, v) behind every tick
+    // and act as sources of the field only; no error is summed for them.  rep == NULL: no rider is replayed.
+    const int32_t *rep_index;    // [R] -1: simulated, else the rider's column of rep
+    const double *rep;           // [n_ticks][n_rep][4] (x, y, psi, v) AFTER tick t: the row alignment of obj
 };
 
 // One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].

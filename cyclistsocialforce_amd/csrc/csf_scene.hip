@@ -13,6 +13,15 @@
 //   at the end                         (sum d^2, sum |d|) -> sums[set * R + rider] in mapped host memory; the host adds the riders
 //                                      of a scene in rider order (no reduction across lanes: the order of the sum is fixed)
 //
+// A rider that follows its recording (csf_scene_calib_replay) is ticked like every other - agent_body is called
+// inside small_tick_body - and its lane then overwrites (x, y, psi, v) with the recorded row of that tick: the sources every lane
+// reads at the top of the next tick (csf_small_body.inc: sx, sy, spsi, and se of the Bicycle field) are rows 0 - 3 of d.s, so the
+// others see the recording.  What the lane does not overwrite - delta, theta, lti, znav, znp, ptr, the status word - is its own and
+// read by no other lane; a status bit it raises says nothing about the evaluation.  No loop of agent_body<.., FUSED = true> depends
+// on the state for its end: the poll loop and the edge chain are compiled out (CHASE, edge_pending are false), update_destination
+// moves the pointer by at most 2, the scaling loop of invpend_step_yaw stops at 40 halvings and at a NaN norm, every other loop has
+// a constant trip count - a rider whose state is reset every tick cannot hold its wave.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -23,17 +32,20 @@ namespace csf {
 
 #include "csf_small_body.inc"
 
-// behind every tick: lane = rider of the scene, its error terms and, on a sampled tick, its state
+// behind every tick: lane = rider of the scene, its error terms (a replayed rider: its recorded state instead) and, on a sampled
+// tick, its state
+template <int MODEL>
 struct SceneHook {
     const SceneDev &c;
     const int64_t rider;          // set * R + first rider of the scene + lane: row of sums and of a sample
     const double *obj;            // objective of this lane's rider at tick 0
+    const double *rep;            // recorded (x, y, psi, v) of this lane's rider after tick 0; NULL: the rider is simulated
     double *smp;                  // where this lane's next sample goes (NULL: none)
     int wait;                     // ticks until the next sampled one
     int taken = 0;                // samples written
     double sse = 0.0, sae = 0.0;
-    __device__ __forceinline__ SceneHook(const SceneDev &c_, int64_t rider_, const double *obj_, double *smp_)
-        : c(c_), rider(rider_), obj(obj_), smp(smp_), wait(c_.stride - 1) {}
+    __device__ __forceinline__ SceneHook(const SceneDev &c_, int64_t rider_, const double *obj_, const double *rep_, double *smp_)
+        : c(c_), rider(rider_), obj(obj_), rep(rep_), smp(smp_), wait(c_.stride - 1) {}
     __device__ __forceinline__ void sample(const Dev &d, int lane) {
         for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
         smp += (int64_t)c.n_sets * c.R * d.ns;
@@ -41,14 +53,35 @@ struct SceneHook {
     }
     __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
         if (lane >= n) return;
-        const double *o = obj + (int64_t)t * c.R * c.n_feat;
-        for (int k = 0; k < c.n_feat; k++) {
-            const int f = c.feat[k];
-            // (a row the class does not have stays zero in the reference's traj: vehicle.py:158-160)
-            const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
-            const double e = sv - o[k];                       // a plain difference, no angle wrap: calibration.py:49, 76
-            sse += e * e;
-            sae += fabs(e);
+        if (rep != nullptr) {
+            // vehicle.s written from the recording (calibration.py:455-460) and what csf_push_state keeps consistent with it
+            // (abi_population.inc): this lane's own stores behind its tick's, program order.  Nothing is added to sse / sae.
+            const double *r = rep + (int64_t)t * c.n_rep * 4;
+            const double x = r[0], y = r[1], psi = r[2], v = r[3];
+            const int64_t cap = d.cap;
+            d.s[lane] = x;
+            d.s[cap + lane] = y;
+            d.s[2 * cap + lane] = psi;
+            d.s[3 * cap + lane] = v;
+            if (MODEL == CSF_BALANCINGRIDER) {                // (ppsi is the speed of the gains there; the yaw is -x[4], unwrapped)
+                const double twopi = 6.283185307179586476925286766559, own = d.lti[4 * cap + lane];
+                d.lti[4 * cap + lane] = -psi + twopi * nearbyint((own + psi) / twopi);
+            } else {
+                d.ppsi[lane] = psi;
+            }
+            const int64_t slot = d.ti[lane] & (d.hist_len - 1);
+            d.hx[slot * cap + lane] = x;
+            d.hy[slot * cap + lane] = y;
+        } else {
+            const double *o = obj + (int64_t)t * c.R * c.n_feat;
+            for (int k = 0; k < c.n_feat; k++) {
+                const int f = c.feat[k];
+                // (a row the class does not have stays zero in the reference's traj: vehicle.py:158-160)
+                const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
+                const double e = sv - o[k];                   // a plain difference, no angle wrap: calibration.py:49, 76
+                sse += e * e;
+                sae += fabs(e);
+            }
         }
         if (smp != nullptr) {
             if (wait == 0) {
@@ -101,7 +134,10 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
     // (the restored block is read by every lane of this wave in the first tick: the wave's own stores, program order - as from
     // tick to tick in small_tick_body)
     const int64_t rider = (int64_t)set * c.R + first + lane;
-    SceneHook hook(c, rider, c.obj + (first + lane) * c.n_feat, c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr);
+    // (rep_index is read by the lanes that have a rider only: it has R entries)
+    const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
+    SceneHook<MODEL> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
+                          c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr);
     small_tick_body<MODEL>(d, len, nullptr, srv_none, 0u, 0, hook);
     if (lane >= n) return;
     c.sums[rider] = make_double2(hook.sse, hook.sae);

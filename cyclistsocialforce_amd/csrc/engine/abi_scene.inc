@@ -22,6 +22,13 @@ struct SceneCalibState {
     HostBuf<SceneSet, false> sets_pin;       // ... and where the host composes them: one copy per call
     HostBuf<double2> sums;                   // [max_sets * R] written by the kernel (mapped)
     int64_t launches = 0;                    // csf_scene_calib_launches
+    // csf_scene_calib_replay: the riders that follow their recording (csf_scene.h).  n_rep == 0: none, and an evaluation is
+    // handed rep == NULL - the kernel's path without a replay
+    std::vector<int32_t> h_len, h_roff;      // the scenes' lengths and first riders, as on the device
+    DevBuf<int32_t> rep_index;               // [R]
+    DevBuf<double> rep;                      // [n_ticks][n_rep][4]
+    int32_t n_rep = 0;
+    double rep_bound = 0.0;                  // largest |coordinate| of a replayed row, relative to the scene origin
 };
 
 }  // extern "C++"
@@ -162,6 +169,7 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
         for (int32_t i = 0; i < R; i++) cb = std::max({cb, std::fabs(s0[(size_t)i * ns] - d0.ox), std::fabs(s0[(size_t)i * ns + 1] - d0.oy)});
         cs->coord_bound = cb;
     }
+    cs->h_len = std::move(ls), cs->h_roff = std::move(ro);
     e->scene_calib = std::move(cs);
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
@@ -210,7 +218,8 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
         if (ss.p.model == CSF_PLANARBIKE) derive_planarbike(ss.p, ss.pb);
         const double vmax = std::max({std::fabs(ss.p.v_max_riding[0]), std::fabs(ss.p.v_max_riding[1]), std::fabs(ss.p.v_max_walk)});
         const double step = ss.p.t_s * vmax * 1.01 + 1e-4;
-        fov_band_consts(e->knobs, step, cs.coord_bound + step * (double)(cs.n_ticks + 2) + 1.0, ss.pc);
+        // (a replayed rider is not bound by the set's clamp: it goes where its recording goes)
+        fov_band_consts(e->knobs, step, std::max(cs.coord_bound + step * (double)(cs.n_ticks + 2), cs.rep_bound) + 1.0, ss.pc);
     }
     SceneDev c{};
     c.obj = cs.obj.p, c.len = cs.len.p, c.roff = cs.roff.p;
@@ -224,6 +233,9 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
     c.stride = states_out ? stride : 1;
     c.n_samples = (int32_t)n_samples;
     c.n_sets = n_sets;
+    c.n_rep = cs.n_rep;
+    c.rep_index = cs.n_rep > 0 ? cs.rep_index.p : nullptr;
+    c.rep = cs.n_rep > 0 ? cs.rep.p : nullptr;
     HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
     HIPCHK(e, hipGetLastError());
@@ -235,6 +247,49 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
     e->device_ahead = true;
     e->mid_synced = false;
     e->bounds_fresh = false;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_replay(csf_engine *e, const uint8_t *replayed, const double *rows) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_replay: no closed-loop data set (csf_scene_calib_load first)");
+    SceneCalibState &cs = *e->scene_calib;
+    const int32_t R = cs.R;
+    std::vector<int32_t> index((size_t)R, -1);
+    int32_t n_rep = 0;
+    for (int32_t r = 0; replayed && r < R; r++)
+        if (replayed[r]) index[(size_t)r] = n_rep++;
+    if (n_rep > 0 && !rows) return fail(e, CSF_E_ARG, "csf_scene_calib_replay: %d riders are replayed and rows is NULL", (int)n_rep);
+    // the rows a tick reads - t < the length of the rider's scene - are finite; the largest coordinate among them sizes the bands
+    double bound = 0.0;
+    for (int32_t q = 0; n_rep > 0 && q < cs.n_scn; q++)
+        for (int32_t r = cs.h_roff[(size_t)q]; r < cs.h_roff[(size_t)q + 1]; r++) {
+            const int32_t k = index[(size_t)r];
+            if (k < 0) continue;
+            for (int64_t t = 0; t < cs.h_len[(size_t)q]; t++) {
+                const double *v = rows + ((size_t)t * (size_t)n_rep + (size_t)k) * 4;
+                if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && std::isfinite(v[3])))
+                    return fail(e, CSF_E_ARG, "csf_scene_calib_replay: the recorded state of rider %d after tick %lld is not finite", (int)r, (long long)t);
+                bound = std::max({bound, std::fabs(v[0] - e->d.ox), std::fabs(v[1] - e->d.oy)});
+            }
+        }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // everything that can fail first: a refused call changes nothing
+    DevBuf<int32_t> d_index;
+    DevBuf<double> d_rows;
+    if (n_rep > 0) {
+        const size_t count = (size_t)cs.n_ticks * (size_t)n_rep * 4;
+        hipError_t r = d_index.alloc((size_t)R);
+        if (r == hipSuccess) r = d_rows.alloc(count);
+        if (r == hipSuccess) r = hipMemcpy(d_index.p, index.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (r == hipSuccess) r = hipMemcpy(d_rows.p, rows, count * sizeof(double), hipMemcpyHostToDevice);
+        if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_replay: no memory for the recorded states: %s", hipGetErrorString(r));
+    }
+    cs.rep_index = std::move(d_index);
+    cs.rep = std::move(d_rows);
+    cs.n_rep = n_rep;
+    cs.rep_bound = bound;
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 

@@ -306,6 +306,26 @@ class Engine:
                                                 None if out is None else _ptr(out)))
         return (sums, out) if states else sums
 
+    def scene_calib_replay(self, replayed, rows=None):
+        """Riders of the loaded scenes that follow their recording: replayed [R] (bool), rows [T, n_rep, 4] = (x, y, psi, v) of the
+        replayed riders, in rider order, after every tick.  They are sources of the field only; their sums are (0, 0).  None (or
+        no rider marked) drops the replay."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_replay: no closed-loop data set (scene_calib_load first)")
+        R, T = self._scene_calib
+        if replayed is None:
+            self._ck(self._lib.csf_scene_calib_replay(self._h, None, None))
+            return
+        mask = np.ascontiguousarray(np.asarray(replayed, dtype=bool), dtype=np.uint8)
+        if mask.shape != (R,):
+            raise ValueError("replayed must have one entry per rider of the data set")
+        n_rep = int(mask.sum())
+        if n_rep:
+            rows = _f64(rows)
+            if rows.shape != (T, n_rep, 4):
+                raise ValueError("rows must be [n_ticks, replayed riders, 4]")
+        self._ck(self._lib.csf_scene_calib_replay(self._h, _ptr(mask), _ptr(rows) if n_rep else None))
+
     def scene_calib_clear(self):
         self._ck(self._lib.csf_scene_calib_clear(self._h))
         self._scene_calib = None

@@ -484,7 +484,19 @@ int csf_calib_clear(csf_engine *e);
  * population, its queues, its parameters or its recording, and csf_calib_load (CSF_E_STATE; csf_scene_calib_load refuses an engine that holds
  * the data set of csf_calib_load likewise); the read-backs show the end of the last evaluation.  csf_scene_calib_clear drops the data set and
  * empties the engine - through the host mirror, so that no dead slot stays behind and a small population added next takes the one-wave
- * tick of csf_step again.  A refused call changes nothing. */
+ * tick of csf_step again.  A refused call changes nothing.
+ *
+ * csf_scene_calib_replay marks riders of the held data set that FOLLOW THEIR RECORDING instead of being fitted:
+ * replayed [R] (non-zero: replayed; n_rep of them, numbered in rider order) and rows [n_ticks][n_rep][4] = (x, y, psi, v) of every replayed
+ * rider AFTER tick t - the row alignment of the objective.  Such a rider starts from its s0 like every other (the recording's time 0), is
+ * put on rows[t] behind every tick t < lengths[its scene] - what csf_push_state does to vehicle.s, with the unwrapped yaw and the position
+ * ring kept consistent - and so acts on the others as a source of the candidate set's field only: its entries of sums_out are (0, 0), its
+ * rows 0 .. 3 of states_out are the recording, its other rows and its status bits say nothing about the evaluation.  This is the ego
+ * (leave-one-out) form of an evaluation, and how a road user that the candidate set cannot simulate enters a scene.  The rows read must be
+ * finite (CSF_E_ARG); the rounding bands of an evaluation cover the largest recorded coordinate.  It may be called any number of times
+ * between evaluations; replayed == NULL (or no non-zero entry) drops the replay, and evaluations are again what they are without one, bit
+ * for bit.  rows may be NULL when nothing is replayed.  CSF_E_STATE without a closed-loop data set; everything that can fail runs before
+ * anything is replaced.  csf_scene_calib_clear frees the replay with the rest. */
 int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks,
                          const double *s0, const double *v_desired,
                          const int64_t *dest_offsets, const double *dest_xyz_stop,
@@ -493,6 +505,7 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
 int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params,
                          size_t params_size, int32_t abi_version,
                          double *sums_out, int32_t stride, double *states_out);
+int csf_scene_calib_replay(csf_engine *e, const uint8_t *replayed, const double *rows);
 int csf_scene_calib_launches(const csf_engine *e, int64_t *n_launches);
 int csf_scene_calib_clear(csf_engine *e);
 

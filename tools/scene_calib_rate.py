@@ -9,7 +9,14 @@ and is timed as it is.)  16 scenes of 3 - 8 riders x 1 000 ticks, TwoDBicycle an
 alternate window by window in one process, after one warm-up call of each.  One JSON line per cell, printed and appended to --out
 as soon as the cell is done: medians of the windows with min / max, milliseconds per evaluation of all n_sets.
 
+--replay adds a leg with every second rider of every scene following its recording (csf_scene_calib_replay; the recording is the
+data set's own run with the base set): the same one launch per evaluation (`replay_ms`), against what the existing pieces cost -
+the engines of the baseline in their batch, per tick one step_batch and per engine state() and push_state of the replayed riders,
+the error in NumPy (`replay_base_ms`; --replay-base-max caps the sets it is built for, it is O(sets x scenes x ticks) host calls) -
+and their ratio.  Without --replay the tool does what it did.
+
     python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
+                                     [--replay [--replay-base-max 4]]
 """
 import argparse
 import json
@@ -59,6 +66,8 @@ def main():
     ap.add_argument("--base-max", type=int, default=256)
     ap.add_argument("--models", default="twod,invpend")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--replay", action="store_true")
+    ap.add_argument("--replay-base-max", type=int, default=4)
     a = ap.parse_args()
     feat = np.array([0, 1], dtype=np.int32)
     if a.out:
@@ -73,6 +82,8 @@ def main():
         rows = np.concatenate([d for _, _, d in per])
         off = np.r_[0, np.cumsum(np.concatenate([np.diff(o) for _, o, _ in per]))]
         obj = np.random.default_rng(1).normal(size=(a.ticks, R, feat.size))
+        mask = np.concatenate([np.arange(n) % 2 == 1 for n in nr])      # every second rider of a scene (>= 3 riders each)
+        rec = None
         for n_sets in [int(x) for x in a.sets.split(",")]:
             sets = pod_sets(base, n_sets)
             e = Engine(base, n_sets * R)
@@ -103,6 +114,25 @@ def main():
                     err[i // a.scenes] += float(np.square(S[:, :, feat] - obj[:, roff[q]: roff[q + 1]]).sum())
                 return err
 
+            def replay_old():
+                """the twin the replay tests compare with, for all engines of the batch: tick, read, overwrite, push"""
+                err = np.zeros(n_sets)
+                idx = [np.flatnonzero(mask[roff[q]: roff[q + 1]]).astype(np.int32) for q in range(a.scenes)]
+                for i, t in enumerate(twins):
+                    s = per[i % a.scenes][0]
+                    t.push_state(np.arange(s.shape[0]), s)
+                    t.set_dest_pointer(np.arange(s.shape[0]), 0)
+                for tick in range(a.ticks):
+                    Engine.step_batch(twins, 1)
+                    for i, t in enumerate(twins):
+                        q = i % a.scenes
+                        s = t.state()
+                        s[idx[q], :4] = rec[tick, roff[q] + idx[q], :4]
+                        t.push_state(idx[q], s[idx[q]])
+                        sim = np.setdiff1d(np.arange(nr[q]), idx[q])
+                        err[i // a.scenes] += float(np.square(s[sim][:, feat] - obj[tick, roff[q] + sim]).sum())
+                return err
+
             first_new = new()
             # (the first baseline call starts from fresh engines: there the two legs do the same job and their errors agree)
             first_gap = float(np.abs(old() / first_new - 1.0).max()) if twins else None
@@ -114,6 +144,22 @@ def main():
             line = dict(model=model, n_sets=n_sets, scenes=a.scenes, riders=R, ticks=a.ticks, windows=a.windows, first_call_rel_gap=first_gap,
                         new_ms=dict(median=float(np.median(t_new)), min=min(t_new), max=max(t_new)),
                         base_ms=dict(median=float(np.median(t_old)), min=min(t_old), max=max(t_old)) if t_old else None)
+            if a.replay:
+                if rec is None:                                  # the recording: the scenes' own run with the base set
+                    rec = e.scene_calib_eval([base], states=True)[1][:, :R]
+                e.scene_calib_replay(mask, rec[:, mask, :4])
+                first_rep = new()
+                with_base = bool(twins) and n_sets <= a.replay_base_max
+                gap = float(np.abs(replay_old() / first_rep - 1.0).max()) if with_base else None
+                t_rep, t_rold = [], []
+                for _ in range(a.windows):
+                    t0 = time.perf_counter(); new(); t_rep.append((time.perf_counter() - t0) * 1e3)
+                    if with_base:
+                        t0 = time.perf_counter(); replay_old(); t_rold.append((time.perf_counter() - t0) * 1e3)
+                line.update(replayed_riders=int(mask.sum()), replay_first_call_rel_gap=gap,
+                            replay_ms=dict(median=float(np.median(t_rep)), min=min(t_rep), max=max(t_rep)),
+                            replay_base_ms=dict(median=float(np.median(t_rold)), min=min(t_rold), max=max(t_rold)) if t_rold else None,
+                            replay_base_over_replay=float(np.median(t_rold) / np.median(t_rep)) if t_rold else None)
             print(json.dumps(line), flush=True)
             if a.out:
                 with open(a.out, "a") as f:
