@@ -16,6 +16,7 @@ Two things are not the reference's:
 import numpy as np
 
 from .engine import Engine
+from .parameters import RoadElementParameters
 
 TRAJ_ROWS = 6  # rows of vehicle.traj an objective can name: x, y, psi, v, delta, theta (calibration.py:352-357)
 
@@ -419,9 +420,16 @@ class SceneData:
     parameters but put on traj[t, i, :4] = (x, y, psi, v) after every tick, act on the others as sources of the field only and
     add nothing to the error - the others of an ego evaluation (`ego_split`), or a road user of another class.  Such a road
     user needs finite columns 0 .. 3 of traj over all `length` rows; its destination queue may be left out (no row between its
-    two offsets): it gets the single row a fresh vehicle has, its own start (vehicle.py:183-185)."""
+    two offsets): it gets the single row a fresh vehicle has, its own start (vehicle.py:183-185).
 
-    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None):
+    road = (offsets [n_edges + 1], verts [n_v, 2], F0 [n_edges], sigma [n_edges]) gives the scene ROAD EDGES, as `Engine.set_road`
+    takes them (default: none): every tick adds their force to every simulated road user (intersection.py:226-242, 853-857).  All
+    edges together have at most ROAD_MAX_VERTS vertices and, padded to a multiple of 64, at most 16 384 / P of them, P the power of two
+    that holds the scene's road users - what the one-wave tick stages."""
+
+    ROAD_MAX_VERTS = 2048
+
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None):
         self.s0 = np.asarray(s0, dtype=float)
         if self.s0.ndim != 2 or self.s0.shape[1] < 4 or not 1 <= self.s0.shape[0] <= 32:
             raise ValueError("a scene has 1 .. 32 road users: s0 is [n, >= 4]")
@@ -457,6 +465,34 @@ class SceneData:
             raise ValueError("length: 0 .. the rows of traj")
         if self.replayed.any() and (self.traj.shape[2] < 4 or not np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()):
             raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over all `length` rows")
+        self.road = None if road is None else self._checked_road(road, n)
+
+    @classmethod
+    def _checked_road(cls, road, n):
+        try:
+            roff, verts, F0, sigma = road
+        except (TypeError, ValueError):
+            raise ValueError("road is (offsets, verts, F0, sigma)") from None
+        roff = np.array(roff, dtype=np.int64).reshape(-1)
+        verts = np.array(verts, dtype=float).reshape(-1, 2)
+        n_edges = roff.size - 1
+        if n_edges < 0 or np.any(roff < 0) or np.any(np.diff(roff) < 0) or (roff.size and roff[-1] > verts.shape[0]):
+            raise ValueError("road: offsets is [n_edges + 1], ascending, within the vertices")
+        try:
+            F0 = np.array(np.broadcast_to(np.asarray(F0, dtype=float), (n_edges,)))
+            sigma = np.array(np.broadcast_to(np.asarray(sigma, dtype=float), (n_edges,)))
+        except ValueError:
+            raise ValueError("road: one F0 and one sigma per edge, or scalars") from None
+        used = np.concatenate([verts[roff[k]: roff[k + 1]] for k in range(n_edges)]) if n_edges else verts[:0]
+        if not (np.isfinite(used).all() and np.isfinite(F0).all() and np.isfinite(sigma).all()):
+            raise ValueError("road: vertices, F0 and sigma must be finite")
+        nv = used.shape[0]
+        P = 1
+        while P < n:
+            P *= 2
+        if nv > cls.ROAD_MAX_VERTS or (nv + 63) // 64 * 64 * P > 256 * 64:
+            raise ValueError(f"road: {nv} vertices; a scene of {n} road users takes {min(cls.ROAD_MAX_VERTS, 256 * 64 // P)}")
+        return roff, verts, F0, sigma
 
     @property
     def n(self):
@@ -465,12 +501,13 @@ class SceneData:
     def ego_split(self):
         """The leave-one-out scenes of this scene, one per simulated road user: scene i simulates that road user alone and replays
         all others from the recording (road users that are replayed here stay so).  Host only.  s0, the queues and traj are
-        shared with this scene, not copied; every scene has a mask of its own."""
+        shared with this scene, not copied; every scene has a mask of its own and this scene's road."""
         out = []
         for i in np.flatnonzero(~self.replayed):
             mask = np.ones(self.n, dtype=bool)
             mask[i] = False
-            out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask))
+            out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask,
+                                 road=self.road))
         return out
 
 
@@ -503,7 +540,14 @@ class InteractionCalibration:
     (`Engine.scene_calib_replay`) and are no part of the error: calc_sse_timesteps sums the simulated riders, calc_maesse_samples
     divides a scene's sum by length x simulated riders x n_feat, another error_func and `simulate` get the simulated riders only.
 
+    Scenes with road edges (`SceneData(road=...)`) are loaded with their roads (`Engine.scene_calib_road`).  "road_F_0" and
+    "road_sigma" among params_keys fit the two RoadElementParameters of the road-edge force: they go to the evaluation's road
+    overrides, one value per candidate set for every edge of every scene, and not into PARAMS_TYPE; with only one of them fitted the
+    other keeps its value from RoadElementParameters().  Either key needs a scene with a road (ValueError otherwise).
+
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
+
+    ROAD_KEYS = {"road_F_0": "F_0", "road_sigma": "sigma"}
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine):
@@ -522,6 +566,11 @@ class InteractionCalibration:
         self.param_args_opt = None
         self._factory = engine_factory
         self._sets = {}
+        self._road_keys = [k for k in self.params_keys if k in self.ROAD_KEYS]
+        if self._road_keys:
+            for name, data in (("train_data", self.train_data), ("test_data", self.test_data)):
+                if data and not any(d.road is not None and d.road[0][-1] > 0 for d in data):
+                    raise ValueError(f"params_keys names {self._road_keys}, and no scene of {name} has a road")
 
     def close(self):
         for ds in self._sets.values():
@@ -532,7 +581,14 @@ class InteractionCalibration:
         return dict(zip(self.params_keys, params_vals))
 
     def _pod(self, params_args):
-        return self.vehicle_type.PARAMS_TYPE(**params_args).to_pod(self.vehicle_type.MODEL)
+        return self.vehicle_type.PARAMS_TYPE(**{k: v for k, v in params_args.items() if k not in self.ROAD_KEYS}).to_pod(self.vehicle_type.MODEL)
+
+    def _road_over(self, args_list):
+        """road_F0, road_sigma [n_sets] of an evaluation (keyword arguments of Engine.scene_calib_eval); {}: no road key is fitted"""
+        if not self._road_keys:
+            return {}
+        rp = [RoadElementParameters(**{self.ROAD_KEYS[k]: float(a[k]) for k in self._road_keys}) for a in args_list]
+        return dict(road_F0=np.array([r.F_0 for r in rp], dtype=float), road_sigma=np.array([r.sigma for r in rp], dtype=float))
 
     def _dataset(self, test=False):
         """the engine that holds the training (test) scenes, loaded on first use"""
@@ -573,6 +629,19 @@ class InteractionCalibration:
                     rec[: d.traj.shape[0], at: at + k] = d.traj[:, d.replayed, :4]
                 at += k
             engine.scene_calib_replay(rep, rec)
+        if any(d.road is not None and d.road[0][-1] > 0 for d in data):
+            es, ro, vs, f0, sg = [], [0], [], [], []
+            for q, d in enumerate(data):
+                if d.road is None:
+                    continue
+                eoff, verts, F0, sigma = d.road
+                for k in range(eoff.size - 1):
+                    es.append(q)
+                    vs.append(verts[eoff[k]: eoff[k + 1]])
+                    ro.append(ro[-1] + vs[-1].shape[0])
+                    f0.append(F0[k])
+                    sg.append(sigma[k])
+            engine.scene_calib_road(np.array(es, dtype=np.int32), np.array(ro, dtype=np.int64), np.concatenate(vs), np.array(f0), np.array(sg))
         ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets, sim=[~d.replayed for d in data],
                   nsim=np.array([int((~d.replayed).sum()) for d in data]),
                   objectives=[d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data])
@@ -595,20 +664,22 @@ class InteractionCalibration:
         """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them."""
         vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
         ds = self._dataset(test)
-        pods = [self._pod(self._update_params_args_dict(v)) for v in vals]
+        args = [self._update_params_args_dict(v) for v in vals]
+        pods = [self._pod(a) for a in args]
         err = np.zeros(len(pods))
         for at in range(0, len(pods), ds["sets"]):
             chunk = pods[at:at + ds["sets"]]
+            road = self._road_over(args[at:at + ds["sets"]])
             if self.error_func is calc_sse_timesteps:
-                sums = ds["engine"].scene_calib_eval(chunk)
+                sums = ds["engine"].scene_calib_eval(chunk, **road)
                 err[at:at + len(chunk)] = _scenes_in_order(_riders_then_scenes(sums[:, :, 0], ds["roff"]))
             elif self.error_func is calc_maesse_samples:
-                sums = ds["engine"].scene_calib_eval(chunk)
+                sums = ds["engine"].scene_calib_eval(chunk, **road)
                 with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
                     mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["lens"] * ds["nsim"] * float(ds["feat"].size))[None, :]
                 err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
             else:
-                _, states = ds["engine"].scene_calib_eval(chunk, states=True)
+                _, states = ds["engine"].scene_calib_eval(chunk, states=True, **road)
                 for k in range(len(chunk)):
                     err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
         return err
@@ -617,7 +688,8 @@ class InteractionCalibration:
         """The trajectories of one parameter vector on the training (test) scenes: ([length, simulated riders, n_feat] per scene -
         the state after each tick -, the objectives)."""
         ds = self._dataset(test)
-        _, states = ds["engine"].scene_calib_eval([self._pod(self._update_params_args_dict(np.asarray(params_vals, dtype=float)))], states=True)
+        args = self._update_params_args_dict(np.asarray(params_vals, dtype=float))
+        _, states = ds["engine"].scene_calib_eval([self._pod(args)], states=True, **self._road_over([args]))
         return self._trajs(ds, states, 0), list(ds["objectives"])
 
     def run(self, params_vals_guess):

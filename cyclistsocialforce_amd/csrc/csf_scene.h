@@ -11,7 +11,10 @@ struct SceneSet {
     csf_params p;
     PairConsts pc;
     double pb[7];
-    double pad;
+    // csf_scene_calib_eval_road: what this set puts in place of (-F0, -(sigma + 1) / 2) of every road vertex, and the Dev::road_np of
+    // its sigma.  Read only when SceneDev::road_blk is set.
+    float road_z, road_w;
+    int32_t road_np, pad[3];
 };
 
 // The data set of csf_scene_calib_load, resident on the device, and the reset image.  The image is indexed by RIDER (0 .. R - 1,
@@ -43,6 +46,13 @@ struct SceneDev {
     // and act as sources of the field only; no error is summed for them.  rep == NULL: no rider is replayed.
     const int32_t *rep_index;    // [R] -1: simulated, else the rider's column of rep
     const double *rep;           // [n_ticks][n_rep][4] (x, y, psi, v) AFTER tick t: the row alignment of obj
+    // Scene roads (csf_scene_calib_road).  The view of a scene with a road points rv / rvo at the scene's part of
+    // road_rv / its tile origins.  With road parameters per candidate set (road_blk != NULL) workgroup (set, scene) first writes the
+    // scene's road with the set's (road_z, road_w) to ITS block road_blk + set * road_stride + (rv - road_rv) and stages from there.
+    const float4 *road_rv;       // the packed roads of all scenes, one after the other (NULL: no scene has a road)
+    float4 *road_blk;            // [n_sets][road_stride], NULL: the roads keep their own parameters
+    int64_t road_stride;         // vertices (padded) of all scenes together
+    uint32_t road_lds;           // bytes of dynamic LDS: the largest nv_pad of the data set x 16
 };
 
 // One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].

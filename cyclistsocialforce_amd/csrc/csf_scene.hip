@@ -22,6 +22,10 @@
 // moves the pointer by at most 2, the scaling loop of invpend_step_yaw stops at 40 halvings and at a NaN norm, every other loop has
 // a constant trip count - a rider whose state is reset every tick cannot hold its wave.
 //
+// Scenes with road edges (csf_scene_calib_road): the view of a scene with a road carries rv / rvo / nv / nv_pad /
+// road_np and the origin of a stand-alone engine that holds the scene, and small_tick_body stages and sums the road as it does for
+// small_batch_kernel, in dynamic LDS sized by the largest road of the data set.  Road parameters per candidate set: see the prologue.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -95,7 +99,7 @@ struct SceneHook {
 
 template <int MODEL>
 __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
-    extern __shared__ float4 srv_none[];                      // (no road: small_tick_body stages nothing)
+    extern __shared__ float4 srv[];                           // c.road_lds bytes: the largest road of the data set (none: 0 bytes)
     const int b = (int)blockIdx.x;
     if (b >= c.n_sets * c.n_scn) return;
     const int set = b / c.n_scn, scn = b - set * c.n_scn;
@@ -106,6 +110,20 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
         d.pc = ss.pc;
 #pragma unroll
         for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        // road parameters of this set: the scene's road with (-F0, -(sigma + 1) / 2) of the set on every vertex - padding keeps
+        // F0 = 0 - goes to this workgroup's own block, and the tick stages it from there.  small_tick_body reads rv[v] for
+        // v = lane, lane + 64, ...: what the same lane has stored here, program order - as the restored block below.
+        if (c.road_blk != nullptr && d.nv_pad > 0) {
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
     }
     const int lane = (int)threadIdx.x, n = (int)d.n;
     const int64_t cap = d.cap, first = c.roff[scn];
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
     const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
     SceneHook<MODEL> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
                           c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr);
-    small_tick_body<MODEL>(d, len, nullptr, srv_none, 0u, 0, hook);
+    small_tick_body<MODEL>(d, len, nullptr, srv, 0u, 0, hook);
     if (lane >= n) return;
     c.sums[rider] = make_double2(hook.sse, hook.sae);
     // an ended (or empty) scene keeps its last state in every later sample
@@ -149,7 +167,7 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
 void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st) {
     const int count = c.n_sets * c.n_scn;
     if (count <= 0) return;
-#define CSF_SCENE(MODEL) hipLaunchKernelGGL((scene_eval_kernel<MODEL>), dim3((unsigned)count), dim3(64), 0, st, table, sets, c)
+#define CSF_SCENE(MODEL) hipLaunchKernelGGL((scene_eval_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c)
     switch (model) {
     case CSF_BICYCLE: CSF_SCENE(CSF_BICYCLE); break;
     case CSF_TWOD: CSF_SCENE(CSF_TWOD); break;

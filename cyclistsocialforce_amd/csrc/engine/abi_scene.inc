@@ -29,6 +29,16 @@ struct SceneCalibState {
     DevBuf<double> rep;                      // [n_ticks][n_rep][4]
     int32_t n_rep = 0;
     double rep_bound = 0.0;                  // largest |coordinate| of a replayed row, relative to the scene origin
+    // csf_scene_calib_road: a road per scene, shared by all candidate sets (DESIGN.md 4.10c).  road_stride == 0: no scene has one,
+    // every view has nv = nv_pad = 0 and a launch asks for no dynamic LDS
+    std::vector<Dev> h_table;                // the table as csf_scene_calib_load built it: no roads, the engine's origin
+    std::vector<double> h_ox, h_oy;          // [n_scn] the origin a stand-alone engine that holds the scene would have (mirror.inc)
+    DevBuf<float4> road_rv;                  // [road_stride] the packed roads of the scenes, one after the other
+    DevBuf<float2> road_rvo;                 // their tile origins
+    DevBuf<float4> road_blk;                 // [sets][road_stride] the roads as a candidate set's parameters make them: allocated by
+                                             // the first evaluation that overrides them
+    int64_t road_stride = 0;
+    int32_t road_max_pad = 0;                // largest nv_pad of a scene
 };
 
 }  // extern "C++"
@@ -46,7 +56,7 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
     if (e->batch) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine belongs to a batch (csf_batch_leave first)");
     if (e->loopback) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine is a member of a loopback group");
     if (e->world > 1 || e->nccl) return fail(e, CSF_E_STATE, "csf_scene_calib_load: a sharded engine holds no scenes");
-    if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has a road (scenes with roads are not evaluated)");
+    if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has a road of its own (csf_set_road_vertices); the roads of scenes are given by csf_scene_calib_road");
     if (e->d.hist != nullptr) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine records (csf_record / csf_enable_history); an evaluation writes its own samples");
     if (e->classes.size() != 1) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has %d parameter sets; the candidates of an evaluation replace ONE", (int)e->classes.size());
     if (e->d.p.model == CSF_UNCONTROLLED) return fail(e, CSF_E_ARG, "csf_scene_calib_load: an UncontrolledVehicle follows its trajectory whatever the field");
@@ -168,6 +178,19 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
         double cb = 0.0;
         for (int32_t i = 0; i < R; i++) cb = std::max({cb, std::fabs(s0[(size_t)i * ns] - d0.ox), std::fabs(s0[(size_t)i * ns + 1] - d0.oy)});
         cs->coord_bound = cb;
+        // the origin of a stand-alone engine that holds scene q: the centre of the box of its start positions (mirror.inc: upload_all)
+        cs->h_ox.assign((size_t)n_scn, 0.0), cs->h_oy.assign((size_t)n_scn, 0.0);
+        for (int32_t q = 0; q < n_scn; q++) {
+            double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+            for (int32_t i = ro[(size_t)q]; i < ro[(size_t)q + 1]; i++) {
+                x0 = std::min(x0, s0[(size_t)i * ns]), x1 = std::max(x1, s0[(size_t)i * ns]);
+                y0 = std::min(y0, s0[(size_t)i * ns + 1]), y1 = std::max(y1, s0[(size_t)i * ns + 1]);
+            }
+            const double ox = 0.5 * (x0 + x1), oy = 0.5 * (y0 + y1);
+            cs->h_ox[(size_t)q] = std::isfinite(ox) ? ox : 0.0;
+            cs->h_oy[(size_t)q] = std::isfinite(oy) ? oy : 0.0;
+        }
+        cs->h_table = std::move(tab);
     }
     cs->h_len = std::move(ls), cs->h_roff = std::move(ro);
     e->scene_calib = std::move(cs);
@@ -175,7 +198,15 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
 } catch (...) { return csf_caught(e); }
 
 int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version, double *sums_out,
-                         int32_t stride, double *states_out) try {
+                         int32_t stride, double *states_out) {
+    return csf_scene_calib_eval_road(e, n_sets, params, params_size, abi_version, nullptr, nullptr, sums_out, stride, states_out);
+}
+
+// Dev::road_np of one sigma, as road_np_of decides it for a road whose edges share it
+static int32_t road_np_sigma(double sg) { return sg == std::floor(sg) && sg >= 1 && sg <= 5 ? (int32_t)sg + 1 : 0; }
+
+int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version,
+                              const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) try {
     if (!e) return CSF_E_ARG;
     if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_eval: no closed-loop data set (csf_scene_calib_load first)");
     // before anything is read from `params` (csf_create_v)
@@ -193,9 +224,28 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
         if (params[k].t_s != e->d.p.t_s || params[k].traj_len != e->d.p.traj_len)
             return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d: t_s and traj_len are the engine's (parameters.py:516-528)", (int)k);
     }
+    // road parameters per candidate set: both arrays or neither.  csf_set_road_vertices places no limit on sigma; a value that is
+    // not finite is refused here as it is by csf_scene_calib_road
+    const bool road_over = road_F0 != nullptr || road_sigma != nullptr;
+    if (road_over) {
+        if (!road_F0 || !road_sigma) return fail(e, CSF_E_ARG, "csf_scene_calib_eval_road: road_F0 and road_sigma are given together or not at all");
+        if (cs.road_stride == 0) return fail(e, CSF_E_STATE, "csf_scene_calib_eval_road: road parameters and no scene has a road (csf_scene_calib_road first)");
+        for (int32_t k = 0; k < n_sets; k++) {
+            if (!std::isfinite(road_F0[k]) || road_F0[k] < 0.0) return fail(e, CSF_E_ARG, "csf_scene_calib_eval_road: road_F0[%d] = %g is not a finite value >= 0", (int)k, road_F0[k]);
+            if (!std::isfinite(road_sigma[k])) return fail(e, CSF_E_ARG, "csf_scene_calib_eval_road: road_sigma[%d] is not finite", (int)k);
+        }
+    }
     HIPCHK(e, hipSetDevice(e->device));
     int rc = upload_all(e);
     if (rc) return rc;
+    if (road_over && (size_t)n_sets * (size_t)cs.road_stride > cs.road_blk.n) {
+        HIPCHK(e, hipStreamSynchronize(e->main));
+        const hipError_t r = cs.road_blk.alloc((size_t)n_sets * (size_t)cs.road_stride);
+        if (r != hipSuccess) {
+            cs.road_blk.release();
+            return fail(e, CSF_E_DEVICE, "csf_scene_calib_eval_road: no memory for the roads of %d parameter sets: %s", (int)n_sets, hipGetErrorString(r));
+        }
+    }
     const int64_t n = (int64_t)n_sets * cs.R;
     const int64_t n_samples = states_out ? cs.n_ticks / stride : 0;
     const size_t n_states = (size_t)n_samples * (size_t)n * (size_t)e->d.ns;
@@ -220,6 +270,11 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
         const double step = ss.p.t_s * vmax * 1.01 + 1e-4;
         // (a replayed rider is not bound by the set's clamp: it goes where its recording goes)
         fov_band_consts(e->knobs, step, std::max(cs.coord_bound + step * (double)(cs.n_ticks + 2), cs.rep_bound) + 1.0, ss.pc);
+        if (road_over) {   // (the roundings of pack_road)
+            ss.road_z = (float)(-road_F0[k]);
+            ss.road_w = (float)(-0.5 * (road_sigma[k] + 1.0));
+            ss.road_np = road_np_sigma(road_sigma[k]);
+        }
     }
     SceneDev c{};
     c.obj = cs.obj.p, c.len = cs.len.p, c.roff = cs.roff.p;
@@ -236,6 +291,10 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
     c.n_rep = cs.n_rep;
     c.rep_index = cs.n_rep > 0 ? cs.rep_index.p : nullptr;
     c.rep = cs.n_rep > 0 ? cs.rep.p : nullptr;
+    c.road_rv = cs.road_stride > 0 ? cs.road_rv.p : nullptr;
+    c.road_blk = road_over ? cs.road_blk.p : nullptr;
+    c.road_stride = cs.road_stride;
+    c.road_lds = (uint32_t)cs.road_max_pad * (uint32_t)sizeof(float4);
     HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
     HIPCHK(e, hipGetLastError());
@@ -247,6 +306,100 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
     e->device_ahead = true;
     e->mid_synced = false;
     e->bounds_fresh = false;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_scene, const int64_t *offsets, const double *xy, const double *F0,
+                         const double *sigma) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) {
+        if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_road: the engine holds the data set of csf_calib_load, whose vehicles are not coupled and feel no road");
+        return fail(e, CSF_E_STATE, "csf_scene_calib_road: no closed-loop data set (csf_scene_calib_load first)");
+    }
+    SceneCalibState &cs = *e->scene_calib;
+    if (n_edges < 0) return fail(e, CSF_E_ARG, "csf_scene_calib_road: n_edges must be >= 0");
+    if (n_edges > 0 && (!edge_scene || !offsets || !xy || !F0 || !sigma)) return fail(e, CSF_E_ARG, "csf_scene_calib_road: NULL array");
+    for (int32_t k = 0; k < n_edges; k++) {
+        if (edge_scene[k] < 0 || edge_scene[k] >= cs.n_scn) return fail(e, CSF_E_ARG, "csf_scene_calib_road: edge %d names scene %d, the data set has %d", (int)k, (int)edge_scene[k], (int)cs.n_scn);
+        if (k > 0 && edge_scene[k] < edge_scene[k - 1]) return fail(e, CSF_E_ARG, "csf_scene_calib_road: edge_scene[%d .. %d] decreases", (int)k - 1, (int)k);
+        if (offsets[k] < 0 || offsets[k + 1] < offsets[k]) return fail(e, CSF_E_ARG, "csf_scene_calib_road: offsets[%d .. %d] run backwards", (int)k, (int)k + 1);
+        if (!std::isfinite(F0[k]) || !std::isfinite(sigma[k])) return fail(e, CSF_E_ARG, "csf_scene_calib_road: F0 or sigma of edge %d is not finite", (int)k);
+        for (int64_t v = offsets[k]; v < offsets[k + 1]; v++)
+            if (!std::isfinite(xy[2 * v]) || !std::isfinite(xy[2 * v + 1])) return fail(e, CSF_E_ARG, "csf_scene_calib_road: vertex %lld of edge %d is not finite", (long long)v, (int)k);
+    }
+    // the road of every scene as csf_set_road_vertices keeps it - rows (x, y, F0, sigma), the edges one after the other - held to what
+    // the one-wave tick stages (tick.inc: small_road_ok) and packed as upload_all packs the road of an engine that holds the scene
+    const size_t n_scn = (size_t)cs.n_scn;
+    std::vector<int64_t> nv(n_scn, 0), at(n_scn, 0), tile_at(n_scn, 0);
+    std::vector<int32_t> np(n_scn, 0);
+    std::vector<float4> rv_all;
+    std::vector<float2> rvo_all;
+    int64_t max_pad = 0;
+    {
+        std::vector<double> road;
+        std::vector<float4> rv;
+        std::vector<float2> rvo;
+        int32_t k = 0;
+        for (size_t q = 0; q < n_scn; q++) {
+            road.clear();
+            for (; k < n_edges && (size_t)edge_scene[k] == q; k++)
+                for (int64_t v = offsets[k]; v < offsets[k + 1]; v++) {
+                    road.push_back(xy[2 * v]);
+                    road.push_back(xy[2 * v + 1]);
+                    road.push_back(F0[k]);
+                    road.push_back(sigma[k]);
+                    if (road.size() / 4 > (size_t)SMALL_ROAD_MAX)
+                        return fail(e, CSF_E_ARG, "csf_scene_calib_road: the road of scene %d has more than %d vertices", (int)q, SMALL_ROAD_MAX);
+                }
+            nv[q] = (int64_t)road.size() / 4;
+            const int64_t nv_pad = (nv[q] + 63) / 64 * 64, n = cs.h_roff[q + 1] - cs.h_roff[q];
+            int64_t P = 1;
+            while (P < n) P <<= 1;
+            if (nv_pad * P > 256 * WAVE)
+                return fail(e, CSF_E_ARG, "csf_scene_calib_road: the road of scene %d has %lld vertices, a scene of %lld road users takes %lld", (int)q,
+                            (long long)nv[q], (long long)n, (long long)(256 * WAVE / P));
+            at[q] = (int64_t)rv_all.size(), tile_at[q] = (int64_t)rvo_all.size();
+            np[q] = pack_road(road.data(), nv[q], cs.h_ox[q], cs.h_oy[q], rv, rvo);
+            rv_all.insert(rv_all.end(), rv.begin(), rv.end());
+            rvo_all.insert(rvo_all.end(), rvo.begin(), rvo.end());
+            max_pad = std::max(max_pad, nv_pad);
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // everything that can fail first: a refused call changes nothing
+    DevBuf<float4> d_rv;
+    DevBuf<float2> d_rvo;
+    DevBuf<Dev> d_table;
+    std::vector<Dev> tab = cs.h_table;
+    hipError_t r = d_table.alloc(tab.size());
+    if (!rv_all.empty()) {
+        if (r == hipSuccess) r = d_rv.alloc(rv_all.size());
+        if (r == hipSuccess) r = d_rvo.alloc(rvo_all.size());
+        if (r == hipSuccess) r = hipMemcpy(d_rv.p, rv_all.data(), rv_all.size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (r == hipSuccess) r = hipMemcpy(d_rvo.p, rvo_all.data(), rvo_all.size() * sizeof(float2), hipMemcpyHostToDevice);
+    }
+    if (r == hipSuccess) {
+        for (int32_t k = 0; k < cs.max_sets; k++)
+            for (size_t q = 0; q < n_scn; q++) {
+                if (nv[q] == 0) continue;
+                Dev &v = tab[(size_t)k * n_scn + q];
+                v.nv = nv[q], v.nv_pad = (nv[q] + 63) / 64 * 64;
+                v.rv = d_rv.p + at[q], v.rvo = d_rvo.p + tile_at[q];
+                v.road_np = np[q];
+                v.ox = cs.h_ox[q], v.oy = cs.h_oy[q];
+                v.rg_nx = v.rg_ny = 0;
+            }
+        r = hipMemcpy(d_table.p, tab.data(), tab.size() * sizeof(Dev), hipMemcpyHostToDevice);
+    }
+    if (r == hipSuccess) r = hipDeviceSynchronize();
+    if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_road: no memory for the roads: %s", hipGetErrorString(r));
+    cs.table = std::move(d_table);
+    cs.road_rv = std::move(d_rv);
+    cs.road_rvo = std::move(d_rvo);
+    cs.road_blk = DevBuf<float4>();
+    cs.road_stride = (int64_t)rv_all.size();
+    cs.road_max_pad = (int32_t)max_pad;
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 

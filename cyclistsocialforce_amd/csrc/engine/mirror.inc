@@ -142,6 +142,47 @@ int upload_classes(csf_engine *e) {
     return CSF_OK;
 }
 
+// Dev::road_np of a road [nv] rows (x, y, F0, sigma): one integer sigma for every edge gives r^-(sigma+1) as a power of rsq(r^2)
+static int32_t road_np_of(const double *road, int64_t nv) {
+    if (nv <= 0) return 0;
+    const double sg = road[3];
+    bool same = sg == std::floor(sg) && sg >= 1 && sg <= 5;
+    for (int64_t k = 1; same && k < nv; k++) same = road[4 * k + 3] == sg;
+    return same ? (int32_t)sg + 1 : 0;
+}
+
+// Road vertices (x, y, -F0, -(sigma+1)/2), padded with inert vertices.  Positions are offsets from the origin of
+// their tile of 1024 consecutive vertices (the centre of its box, rounded to 1/4 m): consecutive vertices of a
+// polyline are neighbours, so a vertex resolves to 2^-24 of ~50 m whatever the extent of the scene, and the road
+// kernel forms receiver - vertex relative to the tile (csf_pair.hip: road_kernel).
+// road: [nv] rows (x, y, F0, sigma); (ox, oy) the origin of the scene.  Fills rv [nv padded to 64] and rvo [tiles] and returns
+// Dev::road_np.  Shared by upload_all and the scene roads of csf_scene_calib_road (engine/abi_scene.inc): a view's road is packed
+// as the road of a stand-alone engine that holds the scene.
+static int32_t pack_road(const double *road, int64_t nv, double ox, double oy, std::vector<float4> &rv, std::vector<float2> &rvo) {
+    const int64_t nv_pad = (nv + 63) / 64 * 64;
+    rv.clear(), rvo.clear();
+    if (nv > 0) {
+        const int64_t tiles = (nv_pad + 1023) / 1024;
+        rv.assign((size_t)nv_pad, make_float4(1e15f, 1e15f, 0.f, -1.f));
+        rvo.assign((size_t)tiles, make_float2(0.f, 0.f));
+        for (int64_t t = 0; t < tiles; t++) {
+            const int64_t k0 = t * 1024, k1 = std::min<int64_t>(nv, k0 + 1024);
+            double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+            for (int64_t k = k0; k < k1; k++) {
+                x0 = std::min(x0, road[4 * k]), x1 = std::max(x1, road[4 * k]);
+                y0 = std::min(y0, road[4 * k + 1]), y1 = std::max(y1, road[4 * k + 1]);
+            }
+            if (!(k1 > k0)) continue;
+            const double tx = 0.25 * std::nearbyint(4.0 * (0.5 * (x0 + x1) - ox)), ty = 0.25 * std::nearbyint(4.0 * (0.5 * (y0 + y1) - oy));
+            rvo[(size_t)t] = make_float2((float)tx, (float)ty);
+            for (int64_t k = k0; k < k1; k++)
+                rv[(size_t)k] = make_float4((float)((road[4 * k] - ox) - tx), (float)((road[4 * k + 1] - oy) - ty),
+                                            (float)(-road[4 * k + 2]), (float)(-0.5 * (road[4 * k + 3] + 1.0)));
+        }
+    }
+    return road_np_of(road, nv);
+}
+
 int upload_all(csf_engine *e) {
     if (e->classes_dirty) {
         int rc = upload_classes(e);
@@ -229,43 +270,20 @@ int upload_all(csf_engine *e) {
         e->coord_bound0 = std::isfinite(cb) ? cb : 0.0;
         e->moves = 0;
     }
-    // Road vertices (x, y, -F0, -(sigma+1)/2), padded with inert vertices.  Positions are offsets from the origin of
-    // their tile of 1024 consecutive vertices (the centre of its box, rounded to 1/4 m): consecutive vertices of a
-    // polyline are neighbours, so a vertex resolves to 2^-24 of ~50 m whatever the extent of the scene, and the road
-    // kernel forms receiver - vertex relative to the tile (csf_pair.hip: road_kernel).
     d.nv = (int64_t)e->h_road.size() / 4;
     d.nv_pad = (d.nv + 63) / 64 * 64;
-    if (d.nv > 0) {
-        const int64_t tiles = (d.nv_pad + 1023) / 1024;
-        if ((size_t)d.nv_pad > e->rv.n) HIPCHK(e, e->rv.alloc((size_t)d.nv_pad));
-        if ((size_t)tiles > e->rvo.n) HIPCHK(e, e->rvo.alloc((size_t)tiles));
-        std::vector<float4> rv((size_t)d.nv_pad, make_float4(1e15f, 1e15f, 0.f, -1.f));
-        std::vector<float2> rvo((size_t)tiles, make_float2(0.f, 0.f));
-        for (int64_t t = 0; t < tiles; t++) {
-            const int64_t k0 = t * 1024, k1 = std::min<int64_t>(d.nv, k0 + 1024);
-            double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
-            for (int64_t k = k0; k < k1; k++) {
-                x0 = std::min(x0, e->h_road[4 * k]), x1 = std::max(x1, e->h_road[4 * k]);
-                y0 = std::min(y0, e->h_road[4 * k + 1]), y1 = std::max(y1, e->h_road[4 * k + 1]);
-            }
-            if (!(k1 > k0)) continue;
-            const double tx = 0.25 * std::nearbyint(4.0 * (0.5 * (x0 + x1) - d.ox)), ty = 0.25 * std::nearbyint(4.0 * (0.5 * (y0 + y1) - d.oy));
-            rvo[(size_t)t] = make_float2((float)tx, (float)ty);
-            for (int64_t k = k0; k < k1; k++)
-                rv[(size_t)k] = make_float4((float)((e->h_road[4 * k] - d.ox) - tx), (float)((e->h_road[4 * k + 1] - d.oy) - ty),
-                                            (float)(-e->h_road[4 * k + 2]), (float)(-0.5 * (e->h_road[4 * k + 3] + 1.0)));
+    {
+        std::vector<float4> rv;
+        std::vector<float2> rvo;
+        d.road_np = pack_road(e->h_road.data(), d.nv, d.ox, d.oy, rv, rvo);
+        if (d.nv > 0) {
+            if (rv.size() > e->rv.n) HIPCHK(e, e->rv.alloc(rv.size()));
+            if (rvo.size() > e->rvo.n) HIPCHK(e, e->rvo.alloc(rvo.size()));
+            HIPCHK(e, hipMemcpy(e->rv.p, rv.data(), rv.size() * sizeof(float4), hipMemcpyHostToDevice));
+            HIPCHK(e, hipMemcpy(e->rvo.p, rvo.data(), rvo.size() * sizeof(float2), hipMemcpyHostToDevice));
         }
-        HIPCHK(e, hipMemcpy(e->rv.p, rv.data(), rv.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(e->rvo.p, rvo.data(), rvo.size() * sizeof(float2), hipMemcpyHostToDevice));
     }
     d.rvo = e->rvo.p;
-    d.road_np = 0;
-    if (d.nv > 0) {   // one integer sigma for every edge: r^-(sigma+1) as a power of rsq(r^2)
-        const double sg = e->h_road[3];
-        bool same = sg == std::floor(sg) && sg >= 1 && sg <= 5;
-        for (int64_t k = 1; same && k < d.nv; k++) same = e->h_road[4 * k + 3] == sg;
-        if (same) d.road_np = (int32_t)sg + 1;
-    }
     d.rv = e->rv.p;
     d.rg_nx = d.rg_ny = 0;
     if (road_grid) {

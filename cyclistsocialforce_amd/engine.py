@@ -291,10 +291,11 @@ class Engine:
                                                 None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat), int(max_sets)))
         self._scene_calib = (R, T)
 
-    def scene_calib_eval(self, pods, states=False, stride=1):
+    def scene_calib_eval(self, pods, states=False, stride=1, road_F0=None, road_sigma=None):
         """Evaluate the parameter sets `pods` (a sequence of csf_params) on the loaded scenes in one launch: sums [n_sets, R, 2] =
         (sum d^2, sum |d|) per set and RIDER (the riders of a scene are added by the caller, in rider order), and with states=True
-        the trajectories [T // stride, n_sets * R, n_states] as well (slot = set * R + rider)."""
+        the trajectories [T // stride, n_sets * R, n_states] as well (slot = set * R + rider).  road_F0 / road_sigma [n_sets] (or
+        scalars; both or neither): F_0 and sigma of every road vertex of the scenes' roads (scene_calib_road) for that set."""
         if getattr(self, "_scene_calib", None) is None:
             raise EngineError("scene_calib_eval: no closed-loop data set (scene_calib_load first)")
         R, T = self._scene_calib
@@ -302,9 +303,33 @@ class Engine:
         tab = (Params * len(pods))(*pods)
         sums = np.zeros((len(pods), R, 2))
         out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * R, self.ns)) if states else None
-        self._ck(self._lib.csf_scene_calib_eval(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION, _ptr(sums), int(stride),
-                                                None if out is None else _ptr(out)))
+        if road_F0 is None and road_sigma is None:
+            self._ck(self._lib.csf_scene_calib_eval(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION, _ptr(sums), int(stride),
+                                                    None if out is None else _ptr(out)))
+        else:
+            f0 = None if road_F0 is None else _f64(np.broadcast_to(np.asarray(road_F0, dtype=np.float64), (len(pods),)))
+            sg = None if road_sigma is None else _f64(np.broadcast_to(np.asarray(road_sigma, dtype=np.float64), (len(pods),)))
+            self._ck(self._lib.csf_scene_calib_eval_road(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION,
+                                                         None if f0 is None else _ptr(f0), None if sg is None else _ptr(sg), _ptr(sums),
+                                                         int(stride), None if out is None else _ptr(out)))
         return (sums, out) if states else sums
+
+    def scene_calib_road(self, edge_scene, offsets, verts, F0, sigma):
+        """Road edges for scenes of the loaded data set, shared by all candidate sets: edge_scene [n_edges] the scene of every edge
+        (non-decreasing), the rest as set_road takes it.  No edge (edge_scene empty or None) drops every road."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_road: no closed-loop data set (scene_calib_load first)")
+        es = np.ascontiguousarray([] if edge_scene is None else edge_scene, dtype=np.int32).reshape(-1)
+        if es.size == 0:
+            self._ck(self._lib.csf_scene_calib_road(self._h, 0, None, None, None, None, None))
+            return
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        verts = _f64(verts).reshape(-1, 2)
+        F0 = _f64(np.broadcast_to(np.asarray(F0, dtype=np.float64), (es.size,)))
+        sigma = _f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (es.size,)))
+        if offsets.shape != (es.size + 1,) or (offsets.size and offsets.max() > verts.shape[0]):
+            raise ValueError("offsets must be [n_edges + 1] and stay within the vertices")
+        self._ck(self._lib.csf_scene_calib_road(self._h, es.size, _ptr(es), _ptr(offsets), _ptr(verts), _ptr(F0), _ptr(sigma)))
 
     def scene_calib_replay(self, replayed, rows=None):
         """Riders of the loaded scenes that follow their recording: replayed [R] (bool), rows [T, n_rep, 4] = (x, y, psi, v) of the

@@ -461,7 +461,7 @@ int csf_calib_clear(csf_engine *e);
 
 /* Calibration of the interaction parameters on closed-loop scenes.  A replay of recorded forces (above) couples
  * no two vehicles, so the parameters of the social-force field - f_0, sigma_0..3, e_0, e_1, hfov, p_0, p_decay, the priority rule - act
- * only when the riders of a scene are simulated together.  csf_scene_calib_load makes an EMPTY engine (one parameter set, no road, no
+ * only when the riders of a scene are simulated together.  csf_scene_calib_load makes an EMPTY engine (one parameter set, no road of its own, no
  * recording; not a member of a batch or of a communicator; not an UncontrolledVehicle's) hold a data set of n_scn scenes: scene q has
  * n_riders[q] road users (1 .. 32) of the engine's class, R = sum n_riders; per rider the start state s0 [R][n_states], v_desired [R] and a
  * destination queue in CSR form as csf_set_dest_queue takes it with reset = 1 (dest_offsets [R + 1], dest_xyz_stop rows of (x, y, stop); at
@@ -496,7 +496,23 @@ int csf_calib_clear(csf_engine *e);
  * finite (CSF_E_ARG); the rounding bands of an evaluation cover the largest recorded coordinate.  It may be called any number of times
  * between evaluations; replayed == NULL (or no non-zero entry) drops the replay, and evaluations are again what they are without one, bit
  * for bit.  rows may be NULL when nothing is replayed.  CSF_E_STATE without a closed-loop data set; everything that can fail runs before
- * anything is replaced.  csf_scene_calib_clear frees the replay with the rest. */
+ * anything is replaced.  csf_scene_calib_clear frees the replay with the rest.
+ *
+ * csf_scene_calib_road gives scenes of the held data set ROAD EDGES, shared by all candidate sets: the edges as
+ * csf_set_road_vertices takes them (offsets [n_edges + 1], xy, F0 [n_edges], sigma [n_edges]) and edge_scene [n_edges], the scene of every
+ * edge, non-decreasing; a scene without an entry has no road.  Every tick adds the road-edge force to every rider of such a scene
+ * (intersection.py:226-242, 853-857) as the one-wave tick of csf_step does for an engine that holds the scene and its road: the road is
+ * packed relative to the origin that engine would have.  A scene's road has at most 2 048 vertices and, padded to a multiple of 64, at most
+ * 16 384 / P of them, P the power of two that holds the scene's riders.  It may be called any number of times between evaluations;
+ * n_edges == 0 drops every road and evaluations are again what they are without one, bit for bit.  Refused with nothing changed:
+ * CSF_E_STATE without a closed-loop data set (the data set of csf_calib_load included); CSF_E_ARG for a NULL array, a scene index out of
+ * range or decreasing, offsets that run backwards, a value that is not finite, a road beyond those limits.  csf_scene_calib_load still
+ * refuses an engine with a road of its own (csf_set_road_vertices).  csf_scene_calib_clear frees the roads with the rest.
+ *
+ * csf_scene_calib_eval_road is csf_scene_calib_eval with road parameters per candidate set: road_F0 [n_sets] and road_sigma [n_sets] replace
+ * F0 and sigma of EVERY road vertex for that set (the reference's edges share one RoadElementParameters).  Both NULL: the loaded roads'
+ * own values - csf_scene_calib_eval is this call with both NULL.  CSF_E_ARG for one array without the other, F0 < 0 or a value that is not
+ * finite (csf_set_road_vertices places no other limit on sigma, and neither does this call); CSF_E_STATE when no scene has a road. */
 int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks,
                          const double *s0, const double *v_desired,
                          const int64_t *dest_offsets, const double *dest_xyz_stop,
@@ -505,7 +521,13 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
 int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params,
                          size_t params_size, int32_t abi_version,
                          double *sums_out, int32_t stride, double *states_out);
+int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *params,
+                              size_t params_size, int32_t abi_version,
+                              const double *road_F0, const double *road_sigma,
+                              double *sums_out, int32_t stride, double *states_out);
 int csf_scene_calib_replay(csf_engine *e, const uint8_t *replayed, const double *rows);
+int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_scene, const int64_t *offsets,
+                         const double *xy, const double *F0, const double *sigma);
 int csf_scene_calib_launches(const csf_engine *e, int64_t *n_launches);
 int csf_scene_calib_clear(csf_engine *e);
 

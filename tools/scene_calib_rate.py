@@ -15,8 +15,12 @@ the engines of the baseline in their batch, per tick one step_batch and per engi
 the error in NumPy (`replay_base_ms`; --replay-base-max caps the sets it is built for, it is O(sets x scenes x ticks) host calls) -
 and their ratio.  Without --replay the tool does what it did.
 
+--road puts every scene between two road edges of --road-verts vertices each on BOTH legs - the data set gets them
+through csf_scene_calib_road, every engine of the baseline through set_road before it joins its batch - and adds `road_over_ms`: the
+same evaluation with road_F0 / road_sigma per candidate set (csf_scene_calib_eval_road), which the baseline has no single call for.
+
     python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
-                                     [--replay [--replay-base-max 4]]
+                                     [--replay [--replay-base-max 4]] [--road [--road-verts 200]]
 """
 import argparse
 import json
@@ -68,6 +72,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--replay", action="store_true")
     ap.add_argument("--replay-base-max", type=int, default=4)
+    ap.add_argument("--road", action="store_true")
+    ap.add_argument("--road-verts", type=int, default=200)
     a = ap.parse_args()
     feat = np.array([0, 1], dtype=np.int32)
     if a.out:
@@ -84,10 +90,16 @@ def main():
         obj = np.random.default_rng(1).normal(size=(a.ticks, R, feat.size))
         mask = np.concatenate([np.arange(n) % 2 == 1 for n in nr])      # every second rider of a scene (>= 3 riders each)
         rec = None
+        xs = np.linspace(-20.0, 34.0, a.road_verts)                 # the box is 14 m: edges 3 m below and above it
+        road = (np.array([0, a.road_verts, 2 * a.road_verts]), np.r_[np.c_[xs, np.full(a.road_verts, -3.0)], np.c_[xs, np.full(a.road_verts, 17.0)]],
+                np.array([0.15, 0.2]), np.array([2.0, 2.0]))
         for n_sets in [int(x) for x in a.sets.split(",")]:
             sets = pod_sets(base, n_sets)
             e = Engine(base, n_sets * R)
             e.scene_calib_load(nr, s0, 5.0, off, rows, obj, feat, max_sets=n_sets)
+            if a.road:
+                e.scene_calib_road(np.repeat(np.arange(a.scenes, dtype=np.int32), 2), np.arange(2 * a.scenes + 1) * a.road_verts,
+                                   np.tile(road[1].reshape(2, -1, 2), (a.scenes, 1, 1)).reshape(-1, 2), np.tile(road[2], a.scenes), np.tile(road[3], a.scenes))
             twins = []
             if n_sets <= a.base_max:
                 for pod in sets:
@@ -95,6 +107,8 @@ def main():
                         t = Engine(pod, s.shape[0])
                         t.add_agents(s, 5.0)
                         t.set_dest_queue(np.arange(s.shape[0]), o, d, reset=True)
+                        if a.road:
+                            t.set_road(*road)
                         t.record(stride=1, capacity=a.ticks, forces=False)
                         twins.append(t)
                 Engine.batch_join(twins)
@@ -144,6 +158,13 @@ def main():
             line = dict(model=model, n_sets=n_sets, scenes=a.scenes, riders=R, ticks=a.ticks, windows=a.windows, first_call_rel_gap=first_gap,
                         new_ms=dict(median=float(np.median(t_new)), min=min(t_new), max=max(t_new)),
                         base_ms=dict(median=float(np.median(t_old)), min=min(t_old), max=max(t_old)) if t_old else None)
+            if a.road:
+                rf, rs = 0.15 * (1.0 + 0.002 * np.arange(n_sets)), np.full(n_sets, 2.0)
+                e.scene_calib_eval(sets, road_F0=rf, road_sigma=rs)          # (allocates the sets' road blocks)
+                t_over = []
+                for _ in range(a.windows):
+                    t0 = time.perf_counter(); e.scene_calib_eval(sets, road_F0=rf, road_sigma=rs); t_over.append((time.perf_counter() - t0) * 1e3)
+                line.update(road_verts=2 * a.road_verts, road_over_ms=dict(median=float(np.median(t_over)), min=min(t_over), max=max(t_over)))
             if a.replay:
                 if rec is None:                                  # the recording: the scenes' own run with the base set
                     rec = e.scene_calib_eval([base], states=True)[1][:, :R]
