@@ -36,6 +36,7 @@ SYMBOLS = (
     "csf_scene_calib_load", "csf_scene_calib_eval", "csf_scene_calib_launches", "csf_scene_calib_clear",
     "csf_scene_calib_replay",
     "csf_scene_calib_road", "csf_scene_calib_eval_road",
+    "csf_scene_calib_windows",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -194,6 +195,8 @@ def load():
     if hasattr(L, "csf_scene_calib_road"):       # (the same)
         L.csf_scene_calib_road.argtypes = [vp, i32, vp, vp, dp, dp, dp]
         L.csf_scene_calib_eval_road.argtypes = [vp, i32, C.POINTER(Params), C.c_size_t, i32, dp, dp, dp, i32, dp]
+    if hasattr(L, "csf_scene_calib_windows"):    # (the same)
+        L.csf_scene_calib_windows.argtypes = [vp, vp, vp]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

@@ -425,11 +425,18 @@ class SceneData:
     road = (offsets [n_edges + 1], verts [n_v, 2], F0 [n_edges], sigma [n_edges]) gives the scene ROAD EDGES, as `Engine.set_road`
     takes them (default: none): every tick adds their force to every simulated road user (intersection.py:226-242, 853-857).  All
     edges together have at most ROAD_MAX_VERTS vertices and, padded to a multiple of 64, at most 16 384 / P of them, P the power of two
-    that holds the scene's road users - what the one-wave tick stages."""
+    that holds the scene's road users - what the one-wave tick stages.
+
+    present = (enter [n], exit [n]) gives every road user a PRESENCE WINDOW [enter, exit) in ticks of the scene, 0 <= enter <= exit
+    <= length (default: all of [0, length)).  At a tick outside its window a road user is not in the scene: it is neither a source
+    nor a receiver of the field, it is not ticked or put on its recording, and nothing is added to its error.  s0 of a road user is
+    its state at the start of tick `enter` (a fresh vehicle joins there: intersection.add_vehicle between two steps); after `exit`
+    it keeps its last state.  enter == exit: never present.  traj outside a road user's window is never read and may be NaN; a
+    replayed road user needs finite (x, y, psi, v) inside its window only."""
 
     ROAD_MAX_VERTS = 2048
 
-    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None):
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None):
         self.s0 = np.asarray(s0, dtype=float)
         if self.s0.ndim != 2 or self.s0.shape[1] < 4 or not 1 <= self.s0.shape[0] <= 32:
             raise ValueError("a scene has 1 .. 32 road users: s0 is [n, >= 4]")
@@ -463,8 +470,30 @@ class SceneData:
         self.length = self.traj.shape[0] if length is None else int(length)
         if not 0 <= self.length <= self.traj.shape[0]:
             raise ValueError("length: 0 .. the rows of traj")
-        if self.replayed.any() and (self.traj.shape[2] < 4 or not np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()):
-            raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over all `length` rows")
+        if present is None:
+            self.enter, self.exit = np.zeros(n, dtype=np.int32), np.full(n, self.length, dtype=np.int32)
+        else:
+            try:
+                enter, exit_ = present
+                enter, exit_ = np.asarray(enter), np.asarray(exit_)
+            except (TypeError, ValueError):
+                raise ValueError("present is (enter [n], exit [n])") from None
+            if enter.shape != (n,) or exit_.shape != (n,) or enter.dtype.kind not in "iu" or exit_.dtype.kind not in "iu":
+                raise ValueError("present: one integer entry tick and one integer exit tick per road user")
+            if np.any(enter < 0) or np.any(enter > exit_) or np.any(exit_ > self.length):
+                raise ValueError("present: 0 <= enter <= exit <= length for every road user")
+            self.enter, self.exit = enter.astype(np.int32), exit_.astype(np.int32)
+        self.windowed = bool(np.any(self.enter != 0) or np.any(self.exit != self.length))
+        if self.replayed.any():
+            if self.traj.shape[2] < 4:
+                raise ValueError("a replayed road user needs (x, y, psi, v): traj has fewer than 4 columns")
+            if not self.windowed:
+                finite = np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()
+            else:
+                finite = all(np.isfinite(self.traj[self.enter[i]: self.exit[i], i, :4]).all() for i in np.flatnonzero(self.replayed))
+            if not finite:
+                raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over the rows of its window "
+                                 "(all `length` rows without one)")
         self.road = None if road is None else self._checked_road(road, n)
 
     @classmethod
@@ -498,16 +527,36 @@ class SceneData:
     def n(self):
         return self.s0.shape[0]
 
+    @property
+    def inside(self):
+        """[length, n] bool: road user i is present at tick t"""
+        t = np.arange(self.length)[:, None]
+        return (self.enter[None, :] <= t) & (t < self.exit[None, :])
+
+    def replay_rows(self):
+        """[n_t, replayed road users, 4]: the recorded (x, y, psi, v) as `Engine.scene_calib_replay` takes them.  Without windows
+        that is traj itself.  Outside its window a row is never used, but the engine wants the rows of a scene finite: there a road
+        user gets the nearest row inside its window (one that is never present: its start state)."""
+        rows = self.traj[:, self.replayed, :4]
+        if self.windowed:
+            rows = rows.copy()
+            for c, i in enumerate(np.flatnonzero(self.replayed)):
+                a, b = int(self.enter[i]), int(self.exit[i])
+                rows[:a, c] = self.traj[a, i, :4] if a < b else self.s0[i, :4]
+                rows[b: self.length, c] = self.traj[b - 1, i, :4] if a < b else self.s0[i, :4]
+        return rows
+
     def ego_split(self):
         """The leave-one-out scenes of this scene, one per simulated road user: scene i simulates that road user alone and replays
         all others from the recording (road users that are replayed here stay so).  Host only.  s0, the queues and traj are
-        shared with this scene, not copied; every scene has a mask of its own and this scene's road."""
+        shared with this scene, not copied; every scene has a mask of its own and this scene's road and presence windows."""
         out = []
-        for i in np.flatnonzero(~self.replayed):
+        # (a road user that is never present in a scene that has ticks is nobody's ego)
+        for i in np.flatnonzero(~self.replayed & ((self.exit > self.enter) | (self.length == 0))):
             mask = np.ones(self.n, dtype=bool)
             mask[i] = False
             out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask,
-                                 road=self.road))
+                                 road=self.road, present=(self.enter, self.exit) if self.windowed else None))
         return out
 
 
@@ -544,6 +593,11 @@ class InteractionCalibration:
     "road_sigma" among params_keys fit the two RoadElementParameters of the road-edge force: they go to the evaluation's road
     overrides, one value per candidate set for every edge of every scene, and not into PARAMS_TYPE; with only one of them fitted the
     other keeps its value from RoadElementParameters().  Either key needs a scene with a road (ValueError otherwise).
+
+    Scenes whose road users enter and leave (`SceneData(present=...)`) are loaded with their windows (`Engine.scene_calib_windows`) and
+    the launch honours them.  Both built-in errors are formed over the present (rider, tick) cells: calc_sse_timesteps sums them,
+    calc_maesse_samples divides a scene's sum by n_feat x the present cells of its simulated riders.  Another error_func and
+    `simulate` get NaN outside a rider's window, in the trajectories and in the objectives alike.
 
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
@@ -609,6 +663,9 @@ class InteractionCalibration:
         for q, d in enumerate(data):
             if d.replayed.all():
                 raise ValueError(f"scene {q}: every road user is replayed - there is nothing to fit")
+            # (an empty scene - length 0 - stays what it was: no tick, no error; a scene that HAS ticks needs somebody to simulate)
+            if d.length > 0 and not np.any(~d.replayed & (d.exit > d.enter)):
+                raise ValueError(f"scene {q}: no simulated road user is ever present - there is nothing to fit")
             if feat.max() >= d.traj.shape[2]:
                 raise ValueError(f"scene {q}: objective_features_traj names row {int(feat.max())} of vehicle.traj, the recorded trajectory has {d.traj.shape[2]}")
             sl = slice(roff[q], roff[q + 1])
@@ -626,7 +683,7 @@ class InteractionCalibration:
             for d in data:
                 k = int(d.replayed.sum())
                 if k:
-                    rec[: d.traj.shape[0], at: at + k] = d.traj[:, d.replayed, :4]
+                    rec[: d.traj.shape[0], at: at + k] = d.replay_rows()
                 at += k
             engine.scene_calib_replay(rep, rec)
         if any(d.road is not None and d.road[0][-1] > 0 for d in data):
@@ -642,21 +699,31 @@ class InteractionCalibration:
                     f0.append(F0[k])
                     sg.append(sigma[k])
             engine.scene_calib_road(np.array(es, dtype=np.int32), np.array(ro, dtype=np.int64), np.concatenate(vs), np.array(f0), np.array(sg))
+        objectives = [d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data]
+        inside = None
+        if any(d.windowed for d in data):                       # (no scene has a window: nothing is passed, the calls are today's)
+            engine.scene_calib_windows(np.concatenate([d.enter for d in data]), np.concatenate([d.exit for d in data]))
+            inside = [d.inside for d in data]
+            for q, d in enumerate(data):
+                objectives[q][~inside[q][:, ~d.replayed]] = np.nan
+        # present (rider, tick) cells of the simulated riders of every scene: length x simulated riders without windows
+        cells = np.array([int((d.exit - d.enter)[~d.replayed].sum()) for d in data])
         ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets, sim=[~d.replayed for d in data],
-                  nsim=np.array([int((~d.replayed).sum()) for d in data]),
-                  objectives=[d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data])
+                  nsim=np.array([int((~d.replayed).sum()) for d in data]), cells=cells, inside=inside, objectives=objectives)
         self._sets[bool(test)] = ds
         return ds
 
     def _trajs(self, ds, states, k):
         """the scenes of parameter set k from the states of one evaluation: [length, simulated riders, n_feat] each (rows the class
-        lacks: 0)"""
+        lacks: 0; NaN outside a rider's presence window)"""
         ns, out = states.shape[2], []
         for q, ln in enumerate(ds["lens"]):
             tr = np.zeros((ln, ds["nr"][q], ds["feat"].size))
             for c, f in enumerate(ds["feat"]):
                 if f < ns:
                     tr[:, :, c] = states[:ln, k * ds["R"] + ds["roff"][q]: k * ds["R"] + ds["roff"][q + 1], f]
+            if ds["inside"] is not None:
+                tr[~ds["inside"][q]] = np.nan
             out.append(tr if ds["sim"][q].all() else tr[:, ds["sim"][q]])
         return out
 
@@ -676,7 +743,7 @@ class InteractionCalibration:
             elif self.error_func is calc_maesse_samples:
                 sums = ds["engine"].scene_calib_eval(chunk, **road)
                 with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
-                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["lens"] * ds["nsim"] * float(ds["feat"].size))[None, :]
+                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["cells"] * float(ds["feat"].size))[None, :]
                 err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
             else:
                 _, states = ds["engine"].scene_calib_eval(chunk, states=True, **road)

@@ -53,6 +53,10 @@ struct SceneDev {
     float4 *road_blk;            // [n_sets][road_stride], NULL: the roads keep their own parameters
     int64_t road_stride;         // vertices (padded) of all scenes together
     uint32_t road_lds;           // bytes of dynamic LDS: the largest nv_pad of the data set x 16
+    // Presence windows (csf_scene_calib_windows): rider r is in its scene at the ticks win_enter[r] <= t < win_exit[r]
+    // and at every other tick neither source nor receiver, not ticked, not replayed and not summed.  NULL: no windows - everybody is
+    // there from tick 0 to the scene's last, and the launch is the instance without a mask.
+    const int32_t *win_enter, *win_exit;   // [R]
 };
 
 // One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].

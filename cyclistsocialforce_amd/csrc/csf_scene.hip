@@ -26,6 +26,13 @@
 // road_np and the origin of a stand-alone engine that holds the scene, and small_tick_body stages and sums the road as it does for
 // small_batch_kernel, in dynamic LDS sized by the largest road of the data set.  Road parameters per candidate set: see the prologue.
 //
+// Road users that enter and leave (csf_scene_calib_windows): rider r is in its scene at the ticks win_enter[r] <= t <
+// win_exit[r].  Every lane keeps the two bounds of its rider in registers, one ballot per tick makes the presence mask of the scene
+// (SceneHook::present), and small_tick_body gates the pair loop, the road term and agent_body with it; the hook below returns before
+// the replay / error part for an absent rider.  Before its entry the slot holds what the restore at the head of the launch put there -
+// nothing ticks it - so s0 IS the state at the start of tick win_enter[r]; after its exit it keeps its last state.  A data set without
+// windows launches scene_eval_kernel<MODEL, false>, where all of this is compiled out.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -38,8 +45,9 @@ namespace csf {
 
 // behind every tick: lane = rider of the scene, its error terms (a replayed rider: its recorded state instead) and, on a sampled
 // tick, its state
-template <int MODEL>
+template <int MODEL, bool WIN>
 struct SceneHook {
+    static constexpr bool MASKED = WIN;
     const SceneDev &c;
     const int64_t rider;          // set * R + first rider of the scene + lane: row of sums and of a sample
     const double *obj;            // objective of this lane's rider at tick 0
@@ -48,8 +56,12 @@ struct SceneHook {
     int wait;                     // ticks until the next sampled one
     int taken = 0;                // samples written
     double sse = 0.0, sae = 0.0;
-    __device__ __forceinline__ SceneHook(const SceneDev &c_, int64_t rider_, const double *obj_, const double *rep_, double *smp_)
-        : c(c_), rider(rider_), obj(obj_), rep(rep_), smp(smp_), wait(c_.stride - 1) {}
+    const int t_in, t_out;        // WIN: this lane's rider is present at the ticks t_in <= t < t_out (a lane without a rider: never)
+    __device__ __forceinline__ SceneHook(const SceneDev &c_, int64_t rider_, const double *obj_, const double *rep_, double *smp_, int t_in_,
+                                         int t_out_)
+        : c(c_), rider(rider_), obj(obj_), rep(rep_), smp(smp_), wait(c_.stride - 1), t_in(t_in_), t_out(t_out_) {}
+    // the riders of the scene that are present at tick t, bit = lane: called by all 64 lanes, the same value in each
+    __device__ __forceinline__ uint64_t present(int t) const { return __ballot(t_in <= t && t < t_out); }
     __device__ __forceinline__ void sample(const Dev &d, int lane) {
         for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
         smp += (int64_t)c.n_sets * c.R * d.ns;
@@ -57,7 +69,9 @@ struct SceneHook {
     }
     __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
         if (lane >= n) return;
-        if (rep != nullptr) {
+        if (WIN && !(t_in <= t && t < t_out)) {
+            // not in the scene: nothing of a recording is written, nothing is summed; a sample shows what the slot holds
+        } else if (rep != nullptr) {
             // vehicle.s written from the recording (calibration.py:455-460) and what csf_push_state keeps consistent with it
             // (abi_population.inc): this lane's own stores behind its tick's, program order.  Nothing is added to sse / sae.
             const double *r = rep + (int64_t)t * c.n_rep * 4;
@@ -97,7 +111,7 @@ struct SceneHook {
     }
 };
 
-template <int MODEL>
+template <int MODEL, bool WIN>
 __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
     extern __shared__ float4 srv[];                           // c.road_lds bytes: the largest road of the data set (none: 0 bytes)
     const int b = (int)blockIdx.x;
@@ -154,8 +168,10 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
     const int64_t rider = (int64_t)set * c.R + first + lane;
     // (rep_index is read by the lanes that have a rider only: it has R entries)
     const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
-    SceneHook<MODEL> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
-                          c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr);
+    // (win_enter / win_exit have R entries, as rep_index)
+    const int t_in = WIN && lane < n ? c.win_enter[first + lane] : 0, t_out = WIN && lane < n ? c.win_exit[first + lane] : 0;
+    SceneHook<MODEL, WIN> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
+                               c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr, t_in, t_out);
     small_tick_body<MODEL>(d, len, nullptr, srv, 0u, 0, hook);
     if (lane >= n) return;
     c.sums[rider] = make_double2(hook.sse, hook.sae);
@@ -167,7 +183,12 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
 void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st) {
     const int count = c.n_sets * c.n_scn;
     if (count <= 0) return;
-#define CSF_SCENE(MODEL) hipLaunchKernelGGL((scene_eval_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c)
+    const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
+#define CSF_SCENE(MODEL)                                                                                                          \
+    do {                                                                                                                          \
+        if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
+        else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
+    } while (0)
     switch (model) {
     case CSF_BICYCLE: CSF_SCENE(CSF_BICYCLE); break;
     case CSF_TWOD: CSF_SCENE(CSF_TWOD); break;

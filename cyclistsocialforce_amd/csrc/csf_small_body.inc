@@ -6,7 +6,15 @@
 // HOOK: what a caller does behind every tick - hook(d, t, lane, n) is called by all 64 lanes once the tick's stores are issued
 // (lanes 0 .. n - 1 have just written their road user's state: their own stores, program order).  NoTickHook is empty and
 // compiles to nothing; csf_scene.hip sums an error there.
+//
+// HOOK::MASKED (DESIGN.md 4.10d): the hook knows which road users are in the scene at a tick.  hook.present(t) is then called by all
+// 64 lanes at the head of tick t and returns the same 64-bit mask in every lane - bit j: road user j is present (a ballot: scalar
+// registers).  An absent road user is no source, no receiver, is not ticked and gets no road term; its lane still stages its
+// (unchanged) state, takes part in every shuffle and barrier and calls the hook - the mask gates work, never the control flow
+// around a barrier or a shuffle.  With MASKED == false every use of the mask is compiled out (if constexpr) and the body is the one
+// it was before there was a mask.
 struct NoTickHook {
+    static constexpr bool MASKED = false;
     __device__ __forceinline__ void operator()(const Dev &, int, int, int) {}
 };
 
@@ -65,6 +73,15 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             rec_wait = d.hist_stride;
         }
         if (rec_wait > 0) rec_wait--;
+        // who is in the scene at this tick (uniform); `act`: this lane's receiver is live and present, `mine`: this lane has a road
+        // user to tick (lane < n: i == lane, the receiver is the lane's own road user)
+        uint64_t here = ~0ull;
+        bool act = live, mine = lane < n;
+        if constexpr (HOOK::MASKED) {
+            here = hook.present(t);
+            act = live && ((here >> i) & 1ull) != 0;
+            mine = mine && act;
+        }
         // (own stores of the previous tick: the lanes of the first group wrote them, in this wave: program order)
         const double x = d.s[a], y = d.s[cap + a], psi = d.s[2 * cap + a];
         double sp, cp;
@@ -83,7 +100,10 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             const double xs = sx[j], ys = sy[j], ps = spsi[j];
             const double ex = x - xs, ey = y - ys;                 // vehicle.py:1615-1616
             // the receiver itself and a road user on the very same spot (D2) add nothing
-            if (!live || j == i || (ex == 0.0 && ey == 0.0)) continue;
+            if constexpr (HOOK::MASKED) {
+                if (((here >> j) & 1ull) == 0) continue;           // (a road user that is not there is nobody's source)
+            }
+            if (!act || j == i || (ex == 0.0 && ey == 0.0)) continue;
             const float dx = (float)ex, dy = (float)ey, r2 = fmaxf(dx * dx + dy * dy, 1e-30f);
             const float4 q = make_float4(0.f, 0.f, (float)scs[j], (float)ssn[j]);
             bool edge;
@@ -144,10 +164,10 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
                 qx += __shfl_xor(qx, o, WAVE);
                 qy += __shfl_xor(qy, o, WAVE);
             }
-            if (lane < n) d.froad[lane] = make_float2(qx, qy);    // (agent_body reads it back: the same lane, program order)
+            if (mine) d.froad[lane] = make_float2(qx, qy);        // (agent_body reads it back: the same lane, program order)
         }
         __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
-        if (lane < n) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+        if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
         hook(d, t, lane, n);
     }
     // csf_step_get_tick: what snapshot_kernel would pack in a launch of its own (slots are the population order here)

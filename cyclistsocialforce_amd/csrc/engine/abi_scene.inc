@@ -39,6 +39,9 @@ struct SceneCalibState {
                                              // the first evaluation that overrides them
     int64_t road_stride = 0;
     int32_t road_max_pad = 0;                // largest nv_pad of a scene
+    // csf_scene_calib_windows: a presence window per rider (DESIGN.md 4.10d).  Empty buffers: no windows, and an evaluation is
+    // handed win_enter == NULL - the kernel instance without a mask
+    DevBuf<int32_t> win_enter, win_exit;     // [R]
 };
 
 }  // extern "C++"
@@ -295,6 +298,8 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
     c.road_blk = road_over ? cs.road_blk.p : nullptr;
     c.road_stride = cs.road_stride;
     c.road_lds = (uint32_t)cs.road_max_pad * (uint32_t)sizeof(float4);
+    c.win_enter = cs.win_enter.n > 0 ? cs.win_enter.p : nullptr;
+    c.win_exit = cs.win_exit.n > 0 ? cs.win_exit.p : nullptr;
     HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
     HIPCHK(e, hipGetLastError());
@@ -443,6 +448,36 @@ int csf_scene_calib_replay(csf_engine *e, const uint8_t *replayed, const double 
     cs.rep = std::move(d_rows);
     cs.n_rep = n_rep;
     cs.rep_bound = bound;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_windows(csf_engine *e, const int32_t *enter, const int32_t *exit) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) {
+        if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_windows: the engine holds the data set of csf_calib_load, whose samples are single vehicles that are there throughout");
+        return fail(e, CSF_E_STATE, "csf_scene_calib_windows: no closed-loop data set (csf_scene_calib_load first)");
+    }
+    SceneCalibState &cs = *e->scene_calib;
+    if ((enter == nullptr) != (exit == nullptr)) return fail(e, CSF_E_ARG, "csf_scene_calib_windows: enter and exit are given together or not at all");
+    const int32_t R = cs.R;
+    for (int32_t q = 0; enter && q < cs.n_scn; q++)
+        for (int32_t r = cs.h_roff[(size_t)q]; r < cs.h_roff[(size_t)q + 1]; r++)
+            if (enter[r] < 0 || enter[r] > exit[r] || exit[r] > cs.h_len[(size_t)q])
+                return fail(e, CSF_E_ARG, "csf_scene_calib_windows: rider %d has the window [%d, %d), scene %d has %d ticks (0 <= enter <= exit <= ticks)",
+                            (int)r, (int)enter[r], (int)exit[r], (int)q, (int)cs.h_len[(size_t)q]);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // everything that can fail first: a refused call changes nothing
+    DevBuf<int32_t> d_enter, d_exit;
+    if (enter) {
+        hipError_t r = d_enter.alloc((size_t)R);
+        if (r == hipSuccess) r = d_exit.alloc((size_t)R);
+        if (r == hipSuccess) r = hipMemcpy(d_enter.p, enter, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (r == hipSuccess) r = hipMemcpy(d_exit.p, exit, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_windows: no memory for the windows: %s", hipGetErrorString(r));
+    }
+    cs.win_enter = std::move(d_enter);
+    cs.win_exit = std::move(d_exit);
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 

@@ -351,6 +351,24 @@ class Engine:
                 raise ValueError("rows must be [n_ticks, replayed riders, 4]")
         self._ck(self._lib.csf_scene_calib_replay(self._h, _ptr(mask), _ptr(rows) if n_rep else None))
 
+    def scene_calib_windows(self, enter, exit):
+        """Presence windows of the riders of the loaded scenes: enter, exit [R] (int32), rider r is in its scene at the ticks
+        enter[r] <= t < exit[r] (0 <= enter <= exit <= the length of its scene) and at every other tick neither a source nor a
+        receiver of the field, not ticked, not put on its recording and not part of its sums.  None, None drops the windows."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_windows: no closed-loop data set (scene_calib_load first)")
+        R, _ = self._scene_calib
+        if enter is None and exit is None:
+            self._ck(self._lib.csf_scene_calib_windows(self._h, None, None))
+            return
+        if enter is None or exit is None:
+            raise ValueError("enter and exit are given together or not at all")
+        en = np.ascontiguousarray(enter, dtype=np.int32)
+        ex = np.ascontiguousarray(exit, dtype=np.int32)
+        if en.shape != (R,) or ex.shape != (R,):
+            raise ValueError("enter and exit must have one entry per rider of the data set")
+        self._ck(self._lib.csf_scene_calib_windows(self._h, _ptr(en), _ptr(ex)))
+
     def scene_calib_clear(self):
         self._ck(self._lib.csf_scene_calib_clear(self._h))
         self._scene_calib = None

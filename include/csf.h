@@ -512,7 +512,19 @@ int csf_calib_clear(csf_engine *e);
  * csf_scene_calib_eval_road is csf_scene_calib_eval with road parameters per candidate set: road_F0 [n_sets] and road_sigma [n_sets] replace
  * F0 and sigma of EVERY road vertex for that set (the reference's edges share one RoadElementParameters).  Both NULL: the loaded roads'
  * own values - csf_scene_calib_eval is this call with both NULL.  CSF_E_ARG for one array without the other, F0 < 0 or a value that is not
- * finite (csf_set_road_vertices places no other limit on sigma, and neither does this call); CSF_E_STATE when no scene has a road. */
+ * finite (csf_set_road_vertices places no other limit on sigma, and neither does this call); CSF_E_STATE when no scene has a road.
+ *
+ * csf_scene_calib_windows gives every rider of the held data set a PRESENCE WINDOW: enter [R] and exit [R], rider
+ * r is in its scene at the ticks enter[r] <= t < exit[r], with 0 <= enter[r] <= exit[r] <= the length of its scene.  At every other tick
+ * the rider is not there (intersection.py: add_vehicle / remove_vehicle between two steps): no other rider reads it as a source, it is not
+ * ticked, not put on its recording (csf_scene_calib_replay), feels no road, and nothing is added to its sums.  Before its entry its slot
+ * holds the fresh vehicle every evaluation starts from, so its row of s0 is its state at the start of tick enter[r]; after its exit the
+ * slot keeps its last state, and the samples of states_out show what the slot holds.  enter[r] == exit[r]: never present, sums (0, 0).
+ * Rows of the objective and of the replayed rows outside a rider's window are never used.  Both arrays NULL drops the windows, and
+ * evaluations are again what they are without them, bit for bit; with windows every evaluation is still ONE launch.  The call is
+ * independent of csf_scene_calib_replay and csf_scene_calib_road and of their order.  Refused with the held windows unchanged: CSF_E_STATE
+ * without a closed-loop data set (the data set of csf_calib_load included); CSF_E_ARG for one array without the other or a bound outside
+ * that range.  csf_scene_calib_clear frees the windows with the rest. */
 int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks,
                          const double *s0, const double *v_desired,
                          const int64_t *dest_offsets, const double *dest_xyz_stop,
@@ -528,6 +540,7 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
 int csf_scene_calib_replay(csf_engine *e, const uint8_t *replayed, const double *rows);
 int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_scene, const int64_t *offsets,
                          const double *xy, const double *F0, const double *sigma);
+int csf_scene_calib_windows(csf_engine *e, const int32_t *enter, const int32_t *exit);
 int csf_scene_calib_launches(const csf_engine *e, int64_t *n_launches);
 int csf_scene_calib_clear(csf_engine *e);
 

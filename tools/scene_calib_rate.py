@@ -19,8 +19,13 @@ and their ratio.  Without --replay the tool does what it did.
 through csf_scene_calib_road, every engine of the baseline through set_road before it joins its batch - and adds `road_over_ms`: the
 same evaluation with road_F0 / road_sigma per candidate set (csf_scene_calib_eval_road), which the baseline has no single call for.
 
+--presence gives every rider a random presence window of at least half the scene (csf_scene_calib_windows) and adds
+`presence_ms`: the same one launch per evaluation, the instance of the kernel with the mask; the windows are dropped again before the
+--replay leg.  (`--windows` was taken: it is the number of timing windows.)  The baseline has no leg for it - riders that come and go
+would be add_agents / remove_agents between 1-tick calls of every engine.
+
     python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
-                                     [--replay [--replay-base-max 4]] [--road [--road-verts 200]]
+                                     [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence]
 """
 import argparse
 import json
@@ -74,6 +79,7 @@ def main():
     ap.add_argument("--replay-base-max", type=int, default=4)
     ap.add_argument("--road", action="store_true")
     ap.add_argument("--road-verts", type=int, default=200)
+    ap.add_argument("--presence", action="store_true")
     a = ap.parse_args()
     feat = np.array([0, 1], dtype=np.int32)
     if a.out:
@@ -165,6 +171,18 @@ def main():
                 for _ in range(a.windows):
                     t0 = time.perf_counter(); e.scene_calib_eval(sets, road_F0=rf, road_sigma=rs); t_over.append((time.perf_counter() - t0) * 1e3)
                 line.update(road_verts=2 * a.road_verts, road_over_ms=dict(median=float(np.median(t_over)), min=min(t_over), max=max(t_over)))
+            if a.presence:
+                rng = np.random.default_rng(7)
+                span = rng.integers((a.ticks + 1) // 2, a.ticks + 1, size=R)      # at least half the scene
+                enter = rng.integers(0, a.ticks - span + 1).astype(np.int32)
+                e.scene_calib_windows(enter, (enter + span).astype(np.int32))
+                new()
+                t_win = []
+                for _ in range(a.windows):
+                    t0 = time.perf_counter(); new(); t_win.append((time.perf_counter() - t0) * 1e3)
+                e.scene_calib_windows(None, None)
+                line["timing_windows"] = line.pop("windows")     # (in these lines "windows" would read as the presence windows)
+                line.update(present_share=float(span.sum() / (a.ticks * R)), presence_ms=dict(median=float(np.median(t_win)), min=min(t_win), max=max(t_win)))
             if a.replay:
                 if rec is None:                                  # the recording: the scenes' own run with the base set
                     rec = e.scene_calib_eval([base], states=True)[1][:, :R]
