@@ -410,7 +410,8 @@ class DownhillSimplexCalibration:
 
 # --------------------------------------------------------------------------- interaction parameters, closed loop
 class SceneData:
-    """One recorded scene of up to 32 road users that interact (plain arrays): start states s0 [n, >= 4] (x, y, psi, v, ...),
+    """One recorded scene of road users that interact - up to 32 of them, or any number on its roster with presence windows that keep
+    at most 32 in the scene at any tick - (plain arrays): start states s0 [n, >= 4] (x, y, psi, v, ...),
     desired speeds v_desired [n] (or a scalar), the riders' destination queues in CSR form (dest_offsets [n + 1], dest_xyz_stop
     [rows, 3] = (x, y, stop); at least one row each), the recorded trajectory traj [n_t, n, n_cols] - row t the state AFTER tick
     t + 1, columns the rows of vehicle.traj (x, y, psi, v, delta, theta) as far as they were recorded - and its length in ticks
@@ -432,14 +433,18 @@ class SceneData:
     nor a receiver of the field, it is not ticked or put on its recording, and nothing is added to its error.  s0 of a road user is
     its state at the start of tick `enter` (a fresh vehicle joins there: intersection.add_vehicle between two steps); after `exit`
     it keeps its last state.  enter == exit: never present.  traj outside a road user's window is never read and may be NaN; a
-    replayed road user needs finite (x, y, psi, v) inside its window only."""
+    replayed road user needs finite (x, y, psi, v) inside its window only.
+
+    A roster above 32 needs `present`, and at no tick more than 32 road users whose window holds it (ValueError names the tick and the
+    count; a road user with an empty window counts for nothing).  Such a scene runs on `lanes()`: road users whose windows do not
+    overlap take turns on one lane of the one-wave tick.  Its road limit is that of the power of two that holds its LANES."""
 
     ROAD_MAX_VERTS = 2048
 
     def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None):
         self.s0 = np.asarray(s0, dtype=float)
-        if self.s0.ndim != 2 or self.s0.shape[1] < 4 or not 1 <= self.s0.shape[0] <= 32:
-            raise ValueError("a scene has 1 .. 32 road users: s0 is [n, >= 4]")
+        if self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > 32 and present is None):
+            raise ValueError("a scene has 1 .. 32 road users, or more with presence windows that keep at most 32 at once: s0 is [n, >= 4]")
         n = self.s0.shape[0]
         try:
             self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (n,)))
@@ -484,6 +489,10 @@ class SceneData:
                 raise ValueError("present: 0 <= enter <= exit <= length for every road user")
             self.enter, self.exit = enter.astype(np.int32), exit_.astype(np.int32)
         self.windowed = bool(np.any(self.enter != 0) or np.any(self.exit != self.length))
+        if n > 32:
+            count = self.inside.sum(axis=1) if self.length else np.zeros(1, dtype=int)
+            if count.max() > 32:
+                raise ValueError(f"present: {int(count.max())} road users are in the scene at tick {int(count.argmax())}; at most 32 at once")
         if self.replayed.any():
             if self.traj.shape[2] < 4:
                 raise ValueError("a replayed road user needs (x, y, psi, v): traj has fewer than 4 columns")
@@ -494,7 +503,7 @@ class SceneData:
             if not finite:
                 raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over the rows of its window "
                                  "(all `length` rows without one)")
-        self.road = None if road is None else self._checked_road(road, n)
+        self.road = None if road is None else self._checked_road(road, n if n <= 32 else self.lanes()[1])
 
     @classmethod
     def _checked_road(cls, road, n):
@@ -533,6 +542,21 @@ class SceneData:
         t = np.arange(self.length)[:, None]
         return (self.enter[None, :] <= t) & (t < self.exit[None, :])
 
+    def lanes(self):
+        """(lane [n] int32, n_lanes): road users whose windows do not overlap share a lane.  In order of (enter, roster index) every
+        road user takes the lowest lane whose last occupant has exit <= enter - for intervals that is optimal, so n_lanes is the
+        largest number present at once (at least 1).  A road user with an empty window occupies nothing: lane 0."""
+        lane, last = np.zeros(self.n, dtype=np.int32), []
+        for i in sorted(np.flatnonzero(self.exit > self.enter).tolist(), key=lambda i: (int(self.enter[i]), i)):
+            for k, x in enumerate(last):
+                if x <= self.enter[i]:
+                    break
+            else:
+                k = len(last)
+                last.append(0)
+            lane[i], last[k] = k, int(self.exit[i])
+        return lane, max(1, len(last))
+
     def replay_rows(self):
         """[n_t, replayed road users, 4]: the recorded (x, y, psi, v) as `Engine.scene_calib_replay` takes them.  Without windows
         that is traj itself.  Outside its window a row is never used, but the engine wants the rows of a scene finite: there a road
@@ -556,7 +580,7 @@ class SceneData:
             mask = np.ones(self.n, dtype=bool)
             mask[i] = False
             out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask,
-                                 road=self.road, present=(self.enter, self.exit) if self.windowed else None))
+                                 road=self.road, present=(self.enter, self.exit) if self.windowed or self.n > 32 else None))
         return out
 
 
@@ -599,13 +623,19 @@ class InteractionCalibration:
     calc_maesse_samples divides a scene's sum by n_feat x the present cells of its simulated riders.  Another error_func and
     `simulate` get NaN outside a rider's window, in the trajectories and in the objectives alike.
 
+    A scene whose roster exceeds 32 runs on shared lanes (`SceneData.lanes`, `Engine.scene_calib_load_shared`): the whole data set is
+    then loaded with one such call, every scene on its lanes, and the windows go with the load.  share_lanes=True asks for that
+    whatever the rosters - fewer lanes than road users make the pair loops narrower.  Errors, `simulate` and a custom error_func are
+    what they are with windows: present cells only, NaN outside.
+
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
     ROAD_KEYS = {"road_F_0": "F_0", "road_sigma": "sigma"}
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
-                 max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine):
+                 max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
+        self.share_lanes = bool(share_lanes)
         self.train_data, self.test_data = list(train_data), list(test_data)
         for d in self.train_data + self.test_data:
             if not isinstance(d, SceneData):
@@ -674,9 +704,18 @@ class InteractionCalibration:
             obj[: d.traj.shape[0], sl] = d.traj[:, :, feat]
             off.extend((d.dest_offsets[1:] + len(rows)).tolist())
             rows.extend(d.dest_xyz_stop.tolist())
-        engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
-        engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
-                                max_sets=self.max_sets)
+        shared = self.share_lanes or any(d.n > 32 for d in data)
+        if shared:                                               # every scene on its lanes; the windows go with the load
+            packed = [d.lanes() for d in data]
+            nl = np.array([p[1] for p in packed], dtype=np.int32)
+            engine = self._factory(self._pod({}), max(R, self.max_sets * int(nl.sum())), device=self.device)
+            engine.scene_calib_load_shared(nr, nl, np.concatenate([p[0] for p in packed]), np.concatenate([d.enter for d in data]),
+                                           np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
+                                           np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets)
+        else:
+            engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
+            engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
+                                    max_sets=self.max_sets)
         if rep.any():                                            # the recorded (x, y, psi, v) of the replayed riders, in rider order
             rec = np.zeros((T, int(rep.sum()), 4))
             at = 0
@@ -701,8 +740,9 @@ class InteractionCalibration:
             engine.scene_calib_road(np.array(es, dtype=np.int32), np.array(ro, dtype=np.int64), np.concatenate(vs), np.array(f0), np.array(sg))
         objectives = [d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data]
         inside = None
-        if any(d.windowed for d in data):                       # (no scene has a window: nothing is passed, the calls are today's)
-            engine.scene_calib_windows(np.concatenate([d.enter for d in data]), np.concatenate([d.exit for d in data]))
+        if shared or any(d.windowed for d in data):             # (no scene has a window: nothing is passed, the calls are today's)
+            if not shared:
+                engine.scene_calib_windows(np.concatenate([d.enter for d in data]), np.concatenate([d.exit for d in data]))
             inside = [d.inside for d in data]
             for q, d in enumerate(data):
                 objectives[q][~inside[q][:, ~d.replayed]] = np.nan

@@ -57,6 +57,18 @@ struct SceneDev {
     // and at every other tick neither source nor receiver, not ticked, not replayed and not summed.  NULL: no windows - everybody is
     // there from tick 0 to the scene's last, and the launch is the instance without a mask.
     const int32_t *win_enter, *win_exit;   // [R]
+    // Shared lanes (csf_scene_calib_load_shared), read by scene_lanes_kernel only.  The view of a scene has n = its
+    // LANES, slot = set * Lsum + lane_off[scene] + lane (Lsum: the lanes of all scenes; the table's views hold it), and a lane carries the riders of its chain one after the other: lane_first,
+    // then rider_next of the rider it carries, -1 ends the chain.  A chain holds riders of the lane's scene with a non-empty window,
+    // in entry order, the windows of two neighbours not overlapping; a rider that is never present is in no chain.  The image then
+    // also holds what was constant per slot while a slot had one rider and agent_body<.., FUSED = true> reads:
+    //   vdes, qbeg, qlen                               the desired speed and the rider's destination queue in Dev::q
+    const int32_t *lane_off;     // [n_scn + 1] first lane of every scene (NULL: the data set does not share lanes)
+    const int32_t *lane_first;   // [Lsum] rider (0 .. R - 1) a lane carries first, -1: nobody
+    const int32_t *rider_next;   // [R] who takes the lane over from this rider, -1: nobody
+    const double *img_vdes;
+    const int64_t *img_qbeg;
+    const int32_t *img_qlen;
 };
 
 // One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].

@@ -33,6 +33,12 @@
 // nothing ticks it - so s0 IS the state at the start of tick win_enter[r]; after its exit it keeps its last state.  A data set without
 // windows launches scene_eval_kernel<MODEL, false>, where all of this is compiled out.
 //
+// Rosters that share the lanes of their scene (csf_scene_calib_load_shared): scene_lanes_kernel.  The workgroup runs
+// the scene's LANES, and a lane carries the riders of its chain (csf_scene.h) one after the other: at the head of the tick its next
+// rider enters at, the lane writes the sums of the rider it carried and makes its slot the newcomer's fresh vehicle from the image -
+// SceneLaneHook::takeover, the restore of the launch's head once more.  Sums and samples stay per RIDER; a sample row is written
+// only at a tick its rider is present (the host has filled the rest with NaN).
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -48,6 +54,7 @@ namespace csf {
 template <int MODEL, bool WIN>
 struct SceneHook {
     static constexpr bool MASKED = WIN;
+    static constexpr bool SHARED = false;
     const SceneDev &c;
     const int64_t rider;          // set * R + first rider of the scene + lane: row of sums and of a sample
     const double *obj;            // objective of this lane's rider at tick 0
@@ -142,6 +149,7 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
     const int lane = (int)threadIdx.x, n = (int)d.n;
     const int64_t cap = d.cap, first = c.roff[scn];
     const int len = c.len[scn];
+    // (TWIN COPY: SceneLaneHook::seat below restores a lane's newcomer the same way)
     if (lane < n) {   // Vehicle.__init__ for this rider (vehicle.py:64-204, 1728-1736): see patch_kernel's spawn
         const int64_t a = lane, r = first + lane, ic = c.img_cap;
 #pragma unroll
@@ -180,13 +188,173 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
         while (hook.taken < c.n_samples) hook.sample(d, lane);
 }
 
+// behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment
+template <int MODEL>
+struct SceneLaneHook {
+    static constexpr bool MASKED = true;
+    static constexpr bool SHARED = true;
+    const SceneDev &c;
+    const int64_t row0;           // set * R: first row of the set in sums and in a sample
+    int cur = -1;                 // the rider this lane carries (0 .. R - 1), -1: nobody yet
+    int nxt = -1;                 // who takes over next, -1: nobody
+    int nxt_in = 0x7fffffff;      // ... and the tick it enters at
+    int t_in = 0, t_out = 0;      // the window of cur (nobody: never present)
+    const double *obj = nullptr;  // objective of cur at tick 0
+    const double *rep = nullptr;  // recorded (x, y, psi, v) of cur after tick 0; NULL: it is simulated
+    int wait;                     // ticks until the next sampled one
+    int taken = 0;                // sampled ticks so far
+    double sse = 0.0, sae = 0.0;
+    __device__ __forceinline__ SceneLaneHook(const SceneDev &c_, int64_t row0_) : c(c_), row0(row0_), wait(c_.stride - 1) {}
+    __device__ __forceinline__ void follower(int r) {
+        nxt = r;
+        nxt_in = r >= 0 ? c.win_enter[r] : 0x7fffffff;
+    }
+    // the lane's slot becomes rider r's fresh vehicle - Vehicle.__init__ as at the head of scene_eval_kernel, and what was constant
+    // per slot there - and the lane's registers become r's.  TWIN COPY: the restore at the head of scene_eval_kernel (above); an
+    // array added to the image goes into both.  (Kept apart so that scene_eval_kernel's instances come out of the compiler as they
+    // were: DESIGN.md 4.10e.)
+    __device__ __forceinline__ void seat(const Dev &d, int lane, int r) {
+        const int64_t a = lane, cap = d.cap, ic = c.img_cap;
+#pragma unroll
+        for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
+        d.ppsi[a] = c.img_ppsi[r];
+        d.ti[a] = c.img_ti[r];
+        d.status[a] = c.img_status[r];
+        d.ptr[a] = c.img_ptr[r];
+        d.znav[a] = c.img_znav[r];
+        d.hx[a] = c.img_hx0[r];
+        d.hy[a] = c.img_hy0[r];
+        const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
+        d.zrid[a] = v < d.p.v_max_walk ? 0 : 1;
+        d.dgood[a] = (-d.p.delta_max_walk < delta && d.p.delta_max_walk > delta) ? 1 : 0;
+        d.vdes[a] = c.img_vdes[r];
+        d.qbeg[a] = c.img_qbeg[r];
+        d.qlen[a] = c.img_qlen[r];
+        cur = r;
+        t_in = c.win_enter[r], t_out = c.win_exit[r];
+        obj = c.obj + (int64_t)r * c.n_feat;
+        const int rcol = c.rep != nullptr ? c.rep_index[r] : -1;
+        rep = rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr;
+        follower(c.rider_next[r]);
+    }
+    // the sums of the rider the lane has carried go to its row
+    __device__ __forceinline__ void flush() {
+        if (cur >= 0) c.sums[row0 + cur] = make_double2(sse, sae);
+        sse = sae = 0.0;
+    }
+    // head of tick t (csf_small_body.inc: HOOK::SHARED): no shuffle, no ballot, no barrier; stores to this lane's own slot and rows
+    __device__ __forceinline__ void takeover(const Dev &d, int t, int lane) {
+        while (nxt_in <= t) {
+            flush();
+            seat(d, lane, nxt);
+        }
+    }
+    __device__ __forceinline__ uint64_t present(int t) const { return __ballot(t_in <= t && t < t_out); }
+    __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
+        if (lane >= n) return;
+        const bool here = t_in <= t && t < t_out;
+        if (!here) {
+            // the lane is empty at this tick
+        } else if (rep != nullptr) {
+            // TWIN COPY of SceneHook::operator()'s replay branch (and the error branch below of its error branch): the lane's own
+            // stores behind its tick's.  A change there is made here too.
+            const double *r = rep + (int64_t)t * c.n_rep * 4;
+            const double x = r[0], y = r[1], psi = r[2], v = r[3];
+            const int64_t cap = d.cap;
+            d.s[lane] = x;
+            d.s[cap + lane] = y;
+            d.s[2 * cap + lane] = psi;
+            d.s[3 * cap + lane] = v;
+            if (MODEL == CSF_BALANCINGRIDER) {
+                const double twopi = 6.283185307179586476925286766559, own = d.lti[4 * cap + lane];
+                d.lti[4 * cap + lane] = -psi + twopi * nearbyint((own + psi) / twopi);
+            } else {
+                d.ppsi[lane] = psi;
+            }
+            const int64_t slot = d.ti[lane] & (d.hist_len - 1);
+            d.hx[slot * cap + lane] = x;
+            d.hy[slot * cap + lane] = y;
+        } else {
+            const double *o = obj + (int64_t)t * c.R * c.n_feat;
+            for (int k = 0; k < c.n_feat; k++) {
+                const int f = c.feat[k];
+                const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
+                const double e = sv - o[k];
+                sse += e * e;
+                sae += fabs(e);
+            }
+        }
+        if (c.states != nullptr) {
+            if (wait == 0) {
+                if (here) {
+                    double *smp = c.states + ((int64_t)taken * c.n_sets * c.R + row0 + cur) * d.ns;
+                    for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
+                }
+                taken++;
+                wait = c.stride;
+            }
+            wait--;
+        }
+    }
+};
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void scene_lanes_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
+    extern __shared__ float4 srv[];                           // as scene_eval_kernel
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * c.n_scn) return;
+    const int set = b / c.n_scn, scn = b - set * c.n_scn;
+    Dev d = table[b];
+    {
+        const SceneSet ss = sets[set];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;          // n: the scene's lanes
+    const int64_t row0 = (int64_t)set * c.R;
+    SceneLaneHook<MODEL> hook(c, row0);
+    // the first rider of every lane is seated here whenever it enters, as scene_eval_kernel restores everybody at its head: before
+    // its entry nothing ticks the slot.  A lane nobody ever rides keeps what it holds and is never present.
+    if (lane < n) {
+        const int r = c.lane_first[c.lane_off[scn] + lane];
+        if (r >= 0) hook.seat(d, lane, r);
+    }
+    small_tick_body<MODEL>(d, c.len[scn], nullptr, srv, 0u, 0, hook);
+    // riders that are never present are in no chain: their sums are (0, 0)
+    for (int r = c.roff[scn] + lane; r < c.roff[scn + 1]; r += WAVE)
+        if (c.win_enter[r] >= c.win_exit[r]) c.sums[row0 + r] = make_double2(0.0, 0.0);
+    // (a chain holds non-empty windows that end within the scene: every rider of it has been seated by the last tick)
+    if (lane < n) hook.flush();
+}
+
 void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st) {
     const int count = c.n_sets * c.n_scn;
     if (count <= 0) return;
     const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
+    const bool lanes = c.lane_off != nullptr;
 #define CSF_SCENE(MODEL)                                                                                                          \
     do {                                                                                                                          \
-        if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
+        if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
+        else if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
         else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
     } while (0)
     switch (model) {

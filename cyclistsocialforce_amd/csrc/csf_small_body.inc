@@ -13,8 +13,14 @@
 // (unchanged) state, takes part in every shuffle and barrier and calls the hook - the mask gates work, never the control flow
 // around a barrier or a shuffle.  With MASKED == false every use of the mask is compiled out (if constexpr) and the body is the one
 // it was before there was a mask.
+//
+// HOOK::SHARED (DESIGN.md 4.10e): a lane's slot takes several road users in turn.  hook.takeover(d, t, lane) is then called by all
+// 64 lanes at the head of tick t, before hook.present(t): a lane whose next occupant enters at t makes its slot that road user's
+// fresh vehicle.  The step holds no shuffle, ballot or barrier and stores to the lane's own slot only; what the other lanes read of
+// it they read afterwards, in program order - as they read the stores of the tick before.  With SHARED == false it is compiled out.
 struct NoTickHook {
     static constexpr bool MASKED = false;
+    static constexpr bool SHARED = false;
     __device__ __forceinline__ void operator()(const Dev &, int, int, int) {}
 };
 
@@ -77,6 +83,7 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         // user to tick (lane < n: i == lane, the receiver is the lane's own road user)
         uint64_t here = ~0ull;
         bool act = live, mine = lane < n;
+        if constexpr (HOOK::SHARED) hook.takeover(d, t, lane);
         if constexpr (HOOK::MASKED) {
             here = hook.present(t);
             act = live && ((here >> i) & 1ull) != 0;

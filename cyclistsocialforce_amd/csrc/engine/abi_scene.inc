@@ -42,46 +42,97 @@ struct SceneCalibState {
     // csf_scene_calib_windows: a presence window per rider (DESIGN.md 4.10d).  Empty buffers: no windows, and an evaluation is
     // handed win_enter == NULL - the kernel instance without a mask
     DevBuf<int32_t> win_enter, win_exit;     // [R]
+    // csf_scene_calib_load_shared: rosters that share the lanes of their scene (DESIGN.md 4.10e).  Lsum == 0: not shared - slot =
+    // set * R + rider.  Else slot = set * Lsum + lane_off[scene] + lane, the windows above came with the load, and the image holds
+    // what was constant per slot before: the desired speed and the destination queue of every rider
+    int32_t Lsum = 0;
+    std::vector<int32_t> h_nl;               // [n_scn] lanes of every scene
+    DevBuf<int32_t> lane_off, lane_first, rider_next, img_qlen;   // [n_scn + 1], [Lsum], [R], [R]
+    DevBuf<int64_t> img_qbeg;                // [R]
+    DevBuf<double> img_vdes;                 // [R]
 };
 
 }  // extern "C++"
 
-int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks, const double *s0, const double *v_desired,
-                         const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
-                         int32_t n_feat, const int32_t *feat, int32_t max_sets) try {
-    if (!e) return CSF_E_ARG;
-    if (!n_riders || !s0 || !v_desired || !dest_offsets || !dest_xyz_stop || !objective || !feat) return fail(e, CSF_E_ARG, "csf_scene_calib_load: NULL array");
+// csf_scene_calib_load (n_lanes == NULL) and csf_scene_calib_load_shared: `fn` names the call in the messages
+static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes, const int32_t *lane,
+                           const int32_t *enter, const int32_t *exit, int64_t n_ticks, const double *s0, const double *v_desired,
+                           const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
+                           int32_t n_feat, const int32_t *feat, int32_t max_sets) {
+    const bool sh = n_lanes != nullptr;
+    if (!n_riders || !s0 || !v_desired || !dest_offsets || !dest_xyz_stop || !objective || !feat) return fail(e, CSF_E_ARG, "%s: NULL array", fn);
+    if (sh && (!lane || !enter || !exit)) return fail(e, CSF_E_ARG, "%s: NULL array", fn);
     if (n_scn < 1 || n_scn > (1 << 20) || n_ticks < 1 || n_ticks > 2000000000 || n_feat < 1 || n_feat > CALIB_MAX_FEAT || max_sets < 1 || max_sets > 256)
-        return fail(e, CSF_E_ARG, "csf_scene_calib_load: 1 <= n_scn <= 2^20, 1 <= n_ticks <= 2e9, 1 <= n_feat <= %d, 1 <= max_sets <= 256", CALIB_MAX_FEAT);
-    if (e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine holds a closed-loop data set already (csf_scene_calib_clear first)");
-    if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine holds a calibration data set (csf_calib_clear first)");
-    if (!e->order.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine is not empty (%lld road users)", (long long)e->order.size());
-    if (e->batch) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine belongs to a batch (csf_batch_leave first)");
-    if (e->loopback) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine is a member of a loopback group");
-    if (e->world > 1 || e->nccl) return fail(e, CSF_E_STATE, "csf_scene_calib_load: a sharded engine holds no scenes");
-    if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has a road of its own (csf_set_road_vertices); the roads of scenes are given by csf_scene_calib_road");
-    if (e->d.hist != nullptr) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine records (csf_record / csf_enable_history); an evaluation writes its own samples");
-    if (e->classes.size() != 1) return fail(e, CSF_E_STATE, "csf_scene_calib_load: the engine has %d parameter sets; the candidates of an evaluation replace ONE", (int)e->classes.size());
-    if (e->d.p.model == CSF_UNCONTROLLED) return fail(e, CSF_E_ARG, "csf_scene_calib_load: an UncontrolledVehicle follows its trajectory whatever the field");
-    int64_t R64 = 0;
+        return fail(e, CSF_E_ARG, "%s: 1 <= n_scn <= 2^20, 1 <= n_ticks <= 2e9, 1 <= n_feat <= %d, 1 <= max_sets <= 256", fn, CALIB_MAX_FEAT);
+    if (e->scene_calib) return fail(e, CSF_E_STATE, "%s: the engine holds a closed-loop data set already (csf_scene_calib_clear first)", fn);
+    if (e->calib) return fail(e, CSF_E_STATE, "%s: the engine holds a calibration data set (csf_calib_clear first)", fn);
+    if (!e->order.empty()) return fail(e, CSF_E_STATE, "%s: the engine is not empty (%lld road users)", fn, (long long)e->order.size());
+    if (e->batch) return fail(e, CSF_E_STATE, "%s: the engine belongs to a batch (csf_batch_leave first)", fn);
+    if (e->loopback) return fail(e, CSF_E_STATE, "%s: the engine is a member of a loopback group", fn);
+    if (e->world > 1 || e->nccl) return fail(e, CSF_E_STATE, "%s: a sharded engine holds no scenes", fn);
+    if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "%s: the engine has a road of its own (csf_set_road_vertices); the roads of scenes are given by csf_scene_calib_road", fn);
+    if (e->d.hist != nullptr) return fail(e, CSF_E_STATE, "%s: the engine records (csf_record / csf_enable_history); an evaluation writes its own samples", fn);
+    if (e->classes.size() != 1) return fail(e, CSF_E_STATE, "%s: the engine has %d parameter sets; the candidates of an evaluation replace ONE", fn, (int)e->classes.size());
+    if (e->d.p.model == CSF_UNCONTROLLED) return fail(e, CSF_E_ARG, "%s: an UncontrolledVehicle follows its trajectory whatever the field", fn);
+    int64_t R64 = 0, L64 = 0;
     for (int32_t q = 0; q < n_scn; q++) {
-        if (n_riders[q] < 1 || n_riders[q] > SMALL_MAX) return fail(e, CSF_E_ARG, "csf_scene_calib_load: scene %d has %d road users (1 .. %d)", (int)q, (int)n_riders[q], SMALL_MAX);
+        // (a shared roster has no bound of its own: what is bounded is its lanes)
+        if (n_riders[q] < 1 || (!sh && n_riders[q] > SMALL_MAX)) return fail(e, CSF_E_ARG, "%s: scene %d has %d road users (1 .. %d)", fn, (int)q, (int)n_riders[q], SMALL_MAX);
+        if (sh && (n_lanes[q] < 1 || n_lanes[q] > SMALL_MAX)) return fail(e, CSF_E_ARG, "%s: scene %d has %d lanes (1 .. %d)", fn, (int)q, (int)n_lanes[q], SMALL_MAX);
         R64 += n_riders[q];
+        L64 += sh ? n_lanes[q] : 0;
     }
-    const int64_t n = (int64_t)max_sets * R64;
-    if (n > e->cap_user) return fail(e, CSF_E_CAPACITY, "csf_scene_calib_load: max_sets x riders = %lld road users, capacity %lld", (long long)n, (long long)e->cap_user);
-    const int32_t R = (int32_t)R64;
+    if (sh && R64 > (1 << 24)) return fail(e, CSF_E_ARG, "%s: %lld road users in all (at most 2^24)", fn, (long long)R64);
+    // the slots: max_sets x R without shared lanes.  With them the engine holds every rider once - the fresh vehicles the image is
+    // taken from, and their queues, which stay where they are - and max_sets x Lsum slots are run: the larger of the two
+    const int64_t n = sh ? std::max(R64, (int64_t)max_sets * L64) : (int64_t)max_sets * R64;
+    if (n > e->cap_user) {
+        if (sh) return fail(e, CSF_E_CAPACITY, "%s: max(riders, max_sets x lanes) = %lld road users, capacity %lld", fn, (long long)n, (long long)e->cap_user);
+        return fail(e, CSF_E_CAPACITY, "%s: max_sets x riders = %lld road users, capacity %lld", fn, (long long)n, (long long)e->cap_user);
+    }
+    const int32_t R = (int32_t)R64, Lsum = (int32_t)L64;
     for (int32_t q = 0; lengths && q < n_scn; q++)
-        if (lengths[q] < 0 || lengths[q] > n_ticks) return fail(e, CSF_E_ARG, "csf_scene_calib_load: lengths[%d] = %d outside 0 .. %lld", (int)q, (int)lengths[q], (long long)n_ticks);
+        if (lengths[q] < 0 || lengths[q] > n_ticks) return fail(e, CSF_E_ARG, "%s: lengths[%d] = %d outside 0 .. %lld", fn, (int)q, (int)lengths[q], (long long)n_ticks);
     for (int32_t k = 0; k < n_feat; k++)
-        if (feat[k] < 0 || feat[k] >= CALIB_MAX_FEAT) return fail(e, CSF_E_ARG, "csf_scene_calib_load: feature %d names no row of vehicle.traj (0 .. %d)", (int)feat[k], CALIB_MAX_FEAT - 1);
+        if (feat[k] < 0 || feat[k] >= CALIB_MAX_FEAT) return fail(e, CSF_E_ARG, "%s: feature %d names no row of vehicle.traj (0 .. %d)", fn, (int)feat[k], CALIB_MAX_FEAT - 1);
     for (int32_t r = 0; r < R; r++) {
         const int64_t rows = dest_offsets[r + 1] - dest_offsets[r];
-        if (dest_offsets[r] < 0 || rows < 1 || rows > MAX_QUEUE_ROWS) return fail(e, CSF_E_ARG, "csf_scene_calib_load: the destination queue of rider %d has %lld rows (1 .. %lld)", (int)r, (long long)rows, (long long)MAX_QUEUE_ROWS);
+        if (dest_offsets[r] < 0 || rows < 1 || rows > MAX_QUEUE_ROWS) return fail(e, CSF_E_ARG, "%s: the destination queue of rider %d has %lld rows (1 .. %lld)", fn, (int)r, (long long)rows, (long long)MAX_QUEUE_ROWS);
+    }
+    // shared lanes: every rider's lane and window, and the occupants of a lane one after the other.  The chain of a lane holds its
+    // riders with a non-empty window in entry order; a rider that is never present sits on no lane (its lane is checked all the same)
+    std::vector<int32_t> lo, lfirst, rnext;
+    if (sh) {
+        lo.assign((size_t)n_scn + 1, 0), lfirst.assign((size_t)Lsum, -1), rnext.assign((size_t)R, -1);
+        std::vector<int32_t> idx;
+        for (int32_t q = 0, r0 = 0; q < n_scn; r0 += n_riders[q], q++) {
+            lo[(size_t)q + 1] = lo[(size_t)q] + n_lanes[q];
+            const int32_t ticks = lengths ? lengths[q] : (int32_t)n_ticks;
+            idx.clear();
+            for (int32_t r = r0; r < r0 + n_riders[q]; r++) {
+                if (lane[r] < 0 || lane[r] >= n_lanes[q]) return fail(e, CSF_E_ARG, "%s: rider %d is on lane %d, scene %d has %d lanes", fn, (int)r, (int)lane[r], (int)q, (int)n_lanes[q]);
+                if (enter[r] < 0 || enter[r] > exit[r] || exit[r] > ticks)
+                    return fail(e, CSF_E_ARG, "%s: rider %d has the window [%d, %d), scene %d has %d ticks (0 <= enter <= exit <= ticks)", fn, (int)r, (int)enter[r], (int)exit[r], (int)q, (int)ticks);
+                if (enter[r] < exit[r]) idx.push_back(r);
+            }
+            std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return lane[a] != lane[b] ? lane[a] < lane[b] : enter[a] < enter[b]; });
+            for (size_t i = 0; i < idx.size(); i++) {
+                const int32_t r = idx[i];
+                if (i > 0 && lane[idx[i - 1]] == lane[r]) {
+                    const int32_t before = idx[i - 1];
+                    if (exit[before] > enter[r])
+                        return fail(e, CSF_E_ARG, "%s: riders %d [%d, %d) and %d [%d, %d) overlap on lane %d of scene %d", fn, (int)before, (int)enter[before], (int)exit[before], (int)r, (int)enter[r], (int)exit[r], (int)lane[r], (int)q);
+                    rnext[(size_t)before] = r;
+                } else {
+                    lfirst[(size_t)lo[(size_t)q] + (size_t)lane[r]] = r;
+                }
+            }
+        }
     }
     HIPCHK(e, hipSetDevice(e->device));
     // everything that can fail first: a refused call changes nothing
     auto cs = std::make_shared<SceneCalibState>();
+    cs->Lsum = Lsum;
     cs->n_scn = n_scn, cs->n_feat = n_feat, cs->max_sets = max_sets, cs->n_ticks = n_ticks, cs->R = R;
     for (int32_t k = 0; k < n_feat; k++) cs->feat[k] = feat[k];
     const size_t Rs = (size_t)R, tn = (size_t)n_ticks * Rs * (size_t)n_feat, views = (size_t)max_sets * (size_t)n_scn;
@@ -101,26 +152,57 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
     if (r == hipSuccess) r = cs->table.alloc(views);
     if (r == hipSuccess) r = cs->sets.alloc((size_t)max_sets);
     if (r == hipSuccess) r = cs->sets_pin.alloc((size_t)max_sets);
-    if (r == hipSuccess) r = cs->sums.alloc((size_t)n);
-    if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_load: no memory for the data set: %s", hipGetErrorString(r));
+    if (r == hipSuccess) r = cs->sums.alloc((size_t)max_sets * Rs);
+    if (sh) {
+        if (r == hipSuccess) r = cs->lane_off.alloc((size_t)n_scn + 1);
+        if (r == hipSuccess) r = cs->lane_first.alloc((size_t)Lsum);
+        if (r == hipSuccess) r = cs->rider_next.alloc(Rs);
+        if (r == hipSuccess) r = cs->win_enter.alloc(Rs);
+        if (r == hipSuccess) r = cs->win_exit.alloc(Rs);
+        if (r == hipSuccess) r = cs->img_vdes.alloc(Rs);
+        if (r == hipSuccess) r = cs->img_qbeg.alloc(Rs);
+        if (r == hipSuccess) r = cs->img_qlen.alloc(Rs);
+    }
+    if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "%s: no memory for the data set: %s", fn, hipGetErrorString(r));
     std::memset(cs->sets_pin.p, 0, (size_t)max_sets * sizeof(SceneSet));
     std::vector<int32_t> ls((size_t)n_scn), ro((size_t)n_scn + 1, 0);
     for (int32_t q = 0; q < n_scn; q++) ls[(size_t)q] = lengths ? lengths[q] : (int32_t)n_ticks, ro[(size_t)q + 1] = ro[(size_t)q] + n_riders[q];
     HIPCHK(e, hipMemcpy(cs->obj.p, objective, tn * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(cs->len.p, ls.data(), ls.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(cs->roff.p, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (sh) {
+        HIPCHK(e, hipMemcpy(cs->lane_off.p, lo.data(), lo.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(cs->lane_first.p, lfirst.data(), lfirst.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(cs->rider_next.p, rnext.data(), rnext.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(cs->win_enter.p, enter, Rs * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(cs->win_exit.p, exit, Rs * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
     // the max_sets x R vehicles, slot set * R + rider: every set starts every scene from the scene's start states, with its queues
     const int ns = e->d.ns;
     const int64_t q0 = dest_offsets[0], q_rows = dest_offsets[R] - q0;
-    std::vector<double> s_all((size_t)n * (size_t)ns), vd((size_t)n), rows_all((size_t)max_sets * (size_t)q_rows * 3);
+    // (shared lanes: the R riders once, then copies of rider 0 with the first row of its queue up to the slots that are run)
+    const int64_t q_all = sh ? q_rows + (n - R) : (int64_t)max_sets * q_rows;
+    std::vector<double> s_all((size_t)n * (size_t)ns), vd((size_t)n), rows_all((size_t)q_all * 3);
     std::vector<int64_t> off_all((size_t)n + 1);
-    for (int32_t k = 0; k < max_sets; k++) {
+    if (sh) {
+        std::memcpy(s_all.data(), s0, Rs * (size_t)ns * sizeof(double));
+        std::memcpy(vd.data(), v_desired, Rs * sizeof(double));
+        std::memcpy(rows_all.data(), dest_xyz_stop + 3 * q0, (size_t)q_rows * 3 * sizeof(double));
+        for (int32_t i = 0; i < R; i++) off_all[(size_t)i] = dest_offsets[i] - q0;
+        for (int64_t i = R; i < n; i++) {
+            std::memcpy(&s_all[(size_t)i * (size_t)ns], s0, (size_t)ns * sizeof(double));
+            vd[(size_t)i] = v_desired[0];
+            std::memcpy(&rows_all[(size_t)(q_rows + (i - R)) * 3], dest_xyz_stop + 3 * dest_offsets[0], 3 * sizeof(double));
+            off_all[(size_t)i] = q_rows + (i - R);
+        }
+    }
+    for (int32_t k = 0; !sh && k < max_sets; k++) {
         std::memcpy(&s_all[(size_t)k * Rs * (size_t)ns], s0, Rs * (size_t)ns * sizeof(double));
         std::memcpy(&vd[(size_t)k * Rs], v_desired, Rs * sizeof(double));
         std::memcpy(&rows_all[(size_t)k * (size_t)q_rows * 3], dest_xyz_stop + 3 * q0, (size_t)q_rows * 3 * sizeof(double));
         for (int32_t i = 0; i < R; i++) off_all[(size_t)k * Rs + (size_t)i] = (int64_t)k * q_rows + (dest_offsets[i] - q0);
     }
-    off_all[(size_t)n] = (int64_t)max_sets * q_rows;
+    off_all[(size_t)n] = q_all;
     int rc = add_agents_impl(e, n, s_all.data(), vd.data(), off_all.data(), rows_all.data());
     auto undo = [&](int code) {       // (the engine was empty: what has been added goes again)
         std::vector<int32_t> all((size_t)e->order.size());
@@ -146,7 +228,12 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
     if (c == hipSuccess) c = hipMemcpy(cs->img_ptr.p, e->ptr.p, Rs * sizeof(int32_t), hipMemcpyDeviceToDevice);
     if (c == hipSuccess) c = hipMemcpy(cs->img_status.p, e->status.p, Rs * sizeof(uint32_t), hipMemcpyDeviceToDevice);
     if (c == hipSuccess) c = hipMemcpy(cs->img_znav.p, e->znav.p, Rs, hipMemcpyDeviceToDevice);
-    if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "csf_scene_calib_load: the reset image: %s", hipGetErrorString(c)));
+    if (sh) {   // what a slot kept for good while it had one rider
+        if (c == hipSuccess) c = hipMemcpy(cs->img_vdes.p, e->vdes.p, Rs * sizeof(double), hipMemcpyDeviceToDevice);
+        if (c == hipSuccess) c = hipMemcpy(cs->img_qbeg.p, e->qbeg.p, Rs * sizeof(int64_t), hipMemcpyDeviceToDevice);
+        if (c == hipSuccess) c = hipMemcpy(cs->img_qlen.p, e->qlen.p, Rs * sizeof(int32_t), hipMemcpyDeviceToDevice);
+    }
+    if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "%s: the reset image: %s", fn, hipGetErrorString(c)));
     // the views: the engine's Dev with every per-slot array shifted to the block of (set, scene) and the population the scene's.  What
     // the one-wave tick does not touch - the binned order, the exchange records, the rings of a recording - is switched off.
     {
@@ -155,8 +242,8 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
         for (int32_t k = 0; k < max_sets; k++)
             for (int32_t q = 0; q < n_scn; q++) {
                 Dev &v = tab[(size_t)k * (size_t)n_scn + (size_t)q];
-                const int64_t b = (int64_t)k * R + ro[(size_t)q];
-                v.n = v.n_live = v.hi = n_riders[q];
+                const int64_t b = sh ? (int64_t)k * Lsum + lo[(size_t)q] : (int64_t)k * R + ro[(size_t)q];
+                v.n = v.n_live = v.hi = sh ? n_lanes[q] : n_riders[q];
                 v.lo = 0;
                 v.n_classes = 1;
                 v.s = d0.s + b, v.vdes = d0.vdes + b, v.qbeg = d0.qbeg + b, v.qlen = d0.qlen + b, v.ptr = d0.ptr + b, v.znav = d0.znav + b;
@@ -177,7 +264,7 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
             }
         c = hipMemcpy(cs->table.p, tab.data(), views * sizeof(Dev), hipMemcpyHostToDevice);
         if (c == hipSuccess) c = hipDeviceSynchronize();
-        if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "csf_scene_calib_load: the table of views: %s", hipGetErrorString(c)));
+        if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "%s: the table of views: %s", fn, hipGetErrorString(c)));
         double cb = 0.0;
         for (int32_t i = 0; i < R; i++) cb = std::max({cb, std::fabs(s0[(size_t)i * ns] - d0.ox), std::fabs(s0[(size_t)i * ns + 1] - d0.oy)});
         cs->coord_bound = cb;
@@ -196,8 +283,27 @@ int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, 
         cs->h_table = std::move(tab);
     }
     cs->h_len = std::move(ls), cs->h_roff = std::move(ro);
+    if (sh) cs->h_nl.assign(n_lanes, n_lanes + n_scn);
     e->scene_calib = std::move(cs);
     return CSF_OK;
+}
+
+int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks, const double *s0, const double *v_desired,
+                         const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
+                         int32_t n_feat, const int32_t *feat, int32_t max_sets) try {
+    if (!e) return CSF_E_ARG;
+    return scene_load_impl(e, "csf_scene_calib_load", n_scn, n_riders, nullptr, nullptr, nullptr, nullptr, n_ticks, s0, v_desired, dest_offsets,
+                           dest_xyz_stop, lengths, objective, n_feat, feat, max_sets);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_load_shared(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes, const int32_t *lane,
+                                const int32_t *enter, const int32_t *exit, int64_t n_ticks, const double *s0, const double *v_desired,
+                                const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
+                                int32_t n_feat, const int32_t *feat, int32_t max_sets) try {
+    if (!e) return CSF_E_ARG;
+    if (!n_lanes) return fail(e, CSF_E_ARG, "csf_scene_calib_load_shared: NULL array");
+    return scene_load_impl(e, "csf_scene_calib_load_shared", n_scn, n_riders, n_lanes, lane, enter, exit, n_ticks, s0, v_desired, dest_offsets,
+                           dest_xyz_stop, lengths, objective, n_feat, feat, max_sets);
 } catch (...) { return csf_caught(e); }
 
 int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version, double *sums_out,
@@ -300,6 +406,12 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
     c.road_lds = (uint32_t)cs.road_max_pad * (uint32_t)sizeof(float4);
     c.win_enter = cs.win_enter.n > 0 ? cs.win_enter.p : nullptr;
     c.win_exit = cs.win_exit.n > 0 ? cs.win_exit.p : nullptr;
+    if (cs.Lsum > 0) {
+        c.lane_off = cs.lane_off.p, c.lane_first = cs.lane_first.p, c.rider_next = cs.rider_next.p;
+        c.img_vdes = cs.img_vdes.p, c.img_qbeg = cs.img_qbeg.p, c.img_qlen = cs.img_qlen.p;
+        // a lane writes the sample rows of the rider it carries at the ticks that rider is present: every other row is NaN
+        if (n_states > 0) HIPCHK(e, hipMemsetAsync(cs.states.p, 0xff, n_states * sizeof(double), e->main));
+    }
     HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
     HIPCHK(e, hipGetLastError());
@@ -357,7 +469,8 @@ int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_sce
                         return fail(e, CSF_E_ARG, "csf_scene_calib_road: the road of scene %d has more than %d vertices", (int)q, SMALL_ROAD_MAX);
                 }
             nv[q] = (int64_t)road.size() / 4;
-            const int64_t nv_pad = (nv[q] + 63) / 64 * 64, n = cs.h_roff[q + 1] - cs.h_roff[q];
+            // (shared lanes: the one-wave tick runs the scene's lanes, not its roster)
+            const int64_t nv_pad = (nv[q] + 63) / 64 * 64, n = cs.Lsum > 0 ? cs.h_nl[q] : cs.h_roff[q + 1] - cs.h_roff[q];
             int64_t P = 1;
             while (P < n) P <<= 1;
             if (nv_pad * P > 256 * WAVE)
@@ -458,6 +571,7 @@ int csf_scene_calib_windows(csf_engine *e, const int32_t *enter, const int32_t *
         return fail(e, CSF_E_STATE, "csf_scene_calib_windows: no closed-loop data set (csf_scene_calib_load first)");
     }
     SceneCalibState &cs = *e->scene_calib;
+    if (cs.Lsum > 0) return fail(e, CSF_E_STATE, "csf_scene_calib_windows: the data set shares its lanes: the windows came with csf_scene_calib_load_shared and decide who sits where");
     if ((enter == nullptr) != (exit == nullptr)) return fail(e, CSF_E_ARG, "csf_scene_calib_windows: enter and exit are given together or not at all");
     const int32_t R = cs.R;
     for (int32_t q = 0; enter && q < cs.n_scn; q++)

@@ -261,11 +261,8 @@ class Engine:
         return int(n.value)
 
     # -- calibration on closed-loop scenes (include/csf.h: csf_scene_calib_load ...; calibration.InteractionCalibration drives it) --
-    def scene_calib_load(self, n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths=None, max_sets=256):
-        """Make this EMPTY engine hold a data set of closed-loop scenes: n_riders [n_scn] road users per scene (1 .. 32, R their
-        sum), start states s0 [R, >= n_states], v_desired [R] (or a scalar), the riders' destination queues in CSR form
-        (dest_offsets [R + 1], dest_xyz_stop [rows, 3]), the objective [T, R, n_feat] and the rows of vehicle.traj (0 .. 5) its
-        columns are compared with; lengths [n_scn]: ticks of every scene (default: T).  capacity >= max_sets * R."""
+    def _scene_arrays(self, n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths):
+        """the arguments the two scene loads share, checked and made contiguous: (nr, R, s0, vd, off, xyz, obj, feat, T, lengths)"""
         nr = np.ascontiguousarray(n_riders, dtype=np.int32).reshape(-1)
         if nr.size < 1:
             raise ValueError("n_riders must name at least one scene")
@@ -283,12 +280,38 @@ class Engine:
         obj = _f64(objective)
         if obj.ndim != 3 or obj.shape[1:] != (R, feat.size) or obj.shape[0] < 1:
             raise ValueError("objective must be [n_ticks, sum(n_riders), n_feat]")
-        T = obj.shape[0]
         ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
         if ln is not None and ln.shape != (nr.size,):
             raise ValueError("lengths must have one entry per scene")
+        return nr, R, s0, vd, off, xyz, obj, feat, obj.shape[0], ln
+
+    def scene_calib_load(self, n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths=None, max_sets=256):
+        """Make this EMPTY engine hold a data set of closed-loop scenes: n_riders [n_scn] road users per scene (1 .. 32, R their
+        sum), start states s0 [R, >= n_states], v_desired [R] (or a scalar), the riders' destination queues in CSR form
+        (dest_offsets [R + 1], dest_xyz_stop [rows, 3]), the objective [T, R, n_feat] and the rows of vehicle.traj (0 .. 5) its
+        columns are compared with; lengths [n_scn]: ticks of every scene (default: T).  capacity >= max_sets * R."""
+        nr, R, s0, vd, off, xyz, obj, feat, T, ln = self._scene_arrays(n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths)
         self._ck(self._lib.csf_scene_calib_load(self._h, nr.size, _ptr(nr), T, _ptr(s0), _ptr(vd), _ptr(off), _ptr(xyz),
                                                 None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat), int(max_sets)))
+        self._scene_calib = (R, T)
+
+    def scene_calib_load_shared(self, n_riders, n_lanes, lane, enter, exit, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat,
+                                lengths=None, max_sets=256):
+        """scene_calib_load for scenes whose riders SHARE LANES: n_riders [n_scn] is the roster of every scene (>= 1, no upper bound, R
+        their sum), n_lanes [n_scn] its lanes (1 .. 32), and per rider lane [R] (0 .. n_lanes - 1 of its scene) and the presence
+        window enter [R], exit [R] (0 <= enter <= exit <= the length of the scene).  Riders of one lane take turns: their non-empty
+        windows do not overlap.  Sums and states stay per RIDER; a row of the states is NaN wherever its rider is not present.
+        capacity >= max(R, max_sets * sum(n_lanes)).  scene_calib_windows is refused on such a data set."""
+        nr, R, s0, vd, off, xyz, obj, feat, T, ln = self._scene_arrays(n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths)
+        nl = np.ascontiguousarray(n_lanes, dtype=np.int32).reshape(-1)
+        if nl.shape != nr.shape:
+            raise ValueError("n_lanes has one entry per scene")
+        ln_, en, ex = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (lane, enter, exit))
+        if ln_.shape != (R,) or en.shape != (R,) or ex.shape != (R,):
+            raise ValueError("lane, enter and exit must have one entry per rider of the data set")
+        self._ck(self._lib.csf_scene_calib_load_shared(self._h, nr.size, _ptr(nr), _ptr(nl), _ptr(ln_), _ptr(en), _ptr(ex), T, _ptr(s0), _ptr(vd),
+                                                       _ptr(off), _ptr(xyz), None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat),
+                                                       int(max_sets)))
         self._scene_calib = (R, T)
 
     def scene_calib_eval(self, pods, states=False, stride=1, road_F0=None, road_sigma=None):

@@ -524,7 +524,28 @@ int csf_calib_clear(csf_engine *e);
  * evaluations are again what they are without them, bit for bit; with windows every evaluation is still ONE launch.  The call is
  * independent of csf_scene_calib_replay and csf_scene_calib_road and of their order.  Refused with the held windows unchanged: CSF_E_STATE
  * without a closed-loop data set (the data set of csf_calib_load included); CSF_E_ARG for one array without the other or a bound outside
- * that range.  csf_scene_calib_clear frees the windows with the rest. */
+ * that range.  csf_scene_calib_clear frees the windows with the rest.
+ *
+ * csf_scene_calib_load_shared is csf_scene_calib_load for scenes whose ROSTER may exceed 32 road users as long as
+ * at most 32 are present at a tick: n_riders[q] >= 1 without an upper bound of its own (R <= 2^24 in all), 1 <= n_lanes[q] <= 32 lanes of the one-wave tick, and per
+ * rider its lane [R] (0 .. n_lanes - 1 of its scene) and its presence window enter [R], exit [R] as csf_scene_calib_windows takes them.
+ * Riders of one lane take turns on it: the non-empty windows of two of them do not overlap (exit == enter of the next is a handover
+ * without an idle tick: at that tick the first is gone and the second is the fresh vehicle).  A rider with enter == exit is never
+ * present whatever its lane.  Every evaluation is still ONE launch; sums_out stays [n_sets][R][2] and states_out [samples][n_sets x R]
+ * [n_states], both per RIDER: a row of states_out is written only at a sampled tick its rider is present at, every other row of it is
+ * NaN, and a rider that is never present has the sums (0, 0).  The engine holds every rider once, the fresh vehicles the reset image
+ * is taken from, and runs max_sets x sum(n_lanes) slots: its capacity must be >= max(R, max_sets x sum(n_lanes)).  The field-of-view
+ * bands are sized from the starts of all R riders.  csf_scene_calib_replay (replayed [R]), csf_scene_calib_road (the vertex limit
+ * is that of the scene's LANES), both evaluation calls, csf_scene_calib_launches and csf_scene_calib_clear work as on any data set;
+ * csf_scene_calib_windows is refused with CSF_E_STATE, because the windows belong to the load.  Refused with the engine empty and
+ * usable: everything csf_scene_calib_load refuses, and CSF_E_ARG for a lane count or a lane out of range, a window outside 0 <= enter
+ * <= exit <= the length of the scene, or two riders of one lane whose non-empty windows overlap. */
+int csf_scene_calib_load_shared(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes,
+                                const int32_t *lane, const int32_t *enter, const int32_t *exit, int64_t n_ticks,
+                                const double *s0, const double *v_desired,
+                                const int64_t *dest_offsets, const double *dest_xyz_stop,
+                                const int32_t *lengths, const double *objective,
+                                int32_t n_feat, const int32_t *feat, int32_t max_sets);
 int csf_scene_calib_load(csf_engine *e, int32_t n_scn, const int32_t *n_riders, int64_t n_ticks,
                          const double *s0, const double *v_desired,
                          const int64_t *dest_offsets, const double *dest_xyz_stop,

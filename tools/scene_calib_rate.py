@@ -24,8 +24,14 @@ same evaluation with road_F0 / road_sigma per candidate set (csf_scene_calib_eva
 --replay leg.  (`--windows` was taken: it is the number of timing windows.)  The baseline has no leg for it - riders that come and go
 would be add_agents / remove_agents between 1-tick calls of every engine.
 
+--presence --share adds a cell of its own: the same number of scenes with a roster of --share-roster riders each (it fits
+32) of whom --share-peak are present at a time - rider r of a scene is there for ticks x peak / roster ticks from tick r x ticks /
+roster on - loaded twice on the SAME library: by csf_scene_calib_load + csf_scene_calib_windows (`unpacked_ms`, P = the power of two
+that holds the roster) and by csf_scene_calib_load_shared on SceneData.lanes() (`packed_ms`, P = the one that holds the peak).  The
+two legs alternate window by window after one warm-up call each; `packed_rel_gap` is the largest relative difference of their errors.
+
     python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
-                                     [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence]
+                                     [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
 """
 import argparse
 import json
@@ -80,7 +86,12 @@ def main():
     ap.add_argument("--road", action="store_true")
     ap.add_argument("--road-verts", type=int, default=200)
     ap.add_argument("--presence", action="store_true")
+    ap.add_argument("--share", action="store_true")
+    ap.add_argument("--share-roster", type=int, default=20)
+    ap.add_argument("--share-peak", type=int, default=6)
     a = ap.parse_args()
+    if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
+        ap.error("--share goes with --presence and 1 <= --share-peak <= --share-roster <= 32")
     feat = np.array([0, 1], dtype=np.int32)
     if a.out:
         open(a.out, "w").close()
@@ -183,6 +194,35 @@ def main():
                 e.scene_calib_windows(None, None)
                 line["timing_windows"] = line.pop("windows")     # (in these lines "windows" would read as the presence windows)
                 line.update(present_share=float(span.sum() / (a.ticks * R)), presence_ms=dict(median=float(np.median(t_win)), min=min(t_win), max=max(t_win)))
+            if a.share:
+                from cyclistsocialforce_amd.calibration import SceneData
+                ro, pk = a.share_roster, a.share_peak
+                big = [scene(model, ro, 150 + q, box=22.0) for q in range(a.scenes)]
+                en1 = (np.arange(ro) * a.ticks // ro).astype(np.int32)
+                ex1 = np.minimum(en1 + a.ticks * pk // ro, a.ticks).astype(np.int32)
+                lane1, nl1 = SceneData(big[0][0], 5.0, big[0][1], big[0][2], np.zeros((a.ticks, ro, 4)), present=(en1, ex1)).lanes()
+                nrb, Rb = np.full(a.scenes, ro, dtype=np.int32), ro * a.scenes
+                sb, rb = np.concatenate([x[0] for x in big]), np.concatenate([x[2] for x in big])
+                ob = np.arange(Rb + 1) * 5
+                objb = np.random.default_rng(2).normal(size=(a.ticks, Rb, feat.size))
+                enb, exb = np.tile(en1, a.scenes), np.tile(ex1, a.scenes)
+                plain = Engine(base, n_sets * Rb)
+                plain.scene_calib_load(nrb, sb, 5.0, ob, rb, objb, feat, max_sets=n_sets)
+                plain.scene_calib_windows(enb, exb)
+                packed = Engine(base, max(Rb, n_sets * nl1 * a.scenes))
+                packed.scene_calib_load_shared(nrb, np.full(a.scenes, nl1, dtype=np.int32), np.tile(lane1, a.scenes), enb, exb, sb, 5.0, ob, rb, objb,
+                                               feat, max_sets=n_sets)
+                legs = [lambda: plain.scene_calib_eval(sets)[:, :, 0].sum(axis=1), lambda: packed.scene_calib_eval(sets)[:, :, 0].sum(axis=1)]
+                first = [leg() for leg in legs]
+                t_leg = [[], []]
+                for _ in range(a.windows):
+                    for k, leg in enumerate(legs):
+                        t0 = time.perf_counter(); leg(); t_leg[k].append((time.perf_counter() - t0) * 1e3)
+                line.update(share=dict(roster=ro, peak=pk, lanes=int(nl1), riders=Rb, packed_rel_gap=float(np.abs(first[1] / first[0] - 1.0).max()),
+                                       unpacked_ms=dict(median=float(np.median(t_leg[0])), min=min(t_leg[0]), max=max(t_leg[0])),
+                                       packed_ms=dict(median=float(np.median(t_leg[1])), min=min(t_leg[1]), max=max(t_leg[1]))))
+                plain.close()
+                packed.close()
             if a.replay:
                 if rec is None:                                  # the recording: the scenes' own run with the base set
                     rec = e.scene_calib_eval([base], states=True)[1][:, :R]
