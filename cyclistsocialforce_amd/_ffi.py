@@ -38,6 +38,7 @@ SYMBOLS = (
     "csf_scene_calib_road", "csf_scene_calib_eval_road",
     "csf_scene_calib_windows",
     "csf_scene_calib_load_shared",
+    "csf_scene_calib_load_wide",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -200,6 +201,8 @@ def load():
         L.csf_scene_calib_windows.argtypes = [vp, vp, vp]
     if hasattr(L, "csf_scene_calib_load_shared"):   # (the same)
         L.csf_scene_calib_load_shared.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, dp, dp, vp, dp, vp, dp, i32, vp, i32]
+    if hasattr(L, "csf_scene_calib_load_wide"):     # (the same)
+        L.csf_scene_calib_load_wide.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, dp, dp, vp, dp, vp, dp, i32, vp, i32, i32]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

@@ -437,13 +437,25 @@ class SceneData:
 
     A roster above 32 needs `present`, and at no tick more than 32 road users whose window holds it (ValueError names the tick and the
     count; a road user with an empty window counts for nothing).  Such a scene runs on `lanes()`: road users whose windows do not
-    overlap take turns on one lane of the one-wave tick.  Its road limit is that of the power of two that holds its LANES."""
+    overlap take turns on one lane of the one-wave tick.  Its road limit is that of the power of two that holds its LANES.
+
+    wide=True lifts the bound to 256 road users AT ONCE (`Engine.scene_calib_load_wide`: one workgroup of 256 threads ticks such a scene).
+    A roster above 32 then needs no `present` - without windows `lanes()` gives lane = index -, the ValueError names tick and count
+    against 256, and the road limit is that of P = 64, 128 or 256, the power of two that holds its lanes and at least 64: 256, 128 or
+    64 vertices (padded to a multiple of 64), whichever kernel the scene ends up on.  With the default wide=False nothing changes."""
 
     ROAD_MAX_VERTS = 2048
 
-    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None):
+    WIDE_MAX = 256
+
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None, wide=False):
         self.s0 = np.asarray(s0, dtype=float)
-        if self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > 32 and present is None):
+        self.wide = bool(wide)
+        if self.wide:
+            if self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > self.WIDE_MAX and present is None):
+                raise ValueError(f"a wide scene has 1 .. {self.WIDE_MAX} road users, or more with presence windows that keep at most "
+                                 f"{self.WIDE_MAX} at once: s0 is [n, >= 4]")
+        elif self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > 32 and present is None):
             raise ValueError("a scene has 1 .. 32 road users, or more with presence windows that keep at most 32 at once: s0 is [n, >= 4]")
         n = self.s0.shape[0]
         try:
@@ -489,10 +501,11 @@ class SceneData:
                 raise ValueError("present: 0 <= enter <= exit <= length for every road user")
             self.enter, self.exit = enter.astype(np.int32), exit_.astype(np.int32)
         self.windowed = bool(np.any(self.enter != 0) or np.any(self.exit != self.length))
-        if n > 32:
+        most = self.WIDE_MAX if self.wide else 32
+        if n > most:
             count = self.inside.sum(axis=1) if self.length else np.zeros(1, dtype=int)
-            if count.max() > 32:
-                raise ValueError(f"present: {int(count.max())} road users are in the scene at tick {int(count.argmax())}; at most 32 at once")
+            if count.max() > most:
+                raise ValueError(f"present: {int(count.max())} road users are in the scene at tick {int(count.argmax())}; at most {most} at once")
         if self.replayed.any():
             if self.traj.shape[2] < 4:
                 raise ValueError("a replayed road user needs (x, y, psi, v): traj has fewer than 4 columns")
@@ -503,10 +516,15 @@ class SceneData:
             if not finite:
                 raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over the rows of its window "
                                  "(all `length` rows without one)")
-        self.road = None if road is None else self._checked_road(road, n if n <= 32 else self.lanes()[1])
+        if road is None:
+            self.road = None
+        elif self.wide:                                           # (the workgroup's P: never below a wave)
+            self.road = self._checked_road(road, n if n <= 32 else self.lanes()[1], p_min=64)
+        else:
+            self.road = self._checked_road(road, n if n <= 32 else self.lanes()[1])
 
     @classmethod
-    def _checked_road(cls, road, n):
+    def _checked_road(cls, road, n, p_min=1):
         try:
             roff, verts, F0, sigma = road
         except (TypeError, ValueError):
@@ -525,7 +543,7 @@ class SceneData:
         if not (np.isfinite(used).all() and np.isfinite(F0).all() and np.isfinite(sigma).all()):
             raise ValueError("road: vertices, F0 and sigma must be finite")
         nv = used.shape[0]
-        P = 1
+        P = p_min
         while P < n:
             P *= 2
         if nv > cls.ROAD_MAX_VERTS or (nv + 63) // 64 * 64 * P > 256 * 64:
@@ -575,12 +593,13 @@ class SceneData:
         all others from the recording (road users that are replayed here stay so).  Host only.  s0, the queues and traj are
         shared with this scene, not copied; every scene has a mask of its own and this scene's road and presence windows."""
         out = []
+        wide = dict(wide=True) if self.wide else {}
         # (a road user that is never present in a scene that has ticks is nobody's ego)
         for i in np.flatnonzero(~self.replayed & ((self.exit > self.enter) | (self.length == 0))):
             mask = np.ones(self.n, dtype=bool)
             mask[i] = False
             out.append(SceneData(self.s0, self.v_desired, self.dest_offsets, self.dest_xyz_stop, self.traj, length=self.length, replayed=mask,
-                                 road=self.road, present=(self.enter, self.exit) if self.windowed or self.n > 32 else None))
+                                 road=self.road, present=(self.enter, self.exit) if self.windowed or self.n > 32 else None, **wide))
         return out
 
 
@@ -628,14 +647,23 @@ class InteractionCalibration:
     whatever the rosters - fewer lanes than road users make the pair loops narrower.  Errors, `simulate` and a custom error_func are
     what they are with windows: present cells only, NaN outside.
 
+    A data set with a scene marked `SceneData(wide=True)` - up to 256 road users at once - is loaded by `Engine.scene_calib_load_wide`:
+    every scene on its lanes as above, the scenes with at least `wide_from` lanes on the workgroup kernel and the others on the one-wave
+    tick; an evaluation is then up to two launches.  wide_from = 33 is the smallest scene the one-wave tick cannot take, not a measured
+    crossover.  Errors, `simulate`, a custom error_func, NaN outside windows and the road keys are what they are under shared lanes.
+
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
     ROAD_KEYS = {"road_F_0": "F_0", "road_sigma": "sigma"}
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
-                 max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False):
+                 max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
+                 wide_from=33):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
         self.share_lanes = bool(share_lanes)
+        self.wide_from = int(wide_from)
+        if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
+            raise ValueError(f"wide_from: 1 .. {SceneData.WIDE_MAX + 1}")
         self.train_data, self.test_data = list(train_data), list(test_data)
         for d in self.train_data + self.test_data:
             if not isinstance(d, SceneData):
@@ -704,14 +732,17 @@ class InteractionCalibration:
             obj[: d.traj.shape[0], sl] = d.traj[:, :, feat]
             off.extend((d.dest_offsets[1:] + len(rows)).tolist())
             rows.extend(d.dest_xyz_stop.tolist())
-        shared = self.share_lanes or any(d.n > 32 for d in data)
+        wide = any(d.wide for d in data)
+        shared = wide or self.share_lanes or any(d.n > 32 for d in data)
         if shared:                                               # every scene on its lanes; the windows go with the load
             packed = [d.lanes() for d in data]
             nl = np.array([p[1] for p in packed], dtype=np.int32)
             engine = self._factory(self._pod({}), max(R, self.max_sets * int(nl.sum())), device=self.device)
-            engine.scene_calib_load_shared(nr, nl, np.concatenate([p[0] for p in packed]), np.concatenate([d.enter for d in data]),
-                                           np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
-                                           np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets)
+            load = engine.scene_calib_load_wide if wide else engine.scene_calib_load_shared
+            load(nr, nl, np.concatenate([p[0] for p in packed]), np.concatenate([d.enter for d in data]),
+                 np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
+                 np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets,
+                 **(dict(wide_from=self.wide_from) if wide else {}))
         else:
             engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
             engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,

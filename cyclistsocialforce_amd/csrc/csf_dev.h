@@ -299,6 +299,7 @@ constexpr unsigned CHASE_SPIN_LIMIT = 1u << 18;   // polls (each behind an s_sle
 // csf_agent.hip: up to SMALL_MAX road users of one TwoD-field class, n_ticks whole ticks in one launch of one wave (the rounding
 // bands of the launch: csf_engine.hip set_fov_band)
 constexpr int SMALL_MAX = 32;
+constexpr int WIDE_MAX = 256;    // csf_scene.hip: lanes of a scene that one workgroup of 256 threads ticks (scene_wide_kernel)
 constexpr int SMALL_ROAD_MAX = 2048;   // road vertices (padded) the one-wave kernel stages; and at most 256 of them per lane and tick
 void launch_small_tick(const Dev &d, int n_ticks, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // csf_step_batch: `count` scenes of vehicle class `model`, one wave each, their Dev records in `table` (device memory); the road of

@@ -71,7 +71,22 @@ struct SceneDev {
     const int32_t *img_qlen;
 };
 
-// One launch: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].
-void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st);
+// Wide scenes (csf_scene_calib_load_wide): a data set on shared lanes whose scenes with n_lanes >= wide_from run on
+// scene_wide_kernel - one workgroup of 256 threads per (set, scene), up to WIDE_MAX lanes - and the others on scene_lanes_kernel as
+// after csf_scene_calib_load_shared.  SceneDev stays the record of the whole data set (scene_wide_kernel reads it by scene index);
+// scene_lanes_kernel is handed the NARROW scenes alone, compacted: its own table, lengths, lane offsets and first riders.  roff_n[k + 1]
+// is the first rider of the NEXT narrow scene (of the data set's end behind the last), so the kernel's loop over the riders that are
+// never present may also write the (0, 0) of such riders of a wide scene in between - the value scene_wide_kernel writes there too,
+// later on the same stream.
+struct SceneWideDev {
+    const Dev *table_w;          // [n_sets][n_wide] the views of the wide scenes
+    const int32_t *scn_w;        // [n_wide] their scene index
+    int32_t n_wide, n_narrow;
+    const int32_t *len_n, *roff_n, *lane_off_n;   // [n_narrow], [n_narrow + 1], [n_narrow]: what scene_lanes_kernel reads per scene
+};
+
+// One evaluation: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].  With `w` (a wide load)
+// `table` holds the narrow scenes and up to two kernels are launched on `st`, the narrow scenes first.  Returns the kernels launched.
+int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w = nullptr);
 
 }  // namespace csf

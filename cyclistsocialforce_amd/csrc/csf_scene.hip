@@ -39,6 +39,11 @@
 // SceneLaneHook::takeover, the restore of the launch's head once more.  Sums and samples stay per RIDER; a sample row is written
 // only at a tick its rider is present (the host has filled the rest with NaN).
 //
+// Scenes with more than 32 road users at once (csf_scene_calib_load_wide): scene_wide_kernel.  One workgroup of 256
+// threads runs up to WIDE_MAX lanes for all ticks of the scene - wide_tick_body (csf_wide_body.inc), the tick of small_tick_body with
+// LDS and workgroup barriers where that one has shuffles and the wave's program order - behind SceneLaneHook, so chains, windows,
+// replay, samples and sums are those of scene_lanes_kernel.  An evaluation of such a data set is up to two launches on one stream.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -48,6 +53,7 @@
 namespace csf {
 
 #include "csf_small_body.inc"
+#include "csf_wide_body.inc"
 
 // behind every tick: lane = rider of the scene, its error terms (a replayed rider: its recorded state instead) and, on a sampled
 // tick, its state
@@ -255,6 +261,8 @@ struct SceneLaneHook {
             seat(d, lane, nxt);
         }
     }
+    // (wide_tick_body: the flag of this lane alone - 256 lanes have no ballot)
+    __device__ __forceinline__ bool here(int t) const { return t_in <= t && t < t_out; }
     __device__ __forceinline__ uint64_t present(int t) const { return __ballot(t_in <= t && t < t_out); }
     __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
         if (lane >= n) return;
@@ -346,9 +354,79 @@ __global__ __launch_bounds__(64) void scene_lanes_kernel(const Dev *__restrict__
     if (lane < n) hook.flush();
 }
 
-void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st) {
+// wide scenes: one workgroup of 256 threads per (set, wide scene); the prologue and the epilogue are scene_lanes_kernel's
+template <int MODEL>
+__global__ __launch_bounds__(256) void scene_wide_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c,
+                                                         const int32_t *__restrict__ scn_w, const int n_wide) {
+    extern __shared__ float4 srv[];                           // as scene_eval_kernel
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * n_wide) return;                       // (the only early return: before any barrier, the same in every thread)
+    const int set = b / n_wide, scn = scn_w[b - set * n_wide];
+    Dev d = table[b];
+    {
+        const SceneSet ss = sets[set];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue, stride 256
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WIDE_MAX) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;          // n: the scene's lanes (1 .. WIDE_MAX)
+    const int64_t row0 = (int64_t)set * c.R;
+    SceneLaneHook<MODEL> hook(c, row0);
+    if (lane < n) {
+        const int r = c.lane_first[c.lane_off[scn] + lane];
+        if (r >= 0) hook.seat(d, lane, r);
+    }
+    wide_tick_body<MODEL>(d, c.len[scn], srv, hook);
+    // riders that are never present are in no chain: their sums are (0, 0)
+    for (int r = c.roff[scn] + lane; r < c.roff[scn + 1]; r += (int)blockDim.x)
+        if (c.win_enter[r] >= c.win_exit[r]) c.sums[row0 + r] = make_double2(0.0, 0.0);
+    if (lane < n) hook.flush();
+}
+
+int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w) {
+    if (w != nullptr) {
+        // the narrow scenes first, scene_lanes_kernel on their compacted record, then the wide ones: the same stream, so in this order
+        int launched = 0;
+        SceneDev cn = c;
+        cn.n_scn = w->n_narrow, cn.len = w->len_n, cn.roff = w->roff_n, cn.lane_off = w->lane_off_n;
+        const int count_n = c.n_sets * w->n_narrow, count_w = c.n_sets * w->n_wide;
+#define CSF_SCENE_WIDE(MODEL)                                                                                                     \
+    do {                                                                                                                          \
+        if (count_n > 0) {                                                                                                        \
+            hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count_n), dim3(64), c.road_lds, st, table, sets, cn);  \
+            launched++;                                                                                                           \
+        }                                                                                                                         \
+        if (count_w > 0) {                                                                                                        \
+            hipLaunchKernelGGL((scene_wide_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c, w->scn_w, \
+                               w->n_wide);                                                                                        \
+            launched++;                                                                                                           \
+        }                                                                                                                         \
+    } while (0)
+        switch (model) {
+        case CSF_BICYCLE: CSF_SCENE_WIDE(CSF_BICYCLE); break;
+        case CSF_TWOD: CSF_SCENE_WIDE(CSF_TWOD); break;
+        case CSF_INVPEND: CSF_SCENE_WIDE(CSF_INVPEND); break;
+        case CSF_PLANARBIKE: CSF_SCENE_WIDE(CSF_PLANARBIKE); break;
+        case CSF_BALANCINGRIDER: CSF_SCENE_WIDE(CSF_BALANCINGRIDER); break;
+        default: CSF_SCENE_WIDE(CSF_PLANARPOINT); break;
+        }
+#undef CSF_SCENE_WIDE
+        return launched;
+    }
     const int count = c.n_sets * c.n_scn;
-    if (count <= 0) return;
+    if (count <= 0) return 0;
     const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
     const bool lanes = c.lane_off != nullptr;
 #define CSF_SCENE(MODEL)                                                                                                          \
@@ -366,6 +444,7 @@ void launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const 
     default: CSF_SCENE(CSF_PLANARPOINT); break;
     }
 #undef CSF_SCENE
+    return 1;
 }
 
 }  // namespace csf

@@ -103,6 +103,7 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         __builtin_amdgcn_wave_barrier();
         const Recv r{0.f, 0.f, (float)cp, (float)sp};
         double rx = 0.0, ry = 0.0;
+        // (TWIN COPY: the pair loop of wide_tick_body, csf_wide_body.inc, is this loop for a workgroup; a change here is made there too)
         for (int j = grp; j < n; j += G) {                         // (lanes of one group: the same j)
             const double xs = sx[j], ys = sy[j], ps = spsi[j];
             const double ex = x - xs, ey = y - ys;                 // vehicle.py:1615-1616

@@ -50,15 +50,48 @@ struct SceneCalibState {
     DevBuf<int32_t> lane_off, lane_first, rider_next, img_qlen;   // [n_scn + 1], [Lsum], [R], [R]
     DevBuf<int64_t> img_qbeg;                // [R]
     DevBuf<double> img_vdes;                 // [R]
+    // csf_scene_calib_load_wide: scenes with up to WIDE_MAX lanes (DESIGN.md 4.10f).  wide_from == 0: not such a load.  Else the scenes
+    // with n_lanes >= wide_from are WIDE - scn_w, their views in table_w - and `table` holds the views of the narrow scenes alone, with
+    // the compacted lengths, first riders and lane offsets scene_lanes_kernel reads (csf_scene.h: SceneWideDev)
+    int32_t wide_from = 0;
+    std::vector<int32_t> h_scn_w, h_scn_n;   // the wide scenes and the narrow ones, ascending
+    DevBuf<Dev> table_w;                     // [max_sets][n_wide]
+    DevBuf<int32_t> scn_w, len_n, roff_n, lane_off_n;
+    bool is_wide(size_t q) const { return wide_from > 0 && h_nl[q] >= wide_from; }
 };
+
+// The views on the device from the whole table [max_sets][n_scn] on the host: all of it in `table`, or - a wide load - the narrow
+// scenes' in `table` and the wide scenes' in `table_w`, both [max_sets][their scenes].  Allocates; the caller waits for the device.
+static hipError_t scene_upload_tables(const SceneCalibState &cs, const std::vector<Dev> &tab, DevBuf<Dev> &table, DevBuf<Dev> &table_w) {
+    const size_t n_scn = (size_t)cs.n_scn, sets = (size_t)cs.max_sets;
+    if (cs.wide_from == 0) {
+        hipError_t r = table.alloc(tab.size());
+        if (r == hipSuccess) r = hipMemcpy(table.p, tab.data(), tab.size() * sizeof(Dev), hipMemcpyHostToDevice);
+        return r;
+    }
+    hipError_t r = hipSuccess;
+    const std::vector<int32_t> *part[2] = {&cs.h_scn_n, &cs.h_scn_w};
+    DevBuf<Dev> *dst[2] = {&table, &table_w};
+    for (int w = 0; w < 2 && r == hipSuccess; w++) {
+        const size_t m = part[w]->size();
+        std::vector<Dev> sub;
+        sub.reserve(sets * m);
+        for (size_t k = 0; k < sets; k++)
+            for (size_t j = 0; j < m; j++) sub.push_back(tab[k * n_scn + (size_t)(*part[w])[j]]);
+        r = dst[w]->alloc(sub.size());
+        if (r == hipSuccess && !sub.empty()) r = hipMemcpy(dst[w]->p, sub.data(), sub.size() * sizeof(Dev), hipMemcpyHostToDevice);
+    }
+    return r;
+}
 
 }  // extern "C++"
 
-// csf_scene_calib_load (n_lanes == NULL) and csf_scene_calib_load_shared: `fn` names the call in the messages
+// csf_scene_calib_load (n_lanes == NULL), csf_scene_calib_load_shared and csf_scene_calib_load_wide: `fn` names the call in the messages,
+// lane_max is the most lanes a scene may have, wide_from == 0 no wide load (else: scenes with n_lanes >= wide_from are wide)
 static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes, const int32_t *lane,
                            const int32_t *enter, const int32_t *exit, int64_t n_ticks, const double *s0, const double *v_desired,
                            const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
-                           int32_t n_feat, const int32_t *feat, int32_t max_sets) {
+                           int32_t n_feat, const int32_t *feat, int32_t max_sets, int32_t lane_max = SMALL_MAX, int32_t wide_from = 0) {
     const bool sh = n_lanes != nullptr;
     if (!n_riders || !s0 || !v_desired || !dest_offsets || !dest_xyz_stop || !objective || !feat) return fail(e, CSF_E_ARG, "%s: NULL array", fn);
     if (sh && (!lane || !enter || !exit)) return fail(e, CSF_E_ARG, "%s: NULL array", fn);
@@ -78,7 +111,9 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
     for (int32_t q = 0; q < n_scn; q++) {
         // (a shared roster has no bound of its own: what is bounded is its lanes)
         if (n_riders[q] < 1 || (!sh && n_riders[q] > SMALL_MAX)) return fail(e, CSF_E_ARG, "%s: scene %d has %d road users (1 .. %d)", fn, (int)q, (int)n_riders[q], SMALL_MAX);
-        if (sh && (n_lanes[q] < 1 || n_lanes[q] > SMALL_MAX)) return fail(e, CSF_E_ARG, "%s: scene %d has %d lanes (1 .. %d)", fn, (int)q, (int)n_lanes[q], SMALL_MAX);
+        if (sh && (n_lanes[q] < 1 || n_lanes[q] > lane_max)) return fail(e, CSF_E_ARG, "%s: scene %d has %d lanes (1 .. %d)", fn, (int)q, (int)n_lanes[q], (int)lane_max);
+        if (sh && wide_from > 0 && n_lanes[q] > SMALL_MAX && n_lanes[q] < wide_from)
+            return fail(e, CSF_E_ARG, "%s: scene %d has %d lanes and wide_from is %d: the one-wave tick takes 1 .. %d", fn, (int)q, (int)n_lanes[q], (int)wide_from, SMALL_MAX);
         R64 += n_riders[q];
         L64 += sh ? n_lanes[q] : 0;
     }
@@ -133,6 +168,9 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
     // everything that can fail first: a refused call changes nothing
     auto cs = std::make_shared<SceneCalibState>();
     cs->Lsum = Lsum;
+    cs->wide_from = sh ? wide_from : 0;
+    if (sh) cs->h_nl.assign(n_lanes, n_lanes + n_scn);
+    for (int32_t q = 0; cs->wide_from > 0 && q < n_scn; q++) (cs->is_wide((size_t)q) ? cs->h_scn_w : cs->h_scn_n).push_back(q);
     cs->n_scn = n_scn, cs->n_feat = n_feat, cs->max_sets = max_sets, cs->n_ticks = n_ticks, cs->R = R;
     for (int32_t k = 0; k < n_feat; k++) cs->feat[k] = feat[k];
     const size_t Rs = (size_t)R, tn = (size_t)n_ticks * Rs * (size_t)n_feat, views = (size_t)max_sets * (size_t)n_scn;
@@ -149,7 +187,7 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
     if (r == hipSuccess) r = cs->img_znav.alloc(Rs);
     if (r == hipSuccess) r = cs->len.alloc((size_t)n_scn);
     if (r == hipSuccess) r = cs->roff.alloc((size_t)n_scn + 1);
-    if (r == hipSuccess) r = cs->table.alloc(views);
+    // (the table itself is allocated where it is filled: scene_upload_tables)
     if (r == hipSuccess) r = cs->sets.alloc((size_t)max_sets);
     if (r == hipSuccess) r = cs->sets_pin.alloc((size_t)max_sets);
     if (r == hipSuccess) r = cs->sums.alloc((size_t)max_sets * Rs);
@@ -162,6 +200,12 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
         if (r == hipSuccess) r = cs->img_vdes.alloc(Rs);
         if (r == hipSuccess) r = cs->img_qbeg.alloc(Rs);
         if (r == hipSuccess) r = cs->img_qlen.alloc(Rs);
+    }
+    if (cs->wide_from > 0) {
+        if (r == hipSuccess) r = cs->scn_w.alloc(cs->h_scn_w.size());
+        if (r == hipSuccess) r = cs->len_n.alloc(cs->h_scn_n.size());
+        if (r == hipSuccess) r = cs->roff_n.alloc(cs->h_scn_n.size() + 1);
+        if (r == hipSuccess) r = cs->lane_off_n.alloc(cs->h_scn_n.size());
     }
     if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "%s: no memory for the data set: %s", fn, hipGetErrorString(r));
     std::memset(cs->sets_pin.p, 0, (size_t)max_sets * sizeof(SceneSet));
@@ -176,6 +220,21 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
         HIPCHK(e, hipMemcpy(cs->rider_next.p, rnext.data(), rnext.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(cs->win_enter.p, enter, Rs * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(e, hipMemcpy(cs->win_exit.p, exit, Rs * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (cs->wide_from > 0) {   // what scene_lanes_kernel reads per scene, for the narrow scenes alone (csf_scene.h: SceneWideDev)
+        const size_t m = cs->h_scn_n.size();
+        std::vector<int32_t> ln(m), rn(m + 1, R), on(m);
+        for (size_t j = 0; j < m; j++) {
+            const size_t q = (size_t)cs->h_scn_n[j];
+            ln[j] = ls[q], rn[j] = ro[q], on[j] = lo[q];
+        }
+        if (m > 0) {
+            rn[m] = ro[(size_t)cs->h_scn_n[m - 1] + 1];
+            HIPCHK(e, hipMemcpy(cs->len_n.p, ln.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHK(e, hipMemcpy(cs->lane_off_n.p, on.data(), m * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        HIPCHK(e, hipMemcpy(cs->roff_n.p, rn.data(), rn.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (!cs->h_scn_w.empty()) HIPCHK(e, hipMemcpy(cs->scn_w.p, cs->h_scn_w.data(), cs->h_scn_w.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     // the max_sets x R vehicles, slot set * R + rider: every set starts every scene from the scene's start states, with its queues
     const int ns = e->d.ns;
@@ -262,7 +321,7 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
                 v.hist = nullptr, v.hist_F = nullptr, v.rec_tick = nullptr, v.hist_stride = 1, v.hist_cap = 1;
                 v.snap = nullptr, v.atrace = nullptr, v.trace = nullptr, v.pair_count = nullptr;
             }
-        c = hipMemcpy(cs->table.p, tab.data(), views * sizeof(Dev), hipMemcpyHostToDevice);
+        c = scene_upload_tables(*cs, tab, cs->table, cs->table_w);
         if (c == hipSuccess) c = hipDeviceSynchronize();
         if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "%s: the table of views: %s", fn, hipGetErrorString(c)));
         double cb = 0.0;
@@ -283,7 +342,6 @@ static int scene_load_impl(csf_engine *e, const char *fn, int32_t n_scn, const i
         cs->h_table = std::move(tab);
     }
     cs->h_len = std::move(ls), cs->h_roff = std::move(ro);
-    if (sh) cs->h_nl.assign(n_lanes, n_lanes + n_scn);
     e->scene_calib = std::move(cs);
     return CSF_OK;
 }
@@ -304,6 +362,17 @@ int csf_scene_calib_load_shared(csf_engine *e, int32_t n_scn, const int32_t *n_r
     if (!n_lanes) return fail(e, CSF_E_ARG, "csf_scene_calib_load_shared: NULL array");
     return scene_load_impl(e, "csf_scene_calib_load_shared", n_scn, n_riders, n_lanes, lane, enter, exit, n_ticks, s0, v_desired, dest_offsets,
                            dest_xyz_stop, lengths, objective, n_feat, feat, max_sets);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_load_wide(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes, const int32_t *lane,
+                              const int32_t *enter, const int32_t *exit, int64_t n_ticks, const double *s0, const double *v_desired,
+                              const int64_t *dest_offsets, const double *dest_xyz_stop, const int32_t *lengths, const double *objective,
+                              int32_t n_feat, const int32_t *feat, int32_t max_sets, int32_t wide_from) try {
+    if (!e) return CSF_E_ARG;
+    if (!n_lanes) return fail(e, CSF_E_ARG, "csf_scene_calib_load_wide: NULL array");
+    if (wide_from < 1 || wide_from > WIDE_MAX + 1) return fail(e, CSF_E_ARG, "csf_scene_calib_load_wide: wide_from = %d outside 1 .. %d", (int)wide_from, WIDE_MAX + 1);
+    return scene_load_impl(e, "csf_scene_calib_load_wide", n_scn, n_riders, n_lanes, lane, enter, exit, n_ticks, s0, v_desired, dest_offsets,
+                           dest_xyz_stop, lengths, objective, n_feat, feat, max_sets, WIDE_MAX, wide_from);
 } catch (...) { return csf_caught(e); }
 
 int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version, double *sums_out,
@@ -413,9 +482,16 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
         if (n_states > 0) HIPCHK(e, hipMemsetAsync(cs.states.p, 0xff, n_states * sizeof(double), e->main));
     }
     HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
-    launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
+    if (cs.wide_from > 0) {   // the narrow scenes on scene_lanes_kernel, the wide ones on scene_wide_kernel: one stream, one wait
+        SceneWideDev w{};
+        w.table_w = cs.table_w.p, w.scn_w = cs.scn_w.p;
+        w.n_wide = (int32_t)cs.h_scn_w.size(), w.n_narrow = (int32_t)cs.h_scn_n.size();
+        w.len_n = cs.len_n.p, w.roff_n = cs.roff_n.p, w.lane_off_n = cs.lane_off_n.p;
+        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main, &w);
+    } else {
+        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
+    }
     HIPCHK(e, hipGetLastError());
-    cs.launches++;
     if (n_states > 0) HIPCHK(e, hipMemcpyAsync(states_out, cs.states.p, n_states * sizeof(double), hipMemcpyDeviceToHost, e->main));
     HIPCHK(e, hipStreamSynchronize(e->main));
     std::memcpy(sums_out, cs.sums.p, (size_t)n * sizeof(double2));
@@ -471,7 +547,7 @@ int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_sce
             nv[q] = (int64_t)road.size() / 4;
             // (shared lanes: the one-wave tick runs the scene's lanes, not its roster)
             const int64_t nv_pad = (nv[q] + 63) / 64 * 64, n = cs.Lsum > 0 ? cs.h_nl[q] : cs.h_roff[q + 1] - cs.h_roff[q];
-            int64_t P = 1;
+            int64_t P = cs.is_wide(q) ? WAVE : 1;              // (a wide scene: the workgroup's P is 64, 128 or 256)
             while (P < n) P <<= 1;
             if (nv_pad * P > 256 * WAVE)
                 return fail(e, CSF_E_ARG, "csf_scene_calib_road: the road of scene %d has %lld vertices, a scene of %lld road users takes %lld", (int)q,
@@ -488,9 +564,9 @@ int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_sce
     // everything that can fail first: a refused call changes nothing
     DevBuf<float4> d_rv;
     DevBuf<float2> d_rvo;
-    DevBuf<Dev> d_table;
+    DevBuf<Dev> d_table, d_table_w;
     std::vector<Dev> tab = cs.h_table;
-    hipError_t r = d_table.alloc(tab.size());
+    hipError_t r = hipSuccess;
     if (!rv_all.empty()) {
         if (r == hipSuccess) r = d_rv.alloc(rv_all.size());
         if (r == hipSuccess) r = d_rvo.alloc(rvo_all.size());
@@ -508,11 +584,12 @@ int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_sce
                 v.ox = cs.h_ox[q], v.oy = cs.h_oy[q];
                 v.rg_nx = v.rg_ny = 0;
             }
-        r = hipMemcpy(d_table.p, tab.data(), tab.size() * sizeof(Dev), hipMemcpyHostToDevice);
+        r = scene_upload_tables(cs, tab, d_table, d_table_w);
     }
     if (r == hipSuccess) r = hipDeviceSynchronize();
     if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_road: no memory for the roads: %s", hipGetErrorString(r));
     cs.table = std::move(d_table);
+    cs.table_w = std::move(d_table_w);
     cs.road_rv = std::move(d_rv);
     cs.road_rvo = std::move(d_rvo);
     cs.road_blk = DevBuf<float4>();

@@ -302,6 +302,12 @@ class Engine:
         window enter [R], exit [R] (0 <= enter <= exit <= the length of the scene).  Riders of one lane take turns: their non-empty
         windows do not overlap.  Sums and states stay per RIDER; a row of the states is NaN wherever its rider is not present.
         capacity >= max(R, max_sets * sum(n_lanes)).  scene_calib_windows is refused on such a data set."""
+        self._scene_load_lanes(self._lib.csf_scene_calib_load_shared, (), n_riders, n_lanes, lane, enter, exit, s0, v_desired, dest_offsets,
+                               dest_xyz_stop, objective, feat, lengths, max_sets)
+
+    def _scene_load_lanes(self, call, more, n_riders, n_lanes, lane, enter, exit, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat,
+                          lengths, max_sets):
+        """scene_calib_load_shared and scene_calib_load_wide: the same arrays, `more` the arguments behind max_sets"""
         nr, R, s0, vd, off, xyz, obj, feat, T, ln = self._scene_arrays(n_riders, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat, lengths)
         nl = np.ascontiguousarray(n_lanes, dtype=np.int32).reshape(-1)
         if nl.shape != nr.shape:
@@ -309,10 +315,20 @@ class Engine:
         ln_, en, ex = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (lane, enter, exit))
         if ln_.shape != (R,) or en.shape != (R,) or ex.shape != (R,):
             raise ValueError("lane, enter and exit must have one entry per rider of the data set")
-        self._ck(self._lib.csf_scene_calib_load_shared(self._h, nr.size, _ptr(nr), _ptr(nl), _ptr(ln_), _ptr(en), _ptr(ex), T, _ptr(s0), _ptr(vd),
-                                                       _ptr(off), _ptr(xyz), None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat),
-                                                       int(max_sets)))
+        self._ck(call(self._h, nr.size, _ptr(nr), _ptr(nl), _ptr(ln_), _ptr(en), _ptr(ex), T, _ptr(s0), _ptr(vd), _ptr(off), _ptr(xyz),
+                      None if ln is None else _ptr(ln), _ptr(obj), feat.size, _ptr(feat), int(max_sets), *more))
         self._scene_calib = (R, T)
+
+    def scene_calib_load_wide(self, n_riders, n_lanes, lane, enter, exit, s0, v_desired, dest_offsets, dest_xyz_stop, objective, feat,
+                              lengths=None, max_sets=256, wide_from=33):
+        """scene_calib_load_shared for scenes with MORE THAN 32 ROAD USERS AT ONCE: n_lanes [n_scn] is 1 .. 256.  A scene with
+        n_lanes >= wide_from (1 .. 257) is simulated by one workgroup of 256 threads for all its ticks, every other scene by the one-wave
+        tick exactly as after scene_calib_load_shared; an evaluation launches one kernel per kind that the data set holds.  33 - the
+        default - is the smallest scene the one-wave tick cannot take, not a measured crossover; 1 sends every scene to the wide
+        kernel.  The road of a wide scene: padded vertices x P <= 16 384 with P = 64, 128 or 256.  Everything else is
+        scene_calib_load_shared's."""
+        self._scene_load_lanes(self._lib.csf_scene_calib_load_wide, (int(wide_from),), n_riders, n_lanes, lane, enter, exit, s0, v_desired,
+                               dest_offsets, dest_xyz_stop, objective, feat, lengths, max_sets)
 
     def scene_calib_eval(self, pods, states=False, stride=1, road_F0=None, road_sigma=None):
         """Evaluate the parameter sets `pods` (a sequence of csf_params) on the loaded scenes in one launch: sums [n_sets, R, 2] =
@@ -397,7 +413,8 @@ class Engine:
         self._scene_calib = None
 
     def scene_calib_launches(self):
-        """kernel launches of scene_calib_eval since scene_calib_load: one per call"""
+        """kernel launches of scene_calib_eval since scene_calib_load: one per call (after scene_calib_load_wide: one per call and kind
+        of scene - narrow, wide - the data set holds)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_scene_calib_launches(self._h, C.byref(n)))
         return int(n.value)

@@ -539,7 +539,28 @@ int csf_calib_clear(csf_engine *e);
  * is that of the scene's LANES), both evaluation calls, csf_scene_calib_launches and csf_scene_calib_clear work as on any data set;
  * csf_scene_calib_windows is refused with CSF_E_STATE, because the windows belong to the load.  Refused with the engine empty and
  * usable: everything csf_scene_calib_load refuses, and CSF_E_ARG for a lane count or a lane out of range, a window outside 0 <= enter
- * <= exit <= the length of the scene, or two riders of one lane whose non-empty windows overlap. */
+ * <= exit <= the length of the scene, or two riders of one lane whose non-empty windows overlap.
+ *
+ * csf_scene_calib_load_wide is csf_scene_calib_load_shared for scenes with MORE THAN 32 ROAD USERS AT ONCE:
+ * 1 <= n_lanes[q] <= 256, and wide_from (1 .. 257) decides per scene which kernel runs it.  A scene with n_lanes[q] >= wide_from is WIDE:
+ * one workgroup of 256 threads per (set, scene) simulates it closed loop for all its ticks - the tick of the one-wave path with the all-to-all
+ * dependence carried through LDS and workgroup barriers, P = 64, 128 or 256 the power of two that holds its lanes.  Every other scene
+ * runs on the one-wave tick exactly as after csf_scene_calib_load_shared, bit for bit.  33 is the natural wide_from - the smallest scene the
+ * one-wave tick cannot take; it is NOT a measured crossover -, 1 sends every scene to the wide kernel, a tuning knob, and above 33 a
+ * scene of more than 32 lanes that stays below wide_from is refused (CSF_E_ARG: the one-wave tick cannot take it).  An evaluation launches, on one stream, the kernel of the narrow
+ * scenes if there are any and then the kernel of the wide ones if there are any - still one copy in and one wait -, and
+ * csf_scene_calib_launches counts each kernel launched.  A wide scene differs from the same scene on the one-wave tick in the order of
+ * the fp64 sums of the pair term (and of the fp32 sums of the road term) alone.  csf_scene_calib_road reads its rule with the P above: a wide scene
+ * takes 256, 128 or 64 vertices (padded).  csf_scene_calib_replay, both evaluation calls, csf_scene_calib_launches, csf_scene_calib_clear and the
+ * refusals while a data set is held are those of any data set; csf_scene_calib_windows is refused as after csf_scene_calib_load_shared.
+ * Refused with the engine empty and usable: everything csf_scene_calib_load_shared refuses with 256 in the place of 32, and CSF_E_ARG
+ * for wide_from outside 1 .. 257.  csf_scene_calib_load and csf_scene_calib_load_shared keep their limit of 32. */
+int csf_scene_calib_load_wide(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes,
+                              const int32_t *lane, const int32_t *enter, const int32_t *exit, int64_t n_ticks,
+                              const double *s0, const double *v_desired,
+                              const int64_t *dest_offsets, const double *dest_xyz_stop,
+                              const int32_t *lengths, const double *objective,
+                              int32_t n_feat, const int32_t *feat, int32_t max_sets, int32_t wide_from);
 int csf_scene_calib_load_shared(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes,
                                 const int32_t *lane, const int32_t *enter, const int32_t *exit, int64_t n_ticks,
                                 const double *s0, const double *v_desired,

@@ -30,8 +30,14 @@ roster on - loaded twice on the SAME library: by csf_scene_calib_load + csf_scen
 that holds the roster) and by csf_scene_calib_load_shared on SceneData.lanes() (`packed_ms`, P = the one that holds the peak).  The
 two legs alternate window by window after one warm-up call each; `packed_rel_gap` is the largest relative difference of their errors.
 
+--riders 40,96 makes the scenes WIDE: scene q has riders[q % len] road users, all present throughout, in a box at the
+density of 32 in 30 m; the data set is loaded by csf_scene_calib_load_wide (--wide-from, default 33) and an evaluation is one launch
+per kind of scene.  The baseline leg is the tool's own: one engine per (set, scene) stepped on the engine's own path.  The option
+stands alone: not with --replay, --road or --presence.
+
     python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
                                      [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
+                                     [--riders 40,96 [--wide-from 33]]
 """
 import argparse
 import json
@@ -89,7 +95,12 @@ def main():
     ap.add_argument("--share", action="store_true")
     ap.add_argument("--share-roster", type=int, default=20)
     ap.add_argument("--share-peak", type=int, default=6)
+    ap.add_argument("--riders", default=None)
+    ap.add_argument("--wide-from", type=int, default=33)
     a = ap.parse_args()
+    riders = [int(x) for x in a.riders.split(",")] if a.riders else None
+    if riders and (a.replay or a.road or a.presence or min(riders) < 1 or max(riders) > 256):
+        ap.error("--riders takes 1 .. 256 road users per scene and stands alone: not with --replay, --road or --presence")
     if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
         ap.error("--share goes with --presence and 1 <= --share-peak <= --share-roster <= 32")
     feat = np.array([0, 1], dtype=np.int32)
@@ -97,7 +108,10 @@ def main():
         open(a.out, "w").close()
     for model in a.models.split(","):
         base = parameters.default_pod(model)
-        per = [scene(model, 3 + q % 6, 50 + q) for q in range(a.scenes)]
+        if riders:
+            per = [scene(model, riders[q % len(riders)], 50 + q, box=30.0 * np.sqrt(riders[q % len(riders)] / 32.0)) for q in range(a.scenes)]
+        else:
+            per = [scene(model, 3 + q % 6, 50 + q) for q in range(a.scenes)]
         nr = np.array([s.shape[0] for s, _, _ in per], dtype=np.int32)
         roff = np.r_[0, np.cumsum(nr)]
         R = int(roff[-1])
@@ -113,7 +127,11 @@ def main():
         for n_sets in [int(x) for x in a.sets.split(",")]:
             sets = pod_sets(base, n_sets)
             e = Engine(base, n_sets * R)
-            e.scene_calib_load(nr, s0, 5.0, off, rows, obj, feat, max_sets=n_sets)
+            if riders:                                           # every rider on a lane of its own, there throughout
+                e.scene_calib_load_wide(nr, nr, np.concatenate([np.arange(n) for n in nr]), np.zeros(R, dtype=np.int32), np.full(R, a.ticks, dtype=np.int32),
+                                        s0, 5.0, off, rows, obj, feat, max_sets=n_sets, wide_from=a.wide_from)
+            else:
+                e.scene_calib_load(nr, s0, 5.0, off, rows, obj, feat, max_sets=n_sets)
             if a.road:
                 e.scene_calib_road(np.repeat(np.arange(a.scenes, dtype=np.int32), 2), np.arange(2 * a.scenes + 1) * a.road_verts,
                                    np.tile(road[1].reshape(2, -1, 2), (a.scenes, 1, 1)).reshape(-1, 2), np.tile(road[2], a.scenes), np.tile(road[3], a.scenes))
@@ -175,6 +193,8 @@ def main():
             line = dict(model=model, n_sets=n_sets, scenes=a.scenes, riders=R, ticks=a.ticks, windows=a.windows, first_call_rel_gap=first_gap,
                         new_ms=dict(median=float(np.median(t_new)), min=min(t_new), max=max(t_new)),
                         base_ms=dict(median=float(np.median(t_old)), min=min(t_old), max=max(t_old)) if t_old else None)
+            if riders:
+                line.update(scene_riders=riders, wide_from=a.wide_from, launches_per_eval=e.scene_calib_launches() // (a.windows + 1))
             if a.road:
                 rf, rs = 0.15 * (1.0 + 0.002 * np.arange(n_sets)), np.full(n_sets, 2.0)
                 e.scene_calib_eval(sets, road_F0=rf, road_sigma=rs)          # (allocates the sets' road blocks)
