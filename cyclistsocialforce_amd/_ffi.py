@@ -39,6 +39,7 @@ SYMBOLS = (
     "csf_scene_calib_windows",
     "csf_scene_calib_load_shared",
     "csf_scene_calib_load_wide",
+    "csf_scene_calib_groups", "csf_scene_calib_eval_groups",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -203,6 +204,9 @@ def load():
         L.csf_scene_calib_load_shared.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, dp, dp, vp, dp, vp, dp, i32, vp, i32]
     if hasattr(L, "csf_scene_calib_load_wide"):     # (the same)
         L.csf_scene_calib_load_wide.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, dp, dp, vp, dp, vp, dp, i32, vp, i32, i32]
+    if hasattr(L, "csf_scene_calib_groups"):        # (the same)
+        L.csf_scene_calib_groups.argtypes = [vp, vp, i32]
+        L.csf_scene_calib_eval_groups.argtypes = [vp, i32, i32, C.POINTER(Params), C.c_size_t, i32, dp, dp, dp, i32, dp]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

@@ -442,13 +442,18 @@ class SceneData:
     wide=True lifts the bound to 256 road users AT ONCE (`Engine.scene_calib_load_wide`: one workgroup of 256 threads ticks such a scene).
     A roster above 32 then needs no `present` - without windows `lanes()` gives lane = index -, the ValueError names tick and count
     against 256, and the road limit is that of P = 64, 128 or 256, the power of two that holds its lanes and at least 64: 256, 128 or
-    64 vertices (padded to a multiple of 64), whichever kernel the scene ends up on.  With the default wide=False nothing changes."""
+    64 vertices (padded to a multiple of 64), whichever kernel the scene ends up on.  With the default wide=False nothing changes.
+
+    group [n] (integers >= 0, default: everybody 0) puts every road user into a GROUP that carries parameters of its own - e-bikes and
+    city bikes, commuters and children (`InteractionCalibration(group_params=...)`, `Engine.scene_calib_groups`): a road user is
+    simulated with its group's parameter set and acts on the others with that set's field and field of view, replayed or not."""
 
     ROAD_MAX_VERTS = 2048
 
     WIDE_MAX = 256
 
-    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None, wide=False):
+    def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None, wide=False,
+                 group=None):
         self.s0 = np.asarray(s0, dtype=float)
         self.wide = bool(wide)
         if self.wide:
@@ -462,6 +467,16 @@ class SceneData:
             self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (n,)))
         except ValueError:
             raise ValueError("v_desired: one desired speed per road user, or a scalar") from None
+        self.grouped = group is not None
+        if group is None:
+            self.group = np.zeros(n, dtype=np.int32)
+        else:
+            g = np.asarray(group)
+            if g.shape != (n,) or g.dtype.kind not in "iu":
+                raise ValueError("group: one integer per road user")
+            if np.any(g < 0):
+                raise ValueError("group: entries are >= 0")
+            self.group = g.astype(np.int32)
         if replayed is None:
             self.replayed = np.zeros(n, dtype=bool)
         else:
@@ -594,6 +609,8 @@ class SceneData:
         shared with this scene, not copied; every scene has a mask of its own and this scene's road and presence windows."""
         out = []
         wide = dict(wide=True) if self.wide else {}
+        if self.grouped:
+            wide["group"] = self.group
         # (a road user that is never present in a scene that has ticks is nobody's ego)
         for i in np.flatnonzero(~self.replayed & ((self.exit > self.enter) | (self.length == 0))):
             mask = np.ones(self.n, dtype=bool)
@@ -652,14 +669,38 @@ class InteractionCalibration:
     tick; an evaluation is then up to two launches.  wide_from = 33 is the smallest scene the one-wave tick cannot take, not a measured
     crossover.  Errors, `simulate`, a custom error_func, NaN outside windows and the road keys are what they are under shared lanes.
 
+    Road users in GROUPS with parameters of their own (`SceneData(group=...)`): group_params is a list of G dicts of FIXED keyword
+    arguments of PARAMS_TYPE, one per group - what is known to differ between the groups; its length defines G (at most 4).  An entry
+    of params_keys is then either "name" - fitted, one value shared by all groups - or ("name", g) - fitted for group g alone; the road
+    keys stay per candidate.  A candidate vector becomes G parameter sets, PARAMS_TYPE(**group_params[g], **shared, **own[g]), and an
+    evaluation is `Engine.scene_calib_eval_groups`.  Both built-in errors, `simulate`, `test` and a custom error_func are per road
+    user and work as without groups.  Groups need `Engine.scene_calib_load`: with shared lanes or a wide scene a ValueError says so.
+    Without group_params nothing changes and no new call is made.
+
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
     ROAD_KEYS = {"road_F_0": "F_0", "road_sigma": "sigma"}
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
-                 wide_from=33):
+                 wide_from=33, group_params=None):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
+        self.group_params = None if group_params is None else [dict(g) for g in group_params]
+        self._G = 1 if self.group_params is None else len(self.group_params)
+        if not 1 <= self._G <= 4:
+            raise ValueError("group_params: 1 .. 4 dicts of keyword arguments of PARAMS_TYPE, one per group")
+        for k in self.params_keys:
+            if isinstance(k, str):
+                continue
+            if not (isinstance(k, tuple) and len(k) == 2 and isinstance(k[0], str) and isinstance(k[1], (int, np.integer))
+                    and not isinstance(k[1], bool)):
+                raise ValueError(f"params_keys: {k!r} is neither \"name\" nor (\"name\", group)")
+            if k[0] in self.ROAD_KEYS:
+                raise ValueError(f"params_keys: {k!r}: the road keys are per candidate set, not per group")
+            if self.group_params is None:
+                raise ValueError(f"params_keys: {k!r} names a group and there is no group_params")
+            if not 0 <= k[1] < self._G:
+                raise ValueError(f"params_keys: {k!r} names group {k[1]}, group_params defines {self._G}")
         self.share_lanes = bool(share_lanes)
         self.wide_from = int(wide_from)
         if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
@@ -668,6 +709,11 @@ class InteractionCalibration:
         for d in self.train_data + self.test_data:
             if not isinstance(d, SceneData):
                 raise TypeError("train_data and test_data are lists of SceneData")
+        for name, data in (("train_data", self.train_data), ("test_data", self.test_data)):
+            for q, d in enumerate(data):
+                if d.group.max() >= self._G:
+                    raise ValueError(f"scene {q} of {name} has a road user in group {int(d.group.max())}, group_params defines {self._G} "
+                                     f"group{'s' if self._G > 1 else ''}")
         if not self.train_data:
             raise ValueError("no scenes to train on")
         self.objective_features_traj = _indicators(objective_features_traj, "objective_features_traj", TRAJ_ROWS)
@@ -694,6 +740,22 @@ class InteractionCalibration:
 
     def _pod(self, params_args):
         return self.vehicle_type.PARAMS_TYPE(**{k: v for k, v in params_args.items() if k not in self.ROAD_KEYS}).to_pod(self.vehicle_type.MODEL)
+
+    def _group_args(self, params_args):
+        """the keyword arguments of PARAMS_TYPE per group: group_params[g], the shared keys, the group's own"""
+        shared = {k: v for k, v in params_args.items() if isinstance(k, str) and k not in self.ROAD_KEYS}
+        return [{**self.group_params[g], **shared, **{k[0]: v for k, v in params_args.items() if isinstance(k, tuple) and k[1] == g}}
+                for g in range(self._G)]
+
+    def _pods(self, params_args):
+        """a candidate as Engine.scene_calib_eval_groups takes it: one parameter set per group"""
+        return tuple(self.vehicle_type.PARAMS_TYPE(**a).to_pod(self.vehicle_type.MODEL) for a in self._group_args(params_args))
+
+    def _eval(self, ds, args_list, **kw):
+        """one evaluation of the candidates args_list: Engine.scene_calib_eval, or - with groups - scene_calib_eval_groups"""
+        if self._G > 1:
+            return ds["engine"].scene_calib_eval_groups([self._pods(a) for a in args_list], **kw)
+        return ds["engine"].scene_calib_eval([self._pod(a) for a in args_list], **kw)
 
     def _road_over(self, args_list):
         """road_F0, road_sigma [n_sets] of an evaluation (keyword arguments of Engine.scene_calib_eval); {}: no road key is fitted"""
@@ -734,19 +796,25 @@ class InteractionCalibration:
             rows.extend(d.dest_xyz_stop.tolist())
         wide = any(d.wide for d in data)
         shared = wide or self.share_lanes or any(d.n > 32 for d in data)
+        if self._G > 1 and shared:
+            raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and this data set needs shared lanes"
+                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)")
+        pod0 = self._pods({})[0] if self._G > 1 else self._pod({})
         if shared:                                               # every scene on its lanes; the windows go with the load
             packed = [d.lanes() for d in data]
             nl = np.array([p[1] for p in packed], dtype=np.int32)
-            engine = self._factory(self._pod({}), max(R, self.max_sets * int(nl.sum())), device=self.device)
+            engine = self._factory(pod0, max(R, self.max_sets * int(nl.sum())), device=self.device)
             load = engine.scene_calib_load_wide if wide else engine.scene_calib_load_shared
             load(nr, nl, np.concatenate([p[0] for p in packed]), np.concatenate([d.enter for d in data]),
                  np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
                  np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets,
                  **(dict(wide_from=self.wide_from) if wide else {}))
         else:
-            engine = self._factory(self._pod({}), self.max_sets * R, device=self.device)
+            engine = self._factory(pod0, self.max_sets * R, device=self.device)
             engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
                                     max_sets=self.max_sets)
+            if self._G > 1:
+                engine.scene_calib_groups(np.concatenate([d.group for d in data]), self._G)
         if rep.any():                                            # the recorded (x, y, psi, v) of the replayed riders, in rider order
             rec = np.zeros((T, int(rep.sum()), 4))
             at = 0
@@ -803,21 +871,20 @@ class InteractionCalibration:
         vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
         ds = self._dataset(test)
         args = [self._update_params_args_dict(v) for v in vals]
-        pods = [self._pod(a) for a in args]
-        err = np.zeros(len(pods))
-        for at in range(0, len(pods), ds["sets"]):
-            chunk = pods[at:at + ds["sets"]]
-            road = self._road_over(args[at:at + ds["sets"]])
+        err = np.zeros(len(args))
+        for at in range(0, len(args), ds["sets"]):
+            chunk = args[at:at + ds["sets"]]
+            road = self._road_over(chunk)
             if self.error_func is calc_sse_timesteps:
-                sums = ds["engine"].scene_calib_eval(chunk, **road)
+                sums = self._eval(ds, chunk, **road)
                 err[at:at + len(chunk)] = _scenes_in_order(_riders_then_scenes(sums[:, :, 0], ds["roff"]))
             elif self.error_func is calc_maesse_samples:
-                sums = ds["engine"].scene_calib_eval(chunk, **road)
+                sums = self._eval(ds, chunk, **road)
                 with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
                     mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["cells"] * float(ds["feat"].size))[None, :]
                 err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
             else:
-                _, states = ds["engine"].scene_calib_eval(chunk, states=True, **road)
+                _, states = self._eval(ds, chunk, states=True, **road)
                 for k in range(len(chunk)):
                     err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
         return err
@@ -827,7 +894,7 @@ class InteractionCalibration:
         the state after each tick -, the objectives)."""
         ds = self._dataset(test)
         args = self._update_params_args_dict(np.asarray(params_vals, dtype=float))
-        _, states = ds["engine"].scene_calib_eval([self._pod(args)], states=True, **self._road_over([args]))
+        _, states = self._eval(ds, [args], states=True, **self._road_over([args]))
         return self._trajs(ds, states, 0), list(ds["objectives"])
 
     def run(self, params_vals_guess):

@@ -17,6 +17,12 @@ struct SceneSet {
     int32_t road_np, pad[3];
 };
 
+// Rider groups (csf_scene_calib_groups): the riders of a scene carry one of up to SCENE_GROUPS_MAX parameter sets of the
+// engine's vehicle class.  The call's table of sets is then [n_sets][n_groups] SceneSet records, record (set, g) what group g carries in
+// candidate set `set`; the road entries and the rounding bands of a set are the same in all of its records, and so is the priority rule
+// (record 0's: the rule belongs to the intersection, as under csf_set_param_classes).
+constexpr int SCENE_GROUPS_MAX = 4;
+
 // The data set of csf_scene_calib_load, resident on the device, and the reset image.  The image is indexed by RIDER (0 .. R - 1,
 // the scenes one after the other): every set starts every scene from the same state, so one copy of what csf_add_agents made of
 // the first set's slots serves all of them.  It holds every per-slot array that a closed-loop tick (agent_body<.., FUSED = true>
@@ -69,6 +75,10 @@ struct SceneDev {
     const double *img_vdes;
     const int64_t *img_qbeg;
     const int32_t *img_qlen;
+    // Rider groups (csf_scene_calib_groups), read by scene_groups_kernel only: the group of every rider, and the sets are
+    // [n_sets][n_groups] records.  NULL: no groups - every rider carries record `set` of [n_sets], and the launch is today's.
+    const uint8_t *group;        // [R] 0 .. n_groups - 1
+    int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group`, else 0
 };
 
 // Wide scenes (csf_scene_calib_load_wide): a data set on shared lanes whose scenes with n_lanes >= wide_from run on

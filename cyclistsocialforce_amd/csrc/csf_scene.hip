@@ -44,6 +44,10 @@
 // LDS and workgroup barriers where that one has shuffles and the wave's program order - behind SceneLaneHook, so chains, windows,
 // replay, samples and sums are those of scene_lanes_kernel.  An evaluation of such a data set is up to two launches on one stream.
 //
+// Rider groups with parameter sets of their own (csf_scene_calib_groups): scene_groups_kernel.  The call's table holds
+// n_groups records per candidate set, a rider is ticked with its group's record and acts as a source with that record's field and field
+// of view (csf_small_body.inc: HOOK::GROUPS).  A data set without groups launches scene_eval_kernel, where none of this exists.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
 #include "csf_agent_dev.h"
@@ -55,12 +59,36 @@ namespace csf {
 #include "csf_small_body.inc"
 #include "csf_wide_body.inc"
 
+// what SceneHook holds of the rider groups (csf_small_body.inc: HOOK::GROUPS): nothing without them
+template <bool GRP>
+struct SceneGroupPart {};
+template <>
+struct SceneGroupPart<true> {
+    int n_groups = 1;             // groups of the call (2 .. SCENE_GROUPS_MAX)
+    int grp = 0;                  // the group of this lane's rider (a lane without a rider: 0)
+    const SceneSet *rec = nullptr;        // the n_groups records of this workgroup's candidate set (global memory, uniform)
+    // staged by the kernel in LDS: the pair constants, field of view and v_max_riding[1] of every group, and the group of every rider
+    const PairConsts *l_pc = nullptr;
+    const double *l_hfov = nullptr, *l_vref = nullptr;
+    const uint8_t *l_grp = nullptr;
+    __device__ __forceinline__ const PairConsts *consts(int j) const { return l_pc + l_grp[j]; }
+    __device__ __forceinline__ double hfov(int j) const { return l_hfov[l_grp[j]]; }
+    __device__ __forceinline__ double v_ref(int) const { return l_vref[grp]; }
+    // (g is uniform: scalar loads from the record)
+    __device__ __forceinline__ void select(Dev &dg, int g) const {
+        dg.p = rec[g].p;
+#pragma unroll
+        for (int k = 0; k < 7; k++) dg.pb[k] = rec[g].pb[k];
+    }
+};
+
 // behind every tick: lane = rider of the scene, its error terms (a replayed rider: its recorded state instead) and, on a sampled
 // tick, its state
-template <int MODEL, bool WIN>
-struct SceneHook {
+template <int MODEL, bool WIN, bool GRP = false>
+struct SceneHook : SceneGroupPart<GRP> {
     static constexpr bool MASKED = WIN;
     static constexpr bool SHARED = false;
+    static constexpr bool GROUPS = GRP;
     const SceneDev &c;
     const int64_t rider;          // set * R + first rider of the scene + lane: row of sums and of a sample
     const double *obj;            // objective of this lane's rider at tick 0
@@ -194,11 +222,98 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
         while (hook.taken < c.n_samples) hook.sample(d, lane);
 }
 
+// Rider groups (csf_scene_calib_groups): scene_eval_kernel with the parameters a property of the RIDER.  `sets` holds
+// c.n_groups records per candidate set; Dev::p / pc / pb become record 0's (the priority rule and the road entries are the set's), the
+// restore takes the limits of the rider's own record, and the tick reads the rest through the hook (csf_small_body.inc: HOOK::GROUPS).
+// TWIN COPY of scene_eval_kernel's prologue, restore and epilogue, kept apart so that its instances come out of the compiler as they
+// were; an array added to the image goes into all three.
+template <int MODEL, bool WIN>
+__global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
+    extern __shared__ float4 srv[];                           // as scene_eval_kernel
+    __shared__ PairConsts g_pc[SCENE_GROUPS_MAX];
+    __shared__ double g_hfov[SCENE_GROUPS_MAX], g_vref[SCENE_GROUPS_MAX];
+    __shared__ uint8_t g_of[SMALL_MAX];
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * c.n_scn) return;
+    const int set = b / c.n_scn, scn = b - set * c.n_scn;
+    const int G = c.n_groups < SCENE_GROUPS_MAX ? c.n_groups : SCENE_GROUPS_MAX;   // (the host refuses more; LDS holds no more)
+    const SceneSet *const rec = sets + (int64_t)set * c.n_groups;
+    Dev d = table[b];
+    {
+        const SceneSet ss = rec[0];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;
+    const int64_t cap = d.cap, first = c.roff[scn];
+    const int len = c.len[scn];
+    // (group has R entries, as rep_index; an entry the host has checked, clamped all the same: it indexes LDS)
+    int grp = lane < n ? (int)c.group[first + lane] : 0;
+    grp = grp < G ? grp : G - 1;
+    // the groups' constants to LDS: lane g < G copies record g word by word; then the wave's own stores, program order (as sx, sy)
+    if (lane < G) {
+        g_pc[lane] = rec[lane].pc;
+        g_hfov[lane] = rec[lane].p.hfov;
+        g_vref[lane] = rec[lane].p.v_max_riding[1];
+    }
+    if (lane < SMALL_MAX) g_of[lane] = (uint8_t)grp;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < n) {   // Vehicle.__init__ for this rider: TWIN COPY of scene_eval_kernel's restore, the limits those of the rider's own set
+        const int64_t a = lane, r = first + lane, ic = c.img_cap;
+#pragma unroll
+        for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
+#pragma unroll
+        for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
+        d.ppsi[a] = c.img_ppsi[r];
+        d.ti[a] = c.img_ti[r];
+        d.status[a] = c.img_status[r];
+        d.ptr[a] = c.img_ptr[r];
+        d.znav[a] = c.img_znav[r];
+        d.hx[a] = c.img_hx0[r];
+        d.hy[a] = c.img_hy0[r];
+        const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
+        const double vw = rec[grp].p.v_max_walk, dw = rec[grp].p.delta_max_walk;
+        d.zrid[a] = v < vw ? 0 : 1;
+        d.dgood[a] = (-dw < delta && dw > delta) ? 1 : 0;
+    }
+    const int64_t rider = (int64_t)set * c.R + first + lane;
+    const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
+    const int t_in = WIN && lane < n ? c.win_enter[first + lane] : 0, t_out = WIN && lane < n ? c.win_exit[first + lane] : 0;
+    SceneHook<MODEL, WIN, true> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
+                                     c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr, t_in, t_out);
+    hook.n_groups = G, hook.grp = grp, hook.rec = rec;
+    hook.l_pc = g_pc, hook.l_hfov = g_hfov, hook.l_vref = g_vref, hook.l_grp = g_of;
+    small_tick_body<MODEL>(d, len, nullptr, srv, 0u, 0, hook);
+    if (lane >= n) return;
+    c.sums[rider] = make_double2(hook.sse, hook.sae);
+    if (hook.smp != nullptr)
+        while (hook.taken < c.n_samples) hook.sample(d, lane);
+}
+
 // behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment
 template <int MODEL>
 struct SceneLaneHook {
     static constexpr bool MASKED = true;
     static constexpr bool SHARED = true;
+    static constexpr bool GROUPS = false;
     const SceneDev &c;
     const int64_t row0;           // set * R: first row of the set in sums and in a sample
     int cur = -1;                 // the rider this lane carries (0 .. R - 1), -1: nobody yet
@@ -429,9 +544,12 @@ int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const S
     if (count <= 0) return 0;
     const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
     const bool lanes = c.lane_off != nullptr;
+    const bool groups = c.group != nullptr && !lanes;         // (the host refuses groups on shared lanes)
 #define CSF_SCENE(MODEL)                                                                                                          \
     do {                                                                                                                          \
-        if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
+        if (groups && win) hipLaunchKernelGGL((scene_groups_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
+        else if (groups) hipLaunchKernelGGL((scene_groups_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);   \
+        else if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
         else if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
         else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
     } while (0)

@@ -18,9 +18,21 @@
 // 64 lanes at the head of tick t, before hook.present(t): a lane whose next occupant enters at t makes its slot that road user's
 // fresh vehicle.  The step holds no shuffle, ballot or barrier and stores to the lane's own slot only; what the other lanes read of
 // it they read afterwards, in program order - as they read the stores of the tick before.  With SHARED == false it is compiled out.
+//
+// HOOK::GROUPS (DESIGN.md 4.10g): the road users carry one of hook.n_groups parameter sets of the one vehicle class, Dev::p / pc / pb
+// being group 0's.  The parameters become a property of the road user:
+//   pair term        hook.consts(j) / hook.hfov(j) are the field constants and the field of view of SOURCE j's set (LDS, indexed by the
+//                    source's group: the loop over the sources keeps its order, so the sum of a receiver is formed in today's order
+//                    whatever the labels); hook.v_ref(lane) the v_max_riding[1] of the lane's own set for its Bicycle (e, ...) entry.
+//                    The priority rule stays Dev::p's - it belongs to the intersection (csf_pair.hip: launch_pair takes d.pc.p2r).
+//   per-agent tick   a loop over the groups, uniform: hook.select(dg, g) puts record g's p / pb into a copy of the Dev and the lanes
+//                    whose road user is of group g run agent_body on it; a group nobody present belongs to is skipped (a ballot).
+//                    n_groups is a kernel argument: no loop added here depends on the state for its end.
+// With GROUPS == false all of it is compiled out and the body is the one it was.
 struct NoTickHook {
     static constexpr bool MASKED = false;
     static constexpr bool SHARED = false;
+    static constexpr bool GROUPS = false;
     __device__ __forceinline__ void operator()(const Dev &, int, int, int) {}
 };
 
@@ -96,7 +108,9 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         if (lane < n) sx[lane] = x, sy[lane] = y, spsi[lane] = psi, scs[lane] = cp, ssn[lane] = sp;
         if (MODEL == CSF_BICYCLE && lane < n) {                    // (what write_record keeps in rec2 for the pair kernels)
             const double v = d.s[3 * cap + a];
-            const double e = v > 0.0 ? fmin(pow(v / d.p.v_max_riding[1], 0.1), 0.7) : 0.0;
+            double vref = d.p.v_max_riding[1];
+            if constexpr (HOOK::GROUPS) vref = hook.v_ref(lane);   // (the lane's own set: what write_record takes for rec2)
+            const double e = v > 0.0 ? fmin(pow(v / vref, 0.1), 0.7) : 0.0;
             se[lane] = make_float2((float)e, (float)(1.0 / sqrt(1.0 - e * e)));
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -106,6 +120,10 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         // (TWIN COPY: the pair loop of wide_tick_body, csf_wide_body.inc, is this loop for a workgroup; a change here is made there too)
         for (int j = grp; j < n; j += G) {                         // (lanes of one group: the same j)
             const double xs = sx[j], ys = sy[j], ps = spsi[j];
+            const PairConsts *kp = &k;                             // the SOURCE's field and field of view (intersection.py:733-735, 815)
+            double hfov = d.p.hfov;
+            if constexpr (HOOK::GROUPS) kp = hook.consts(j), hfov = hook.hfov(j);
+            const PairConsts &ks = *kp;
             const double ex = x - xs, ey = y - ys;                 // vehicle.py:1615-1616
             // the receiver itself and a road user on the very same spot (D2) add nothing
             if constexpr (HOOK::MASKED) {
@@ -115,20 +133,20 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             const float dx = (float)ex, dy = (float)ey, r2 = fmaxf(dx * dx + dy * dy, 1e-30f);
             const float4 q = make_float4(0.f, 0.f, (float)scs[j], (float)ssn[j]);
             bool edge;
-            bool seen = p2r ? tracked_precise<true>(k, k.chs, r, dx, dy, r2, edge) : tracked_precise<false>(k, k.chs, r, dx, dy, r2, edge);
-            if (edge) seen = !untracked_exact_xy(xs, ys, x, y, psi, d.p.hfov, p2r);   // (one pair in a million)
+            bool seen = p2r ? tracked_precise<true>(ks, ks.chs, r, dx, dy, r2, edge) : tracked_precise<false>(ks, ks.chs, r, dx, dy, r2, edge);
+            if (edge) seen = !untracked_exact_xy(xs, ys, x, y, psi, hfov, p2r);   // (one pair in a million)
             if (!seen) continue;
             int sg = 1;
             float F, gx, gy;
             if (MODEL == CSF_BICYCLE) {                             // vehicle.py:1054-1147: no jump at phi = 0
-                field_bicycle(k, q, se[j], dx, dy, r2, F, gx, gy);
+                field_bicycle(ks, q, se[j], dx, dy, r2, F, gx, gy);
             } else {
                 float sgf = 0.0f;                                   // 0: the sign of the fp32 sine
-                if (side_undecided(k, q, dx, dy, r2)) {
+                if (side_undecided(ks, q, dx, dy, r2)) {
                     sg = sign_phi_exact(xs, ys, ps, x, y);
                     sgf = sg < 0 ? -1.0f : 1.0f;
                 }
-                field_twod(k, r, q, dx, dy, r2, F, gx, gy, sgf);
+                field_twod(ks, r, q, dx, dy, r2, F, gx, gy, sgf);
             }
             double wx = (double)(F * gx), wy = (double)(F * gy);
             if (sg == 0) {                                          // phi = 0 exactly: no tangential part, |F| = P along the line
@@ -175,7 +193,18 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             if (mine) d.froad[lane] = make_float2(qx, qy);        // (agent_body reads it back: the same lane, program order)
         }
         __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
-        if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+        if constexpr (HOOK::GROUPS) {
+            Dev dg = d;
+#pragma nounroll
+            for (int g = 0; g < hook.n_groups; g++) {               // (uniform; the body of agent_body is emitted once, here)
+                const bool turn = mine && hook.grp == g;
+                if (__ballot(turn) == 0ull) continue;
+                hook.select(dg, g);
+                if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+            }
+        } else {
+            if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+        }
         hook(d, t, lane, n);
     }
     // csf_step_get_tick: what snapshot_kernel would pack in a launch of its own (slots are the population order here)

@@ -58,6 +58,12 @@ struct SceneCalibState {
     DevBuf<Dev> table_w;                     // [max_sets][n_wide]
     DevBuf<int32_t> scn_w, len_n, roff_n, lane_off_n;
     bool is_wide(size_t q) const { return wide_from > 0 && h_nl[q] >= wide_from; }
+    // csf_scene_calib_groups: rider groups with parameter sets of their own (DESIGN.md 4.10g).  n_groups == 0: none, an evaluation is
+    // handed group == NULL and launches what it launched before.  Else the call's table is [n_sets][n_groups] records in sets_g
+    int32_t n_groups = 0;
+    DevBuf<uint8_t> group;                   // [R]
+    DevBuf<SceneSet> sets_g;                 // [max_sets][n_groups]
+    std::unique_ptr<HostBuf<SceneSet, false>> sets_g_pin;
 };
 
 // The views on the device from the whole table [max_sets][n_scn] on the host: all of it in `table`, or - a wide load - the narrow
@@ -383,9 +389,69 @@ int csf_scene_calib_eval(csf_engine *e, int32_t n_sets, const csf_params *params
 // Dev::road_np of one sigma, as road_np_of decides it for a road whose edges share it
 static int32_t road_np_sigma(double sg) { return sg == std::floor(sg) && sg >= 1 && sg <= 5 ? (int32_t)sg + 1 : 0; }
 
+// csf_scene_calib_eval_road (n_groups == 0: one record per set) and csf_scene_calib_eval_groups (params is [n_sets][n_groups])
+static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params, size_t params_size, int32_t abi_version,
+                           const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out);
+
 int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version,
                               const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) try {
     if (!e) return CSF_E_ARG;
+    if (e->scene_calib && e->scene_calib->n_groups > 0)
+        return fail(e, CSF_E_STATE, "csf_scene_calib_eval: the riders are in %d groups (csf_scene_calib_groups) and one set cannot say what group 1 carries: csf_scene_calib_eval_groups",
+                    (int)e->scene_calib->n_groups);
+    return scene_eval_impl(e, n_sets, 0, params, params_size, abi_version, road_F0, road_sigma, sums_out, stride, states_out);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params, size_t params_size, int32_t abi_version,
+                                const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_eval_groups: no closed-loop data set (csf_scene_calib_load first)");
+    const int32_t held = e->scene_calib->n_groups > 0 ? e->scene_calib->n_groups : 1;
+    if (n_groups != held) return fail(e, CSF_E_ARG, "csf_scene_calib_eval_groups: %d groups, the data set holds %d (csf_scene_calib_groups)", (int)n_groups, (int)held);
+    // (no groups loaded: one record per set, the call is csf_scene_calib_eval_road)
+    return scene_eval_impl(e, n_sets, e->scene_calib->n_groups, params, params_size, abi_version, road_F0, road_sigma, sums_out, stride, states_out);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {
+    if (!e) return CSF_E_ARG;
+    if (!e->scene_calib) {
+        if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_groups: the engine holds the data set of csf_calib_load, whose candidate sets are whole populations already");
+        return fail(e, CSF_E_STATE, "csf_scene_calib_groups: no closed-loop data set (csf_scene_calib_load first)");
+    }
+    SceneCalibState &cs = *e->scene_calib;
+    if (cs.Lsum > 0)
+        return fail(e, CSF_E_STATE, "csf_scene_calib_groups: the data set shares its lanes (csf_scene_calib_load_shared / _load_wide): a lane's parameters would change with its rider; groups need csf_scene_calib_load");
+    const bool drop = group == nullptr || n_groups <= 1;
+    if (!drop) {
+        if (n_groups > SCENE_GROUPS_MAX) return fail(e, CSF_E_ARG, "csf_scene_calib_groups: %d groups (at most %d)", (int)n_groups, SCENE_GROUPS_MAX);
+        for (int32_t r = 0; r < cs.R; r++)
+            if (group[r] >= n_groups) return fail(e, CSF_E_ARG, "csf_scene_calib_groups: rider %d is in group %d of %d", (int)r, (int)group[r], (int)n_groups);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // everything that can fail first: a refused call changes nothing
+    DevBuf<uint8_t> d_group;
+    DevBuf<SceneSet> d_sets;
+    std::unique_ptr<HostBuf<SceneSet, false>> pin;
+    if (!drop) {
+        const size_t recs = (size_t)cs.max_sets * (size_t)n_groups;
+        pin.reset(new HostBuf<SceneSet, false>());
+        hipError_t r = d_group.alloc((size_t)cs.R);
+        if (r == hipSuccess) r = d_sets.alloc(recs);
+        if (r == hipSuccess) r = pin->alloc(recs);
+        if (r == hipSuccess) r = hipMemcpy(d_group.p, group, (size_t)cs.R, hipMemcpyHostToDevice);
+        if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_groups: no memory for the groups: %s", hipGetErrorString(r));
+        std::memset(pin->p, 0, recs * sizeof(SceneSet));
+    }
+    cs.group = std::move(d_group);
+    cs.sets_g = std::move(d_sets);
+    cs.sets_g_pin = std::move(pin);
+    cs.n_groups = drop ? 0 : n_groups;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params, size_t params_size, int32_t abi_version,
+                           const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) {
     if (!e->scene_calib) return fail(e, CSF_E_STATE, "csf_scene_calib_eval: no closed-loop data set (csf_scene_calib_load first)");
     // before anything is read from `params` (csf_create_v)
     if (params_size != sizeof(csf_params) || abi_version != CSF_ABI_VERSION)
@@ -395,7 +461,8 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
     if (!params || !sums_out) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: NULL array");
     if (n_sets < 1 || n_sets > cs.max_sets) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: %d parameter sets, the data set was loaded for 1 .. %d", (int)n_sets, (int)cs.max_sets);
     if (stride < 1) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: stride must be >= 1");
-    for (int32_t k = 0; k < n_sets; k++) {
+    const int32_t G = n_groups > 0 ? n_groups : 1;            // records per candidate set
+    for (int32_t k = 0; k < n_sets * G; k++) {
         int rc = check_params(e, params + k);
         if (rc) return rc;
         if (params[k].model != e->d.p.model) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d is of vehicle class %d, the data set was loaded for class %d", (int)k, (int)params[k].model, (int)e->d.p.model);
@@ -435,23 +502,29 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
     // and side decisions (consts.inc: fov_band_consts) are those of the largest coordinate any rider can reach in n_ticks from the
     // start of its scene with the set's speed clamp: conservative for every tick, and inside a band the kernel decides by the
     // reference's fp64 chain, so its width changes no result.
-    for (int32_t k = 0; k < n_sets; k++) {
-        SceneSet &ss = cs.sets_pin.p[k];
+    SceneSet *const pin = n_groups > 0 ? cs.sets_g_pin->p : cs.sets_pin.p;
+    for (int32_t k = 0; k < n_sets * G; k++) {
+        SceneSet &ss = pin[k];
         std::memset(&ss, 0, sizeof ss);
         ss.p = params[k];
+        // (groups: the rule belongs to the intersection - the candidate's first record has it, as csf_set_param_classes gives every set
+        // the engine's)
+        if (n_groups > 0) ss.p.priority_rule = params[k - k % G].priority_rule;
         // (derive_consts without update_far_radius: rfar, reach and tA0 .. tB1 stay 0.  They are the cull of the pair kernels
         // (csf_field.h: keep_x2) and depend on the population size, which differs from scene to scene; the one-wave tick culls
         // nothing and reads none of them.  A tick that does must get them per (set, scene), not from this record.)
         derive_pair_consts(ss.p, ss.pc, e->knobs.rnear);
         if (ss.p.model == CSF_PLANARBIKE) derive_planarbike(ss.p, ss.pb);
-        const double vmax = std::max({std::fabs(ss.p.v_max_riding[0]), std::fabs(ss.p.v_max_riding[1]), std::fabs(ss.p.v_max_walk)});
+        double vmax = 0.0;                                      // (groups: the largest clamp among the candidate's records)
+        for (int32_t g = k - k % G; g < k - k % G + G; g++)
+            vmax = std::max({vmax, std::fabs(params[g].v_max_riding[0]), std::fabs(params[g].v_max_riding[1]), std::fabs(params[g].v_max_walk)});
         const double step = ss.p.t_s * vmax * 1.01 + 1e-4;
         // (a replayed rider is not bound by the set's clamp: it goes where its recording goes)
         fov_band_consts(e->knobs, step, std::max(cs.coord_bound + step * (double)(cs.n_ticks + 2), cs.rep_bound) + 1.0, ss.pc);
         if (road_over) {   // (the roundings of pack_road)
-            ss.road_z = (float)(-road_F0[k]);
-            ss.road_w = (float)(-0.5 * (road_sigma[k] + 1.0));
-            ss.road_np = road_np_sigma(road_sigma[k]);
+            ss.road_z = (float)(-road_F0[k / G]);
+            ss.road_w = (float)(-0.5 * (road_sigma[k / G] + 1.0));
+            ss.road_np = road_np_sigma(road_sigma[k / G]);
         }
     }
     SceneDev c{};
@@ -481,15 +554,17 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
         // a lane writes the sample rows of the rider it carries at the ticks that rider is present: every other row is NaN
         if (n_states > 0) HIPCHK(e, hipMemsetAsync(cs.states.p, 0xff, n_states * sizeof(double), e->main));
     }
-    HIPCHK(e, hipMemcpyAsync(cs.sets.p, cs.sets_pin.p, (size_t)n_sets * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
+    SceneSet *const d_sets = n_groups > 0 ? cs.sets_g.p : cs.sets.p;
+    if (n_groups > 0) c.group = cs.group.p, c.n_groups = n_groups;
+    HIPCHK(e, hipMemcpyAsync(d_sets, pin, (size_t)n_sets * (size_t)G * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     if (cs.wide_from > 0) {   // the narrow scenes on scene_lanes_kernel, the wide ones on scene_wide_kernel: one stream, one wait
         SceneWideDev w{};
         w.table_w = cs.table_w.p, w.scn_w = cs.scn_w.p;
         w.n_wide = (int32_t)cs.h_scn_w.size(), w.n_narrow = (int32_t)cs.h_scn_n.size();
         w.len_n = cs.len_n.p, w.roff_n = cs.roff_n.p, w.lane_off_n = cs.lane_off_n.p;
-        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main, &w);
+        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main, &w);
     } else {
-        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, cs.sets.p, c, e->main);
+        cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main);
     }
     HIPCHK(e, hipGetLastError());
     if (n_states > 0) HIPCHK(e, hipMemcpyAsync(states_out, cs.states.p, n_states * sizeof(double), hipMemcpyDeviceToHost, e->main));
@@ -500,7 +575,7 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
     e->mid_synced = false;
     e->bounds_fresh = false;
     return CSF_OK;
-} catch (...) { return csf_caught(e); }
+}
 
 int csf_scene_calib_road(csf_engine *e, int32_t n_edges, const int32_t *edge_scene, const int64_t *offsets, const double *xy, const double *F0,
                          const double *sigma) try {

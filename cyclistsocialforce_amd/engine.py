@@ -408,6 +408,45 @@ class Engine:
             raise ValueError("enter and exit must have one entry per rider of the data set")
         self._ck(self._lib.csf_scene_calib_windows(self._h, _ptr(en), _ptr(ex)))
 
+    def scene_calib_groups(self, group, n_groups=None):
+        """Rider GROUPS of the loaded scenes (scene_calib_load only), each with parameter sets of its own: group [R] (integers
+        0 .. n_groups - 1), n_groups <= 4 (default: the largest entry + 1).  None, or n_groups <= 1, drops the groups.  With groups
+        loaded an evaluation is scene_calib_eval_groups; scene_calib_eval is refused."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_groups: no closed-loop data set (scene_calib_load first)")
+        R, _ = self._scene_calib
+        if group is None:
+            self._ck(self._lib.csf_scene_calib_groups(self._h, None, 0))
+            return
+        g = np.asarray(group)
+        if g.shape != (R,) or g.dtype.kind not in "iub":
+            raise ValueError("group must have one integer entry per rider of the data set")
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("group: entries are 0 .. n_groups - 1")
+        g8 = np.ascontiguousarray(g, dtype=np.uint8)
+        self._ck(self._lib.csf_scene_calib_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+
+    def scene_calib_eval_groups(self, pods, road_F0=None, road_sigma=None, states=False, stride=1):
+        """scene_calib_eval for riders in groups: `pods` is a sequence of n_groups-tuples of csf_params, tuple k the candidate k and
+        its entry g what the riders of group g carry.  A rider is simulated with its own set and acts on the others with its own
+        set's field and field of view; the priority rule of a candidate is its first entry's.  Returns what scene_calib_eval returns."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_eval_groups: no closed-loop data set (scene_calib_load first)")
+        R, T = self._scene_calib
+        pods = [tuple(p) if isinstance(p, (tuple, list)) else (p,) for p in pods]
+        if not pods or any(len(p) != len(pods[0]) or not p for p in pods):
+            raise ValueError("pods: a non-empty sequence of tuples of one length, one csf_params per group")
+        G = len(pods[0])
+        tab = (Params * (len(pods) * G))(*[p for t in pods for p in t])
+        sums = np.zeros((len(pods), R, 2))
+        out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * R, self.ns)) if states else None
+        f0 = None if road_F0 is None else _f64(np.broadcast_to(np.asarray(road_F0, dtype=np.float64), (len(pods),)))
+        sg = None if road_sigma is None else _f64(np.broadcast_to(np.asarray(road_sigma, dtype=np.float64), (len(pods),)))
+        self._ck(self._lib.csf_scene_calib_eval_groups(self._h, len(pods), G, tab, C.sizeof(Params), _ffi.ABI_VERSION,
+                                                       None if f0 is None else _ptr(f0), None if sg is None else _ptr(sg), _ptr(sums),
+                                                       int(stride), None if out is None else _ptr(out)))
+        return (sums, out) if states else sums
+
     def scene_calib_clear(self):
         self._ck(self._lib.csf_scene_calib_clear(self._h))
         self._scene_calib = None

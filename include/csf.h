@@ -400,8 +400,9 @@ int csf_small_ticks(const csf_engine *e, int64_t *n_ticks);
 /* Ticks this engine has run as ONE launch each (ABI 7; csf_mid.hip).  Between 33 and ~3 000 road users of one parameter set on
  * one device - BASELINE config 2, and what the reference runs under SUMO - a tick is launch latency, not work: the pair sums
  * of a receiver group (intersection.py:690-745, 814-843) and the per-agent tick of its road users (:841-862, 891-892) share
- * one grid, the group's last workgroup to finish its sums carrying on with the road users; the next tick's records go to the
- * other half of a double buffer.  CSF_FUSED_MID=0, a pinned CSF_PAIR_VARIANT or per-kernel profiling keep the two launches. */
+ * one grid, ONE workgroup per receiver group: its first wave runs the destination-force phase while the others form the pair
+ * sums, and behind the workgroup's barrier the same wave carries on with the group's road users; the
+ * next tick's records go to the other half of a double buffer.  CSF_FUSED_MID=0, a pinned CSF_PAIR_VARIANT or per-kernel profiling keep the two launches. */
 int csf_mid_ticks(const csf_engine *e, int64_t *n_ticks);
 /* Ticks whose per-agent launch ran BESIDE the pair launch that feeds it (ABI 9).  From a few thousand road users
  * of one TwoD-field class on one device, a tick of csf_step(e, n >= 4) is a pair launch on one of the engine's two streams and the
@@ -554,7 +555,29 @@ int csf_calib_clear(csf_engine *e);
  * takes 256, 128 or 64 vertices (padded).  csf_scene_calib_replay, both evaluation calls, csf_scene_calib_launches, csf_scene_calib_clear and the
  * refusals while a data set is held are those of any data set; csf_scene_calib_windows is refused as after csf_scene_calib_load_shared.
  * Refused with the engine empty and usable: everything csf_scene_calib_load_shared refuses with 256 in the place of 32, and CSF_E_ARG
- * for wide_from outside 1 .. 257.  csf_scene_calib_load and csf_scene_calib_load_shared keep their limit of 32. */
+ * for wide_from outside 1 .. 257.  csf_scene_calib_load and csf_scene_calib_load_shared keep their limit of 32.
+ *
+ * csf_scene_calib_groups gives the riders of the held data set GROUPS that carry parameter sets of their own -
+ * e-bikes and city bikes, commuters and children: group [R] holds 0 .. n_groups - 1 per rider, n_groups <= 4.  It may be called any
+ * number of times between evaluations on an engine that holds a csf_scene_calib_load data set; NULL or n_groups <= 1 drops the groups, and
+ * evaluations are then what they were, bit for bit.  Refused with a message and nothing changed: CSF_E_STATE without a closed-loop data
+ * set (the data set of csf_calib_load included) and after csf_scene_calib_load_shared / _load_wide; CSF_E_ARG for n_groups > 4 and for an
+ * entry >= n_groups.  Device buffers are allocated and filled before anything is replaced; csf_scene_calib_clear frees them.
+ *
+ * csf_scene_calib_eval_groups evaluates n_sets candidates of n_groups parameter sets each: params [n_sets][n_groups], record (k, g) what
+ * the riders of group g carry in candidate k; everything else - road_F0 / road_sigma (NULL or [n_sets], per candidate), sums_out,
+ * stride, states_out and their layout - is csf_scene_calib_eval_road's.  A rider is ticked with its own record and restored with its
+ * limits; as a source of the field it acts with its own record's field and field of view (intersection.py:733-735, 815), replayed riders
+ * included; the priority rule of a candidate is record (k, 0)'s (it belongs to the intersection, as under csf_set_param_classes) and
+ * the rounding bands take the largest speed clamp among the candidate's records.  n_groups must equal the loaded one (CSF_E_ARG), every
+ * record is checked as csf_scene_calib_eval checks a set and must be of the engine's vehicle class (CSF_E_ARG).  Without loaded groups
+ * n_groups must be 1 and the call IS csf_scene_calib_eval_road.  While groups are loaded csf_scene_calib_eval and
+ * csf_scene_calib_eval_road are refused with CSF_E_STATE: one set cannot say what group 1 carries. */
+int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
+int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params,
+                                size_t params_size, int32_t abi_version,
+                                const double *road_F0, const double *road_sigma,
+                                double *sums_out, int32_t stride, double *states_out);
 int csf_scene_calib_load_wide(csf_engine *e, int32_t n_scn, const int32_t *n_riders, const int32_t *n_lanes,
                               const int32_t *lane, const int32_t *enter, const int32_t *exit, int64_t n_ticks,
                               const double *s0, const double *v_desired,

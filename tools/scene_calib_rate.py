@@ -35,7 +35,13 @@ density of 32 in 30 m; the data set is loaded by csf_scene_calib_load_wide (--wi
 per kind of scene.  The baseline leg is the tool's own: one engine per (set, scene) stepped on the engine's own path.  The option
 stands alone: not with --replay, --road or --presence.
 
-    python tools/scene_calib_rate.py [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
+--groups G puts rider r of every scene into group r % G (G = 2: every second rider in group 1), group g carrying the
+candidate's set with f_0 x (1 + 0.1 g), and adds `groups_ms`: csf_scene_calib_groups + csf_scene_calib_eval_groups, one launch per
+evaluation.  Its baseline (`groups_base_ms`, built for up to --groups-base-max sets) is what a caller had before: one engine per (set,
+scene) that holds the G sets as parameter classes - such an engine is on the general path and a batch steps it in turn -, per call the
+start states pushed back, csf_step for all ticks with csf_record, the recorded states read back and the NumPy error.
+
+    python tools/scene_calib_rate.py [--groups 2 [--groups-base-max 16]] [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
                                      [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
                                      [--riders 40,96 [--wide-from 33]]
 """
@@ -97,10 +103,14 @@ def main():
     ap.add_argument("--share-peak", type=int, default=6)
     ap.add_argument("--riders", default=None)
     ap.add_argument("--wide-from", type=int, default=33)
+    ap.add_argument("--groups", type=int, default=0)
+    ap.add_argument("--groups-base-max", type=int, default=16)
     a = ap.parse_args()
     riders = [int(x) for x in a.riders.split(",")] if a.riders else None
     if riders and (a.replay or a.road or a.presence or min(riders) < 1 or max(riders) > 256):
         ap.error("--riders takes 1 .. 256 road users per scene and stands alone: not with --replay, --road or --presence")
+    if a.groups and (riders or not 2 <= a.groups <= 4):
+        ap.error("--groups takes 2 .. 4 and does not go with --riders (groups run on csf_scene_calib_load)")
     if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
         ap.error("--share goes with --presence and 1 <= --share-peak <= --share-roster <= 32")
     feat = np.array([0, 1], dtype=np.int32)
@@ -259,6 +269,65 @@ def main():
                             replay_ms=dict(median=float(np.median(t_rep)), min=min(t_rep), max=max(t_rep)),
                             replay_base_ms=dict(median=float(np.median(t_rold)), min=min(t_rold), max=max(t_rold)) if t_rold else None,
                             replay_base_over_replay=float(np.median(t_rold) / np.median(t_rep)) if t_rold else None)
+            if a.groups:
+                G = a.groups
+                if a.replay:
+                    e.scene_calib_replay(None)
+                grp = np.concatenate([np.arange(n) % G for n in nr]).astype(np.uint8)
+                tups = []
+                for p in sets:
+                    tup = []
+                    for g in range(G):
+                        c = _ffi.Params.from_buffer_copy(p)
+                        c.f_0, c.p_0 = p.f_0 * (1.0 + 0.1 * g), p.p_0 * (1.0 + 0.1 * g)
+                        tup.append(c)
+                    tups.append(tuple(tup))
+                e.scene_calib_groups(grp, G)
+                gtwins = []
+                if n_sets <= a.groups_base_max:
+                    for tup in tups:
+                        for q, (s, o, d) in enumerate(per):
+                            t = Engine(tup[0], s.shape[0])
+                            t.set_param_classes(list(tup))
+                            t.add_agents(s, 5.0)
+                            t.set_agent_class(np.arange(s.shape[0]), grp[roff[q]: roff[q + 1]])
+                            t.set_dest_queue(np.arange(s.shape[0]), o, d, reset=True)
+                            if a.road:
+                                t.set_road(*road)
+                            t.record(stride=1, capacity=a.ticks, forces=False)
+                            gtwins.append(t)
+
+                def groups_new():
+                    return e.scene_calib_eval_groups(tups)[:, :, 0].sum(axis=1)
+
+                g_calls = [0]                                   # (csf_record numbers its samples from the engine's first tick)
+
+                def groups_old():
+                    err = np.zeros(n_sets)
+                    for i, t in enumerate(gtwins):
+                        s = per[i % a.scenes][0]
+                        t.push_state(np.arange(s.shape[0]), s)
+                        t.set_dest_pointer(np.arange(s.shape[0]), 0)
+                        t.step(a.ticks)
+                    for i, t in enumerate(gtwins):
+                        q = i % a.scenes
+                        S, _ = t.recorded(g_calls[0] * a.ticks, a.ticks)
+                        err[i // a.scenes] += float(np.square(S[:, :, feat] - obj[:, roff[q]: roff[q + 1]]).sum())
+                    g_calls[0] += 1
+                    return err
+
+                first_g = groups_new()
+                g_gap = float(np.abs(groups_old() / first_g - 1.0).max()) if gtwins else None
+                t_g, t_gold = [], []
+                for _ in range(a.windows):
+                    t0 = time.perf_counter(); groups_new(); t_g.append((time.perf_counter() - t0) * 1e3)
+                    if gtwins:
+                        t0 = time.perf_counter(); groups_old(); t_gold.append((time.perf_counter() - t0) * 1e3)
+                line.update(groups=G, groups_first_call_rel_gap=g_gap,
+                            groups_ms=dict(median=float(np.median(t_g)), min=min(t_g), max=max(t_g)),
+                            groups_base_ms=dict(median=float(np.median(t_gold)), min=min(t_gold), max=max(t_gold)) if t_gold else None)
+                for t in gtwins:
+                    t.close()
             print(json.dumps(line), flush=True)
             if a.out:
                 with open(a.out, "a") as f:
