@@ -48,8 +48,16 @@
 // n_groups records per candidate set, a rider is ticked with its group's record and acts as a source with that record's field and field
 // of view (csf_small_body.inc: HOOK::GROUPS).  A data set without groups launches scene_eval_kernel, where none of this exists.
 //
+// What exists once ("Folded"): scene_rider_step - the replay write-back or the error terms behind a tick, called by both
+// hooks -, and for_vehicle_class, which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
+// slot becomes a fresh vehicle from the image - serves scene_groups_kernel and SceneLaneHook::seat; scene_eval_kernel has the same lines
+// written out.  The per-set prologue is written out in all four kernels, and scene_groups_kernel / scene_wide_kernel repeat the skeleton
+// of scene_eval_kernel / scene_lanes_kernel: with one function for either, sums and states were no longer the parent's bit for bit.
+//
 // The Dev is copied into the kernel (read through a reference to global memory the compiler contracted a few fp64
 // chains differently).  A scene that has ended keeps its last state in every later sample of the optional trajectories.
+#include <type_traits>
+
 #include "csf_agent_dev.h"
 #include "csf_field.h"
 #include "csf_scene.h"
@@ -58,6 +66,69 @@ namespace csf {
 
 #include "csf_small_body.inc"
 #include "csf_wide_body.inc"
+
+// slot `slot` of the block becomes the fresh vehicle of rider `rider` (row of the image): Vehicle.__init__ (vehicle.py:64-204,
+// 1728-1736), see patch_kernel's spawn.  The walk limits are those of the rider's own parameter set.  An array added to the image
+// goes in here and into the copy at the head of scene_eval_kernel.
+__device__ __forceinline__ void scene_restore(const Dev &d, const SceneDev &c, int64_t slot, int64_t rider, double v_max_walk,
+                                              double delta_max_walk) {
+    const int64_t a = slot, r = rider, cap = d.cap, ic = c.img_cap;
+#pragma unroll
+    for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
+#pragma unroll
+    for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
+#pragma unroll
+    for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
+#pragma unroll
+    for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
+    d.ppsi[a] = c.img_ppsi[r];
+    d.ti[a] = c.img_ti[r];
+    d.status[a] = c.img_status[r];
+    d.ptr[a] = c.img_ptr[r];
+    d.znav[a] = c.img_znav[r];
+    d.hx[a] = c.img_hx0[r];
+    d.hy[a] = c.img_hy0[r];
+    const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
+    d.zrid[a] = v < v_max_walk ? 0 : 1;
+    d.dgood[a] = (-delta_max_walk < delta && delta_max_walk > delta) ? 1 : 0;
+}
+
+// behind tick t, for a lane whose rider is present: a replayed rider (rep: its recorded (x, y, psi, v) after tick 0) takes the
+// recorded row, a simulated one adds its error terms against obj (its objective at tick 0) to sse / sae
+template <int MODEL>
+__device__ __forceinline__ void scene_rider_step(const Dev &d, const SceneDev &c, int t, int lane, const double *rep, const double *obj,
+                                                 double &sse, double &sae) {
+    if (rep != nullptr) {
+        // vehicle.s written from the recording (calibration.py:455-460) and what csf_push_state keeps consistent with it
+        // (abi_population.inc): this lane's own stores behind its tick's, program order.  Nothing is added to sse / sae.
+        const double *r = rep + (int64_t)t * c.n_rep * 4;
+        const double x = r[0], y = r[1], psi = r[2], v = r[3];
+        const int64_t cap = d.cap;
+        d.s[lane] = x;
+        d.s[cap + lane] = y;
+        d.s[2 * cap + lane] = psi;
+        d.s[3 * cap + lane] = v;
+        if (MODEL == CSF_BALANCINGRIDER) {                // (ppsi is the speed of the gains there; the yaw is -x[4], unwrapped)
+            const double twopi = 6.283185307179586476925286766559, own = d.lti[4 * cap + lane];
+            d.lti[4 * cap + lane] = -psi + twopi * nearbyint((own + psi) / twopi);
+        } else {
+            d.ppsi[lane] = psi;
+        }
+        const int64_t slot = d.ti[lane] & (d.hist_len - 1);
+        d.hx[slot * cap + lane] = x;
+        d.hy[slot * cap + lane] = y;
+    } else {
+        const double *o = obj + (int64_t)t * c.R * c.n_feat;
+        for (int k = 0; k < c.n_feat; k++) {
+            const int f = c.feat[k];
+            // (a row the class does not have stays zero in the reference's traj: vehicle.py:158-160)
+            const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
+            const double e = sv - o[k];                   // a plain difference, no angle wrap: calibration.py:49, 76
+            sse += e * e;
+            sae += fabs(e);
+        }
+    }
+}
 
 // what SceneHook holds of the rider groups (csf_small_body.inc: HOOK::GROUPS): nothing without them
 template <bool GRP>
@@ -110,38 +181,8 @@ struct SceneHook : SceneGroupPart<GRP> {
     }
     __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
         if (lane >= n) return;
-        if (WIN && !(t_in <= t && t < t_out)) {
-            // not in the scene: nothing of a recording is written, nothing is summed; a sample shows what the slot holds
-        } else if (rep != nullptr) {
-            // vehicle.s written from the recording (calibration.py:455-460) and what csf_push_state keeps consistent with it
-            // (abi_population.inc): this lane's own stores behind its tick's, program order.  Nothing is added to sse / sae.
-            const double *r = rep + (int64_t)t * c.n_rep * 4;
-            const double x = r[0], y = r[1], psi = r[2], v = r[3];
-            const int64_t cap = d.cap;
-            d.s[lane] = x;
-            d.s[cap + lane] = y;
-            d.s[2 * cap + lane] = psi;
-            d.s[3 * cap + lane] = v;
-            if (MODEL == CSF_BALANCINGRIDER) {                // (ppsi is the speed of the gains there; the yaw is -x[4], unwrapped)
-                const double twopi = 6.283185307179586476925286766559, own = d.lti[4 * cap + lane];
-                d.lti[4 * cap + lane] = -psi + twopi * nearbyint((own + psi) / twopi);
-            } else {
-                d.ppsi[lane] = psi;
-            }
-            const int64_t slot = d.ti[lane] & (d.hist_len - 1);
-            d.hx[slot * cap + lane] = x;
-            d.hy[slot * cap + lane] = y;
-        } else {
-            const double *o = obj + (int64_t)t * c.R * c.n_feat;
-            for (int k = 0; k < c.n_feat; k++) {
-                const int f = c.feat[k];
-                // (a row the class does not have stays zero in the reference's traj: vehicle.py:158-160)
-                const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
-                const double e = sv - o[k];                   // a plain difference, no angle wrap: calibration.py:49, 76
-                sse += e * e;
-                sae += fabs(e);
-            }
-        }
+        // (not in the scene: nothing of a recording is written, nothing is summed; a sample shows what the slot holds)
+        if (!WIN || (t_in <= t && t < t_out)) scene_rider_step<MODEL>(d, c, t, lane, rep, obj, sse, sae);
         if (smp != nullptr) {
             if (wait == 0) {
                 sample(d, lane);
@@ -166,8 +207,8 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
 #pragma unroll
         for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
         // road parameters of this set: the scene's road with (-F0, -(sigma + 1) / 2) of the set on every vertex - padding keeps
-        // F0 = 0 - goes to this workgroup's own block, and the tick stages it from there.  small_tick_body reads rv[v] for
-        // v = lane, lane + 64, ...: what the same lane has stored here, program order - as the restored block below.
+        // F0 = 0 - goes to this workgroup's own block, and the tick stages it from there.  The tick reads rv[v] for v = thread,
+        // thread + WAVE, ...: what the same lane has stored here, program order - as the restored block below.
         if (c.road_blk != nullptr && d.nv_pad > 0) {
             float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
             const int nv = (int)d.nv, nvp = (int)d.nv_pad;
@@ -181,11 +222,12 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
         }
     }
     const int lane = (int)threadIdx.x, n = (int)d.n;
-    const int64_t cap = d.cap, first = c.roff[scn];
+    const int64_t first = c.roff[scn];
     const int len = c.len[scn];
-    // (TWIN COPY: SceneLaneHook::seat below restores a lane's newcomer the same way)
-    if (lane < n) {   // Vehicle.__init__ for this rider (vehicle.py:64-204, 1728-1736): see patch_kernel's spawn
-        const int64_t a = lane, r = first + lane, ic = c.img_cap;
+    // The restore written out, a second copy of scene_restore: with the call in its place scene_eval_kernel<InvPendulum, false> takes
+    // 0.7 - 1.1 % longer on scenes with a road ("Folded").  An array added to the image goes into both.
+    if (lane < n) {
+        const int64_t a = lane, r = first + lane, cap = d.cap, ic = c.img_cap;
 #pragma unroll
         for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
 #pragma unroll
@@ -208,9 +250,8 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
     // (the restored block is read by every lane of this wave in the first tick: the wave's own stores, program order - as from
     // tick to tick in small_tick_body)
     const int64_t rider = (int64_t)set * c.R + first + lane;
-    // (rep_index is read by the lanes that have a rider only: it has R entries)
+    // (rep_index, win_enter / win_exit and group have R entries: read by the lanes that have a rider only)
     const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
-    // (win_enter / win_exit have R entries, as rep_index)
     const int t_in = WIN && lane < n ? c.win_enter[first + lane] : 0, t_out = WIN && lane < n ? c.win_exit[first + lane] : 0;
     SceneHook<MODEL, WIN> hook(c, rider, c.obj + (first + lane) * c.n_feat, rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr,
                                c.states != nullptr && lane < n ? c.states + rider * d.ns : nullptr, t_in, t_out);
@@ -225,8 +266,8 @@ __global__ __launch_bounds__(64) void scene_eval_kernel(const Dev *__restrict__ 
 // Rider groups (csf_scene_calib_groups): scene_eval_kernel with the parameters a property of the RIDER.  `sets` holds
 // c.n_groups records per candidate set; Dev::p / pc / pb become record 0's (the priority rule and the road entries are the set's), the
 // restore takes the limits of the rider's own record, and the tick reads the rest through the hook (csf_small_body.inc: HOOK::GROUPS).
-// TWIN COPY of scene_eval_kernel's prologue, restore and epilogue, kept apart so that its instances come out of the compiler as they
-// were; an array added to the image goes into all three.
+// The kernel is scene_eval_kernel line for line around the staging of the groups - prologue, hook, epilogue: a change to one is made in
+// the other.  The two are not one body, and the prologue is not one function: either gave other bits ("Folded").
 template <int MODEL, bool WIN>
 __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
     extern __shared__ float4 srv[];                           // as scene_eval_kernel
@@ -245,7 +286,7 @@ __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict_
         d.pc = ss.pc;
 #pragma unroll
         for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
-        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: a copy of scene_eval_kernel's lines, one of four
             float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
             const int nv = (int)d.nv, nvp = (int)d.nv_pad;
             for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
@@ -258,9 +299,9 @@ __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict_
         }
     }
     const int lane = (int)threadIdx.x, n = (int)d.n;
-    const int64_t cap = d.cap, first = c.roff[scn];
+    const int64_t first = c.roff[scn];
     const int len = c.len[scn];
-    // (group has R entries, as rep_index; an entry the host has checked, clamped all the same: it indexes LDS)
+    // (an entry the host has checked, clamped all the same: it indexes LDS)
     int grp = lane < n ? (int)c.group[first + lane] : 0;
     grp = grp < G ? grp : G - 1;
     // the groups' constants to LDS: lane g < G copies record g word by word; then the wave's own stores, program order (as sx, sy)
@@ -272,28 +313,7 @@ __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict_
     if (lane < SMALL_MAX) g_of[lane] = (uint8_t)grp;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (lane < n) {   // Vehicle.__init__ for this rider: TWIN COPY of scene_eval_kernel's restore, the limits those of the rider's own set
-        const int64_t a = lane, r = first + lane, ic = c.img_cap;
-#pragma unroll
-        for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
-        d.ppsi[a] = c.img_ppsi[r];
-        d.ti[a] = c.img_ti[r];
-        d.status[a] = c.img_status[r];
-        d.ptr[a] = c.img_ptr[r];
-        d.znav[a] = c.img_znav[r];
-        d.hx[a] = c.img_hx0[r];
-        d.hy[a] = c.img_hy0[r];
-        const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
-        const double vw = rec[grp].p.v_max_walk, dw = rec[grp].p.delta_max_walk;
-        d.zrid[a] = v < vw ? 0 : 1;
-        d.dgood[a] = (-dw < delta && dw > delta) ? 1 : 0;
-    }
+    if (lane < n) scene_restore(d, c, lane, first + lane, rec[grp].p.v_max_walk, rec[grp].p.delta_max_walk);
     const int64_t rider = (int64_t)set * c.R + first + lane;
     const int rcol = c.rep != nullptr && lane < n ? c.rep_index[first + lane] : -1;
     const int t_in = WIN && lane < n ? c.win_enter[first + lane] : 0, t_out = WIN && lane < n ? c.win_exit[first + lane] : 0;
@@ -330,30 +350,12 @@ struct SceneLaneHook {
         nxt = r;
         nxt_in = r >= 0 ? c.win_enter[r] : 0x7fffffff;
     }
-    // the lane's slot becomes rider r's fresh vehicle - Vehicle.__init__ as at the head of scene_eval_kernel, and what was constant
-    // per slot there - and the lane's registers become r's.  TWIN COPY: the restore at the head of scene_eval_kernel (above); an
-    // array added to the image goes into both.  (Kept apart so that scene_eval_kernel's instances come out of the compiler as they
-    // were: DESIGN.md 4.10e.)
+    // the lane's slot becomes rider r's fresh vehicle - what scene_eval_kernel restores at its head, and what was constant per slot
+    // there - and the lane's registers become r's
     __device__ __forceinline__ void seat(const Dev &d, int lane, int r) {
-        const int64_t a = lane, cap = d.cap, ic = c.img_cap;
-#pragma unroll
-        for (int k = 0; k < STATE_ROWS; k++) d.s[k * cap + a] = c.img_s[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 5; k++) d.lti[k * cap + a] = c.img_lti[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 3; k++) d.znp[k * cap + a] = c.img_znp[k * ic + r];
-#pragma unroll
-        for (int k = 0; k < 6; k++) d.F[k * cap + a] = 0.0;
-        d.ppsi[a] = c.img_ppsi[r];
-        d.ti[a] = c.img_ti[r];
-        d.status[a] = c.img_status[r];
-        d.ptr[a] = c.img_ptr[r];
-        d.znav[a] = c.img_znav[r];
-        d.hx[a] = c.img_hx0[r];
-        d.hy[a] = c.img_hy0[r];
-        const double v = c.img_s[3 * ic + r], delta = c.img_s[4 * ic + r];
-        d.zrid[a] = v < d.p.v_max_walk ? 0 : 1;
-        d.dgood[a] = (-d.p.delta_max_walk < delta && d.p.delta_max_walk > delta) ? 1 : 0;
+        const int64_t a = lane;
+        scene_restore(d, c, a, r, d.p.v_max_walk, d.p.delta_max_walk);
+        // (what scene_eval_kernel's riders keep from the load of the data set: a slot is theirs alone there)
         d.vdes[a] = c.img_vdes[r];
         d.qbeg[a] = c.img_qbeg[r];
         d.qlen[a] = c.img_qlen[r];
@@ -382,37 +384,7 @@ struct SceneLaneHook {
     __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
         if (lane >= n) return;
         const bool here = t_in <= t && t < t_out;
-        if (!here) {
-            // the lane is empty at this tick
-        } else if (rep != nullptr) {
-            // TWIN COPY of SceneHook::operator()'s replay branch (and the error branch below of its error branch): the lane's own
-            // stores behind its tick's.  A change there is made here too.
-            const double *r = rep + (int64_t)t * c.n_rep * 4;
-            const double x = r[0], y = r[1], psi = r[2], v = r[3];
-            const int64_t cap = d.cap;
-            d.s[lane] = x;
-            d.s[cap + lane] = y;
-            d.s[2 * cap + lane] = psi;
-            d.s[3 * cap + lane] = v;
-            if (MODEL == CSF_BALANCINGRIDER) {
-                const double twopi = 6.283185307179586476925286766559, own = d.lti[4 * cap + lane];
-                d.lti[4 * cap + lane] = -psi + twopi * nearbyint((own + psi) / twopi);
-            } else {
-                d.ppsi[lane] = psi;
-            }
-            const int64_t slot = d.ti[lane] & (d.hist_len - 1);
-            d.hx[slot * cap + lane] = x;
-            d.hy[slot * cap + lane] = y;
-        } else {
-            const double *o = obj + (int64_t)t * c.R * c.n_feat;
-            for (int k = 0; k < c.n_feat; k++) {
-                const int f = c.feat[k];
-                const double sv = f < d.ns ? d.s[(int64_t)f * d.cap + lane] : 0.0;
-                const double e = sv - o[k];
-                sse += e * e;
-                sae += fabs(e);
-            }
-        }
+        if (here) scene_rider_step<MODEL>(d, c, t, lane, rep, obj, sse, sae);   // (else: the lane is empty at this tick)
         if (c.states != nullptr) {
             if (wait == 0) {
                 if (here) {
@@ -440,7 +412,7 @@ __global__ __launch_bounds__(64) void scene_lanes_kernel(const Dev *__restrict__
         d.pc = ss.pc;
 #pragma unroll
         for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
-        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: a copy of scene_eval_kernel's lines, one of four
             float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
             const int nv = (int)d.nv, nvp = (int)d.nv_pad;
             for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
@@ -469,7 +441,9 @@ __global__ __launch_bounds__(64) void scene_lanes_kernel(const Dev *__restrict__
     if (lane < n) hook.flush();
 }
 
-// wide scenes: one workgroup of 256 threads per (set, wide scene); the prologue and the epilogue are scene_lanes_kernel's
+// wide scenes: one workgroup of 256 threads per (set, wide scene), scn_w[0 .. n_wide) the wide scenes of the data set.  The kernel is
+// scene_lanes_kernel line for line but for where the scene comes from, the stride and wide_tick_body; a change to one is made in the other;
+// they are not one body for the reason given at scene_groups_kernel.
 template <int MODEL>
 __global__ __launch_bounds__(256) void scene_wide_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c,
                                                          const int32_t *__restrict__ scn_w, const int n_wide) {
@@ -484,7 +458,7 @@ __global__ __launch_bounds__(256) void scene_wide_kernel(const Dev *__restrict__
         d.pc = ss.pc;
 #pragma unroll
         for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
-        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: TWIN COPY of scene_eval_kernel's prologue, stride 256
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: a copy of scene_eval_kernel's lines, one of four
             float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
             const int nv = (int)d.nv, nvp = (int)d.nv_pad;
             for (int v = (int)threadIdx.x; v < nvp; v += WIDE_MAX) {
@@ -510,59 +484,53 @@ __global__ __launch_bounds__(256) void scene_wide_kernel(const Dev *__restrict__
     if (lane < n) hook.flush();
 }
 
-int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w) {
-    if (w != nullptr) {
-        // the narrow scenes first, scene_lanes_kernel on their compacted record, then the wide ones: the same stream, so in this order
-        int launched = 0;
-        SceneDev cn = c;
-        cn.n_scn = w->n_narrow, cn.len = w->len_n, cn.roff = w->roff_n, cn.lane_off = w->lane_off_n;
-        const int count_n = c.n_sets * w->n_narrow, count_w = c.n_sets * w->n_wide;
-#define CSF_SCENE_WIDE(MODEL)                                                                                                     \
-    do {                                                                                                                          \
-        if (count_n > 0) {                                                                                                        \
-            hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count_n), dim3(64), c.road_lds, st, table, sets, cn);  \
-            launched++;                                                                                                           \
-        }                                                                                                                         \
-        if (count_w > 0) {                                                                                                        \
-            hipLaunchKernelGGL((scene_wide_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c, w->scn_w, \
-                               w->n_wide);                                                                                        \
-            launched++;                                                                                                           \
-        }                                                                                                                         \
-    } while (0)
-        switch (model) {
-        case CSF_BICYCLE: CSF_SCENE_WIDE(CSF_BICYCLE); break;
-        case CSF_TWOD: CSF_SCENE_WIDE(CSF_TWOD); break;
-        case CSF_INVPEND: CSF_SCENE_WIDE(CSF_INVPEND); break;
-        case CSF_PLANARBIKE: CSF_SCENE_WIDE(CSF_PLANARBIKE); break;
-        case CSF_BALANCINGRIDER: CSF_SCENE_WIDE(CSF_BALANCINGRIDER); break;
-        default: CSF_SCENE_WIDE(CSF_PLANARPOINT); break;
-        }
-#undef CSF_SCENE_WIDE
-        return launched;
-    }
-    const int count = c.n_sets * c.n_scn;
-    if (count <= 0) return 0;
-    const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
-    const bool lanes = c.lane_off != nullptr;
-    const bool groups = c.group != nullptr && !lanes;         // (the host refuses groups on shared lanes)
-#define CSF_SCENE(MODEL)                                                                                                          \
-    do {                                                                                                                          \
-        if (groups && win) hipLaunchKernelGGL((scene_groups_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
-        else if (groups) hipLaunchKernelGGL((scene_groups_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);   \
-        else if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
-        else if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);  \
-        else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), dim3((unsigned)count), dim3(64), c.road_lds, st, table, sets, c);     \
-    } while (0)
+// f(std::integral_constant<int, MODEL>) for the vehicle class of the call (host)
+template <class F>
+static void for_vehicle_class(int model, F &&f) {
     switch (model) {
-    case CSF_BICYCLE: CSF_SCENE(CSF_BICYCLE); break;
-    case CSF_TWOD: CSF_SCENE(CSF_TWOD); break;
-    case CSF_INVPEND: CSF_SCENE(CSF_INVPEND); break;
-    case CSF_PLANARBIKE: CSF_SCENE(CSF_PLANARBIKE); break;
-    case CSF_BALANCINGRIDER: CSF_SCENE(CSF_BALANCINGRIDER); break;
-    default: CSF_SCENE(CSF_PLANARPOINT); break;
+    case CSF_BICYCLE: f(std::integral_constant<int, CSF_BICYCLE>{}); break;
+    case CSF_TWOD: f(std::integral_constant<int, CSF_TWOD>{}); break;
+    case CSF_INVPEND: f(std::integral_constant<int, CSF_INVPEND>{}); break;
+    case CSF_PLANARBIKE: f(std::integral_constant<int, CSF_PLANARBIKE>{}); break;
+    case CSF_BALANCINGRIDER: f(std::integral_constant<int, CSF_BALANCINGRIDER>{}); break;
+    default: f(std::integral_constant<int, CSF_PLANARPOINT>{}); break;
     }
-#undef CSF_SCENE
-    return 1;
+}
+
+int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w) {
+    int launched = 0;
+    for_vehicle_class(model, [&](auto m) {
+        constexpr int MODEL = decltype(m)::value;
+        if (w != nullptr) {
+            // the narrow scenes first, scene_lanes_kernel on their compacted record, then the wide ones: the same stream, so in this order
+            SceneDev cn = c;
+            cn.n_scn = w->n_narrow, cn.len = w->len_n, cn.roff = w->roff_n, cn.lane_off = w->lane_off_n;
+            const int count_n = c.n_sets * w->n_narrow, count_w = c.n_sets * w->n_wide;
+            if (count_n > 0) {
+                hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count_n), dim3(WAVE), c.road_lds, st, table, sets, cn);
+                launched++;
+            }
+            if (count_w > 0) {
+                hipLaunchKernelGGL((scene_wide_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c,
+                                   w->scn_w, w->n_wide);
+                launched++;
+            }
+            return;
+        }
+        const int count = c.n_sets * c.n_scn;
+        if (count <= 0) return;
+        const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
+        const bool lanes = c.lane_off != nullptr;
+        const bool groups = c.group != nullptr && !lanes;     // (the host refuses groups on shared lanes)
+        const dim3 grid((unsigned)count), block(WAVE);
+        if (groups && win) hipLaunchKernelGGL((scene_groups_kernel<MODEL, true>), grid, block, c.road_lds, st, table, sets, c);
+        else if (groups) hipLaunchKernelGGL((scene_groups_kernel<MODEL, false>), grid, block, c.road_lds, st, table, sets, c);
+        else if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), grid, block, c.road_lds, st, table, sets, c);
+        else if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), grid, block, c.road_lds, st, table, sets, c);
+        else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), grid, block, c.road_lds, st, table, sets, c);
+        launched = 1;
+    });
+    return launched;
 }
 
 }  // namespace csf
