@@ -674,8 +674,9 @@ class InteractionCalibration:
     of params_keys is then either "name" - fitted, one value shared by all groups - or ("name", g) - fitted for group g alone; the road
     keys stay per candidate.  A candidate vector becomes G parameter sets, PARAMS_TYPE(**group_params[g], **shared, **own[g]), and an
     evaluation is `Engine.scene_calib_eval_groups`.  Both built-in errors, `simulate`, `test` and a custom error_func are per road
-    user and work as without groups.  Groups need `Engine.scene_calib_load`: with shared lanes or a wide scene a ValueError says so.
-    Without group_params nothing changes and no new call is made.
+    user and work as without groups.  Groups need `Engine.scene_calib_load`: with shared lanes or a wide scene a ValueError says so -
+    unless lane_groups=True, which loads such a data set as above and then hands the groups to `Engine.scene_calib_lane_groups`: a lane
+    then carries the parameters of the rider it holds.  Without group_params nothing changes and no new call is made.
 
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
@@ -683,7 +684,7 @@ class InteractionCalibration:
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
-                 wide_from=33, group_params=None):
+                 wide_from=33, group_params=None, lane_groups=False):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
         self.group_params = None if group_params is None else [dict(g) for g in group_params]
         self._G = 1 if self.group_params is None else len(self.group_params)
@@ -702,6 +703,7 @@ class InteractionCalibration:
             if not 0 <= k[1] < self._G:
                 raise ValueError(f"params_keys: {k!r} names group {k[1]}, group_params defines {self._G}")
         self.share_lanes = bool(share_lanes)
+        self.lane_groups = bool(lane_groups)
         self.wide_from = int(wide_from)
         if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
             raise ValueError(f"wide_from: 1 .. {SceneData.WIDE_MAX + 1}")
@@ -796,9 +798,9 @@ class InteractionCalibration:
             rows.extend(d.dest_xyz_stop.tolist())
         wide = any(d.wide for d in data)
         shared = wide or self.share_lanes or any(d.n > 32 for d in data)
-        if self._G > 1 and shared:
+        if self._G > 1 and shared and not self.lane_groups:
             raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and this data set needs shared lanes"
-                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)")
+                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True); or pass lane_groups=True")
         pod0 = self._pods({})[0] if self._G > 1 else self._pod({})
         if shared:                                               # every scene on its lanes; the windows go with the load
             packed = [d.lanes() for d in data]
@@ -809,6 +811,8 @@ class InteractionCalibration:
                  np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
                  np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets,
                  **(dict(wide_from=self.wide_from) if wide else {}))
+            if self._G > 1:                                      # (lane_groups=True: the group goes with the rider a lane carries)
+                engine.scene_calib_lane_groups(np.concatenate([d.group for d in data]), self._G)
         else:
             engine = self._factory(pod0, self.max_sets * R, device=self.device)
             engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,

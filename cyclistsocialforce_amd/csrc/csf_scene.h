@@ -75,7 +75,8 @@ struct SceneDev {
     const double *img_vdes;
     const int64_t *img_qbeg;
     const int32_t *img_qlen;
-    // Rider groups (csf_scene_calib_groups), read by scene_groups_kernel only: the group of every rider, and the sets are
+    // Rider groups (csf_scene_calib_groups), read by scene_groups_kernel - and, on shared lanes (csf_scene_calib_lane_groups;
+    // DESIGN.md 4.10h), by scene_lanes_groups_kernel / scene_wide_groups_kernel - only: the group of every rider, and the sets are
     // [n_sets][n_groups] records.  NULL: no groups - every rider carries record `set` of [n_sets], and the launch is today's.
     const uint8_t *group;        // [R] 0 .. n_groups - 1
     int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group`, else 0

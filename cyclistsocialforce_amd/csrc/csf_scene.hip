@@ -48,6 +48,11 @@
 // n_groups records per candidate set, a rider is ticked with its group's record and acts as a source with that record's field and field
 // of view (csf_small_body.inc: HOOK::GROUPS).  A data set without groups launches scene_eval_kernel, where none of this exists.
 //
+// Rider groups on shared lanes and on wide scenes (csf_scene_calib_lane_groups): scene_lanes_groups_kernel and
+// scene_wide_groups_kernel.  The group is a property of the RIDER, so a lane's group changes at a takeover: SceneLaneHook<MODEL, true>::seat
+// takes it from c.group, restores with the limits of that record and renews the lane's cell of the staged table of source groups.  A
+// data set without groups launches scene_lanes_kernel / scene_wide_kernel, where none of this exists.
+//
 // What exists once ("Folded"): scene_rider_step - the replay write-back or the error terms behind a tick, called by both
 // hooks -, and for_vehicle_class, which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
 // slot becomes a fresh vehicle from the image - serves scene_groups_kernel and SceneLaneHook::seat; scene_eval_kernel has the same lines
@@ -328,12 +333,23 @@ __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict_
         while (hook.taken < c.n_samples) hook.sample(d, lane);
 }
 
-// behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment
-template <int MODEL>
-struct SceneLaneHook {
+// what SceneLaneHook holds of the rider groups beside SceneGroupPart: the staged table of the lanes' groups once more, to write to - a
+// lane's group changes with its rider
+template <bool GRP>
+struct SceneLaneGroupPart : SceneGroupPart<GRP> {};
+template <>
+struct SceneLaneGroupPart<true> : SceneGroupPart<true> {
+    uint8_t *w_grp = nullptr;     // l_grp, writable: a lane stores to its own cell only
+};
+
+// behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment.  GRP (csf_scene_calib_lane_groups;
+// DESIGN.md 4.10h): the riders are in groups, and the lane's group is its rider's - `grp` and the lane's cell of the staged table are
+// renewed by seat.  A lane nobody rides yet has group 0 and is never present.
+template <int MODEL, bool GRP = false>
+struct SceneLaneHook : SceneLaneGroupPart<GRP> {
     static constexpr bool MASKED = true;
     static constexpr bool SHARED = true;
-    static constexpr bool GROUPS = false;
+    static constexpr bool GROUPS = GRP;
     const SceneDev &c;
     const int64_t row0;           // set * R: first row of the set in sums and in a sample
     int cur = -1;                 // the rider this lane carries (0 .. R - 1), -1: nobody yet
@@ -354,7 +370,22 @@ struct SceneLaneHook {
     // there - and the lane's registers become r's
     __device__ __forceinline__ void seat(const Dev &d, int lane, int r) {
         const int64_t a = lane;
-        scene_restore(d, c, a, r, d.p.v_max_walk, d.p.delta_max_walk);
+        if constexpr (GRP) {
+            // the lane's group becomes r's (an entry the host has checked, clamped all the same: it indexes LDS), the restore takes the
+            // limits of r's own record.  The store goes to the lane's OWN cell of the staged table and to no other; the other lanes
+            // read it in the pair loop of this tick, and what orders the two is what orders the takeover's stores to the slot:
+            //   one-wave tick   the takeover stands at the head of the tick, in front of the staging stores and their fence + wave
+            //                   barrier; the pair loop of the tick before ended in front of the wave barrier at that tick's foot
+            //   wide tick       the takeover stands behind barrier 2 of the tick before - its pair loop has ended - and in front of
+            //                   barrier 1 of its own tick, behind which the pair loop reads the table
+            int g = (int)c.group[r];
+            g = g < this->n_groups ? g : this->n_groups - 1;
+            this->grp = g;
+            this->w_grp[lane] = (uint8_t)g;
+            scene_restore(d, c, a, r, this->rec[g].p.v_max_walk, this->rec[g].p.delta_max_walk);
+        } else {
+            scene_restore(d, c, a, r, d.p.v_max_walk, d.p.delta_max_walk);
+        }
         // (what scene_eval_kernel's riders keep from the load of the data set: a slot is theirs alone there)
         d.vdes[a] = c.img_vdes[r];
         d.qbeg[a] = c.img_qbeg[r];
@@ -484,6 +515,125 @@ __global__ __launch_bounds__(256) void scene_wide_kernel(const Dev *__restrict__
     if (lane < n) hook.flush();
 }
 
+// Rider groups on shared lanes (csf_scene_calib_lane_groups): scene_lanes_kernel with the parameters a property of the
+// RIDER a lane carries.  `sets` holds c.n_groups records per candidate set, Dev::p / pc / pb become record 0's (the priority rule and the
+// road entries are the set's), and the tick reads the rest through the hook (csf_small_body.inc: HOOK::GROUPS).  The kernel is
+// scene_lanes_kernel line for line around the staging of the groups, and the staging is scene_groups_kernel's but for the table of the
+// lanes' groups, which starts at 0 and is filled by SceneLaneHook::seat: a change to one is made in the others.  Not one body with
+// either, for the reason given at scene_groups_kernel.
+template <int MODEL>
+__global__ __launch_bounds__(64) void scene_lanes_groups_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {
+    extern __shared__ float4 srv[];                           // as scene_eval_kernel
+    __shared__ PairConsts g_pc[SCENE_GROUPS_MAX];
+    __shared__ double g_hfov[SCENE_GROUPS_MAX], g_vref[SCENE_GROUPS_MAX];
+    __shared__ uint8_t g_of[SMALL_MAX];                       // the group of every LANE: that of the rider it carries
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * c.n_scn) return;
+    const int set = b / c.n_scn, scn = b - set * c.n_scn;
+    const int G = c.n_groups < SCENE_GROUPS_MAX ? c.n_groups : SCENE_GROUPS_MAX;   // (the host refuses more; LDS holds no more)
+    const SceneSet *const rec = sets + (int64_t)set * c.n_groups;
+    Dev d = table[b];
+    {
+        const SceneSet ss = rec[0];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: a copy of scene_eval_kernel's lines
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WAVE) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;          // n: the scene's lanes
+    const int64_t row0 = (int64_t)set * c.R;
+    // the groups' constants to LDS: lane g < G copies record g word by word; every lane starts in group 0.  Then the wave's own stores,
+    // program order (as sx, sy); seat below stores to the lane's own cell behind this lane's store of the 0.
+    if (lane < G) {
+        g_pc[lane] = rec[lane].pc;
+        g_hfov[lane] = rec[lane].p.hfov;
+        g_vref[lane] = rec[lane].p.v_max_riding[1];
+    }
+    if (lane < SMALL_MAX) g_of[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    SceneLaneHook<MODEL, true> hook(c, row0);
+    hook.n_groups = G, hook.rec = rec;
+    hook.l_pc = g_pc, hook.l_hfov = g_hfov, hook.l_vref = g_vref, hook.l_grp = g_of, hook.w_grp = g_of;
+    if (lane < n) {
+        const int r = c.lane_first[c.lane_off[scn] + lane];
+        if (r >= 0) hook.seat(d, lane, r);
+    }
+    small_tick_body<MODEL>(d, c.len[scn], nullptr, srv, 0u, 0, hook);
+    // riders that are never present are in no chain: their sums are (0, 0)
+    for (int r = c.roff[scn] + lane; r < c.roff[scn + 1]; r += WAVE)
+        if (c.win_enter[r] >= c.win_exit[r]) c.sums[row0 + r] = make_double2(0.0, 0.0);
+    if (lane < n) hook.flush();
+}
+
+// ... and on wide scenes: scene_wide_kernel line for line around the same staging, a change to one is made in the other.  What thread g < G
+// stages is read by every thread at the head of the first tick (wide_tick_body: hook.v_ref) - other waves, so a workgroup barrier stands
+// behind the staging, reached by all 256 threads: the only return in front of it is the uniform one.
+template <int MODEL>
+__global__ __launch_bounds__(256) void scene_wide_groups_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c,
+                                                                const int32_t *__restrict__ scn_w, const int n_wide) {
+    extern __shared__ float4 srv[];                           // as scene_eval_kernel
+    __shared__ PairConsts g_pc[SCENE_GROUPS_MAX];
+    __shared__ double g_hfov[SCENE_GROUPS_MAX], g_vref[SCENE_GROUPS_MAX];
+    __shared__ uint8_t g_of[WIDE_MAX];                        // the group of every LANE: that of the rider it carries
+    const int b = (int)blockIdx.x;
+    if (b >= c.n_sets * n_wide) return;                       // (the only early return: before any barrier, the same in every thread)
+    const int set = b / n_wide, scn = scn_w[b - set * n_wide];
+    const int G = c.n_groups < SCENE_GROUPS_MAX ? c.n_groups : SCENE_GROUPS_MAX;   // (the host refuses more; LDS holds no more)
+    const SceneSet *const rec = sets + (int64_t)set * c.n_groups;
+    Dev d = table[b];
+    {
+        const SceneSet ss = rec[0];
+        d.p = ss.p;
+        d.pc = ss.pc;
+#pragma unroll
+        for (int k = 0; k < 7; k++) d.pb[k] = ss.pb[k];
+        if (c.road_blk != nullptr && d.nv_pad > 0) {          // road parameters of this set: a copy of scene_eval_kernel's lines
+            float4 *const blk = c.road_blk + (int64_t)set * c.road_stride + (d.rv - c.road_rv);
+            const int nv = (int)d.nv, nvp = (int)d.nv_pad;
+            for (int v = (int)threadIdx.x; v < nvp; v += WIDE_MAX) {
+                float4 r = d.rv[v];
+                if (v < nv) r.z = ss.road_z, r.w = ss.road_w;
+                blk[v] = r;
+            }
+            d.rv = blk;
+            d.road_np = ss.road_np;
+        }
+    }
+    const int lane = (int)threadIdx.x, n = (int)d.n;          // n: the scene's lanes (1 .. WIDE_MAX)
+    const int64_t row0 = (int64_t)set * c.R;
+    if (lane < G) {
+        g_pc[lane] = rec[lane].pc;
+        g_hfov[lane] = rec[lane].p.hfov;
+        g_vref[lane] = rec[lane].p.v_max_riding[1];
+    }
+    if (lane < WIDE_MAX) g_of[lane] = 0;                      // (seat below: the same thread's store to the same cell, program order)
+    __syncthreads();                                          // the groups' constants are staged
+    SceneLaneHook<MODEL, true> hook(c, row0);
+    hook.n_groups = G, hook.rec = rec;
+    hook.l_pc = g_pc, hook.l_hfov = g_hfov, hook.l_vref = g_vref, hook.l_grp = g_of, hook.w_grp = g_of;
+    if (lane < n) {
+        const int r = c.lane_first[c.lane_off[scn] + lane];
+        if (r >= 0) hook.seat(d, lane, r);
+    }
+    wide_tick_body<MODEL>(d, c.len[scn], srv, hook);
+    // riders that are never present are in no chain: their sums are (0, 0)
+    for (int r = c.roff[scn] + lane; r < c.roff[scn + 1]; r += (int)blockDim.x)
+        if (c.win_enter[r] >= c.win_exit[r]) c.sums[row0 + r] = make_double2(0.0, 0.0);
+    if (lane < n) hook.flush();
+}
+
 // f(std::integral_constant<int, MODEL>) for the vehicle class of the call (host)
 template <class F>
 static void for_vehicle_class(int model, F &&f) {
@@ -506,13 +656,19 @@ int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const S
             SceneDev cn = c;
             cn.n_scn = w->n_narrow, cn.len = w->len_n, cn.roff = w->roff_n, cn.lane_off = w->lane_off_n;
             const int count_n = c.n_sets * w->n_narrow, count_w = c.n_sets * w->n_wide;
+            const bool lane_groups = c.group != nullptr;      // (csf_scene_calib_lane_groups: both launches take the grouped kernel)
             if (count_n > 0) {
-                hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count_n), dim3(WAVE), c.road_lds, st, table, sets, cn);
+                if (lane_groups) hipLaunchKernelGGL((scene_lanes_groups_kernel<MODEL>), dim3((unsigned)count_n), dim3(WAVE), c.road_lds, st, table, sets, cn);
+                else hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), dim3((unsigned)count_n), dim3(WAVE), c.road_lds, st, table, sets, cn);
                 launched++;
             }
             if (count_w > 0) {
-                hipLaunchKernelGGL((scene_wide_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c,
-                                   w->scn_w, w->n_wide);
+                if (lane_groups)
+                    hipLaunchKernelGGL((scene_wide_groups_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c,
+                                       w->scn_w, w->n_wide);
+                else
+                    hipLaunchKernelGGL((scene_wide_kernel<MODEL>), dim3((unsigned)count_w), dim3(WIDE_MAX), c.road_lds, st, w->table_w, sets, c,
+                                       w->scn_w, w->n_wide);
                 launched++;
             }
             return;
@@ -521,10 +677,12 @@ int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const S
         if (count <= 0) return;
         const bool win = c.win_enter != nullptr && c.win_exit != nullptr;
         const bool lanes = c.lane_off != nullptr;
-        const bool groups = c.group != nullptr && !lanes;     // (the host refuses groups on shared lanes)
+        const bool groups = c.group != nullptr && !lanes;     // (csf_scene_calib_groups: one slot per rider)
+        const bool lane_groups = c.group != nullptr && lanes; // (csf_scene_calib_lane_groups: the group goes with the rider a lane carries)
         const dim3 grid((unsigned)count), block(WAVE);
         if (groups && win) hipLaunchKernelGGL((scene_groups_kernel<MODEL, true>), grid, block, c.road_lds, st, table, sets, c);
         else if (groups) hipLaunchKernelGGL((scene_groups_kernel<MODEL, false>), grid, block, c.road_lds, st, table, sets, c);
+        else if (lane_groups) hipLaunchKernelGGL((scene_lanes_groups_kernel<MODEL>), grid, block, c.road_lds, st, table, sets, c);
         else if (lanes) hipLaunchKernelGGL((scene_lanes_kernel<MODEL>), grid, block, c.road_lds, st, table, sets, c);
         else if (win) hipLaunchKernelGGL((scene_eval_kernel<MODEL, true>), grid, block, c.road_lds, st, table, sets, c);
         else hipLaunchKernelGGL((scene_eval_kernel<MODEL, false>), grid, block, c.road_lds, st, table, sets, c);

@@ -27,6 +27,12 @@
 //
 // HOOK is SceneLaneHook's interface: takeover(d, t, lane) and here(t) at the head of a tick (no shuffle, ballot or barrier, stores to
 // the thread's own slot only), hook(d, t, lane, n) behind it.
+//
+// HOOK::GROUPS (DESIGN.md 4.10h): the parts of small_tick_body of that name, all behind `if constexpr` - the source's PairConsts and field
+// of view in the pair loop (LDS, indexed by the source's group: the order of a receiver's sum does not depend on the labels), hook.v_ref
+// for the Bicycle se entry, and the loop over the groups around agent_body.  A lane's cell of the staged group table is written by
+// hook.takeover - behind barrier 2 of the tick before, in front of barrier 1 of its own - and read in the pair loop between the two
+// barriers of the tick.  The skip ballot of the group loop is per wave; groups gate work, never a barrier.
 template <int MODEL, class HOOK>
 __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, float4 *const srv, HOOK &hook) {
     __shared__ double sx[WIDE_MAX], sy[WIDE_MAX], spsi[WIDE_MAX], scs[WIDE_MAX], ssn[WIDE_MAX];
@@ -59,7 +65,9 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
             shere[tid] = own_here ? 1 : 0;
             if (MODEL == CSF_BICYCLE) {
                 const double v = d.s[3 * cap + tid];
-                const double e = v > 0.0 ? fmin(pow(v / d.p.v_max_riding[1], 0.1), 0.7) : 0.0;
+                double vref = d.p.v_max_riding[1];
+                if constexpr (HOOK::GROUPS) vref = hook.v_ref(tid);   // (the lane's own set, as in small_tick_body)
+                const double e = v > 0.0 ? fmin(pow(v / vref, 0.1), 0.7) : 0.0;
                 se[tid] = make_float2((float)e, (float)(1.0 / sqrt(1.0 - e * e)));
             }
         }
@@ -74,6 +82,10 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
         // the same predicates and fields, fp32 field, fp64 sum.  A change there is made here too. ----
         for (int j = grp; j < n; j += G) {                         // (threads of one group: the same j)
             const double xs = sx[j], ys = sy[j], ps = spsi[j];
+            const PairConsts *kp = &k;                             // the SOURCE's field and field of view (intersection.py:733-735, 815)
+            double hfov = d.p.hfov;
+            if constexpr (HOOK::GROUPS) kp = hook.consts(j), hfov = hook.hfov(j);
+            const PairConsts &ks = *kp;
             const double ex = x - xs, ey = y - ys;                 // vehicle.py:1615-1616
             if (shere[j] == 0) continue;                           // (a road user that is not there is nobody's source)
             // the receiver itself and a road user on the very same spot (D2) add nothing
@@ -81,20 +93,20 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
             const float dx = (float)ex, dy = (float)ey, r2 = fmaxf(dx * dx + dy * dy, 1e-30f);
             const float4 q = make_float4(0.f, 0.f, (float)scs[j], (float)ssn[j]);
             bool edge;
-            bool seen = p2r ? tracked_precise<true>(k, k.chs, r, dx, dy, r2, edge) : tracked_precise<false>(k, k.chs, r, dx, dy, r2, edge);
-            if (edge) seen = !untracked_exact_xy(xs, ys, x, y, psi, d.p.hfov, p2r);   // (one pair in a million)
+            bool seen = p2r ? tracked_precise<true>(ks, ks.chs, r, dx, dy, r2, edge) : tracked_precise<false>(ks, ks.chs, r, dx, dy, r2, edge);
+            if (edge) seen = !untracked_exact_xy(xs, ys, x, y, psi, hfov, p2r);   // (one pair in a million)
             if (!seen) continue;
             int sg = 1;
             float F, gx, gy;
             if (MODEL == CSF_BICYCLE) {                             // vehicle.py:1054-1147: no jump at phi = 0
-                field_bicycle(k, q, se[j], dx, dy, r2, F, gx, gy);
+                field_bicycle(ks, q, se[j], dx, dy, r2, F, gx, gy);
             } else {
                 float sgf = 0.0f;                                   // 0: the sign of the fp32 sine
-                if (side_undecided(k, q, dx, dy, r2)) {
+                if (side_undecided(ks, q, dx, dy, r2)) {
                     sg = sign_phi_exact(xs, ys, ps, x, y);
                     sgf = sg < 0 ? -1.0f : 1.0f;
                 }
-                field_twod(k, r, q, dx, dy, r2, F, gx, gy, sgf);
+                field_twod(ks, r, q, dx, dy, r2, F, gx, gy, sgf);
             }
             double wx = (double)(F * gx), wy = (double)(F * gy);
             if (sg == 0) {                                          // phi = 0 exactly: no tangential part, |F| = P along the line
@@ -155,7 +167,22 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
                 }
                 d.froad[tid] = q;                                 // (agent_body reads it back: the same thread, program order)
             }
-            if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, tid, nullptr, 0u, rx, ry, -1);
+            if constexpr (!HOOK::GROUPS) {
+                if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, tid, nullptr, 0u, rx, ry, -1);
+            }
+        }
+        if constexpr (HOOK::GROUPS) {
+            // the loop over the groups of small_tick_body, per WAVE: g and the ballot are uniform in a wave, agent_body holds no barrier,
+            // and a wave none of whose present owners is of group g skips the pass.  It stands outside `tid < n` - all 64 lanes of a
+            // wave take the same trips - and in front of no barrier that a skipped pass could miss: the next one is barrier 1.
+            Dev dg = d;
+#pragma nounroll
+            for (int g = 0; g < hook.n_groups; g++) {               // (the body of agent_body is emitted once, here)
+                const bool turn = mine && hook.grp == g;
+                if (__ballot(turn) == 0ull) continue;
+                hook.select(dg, g);
+                if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, tid, nullptr, 0u, rx, ry, -1);
+            }
         }
         hook(d, t, tid, n);
     }

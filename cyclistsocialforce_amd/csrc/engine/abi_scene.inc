@@ -58,7 +58,7 @@ struct SceneCalibState {
     DevBuf<Dev> table_w;                     // [max_sets][n_wide]
     DevBuf<int32_t> scn_w, len_n, roff_n, lane_off_n;
     bool is_wide(size_t q) const { return wide_from > 0 && h_nl[q] >= wide_from; }
-    // csf_scene_calib_groups: rider groups with parameter sets of their own (DESIGN.md 4.10g).  n_groups == 0: none, an evaluation is
+    // csf_scene_calib_groups, and on shared lanes csf_scene_calib_lane_groups (DESIGN.md 4.10g, 4.10h): rider groups with parameter sets of their own.  n_groups == 0: none, an evaluation is
     // handed group == NULL and launches what it launched before.  Else the call's table is [n_sets][n_groups] records in sets_g
     int32_t n_groups = 0;
     DevBuf<uint8_t> group;                   // [R]
@@ -397,7 +397,7 @@ int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *p
                               const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) try {
     if (!e) return CSF_E_ARG;
     if (e->scene_calib && e->scene_calib->n_groups > 0)
-        return fail(e, CSF_E_STATE, "csf_scene_calib_eval: the riders are in %d groups (csf_scene_calib_groups) and one set cannot say what group 1 carries: csf_scene_calib_eval_groups",
+        return fail(e, CSF_E_STATE, "csf_scene_calib_eval: the riders are in %d groups (csf_scene_calib_groups / _lane_groups) and one set cannot say what group 1 carries: csf_scene_calib_eval_groups",
                     (int)e->scene_calib->n_groups);
     return scene_eval_impl(e, n_sets, 0, params, params_size, abi_version, road_F0, road_sigma, sums_out, stride, states_out);
 } catch (...) { return csf_caught(e); }
@@ -412,20 +412,24 @@ int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups,
     return scene_eval_impl(e, n_sets, e->scene_calib->n_groups, params, params_size, abi_version, road_F0, road_sigma, sums_out, stride, states_out);
 } catch (...) { return csf_caught(e); }
 
-int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {
-    if (!e) return CSF_E_ARG;
+// csf_scene_calib_groups (lanes == false: a csf_scene_calib_load data set, one slot per rider) and csf_scene_calib_lane_groups (lanes ==
+// true: a data set of csf_scene_calib_load_shared / _load_wide, the group goes with the rider a lane carries).  `fn` names the call in
+// the messages; the checks, the allocate-before-replace order and the drop are one.
+static int scene_groups_impl(csf_engine *e, const char *fn, bool lanes, const uint8_t *group, int32_t n_groups) {
     if (!e->scene_calib) {
-        if (e->calib) return fail(e, CSF_E_STATE, "csf_scene_calib_groups: the engine holds the data set of csf_calib_load, whose candidate sets are whole populations already");
-        return fail(e, CSF_E_STATE, "csf_scene_calib_groups: no closed-loop data set (csf_scene_calib_load first)");
+        if (e->calib) return fail(e, CSF_E_STATE, "%s: the engine holds the data set of csf_calib_load, whose candidate sets are whole populations already", fn);
+        return fail(e, CSF_E_STATE, "%s: no closed-loop data set (csf_scene_calib_load first)", fn);
     }
     SceneCalibState &cs = *e->scene_calib;
-    if (cs.Lsum > 0)
-        return fail(e, CSF_E_STATE, "csf_scene_calib_groups: the data set shares its lanes (csf_scene_calib_load_shared / _load_wide): a lane's parameters would change with its rider; groups need csf_scene_calib_load");
+    if (!lanes && cs.Lsum > 0)
+        return fail(e, CSF_E_STATE, "csf_scene_calib_groups: the data set shares its lanes (csf_scene_calib_load_shared / _load_wide): a lane's parameters would change with its rider; groups need csf_scene_calib_load, or csf_scene_calib_lane_groups on this data set");
+    if (lanes && cs.Lsum == 0)
+        return fail(e, CSF_E_STATE, "csf_scene_calib_lane_groups: the data set has one slot per rider (csf_scene_calib_load): its groups are loaded by csf_scene_calib_groups");
     const bool drop = group == nullptr || n_groups <= 1;
     if (!drop) {
-        if (n_groups > SCENE_GROUPS_MAX) return fail(e, CSF_E_ARG, "csf_scene_calib_groups: %d groups (at most %d)", (int)n_groups, SCENE_GROUPS_MAX);
+        if (n_groups > SCENE_GROUPS_MAX) return fail(e, CSF_E_ARG, "%s: %d groups (at most %d)", fn, (int)n_groups, SCENE_GROUPS_MAX);
         for (int32_t r = 0; r < cs.R; r++)
-            if (group[r] >= n_groups) return fail(e, CSF_E_ARG, "csf_scene_calib_groups: rider %d is in group %d of %d", (int)r, (int)group[r], (int)n_groups);
+            if (group[r] >= n_groups) return fail(e, CSF_E_ARG, "%s: rider %d is in group %d of %d", fn, (int)r, (int)group[r], (int)n_groups);
     }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->main));
@@ -440,7 +444,7 @@ int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups
         if (r == hipSuccess) r = d_sets.alloc(recs);
         if (r == hipSuccess) r = pin->alloc(recs);
         if (r == hipSuccess) r = hipMemcpy(d_group.p, group, (size_t)cs.R, hipMemcpyHostToDevice);
-        if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_scene_calib_groups: no memory for the groups: %s", hipGetErrorString(r));
+        if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "%s: no memory for the groups: %s", fn, hipGetErrorString(r));
         std::memset(pin->p, 0, recs * sizeof(SceneSet));
     }
     cs.group = std::move(d_group);
@@ -448,6 +452,16 @@ int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups
     cs.sets_g_pin = std::move(pin);
     cs.n_groups = drop ? 0 : n_groups;
     return CSF_OK;
+}
+
+int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {
+    if (!e) return CSF_E_ARG;
+    return scene_groups_impl(e, "csf_scene_calib_groups", false, group, n_groups);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_lane_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {
+    if (!e) return CSF_E_ARG;
+    return scene_groups_impl(e, "csf_scene_calib_lane_groups", true, group, n_groups);
 } catch (...) { return csf_caught(e); }
 
 static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params, size_t params_size, int32_t abi_version,

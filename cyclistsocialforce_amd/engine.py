@@ -426,6 +426,25 @@ class Engine:
         g8 = np.ascontiguousarray(g, dtype=np.uint8)
         self._ck(self._lib.csf_scene_calib_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
 
+    def scene_calib_lane_groups(self, group, n_groups=None):
+        """scene_calib_groups for a data set of scene_calib_load_shared / scene_calib_load_wide: group [R] per RIDER (integers
+        0 .. n_groups - 1), n_groups <= 4 (default: the largest entry + 1); a lane's parameters are those of the rider it carries and
+        change at a takeover.  None, or n_groups <= 1, drops the groups.  With groups loaded an evaluation is scene_calib_eval_groups;
+        scene_calib_eval is refused.  A scene_calib_load data set takes scene_calib_groups and refuses this call."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_lane_groups: no closed-loop data set (scene_calib_load_shared / scene_calib_load_wide first)")
+        R, _ = self._scene_calib
+        if group is None:
+            self._ck(self._lib.csf_scene_calib_lane_groups(self._h, None, 0))
+            return
+        g = np.asarray(group)
+        if g.shape != (R,) or g.dtype.kind not in "iub":
+            raise ValueError("group must have one integer entry per rider of the data set")
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("group: entries are 0 .. n_groups - 1")
+        g8 = np.ascontiguousarray(g, dtype=np.uint8)
+        self._ck(self._lib.csf_scene_calib_lane_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+
     def scene_calib_eval_groups(self, pods, road_F0=None, road_sigma=None, states=False, stride=1):
         """scene_calib_eval for riders in groups: `pods` is a sequence of n_groups-tuples of csf_params, tuple k the candidate k and
         its entry g what the riders of group g carry.  A rider is simulated with its own set and acts on the others with its own

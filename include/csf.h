@@ -572,8 +572,19 @@ int csf_calib_clear(csf_engine *e);
  * the rounding bands take the largest speed clamp among the candidate's records.  n_groups must equal the loaded one (CSF_E_ARG), every
  * record is checked as csf_scene_calib_eval checks a set and must be of the engine's vehicle class (CSF_E_ARG).  Without loaded groups
  * n_groups must be 1 and the call IS csf_scene_calib_eval_road.  While groups are loaded csf_scene_calib_eval and
- * csf_scene_calib_eval_road are refused with CSF_E_STATE: one set cannot say what group 1 carries. */
+ * csf_scene_calib_eval_road are refused with CSF_E_STATE: one set cannot say what group 1 carries.
+ *
+ * csf_scene_calib_lane_groups is csf_scene_calib_groups for a data set of csf_scene_calib_load_shared /
+ * csf_scene_calib_load_wide: group [R] per RIDER as there, and a lane's parameters change with the rider it carries - at a takeover the
+ * lane's slot is restored with the newcomer's limits, it is ticked with the newcomer's record and acts as a source with that record's
+ * field and field of view.  The evaluation is csf_scene_calib_eval_groups, on the kernels of the shared and the wide scenes (one launch,
+ * or up to two after csf_scene_calib_load_wide); presence windows, replay, roads, samples and sums are what they are without groups.
+ * NULL or n_groups <= 1 drops the groups, and evaluations are then what they were, bit for bit.  The checks, the allocate-before-replace
+ * order and the refusals are csf_scene_calib_groups's, but for the data set: CSF_E_STATE on a plain csf_scene_calib_load data set (that one
+ * takes csf_scene_calib_groups), without a closed-loop data set and with csf_calib_load's; CSF_E_ARG for n_groups > 4 and for an entry
+ * >= n_groups.  csf_scene_calib_clear frees the groups with the rest.  csf_scene_calib_groups keeps its refusal on such a data set. */
 int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
+int csf_scene_calib_lane_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
 int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params,
                                 size_t params_size, int32_t abi_version,
                                 const double *road_F0, const double *road_sigma,

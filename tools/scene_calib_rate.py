@@ -40,6 +40,10 @@ candidate's set with f_0 x (1 + 0.1 g), and adds `groups_ms`: csf_scene_calib_gr
 evaluation.  Its baseline (`groups_base_ms`, built for up to --groups-base-max sets) is what a caller had before: one engine per (set,
 scene) that holds the G sets as parameter classes - such an engine is on the general path and a batch steps it in turn -, per call the
 start states pushed back, csf_step for all ticks with csf_record, the recorded states read back and the NumPy error.
+With --riders the groups go to the wide data set through csf_scene_calib_lane_groups and the same leg and baseline
+are timed there.  With --presence --share the packed data set of that cell gets them too: `packed_groups_ms`, against
+`packed_groups_base_ms` - per (set, scene) one general-path engine that holds the G sets, stepped tick by tick, a rider added
+(add_agents, set_agent_class, set_dest_queue) at its entry and removed at its exit, the state read back after every tick.
 
     python tools/scene_calib_rate.py [--groups 2 [--groups-base-max 16]] [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
                                      [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
@@ -109,8 +113,8 @@ def main():
     riders = [int(x) for x in a.riders.split(",")] if a.riders else None
     if riders and (a.replay or a.road or a.presence or min(riders) < 1 or max(riders) > 256):
         ap.error("--riders takes 1 .. 256 road users per scene and stands alone: not with --replay, --road or --presence")
-    if a.groups and (riders or not 2 <= a.groups <= 4):
-        ap.error("--groups takes 2 .. 4 and does not go with --riders (groups run on csf_scene_calib_load)")
+    if a.groups and not 2 <= a.groups <= 4:
+        ap.error("--groups takes 2 .. 4")
     if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
         ap.error("--share goes with --presence and 1 <= --share-peak <= --share-roster <= 32")
     feat = np.array([0, 1], dtype=np.int32)
@@ -251,6 +255,56 @@ def main():
                 line.update(share=dict(roster=ro, peak=pk, lanes=int(nl1), riders=Rb, packed_rel_gap=float(np.abs(first[1] / first[0] - 1.0).max()),
                                        unpacked_ms=dict(median=float(np.median(t_leg[0])), min=min(t_leg[0]), max=max(t_leg[0])),
                                        packed_ms=dict(median=float(np.median(t_leg[1])), min=min(t_leg[1]), max=max(t_leg[1]))))
+                if a.groups:                                     # the packed data set with groups: a lane's set changes with its rider
+                    G = a.groups
+                    grpb = np.tile(np.arange(ro) % G, a.scenes).astype(np.uint8)
+                    tupb = [tuple(_ffi.Params.from_buffer_copy(p) for _ in range(G)) for p in sets]
+                    for tup in tupb:
+                        for g, c in enumerate(tup):
+                            c.f_0, c.p_0 = c.f_0 * (1.0 + 0.1 * g), c.p_0 * (1.0 + 0.1 * g)
+                    packed.scene_calib_lane_groups(grpb, G)
+
+                    def lanes_new():
+                        return packed.scene_calib_eval_groups(tupb)[:, :, 0].sum(axis=1)
+
+                    def lanes_old():
+                        """the host-stepped twin: riders come and go between 1-tick steps of a general-path engine per (set, scene)"""
+                        err = np.zeros(n_sets)
+                        for k, tup in enumerate(tupb):
+                            for q, (s, o, d) in enumerate(big):
+                                t = Engine(tup[0], ro)
+                                t.set_param_classes(list(tup))
+                                ids = []
+                                for tick in range(a.ticks):
+                                    gone = [i for i, r in enumerate(ids) if ex1[r] == tick]
+                                    if gone:
+                                        t.remove_agents(gone)
+                                        ids = [r for r in ids if ex1[r] != tick]
+                                    come = [r for r in range(ro) if en1[r] == tick and ex1[r] > tick]
+                                    if come:
+                                        t.add_agents(s[come], 5.0)
+                                        where = np.arange(len(ids), len(ids) + len(come))
+                                        t.set_agent_class(where, grpb[come])
+                                        t.set_dest_queue(where, np.arange(len(come) + 1) * 5, np.concatenate([d[o[r]: o[r + 1]] for r in come]), reset=True)
+                                        ids += come
+                                    if ids:
+                                        t.step(1)
+                                        st = t.state()
+                                        err[k] += float(np.square(st[:, feat] - objb[tick, q * ro + np.array(ids)]).sum())
+                                t.close()
+                        return err
+
+                    first_l = lanes_new()
+                    with_lbase = n_sets <= a.groups_base_max
+                    l_gap = float(np.abs(lanes_old() / first_l - 1.0).max()) if with_lbase else None
+                    t_l, t_lold = [], []
+                    for _ in range(a.windows):
+                        t0 = time.perf_counter(); lanes_new(); t_l.append((time.perf_counter() - t0) * 1e3)
+                        if with_lbase:
+                            t0 = time.perf_counter(); lanes_old(); t_lold.append((time.perf_counter() - t0) * 1e3)
+                    line["share"].update(groups=G, packed_groups_rel_gap=l_gap,
+                                         packed_groups_ms=dict(median=float(np.median(t_l)), min=min(t_l), max=max(t_l)),
+                                         packed_groups_base_ms=dict(median=float(np.median(t_lold)), min=min(t_lold), max=max(t_lold)) if t_lold else None)
                 plain.close()
                 packed.close()
             if a.replay:
@@ -282,7 +336,7 @@ def main():
                         c.f_0, c.p_0 = p.f_0 * (1.0 + 0.1 * g), p.p_0 * (1.0 + 0.1 * g)
                         tup.append(c)
                     tups.append(tuple(tup))
-                e.scene_calib_groups(grp, G)
+                (e.scene_calib_lane_groups if riders else e.scene_calib_groups)(grp, G)    # (--riders: the data set is on lanes)
                 gtwins = []
                 if n_sets <= a.groups_base_max:
                     for tup in tups:

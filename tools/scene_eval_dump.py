@@ -2,7 +2,7 @@
 """Sums and sampled states of a fixed set of tiny closed-loop calibration data sets (GPU box), for comparing two builds of the library
 BIT FOR BIT: the GPU tests hold the scene kernels to their twins at 2e-7, which does not see a changed rounding.  Everything goes
 through the Python Engine API, so the tool runs unchanged from the tools/ folder of any checkout that has the scene calibration of
-DESIGN.md 4.10 - 4.10g; run it in both, then compare:
+DESIGN.md 4.10 - 4.10h; run it in both, then compare:
 
     python tools/scene_eval_dump.py --out a.npz                    (in the one checkout)
     python tools/scene_eval_dump.py --out b.npz --compare a.npz    (in the other: evaluates, writes, compares; exit status 1 on a difference)
@@ -19,6 +19,8 @@ The data sets are the smallest that reach every piece the kernels of csf_scene.h
          a road with per-set parameters                                            scene_lanes_kernel
     g    a roster of 48 on 40 wide lanes with handovers and a narrow scene of 5 in one data set, a road of 100 vertices on each with
          per-set parameters: two launches                                          scene_wide_kernel + scene_lanes_kernel
+    fg, gg   fr and g with the riders in two groups (csf_scene_calib_lane_groups; left out where the library lacks the call)
+                                                                                   scene_lanes_groups_kernel, scene_wide_groups_kernel
 """
 import argparse
 import os
@@ -103,6 +105,9 @@ def shared_cases(model, out):
     e.scene_calib_replay(np.arange(6) == 3, rec)
     e.scene_calib_road(*road_call([edge_below(model, 6, count=100)]))
     out["fr"] = e.scene_calib_eval(sets, states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
+    if hasattr(e._lib, "csf_scene_calib_lane_groups"):           # (riders 0 and 3 share lane 0: its group changes at the handover)
+        e.scene_calib_lane_groups((np.arange(6) % 2).astype(np.uint8), 2)
+        out["fg"] = e.scene_calib_eval_groups(group_sets(model, 3, 2), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
     e.close()
 
 
@@ -120,6 +125,10 @@ def wide_cases(model, out):
     before = e.scene_calib_launches()
     out["g"] = e.scene_calib_eval(sets, states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
     assert e.scene_calib_launches() == before + 2                 # (the narrow scene and the wide one: both kernels)
+    if hasattr(e._lib, "csf_scene_calib_lane_groups"):           # (riders r and 40 + r share a lane; at two of three handovers its group changes)
+        e.scene_calib_lane_groups((np.arange(53) % 3 % 2).astype(np.uint8), 2)
+        out["gg"] = e.scene_calib_eval_groups(group_sets(model, 3, 2), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
+        assert e.scene_calib_launches() == before + 4
     e.close()
 
 
