@@ -41,6 +41,7 @@ SYMBOLS = (
     "csf_scene_calib_load_wide",
     "csf_scene_calib_groups", "csf_scene_calib_eval_groups",
     "csf_scene_calib_lane_groups",
+    "csf_scene_calib_classes",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -210,6 +211,8 @@ def load():
         L.csf_scene_calib_eval_groups.argtypes = [vp, i32, i32, C.POINTER(Params), C.c_size_t, i32, dp, dp, dp, i32, dp]
     if hasattr(L, "csf_scene_calib_lane_groups"):   # (the same)
         L.csf_scene_calib_lane_groups.argtypes = [vp, vp, i32]
+    if hasattr(L, "csf_scene_calib_classes"):       # (the same)
+        L.csf_scene_calib_classes.argtypes = [vp, vp, i32, vp, dp]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

@@ -15,6 +15,7 @@ Two things are not the reference's:
 """
 import numpy as np
 
+from . import _ffi
 from .engine import Engine
 from .parameters import RoadElementParameters
 
@@ -620,6 +621,20 @@ class SceneData:
         return out
 
 
+def _init_names(cls):
+    """the keyword arguments the constructor of a PARAMS_TYPE takes, its base classes' included where it passes **kwargs on"""
+    import inspect
+    names = set()
+    for c in cls.__mro__:
+        if "__init__" not in vars(c):
+            continue
+        sig = inspect.signature(c.__init__).parameters
+        names |= {n for n, q in sig.items() if n != "self" and q.kind in (q.POSITIONAL_OR_KEYWORD, q.KEYWORD_ONLY)}
+        if not any(q.kind == q.VAR_KEYWORD for q in sig.values()):
+            break
+    return names
+
+
 def _riders_then_scenes(per_rider, roff):
     """[k, R] per-rider figures -> [k, n_scn]: the riders of a scene added in rider order (the order of the sum is fixed)"""
     out = np.zeros((per_rider.shape[0], len(roff) - 1))
@@ -678,6 +693,16 @@ class InteractionCalibration:
     unless lane_groups=True, which loads such a data set as above and then hands the groups to `Engine.scene_calib_lane_groups`: a lane
     then carries the parameters of the rider it holds.  Without group_params nothing changes and no new call is made.
 
+    Road users of SEVERAL VEHICLE CLASSES, all simulated: vehicle_type is then a list or tuple of G vehicle types, group g
+    of `SceneData(group=...)` being of class vehicle_type[g] - a Bicycle among TwoDBicycles, a BalancingRiderBicycle among
+    InvPendulumBicycles.  group_params defaults to G empty dicts and must have length G, at most 12 (six classes x two kinds of rider);
+    ("name", g) fits a parameter of group g's PARAMS_TYPE, "name" one value shared by all groups - it must be a parameter of EVERY
+    group's PARAMS_TYPE (ValueError names key and group).  Record g of a candidate is vehicle_type[g].PARAMS_TYPE(...).to_pod(
+    vehicle_type[g].MODEL); the data set is loaded by `Engine.scene_calib_load` and then `Engine.scene_calib_classes`, and everything
+    else - both built-in errors, a custom error_func, `simulate`, `run`, `run_many`, `test`, replay, windows, roads and the road keys -
+    works as with groups.  Mixed classes run on Engine.scene_calib_load only: a data set that needs shared lanes or a wide scene raises
+    ValueError.  With a single vehicle_type nothing changes and no new call is made.
+
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
     ROAD_KEYS = {"road_F_0": "F_0", "road_sigma": "sigma"}
@@ -686,9 +711,20 @@ class InteractionCalibration:
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
                  wide_from=33, group_params=None, lane_groups=False):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
+        self._types = list(vehicle_type) if isinstance(vehicle_type, (list, tuple)) else None      # several vehicle classes: one per group
+        if self._types is not None:
+            if not 2 <= len(self._types) <= 12:
+                raise ValueError("vehicle_type: a vehicle type, or a list of 2 .. 12 of them - one per group")
+            for g, t in enumerate(self._types):
+                if getattr(t, "MODEL", None) is None or t.MODEL == _ffi.UNCONTROLLED:
+                    raise ValueError(f"vehicle_type[{g}]: {getattr(t, '__name__', t)!r} is not one of the six simulated vehicle classes")
+            if group_params is None:
+                group_params = [{} for _ in self._types]
+            if len(group_params) != len(self._types):
+                raise ValueError(f"group_params: {len(group_params)} dicts for {len(self._types)} vehicle types - one per group")
         self.group_params = None if group_params is None else [dict(g) for g in group_params]
         self._G = 1 if self.group_params is None else len(self.group_params)
-        if not 1 <= self._G <= 4:
+        if self._types is None and not 1 <= self._G <= 4:
             raise ValueError("group_params: 1 .. 4 dicts of keyword arguments of PARAMS_TYPE, one per group")
         for k in self.params_keys:
             if isinstance(k, str):
@@ -702,6 +738,15 @@ class InteractionCalibration:
                 raise ValueError(f"params_keys: {k!r} names a group and there is no group_params")
             if not 0 <= k[1] < self._G:
                 raise ValueError(f"params_keys: {k!r} names group {k[1]}, group_params defines {self._G}")
+        if self._types is not None:                               # a key must be a parameter of the PARAMS_TYPE of every group it reaches
+            for k in self.params_keys:
+                name = k if isinstance(k, str) else k[0]
+                if name in self.ROAD_KEYS:
+                    continue
+                for g in (range(self._G) if isinstance(k, str) else (k[1],)):
+                    if name not in _init_names(self._types[g].PARAMS_TYPE):
+                        raise ValueError(f"params_keys: {k!r}: {name!r} is no parameter of {self._types[g].PARAMS_TYPE.__name__}, "
+                                         f"the PARAMS_TYPE of group {g} ({self._types[g].__name__})")
         self.share_lanes = bool(share_lanes)
         self.lane_groups = bool(lane_groups)
         self.wide_from = int(wide_from)
@@ -751,6 +796,15 @@ class InteractionCalibration:
 
     def _pods(self, params_args):
         """a candidate as Engine.scene_calib_eval_groups takes it: one parameter set per group"""
+        if self._types is not None:                               # (several vehicle classes: record g is of vehicle_type[g]'s)
+            out = []
+            for g, (t, a) in enumerate(zip(self._types, self._group_args(params_args))):
+                try:
+                    out.append(t.PARAMS_TYPE(**a).to_pod(t.MODEL))
+                except TypeError as exc:
+                    bad = [k for k in a if k not in _init_names(t.PARAMS_TYPE)]
+                    raise ValueError(f"group {g} ({t.__name__}): {bad or sorted(a)} - {exc}") from None
+            return tuple(out)
         return tuple(self.vehicle_type.PARAMS_TYPE(**a).to_pod(self.vehicle_type.MODEL) for a in self._group_args(params_args))
 
     def _eval(self, ds, args_list, **kw):
@@ -798,6 +852,9 @@ class InteractionCalibration:
             rows.extend(d.dest_xyz_stop.tolist())
         wide = any(d.wide for d in data)
         shared = wide or self.share_lanes or any(d.n > 32 for d in data)
+        if self._types is not None and shared:
+            raise ValueError("mixed classes run on Engine.scene_calib_load only, and this data set needs shared lanes"
+                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)")
         if self._G > 1 and shared and not self.lane_groups:
             raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and this data set needs shared lanes"
                              + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True); or pass lane_groups=True")
@@ -817,7 +874,9 @@ class InteractionCalibration:
             engine = self._factory(pod0, self.max_sets * R, device=self.device)
             engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
                                     max_sets=self.max_sets)
-            if self._G > 1:
+            if self._types is not None:
+                engine.scene_calib_classes(np.concatenate([d.group for d in data]), [t.MODEL for t in self._types], s0)
+            elif self._G > 1:
                 engine.scene_calib_groups(np.concatenate([d.group for d in data]), self._G)
         if rep.any():                                            # the recorded (x, y, psi, v) of the replayed riders, in rider order
             rec = np.zeros((T, int(rep.sum()), 4))

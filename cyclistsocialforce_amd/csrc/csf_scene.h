@@ -23,6 +23,11 @@ struct SceneSet {
 // (record 0's: the rule belongs to the intersection, as under csf_set_param_classes).
 constexpr int SCENE_GROUPS_MAX = 4;
 
+// Several vehicle classes in one scene (csf_scene_calib_classes): the groups are then also of different vehicle classes -
+// record (set, g) names the class of group g -, and the call takes up to SCENE_CLASS_GROUPS_MAX of them: six classes x two kinds of rider.
+// Every other call keeps SCENE_GROUPS_MAX.
+constexpr int SCENE_CLASS_GROUPS_MAX = 12;
+
 // The data set of csf_scene_calib_load, resident on the device, and the reset image.  The image is indexed by RIDER (0 .. R - 1,
 // the scenes one after the other): every set starts every scene from the same state, so one copy of what csf_add_agents made of
 // the first set's slots serves all of them.  It holds every per-slot array that a closed-loop tick (agent_body<.., FUSED = true>
@@ -79,7 +84,7 @@ struct SceneDev {
     // DESIGN.md 4.10h), by scene_lanes_groups_kernel / scene_wide_groups_kernel - only: the group of every rider, and the sets are
     // [n_sets][n_groups] records.  NULL: no groups - every rider carries record `set` of [n_sets], and the launch is today's.
     const uint8_t *group;        // [R] 0 .. n_groups - 1
-    int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group`, else 0
+    int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group` (scene_mixed_kernel: 2 .. SCENE_CLASS_GROUPS_MAX), else 0
 };
 
 // Wide scenes (csf_scene_calib_load_wide): a data set on shared lanes whose scenes with n_lanes >= wide_from run on
@@ -99,5 +104,9 @@ struct SceneWideDev {
 // One evaluation: workgroup b = set * n_scn + scene runs the scene of table[b] with the constants of sets[set].  With `w` (a wide load)
 // `table` holds the narrow scenes and up to two kernels are launched on `st`, the narrow scenes first.  Returns the kernels launched.
 int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w = nullptr);
+
+// One evaluation with vehicle classes loaded (csf_scene_calib_classes): scene_mixed_kernel on a csf_scene_calib_load data set, `ns` the
+// widest state of the loaded classes.  Returns the kernels launched (1).
+int launch_scene_mixed(const Dev *table, const SceneSet *sets, const SceneDev &c, int ns, hipStream_t st);
 
 }  // namespace csf

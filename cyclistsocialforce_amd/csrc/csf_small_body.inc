@@ -1,5 +1,5 @@
 // csf_small_body.inc - the one-wave tick of a handful of road users (DESIGN.md 4.6): included by csf_agent.hip (small_tick_kernel,
-// small_batch_kernel) and by csf_scene.hip (scene_eval_kernel) inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
+// small_batch_kernel), by csf_scene.hip (scene_eval_kernel) and by csf_scene_mixed.hip (scene_mixed_kernel) inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
 // include and not a __device__ function of a translation unit of its own, as csf_mid_body.inc is (DESIGN.md 4.6d): the kernels of
 // csf_agent.hip keep the instruction stream they had when the body stood in that file.
 //
@@ -29,6 +29,18 @@
 //                    whose road user is of group g run agent_body on it; a group nobody present belongs to is skipped (a ballot).
 //                    n_groups is a kernel argument: no loop added here depends on the state for its end.
 // With GROUPS == false all of it is compiled out and the body is the one it was.
+//
+// MODEL == SMALL_MIXED (DESIGN.md 4.10i; csf_scene.hip: scene_mixed_kernel): the vehicle CLASS is a property of the group too.  The hook
+// is a GROUPS hook that also knows the classes - hook.own_model() the class of the lane's own road user, hook.src_model(j) that of
+// source j (LDS), hook.group_model(g) that of group g (uniform):
+//   pair term        source j acts with the field of ITS class (intersection.py:797-823; csf_pair.hip for has_bike && (model_mask & ~1)):
+//                    field_bicycle with the (e, 1 / sqrt(1 - e^2)) its own lane has staged, or field_twod.  `se` has a cell per lane
+//                    and is written by the lanes whose road user is a Bicycle; nobody reads another cell.  The loop order is unchanged.
+//   per-agent tick   inside the uniform loop over the groups a uniform switch on the group's class to agent_body<M>; no barrier,
+//                    shuffle or ballot stands under a divergent condition.
+// Every line of it stands under `if constexpr (MIXED)`: an instance of a real class is the one it was.
+constexpr int SMALL_MIXED = -1;   // (no enum csf_model)
+
 struct NoTickHook {
     static constexpr bool MASKED = false;
     static constexpr bool SHARED = false;
@@ -61,7 +73,8 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
     // one of 64 / P groups that share the sources between them (source j belongs to group j % G) - all 64 lanes work on the
     // pair term whatever the population, and the groups' sums meet in lanes 0 .. n - 1, which then tick their road user.
     __shared__ double sx[SMALL_MAX], sy[SMALL_MAX], spsi[SMALL_MAX], scs[SMALL_MAX], ssn[SMALL_MAX];
-    __shared__ float2 se[MODEL == CSF_BICYCLE ? SMALL_MAX : 1];   // Bicycle field: (e, 1 / sqrt(1 - e^2)) of every source (vehicle.py:1062-1064)
+    constexpr bool MIXED = MODEL == SMALL_MIXED;
+    __shared__ float2 se[MODEL == CSF_BICYCLE || MIXED ? SMALL_MAX : 1];   // Bicycle field: (e, 1 / sqrt(1 - e^2)) of every source (vehicle.py:1062-1064)
     const int lane = (int)threadIdx.x;
     const int n = (int)d.n;
     int P = 1;
@@ -106,7 +119,9 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         double sp, cp;
         sincos(psi, &sp, &cp);
         if (lane < n) sx[lane] = x, sy[lane] = y, spsi[lane] = psi, scs[lane] = cp, ssn[lane] = sp;
-        if (MODEL == CSF_BICYCLE && lane < n) {                    // (what write_record keeps in rec2 for the pair kernels)
+        bool bike = MODEL == CSF_BICYCLE;
+        if constexpr (MIXED) bike = hook.own_model() == CSF_BICYCLE;
+        if (bike && lane < n) {                                    // (what write_record keeps in rec2 for the pair kernels)
             const double v = d.s[3 * cap + a];
             double vref = d.p.v_max_riding[1];
             if constexpr (HOOK::GROUPS) vref = hook.v_ref(lane);   // (the lane's own set: what write_record takes for rec2)
@@ -138,7 +153,9 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             if (!seen) continue;
             int sg = 1;
             float F, gx, gy;
-            if (MODEL == CSF_BICYCLE) {                             // vehicle.py:1054-1147: no jump at phi = 0
+            bool bike_src = MODEL == CSF_BICYCLE;
+            if constexpr (MIXED) bike_src = hook.src_model(j) == CSF_BICYCLE;
+            if (bike_src) {                                         // vehicle.py:1054-1147: no jump at phi = 0
                 field_bicycle(ks, q, se[j], dx, dy, r2, F, gx, gy);
             } else {
                 float sgf = 0.0f;                                   // 0: the sign of the fp32 sine
@@ -200,7 +217,20 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
                 const bool turn = mine && hook.grp == g;
                 if (__ballot(turn) == 0ull) continue;
                 hook.select(dg, g);
-                if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+                if constexpr (MIXED) {
+                    constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
+                    switch (hook.group_model(g)) {                  // (uniform: the class of the group, from its record)
+                    case CSF_BICYCLE: if (turn) agent_body<CSF_BICYCLE, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    case CSF_TWOD: if (turn) agent_body<CSF_TWOD, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    case CSF_INVPEND: if (turn) agent_body<CSF_INVPEND, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    case CSF_PLANARPOINT: if (turn) agent_body<CSF_PLANARPOINT, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    case CSF_PLANARBIKE: if (turn) agent_body<CSF_PLANARBIKE, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    case CSF_BALANCINGRIDER: if (turn) agent_body<CSF_BALANCINGRIDER, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                    default: break;                                 // (the host admits the six classes only)
+                    }
+                } else {
+                    if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);
+                }
             }
         } else {
             if (mine) agent_body<MODEL, false, true>(d, PH_DEST | PH_COMBINE | PH_INTEGRATE, lane, nullptr, ka_lines, rx, ry, rec_slot);

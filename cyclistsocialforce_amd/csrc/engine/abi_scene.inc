@@ -64,7 +64,24 @@ struct SceneCalibState {
     DevBuf<uint8_t> group;                   // [R]
     DevBuf<SceneSet> sets_g;                 // [max_sets][n_groups]
     std::unique_ptr<HostBuf<SceneSet, false>> sets_g_pin;
+    // csf_scene_calib_classes (DESIGN.md 4.10i): the groups are of different vehicle classes.  Empty: none.  Else n_groups, group, sets_g are
+    // those of this call, class_models [n_groups] the class of every group, the engine's state width (Dev::ns, csf_num_states) is the widest
+    // of them while they are held - ns_own is what it was -, and an evaluation restores from cimg_*: the image's state rows, side state and
+    // first ring row as a fresh vehicle of the rider's OWN class has them (abi_population.inc: add_agents_impl, side_state)
+    std::vector<int32_t> class_models;
+    int32_t ns_own = 0;
+    DevBuf<double> cimg_s, cimg_lti, cimg_ppsi, cimg_hx0, cimg_hy0;
+    bool mixed() const { return !class_models.empty(); }
 };
+
+// the classes of csf_scene_calib_classes go: the state width is the engine's own again, the image the load's
+static void scene_drop_classes(csf_engine *e, SceneCalibState &cs) {
+    if (!cs.mixed()) return;
+    e->d.ns = cs.ns_own;
+    cs.class_models.clear();
+    cs.cimg_s = DevBuf<double>(), cs.cimg_lti = DevBuf<double>(), cs.cimg_ppsi = DevBuf<double>();
+    cs.cimg_hx0 = DevBuf<double>(), cs.cimg_hy0 = DevBuf<double>();
+}
 
 // The views on the device from the whole table [max_sets][n_scn] on the host: all of it in `table`, or - a wide load - the narrow
 // scenes' in `table` and the wide scenes' in `table_w`, both [max_sets][their scenes].  Allocates; the caller waits for the device.
@@ -396,6 +413,9 @@ static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, cons
 int csf_scene_calib_eval_road(csf_engine *e, int32_t n_sets, const csf_params *params, size_t params_size, int32_t abi_version,
                               const double *road_F0, const double *road_sigma, double *sums_out, int32_t stride, double *states_out) try {
     if (!e) return CSF_E_ARG;
+    if (e->scene_calib && e->scene_calib->mixed())
+        return fail(e, CSF_E_STATE, "csf_scene_calib_eval: the riders are in %d groups of several vehicle classes (csf_scene_calib_classes) and one set cannot say what group 1 carries: csf_scene_calib_eval_groups",
+                    (int)e->scene_calib->n_groups);
     if (e->scene_calib && e->scene_calib->n_groups > 0)
         return fail(e, CSF_E_STATE, "csf_scene_calib_eval: the riders are in %d groups (csf_scene_calib_groups / _lane_groups) and one set cannot say what group 1 carries: csf_scene_calib_eval_groups",
                     (int)e->scene_calib->n_groups);
@@ -447,12 +467,98 @@ static int scene_groups_impl(csf_engine *e, const char *fn, bool lanes, const ui
         if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "%s: no memory for the groups: %s", fn, hipGetErrorString(r));
         std::memset(pin->p, 0, recs * sizeof(SceneSet));
     }
+    scene_drop_classes(e, cs);                                 // (these groups replace the classes of csf_scene_calib_classes)
     cs.group = std::move(d_group);
     cs.sets_g = std::move(d_sets);
     cs.sets_g_pin = std::move(pin);
     cs.n_groups = drop ? 0 : n_groups;
     return CSF_OK;
 }
+
+int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0) try {
+    if (!e) return CSF_E_ARG;
+    const char *fn = "csf_scene_calib_classes";
+    if (!e->scene_calib) {
+        if (e->calib) return fail(e, CSF_E_STATE, "%s: the engine holds the data set of csf_calib_load, whose candidate sets are whole populations already", fn);
+        return fail(e, CSF_E_STATE, "%s: no closed-loop data set (csf_scene_calib_load first)", fn);
+    }
+    SceneCalibState &cs = *e->scene_calib;
+    if (cs.Lsum > 0)
+        return fail(e, CSF_E_STATE, "%s: the data set shares its lanes (csf_scene_calib_load_shared / _load_wide): mixed classes need csf_scene_calib_load - one slot per rider, at most %d riders per scene", fn, SMALL_MAX);
+    const bool drop = group == nullptr && n_groups == 0 && models == nullptr && s0 == nullptr;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (drop) {                                                // the data set is what it was after the load (groups of either call go)
+        HIPCHK(e, hipStreamSynchronize(e->main));
+        scene_drop_classes(e, cs);
+        cs.group = DevBuf<uint8_t>();
+        cs.sets_g = DevBuf<SceneSet>();
+        cs.sets_g_pin.reset();
+        cs.n_groups = 0;
+        return CSF_OK;
+    }
+    if (n_groups < 2 || n_groups > SCENE_CLASS_GROUPS_MAX) return fail(e, CSF_E_ARG, "%s: %d groups (2 .. %d)", fn, (int)n_groups, SCENE_CLASS_GROUPS_MAX);
+    if (!group || !models) return fail(e, CSF_E_ARG, "%s: NULL array", fn);
+    if (!s0) return fail(e, CSF_E_ARG, "%s: s0 is NULL: the start states in the widest layout, [R][%d]", fn, STATE_ROWS);
+    for (int32_t g = 0; g < n_groups; g++)
+        if (models[g] < 0 || models[g] > CSF_BALANCINGRIDER || models[g] == CSF_UNCONTROLLED)
+            return fail(e, CSF_E_ARG, "%s: group %d is of vehicle class %d: not one of the six simulated classes", fn, (int)g, (int)models[g]);
+    for (int32_t r = 0; r < cs.R; r++)
+        if (group[r] >= n_groups) return fail(e, CSF_E_ARG, "%s: rider %d is in group %d of %d", fn, (int)r, (int)group[r], (int)n_groups);
+    // the image per rider and class: what csf_add_agents and side_state make of a fresh vehicle of that class (vehicle.py:64-204, 1728-1736;
+    // dynamics.py:306-307, 350-371 for the BalancingRider's mirrored layout).  zrid and dgood follow in the kernel from the rider's own record
+    const size_t Rs = (size_t)cs.R;
+    std::vector<double> is(STATE_ROWS * Rs, 0.0), il(5 * Rs, 0.0), ip(Rs, 0.0), hx(Rs), hy(Rs);
+    int32_t ns = 0;
+    for (int32_t g = 0; g < n_groups; g++) ns = std::max(ns, (int32_t)NS_OF[models[g]]);
+    for (size_t r = 0; r < Rs; r++) {
+        const int m = models[group[r]];
+        const double *s = s0 + r * STATE_ROWS;
+        double v[STATE_ROWS];
+        for (int c = 0; c < STATE_ROWS; c++) v[c] = c < NS_OF[m] ? s[c] : 0.0;
+        v[2] = limit_angle_h(s[2]);                            // vehicle.py:154-155
+        for (int c = 0; c < STATE_ROWS; c++) is[(size_t)c * Rs + r] = v[c];
+        hx[r] = s[0], hy[r] = s[1];                            // traj[:, 0] = s  (vehicle.py:159-160)
+        if (m == CSF_BALANCINGRIDER) {
+            il[0 * Rs + r] = v[5], il[1 * Rs + r] = -v[4], il[2 * Rs + r] = v[7], il[3 * Rs + r] = -v[6], il[4 * Rs + r] = -v[2];
+            ip[r] = v[3];
+        } else {
+            il[0 * Rs + r] = v[4], il[2 * Rs + r] = v[5], il[4 * Rs + r] = v[2];
+            ip[r] = v[2];
+        }
+    }
+    HIPCHK(e, hipStreamSynchronize(e->main));
+    // everything that can fail first: a refused call changes nothing
+    DevBuf<uint8_t> d_group;
+    DevBuf<SceneSet> d_sets;
+    DevBuf<double> d_s, d_l, d_p, d_hx, d_hy;
+    std::unique_ptr<HostBuf<SceneSet, false>> pin(new HostBuf<SceneSet, false>());
+    const size_t recs = (size_t)cs.max_sets * (size_t)n_groups;
+    hipError_t r = d_group.alloc(Rs);
+    if (r == hipSuccess) r = d_sets.alloc(recs);
+    if (r == hipSuccess) r = pin->alloc(recs);
+    if (r == hipSuccess) r = d_s.alloc(is.size());
+    if (r == hipSuccess) r = d_l.alloc(il.size());
+    if (r == hipSuccess) r = d_p.alloc(Rs);
+    if (r == hipSuccess) r = d_hx.alloc(Rs);
+    if (r == hipSuccess) r = d_hy.alloc(Rs);
+    if (r == hipSuccess) r = hipMemcpy(d_group.p, group, Rs, hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipMemcpy(d_s.p, is.data(), is.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipMemcpy(d_l.p, il.data(), il.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipMemcpy(d_p.p, ip.data(), Rs * sizeof(double), hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipMemcpy(d_hx.p, hx.data(), Rs * sizeof(double), hipMemcpyHostToDevice);
+    if (r == hipSuccess) r = hipMemcpy(d_hy.p, hy.data(), Rs * sizeof(double), hipMemcpyHostToDevice);
+    if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "%s: no memory for the classes: %s", fn, hipGetErrorString(r));
+    std::memset(pin->p, 0, recs * sizeof(SceneSet));
+    if (!cs.mixed()) cs.ns_own = e->d.ns;
+    cs.group = std::move(d_group);
+    cs.sets_g = std::move(d_sets);
+    cs.sets_g_pin = std::move(pin);
+    cs.n_groups = n_groups;
+    cs.class_models.assign(models, models + n_groups);
+    cs.cimg_s = std::move(d_s), cs.cimg_lti = std::move(d_l), cs.cimg_ppsi = std::move(d_p), cs.cimg_hx0 = std::move(d_hx), cs.cimg_hy0 = std::move(d_hy);
+    e->d.ns = ns;                                              // csf_num_states: the widest class while the classes are held
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
 
 int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {
     if (!e) return CSF_E_ARG;
@@ -479,7 +585,11 @@ static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, cons
     for (int32_t k = 0; k < n_sets * G; k++) {
         int rc = check_params(e, params + k);
         if (rc) return rc;
-        if (params[k].model != e->d.p.model) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d is of vehicle class %d, the data set was loaded for class %d", (int)k, (int)params[k].model, (int)e->d.p.model);
+        if (cs.mixed()) {                                      // (csf_scene_calib_classes: record (set, g) is of the class loaded for group g)
+            if (params[k].model != cs.class_models[(size_t)(k % G)])
+                return fail(e, CSF_E_ARG, "csf_scene_calib_eval_groups: the record of set %d, group %d is of vehicle class %d, the group was loaded with class %d (csf_scene_calib_classes)",
+                            (int)(k / G), (int)(k % G), (int)params[k].model, (int)cs.class_models[(size_t)(k % G)]);
+        } else if (params[k].model != e->d.p.model) return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d is of vehicle class %d, the data set was loaded for class %d", (int)k, (int)params[k].model, (int)e->d.p.model);
         if (params[k].t_s != e->d.p.t_s || params[k].traj_len != e->d.p.traj_len)
             return fail(e, CSF_E_ARG, "csf_scene_calib_eval: parameter set %d: t_s and traj_len are the engine's (parameters.py:516-528)", (int)k);
     }
@@ -570,6 +680,7 @@ static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, cons
     }
     SceneSet *const d_sets = n_groups > 0 ? cs.sets_g.p : cs.sets.p;
     if (n_groups > 0) c.group = cs.group.p, c.n_groups = n_groups;
+    if (cs.mixed()) c.img_s = cs.cimg_s.p, c.img_lti = cs.cimg_lti.p, c.img_ppsi = cs.cimg_ppsi.p, c.img_hx0 = cs.cimg_hx0.p, c.img_hy0 = cs.cimg_hy0.p;
     HIPCHK(e, hipMemcpyAsync(d_sets, pin, (size_t)n_sets * (size_t)G * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
     if (cs.wide_from > 0) {   // the narrow scenes on scene_lanes_kernel, the wide ones on scene_wide_kernel: one stream, one wait
         SceneWideDev w{};
@@ -577,6 +688,8 @@ static int scene_eval_impl(csf_engine *e, int32_t n_sets, int32_t n_groups, cons
         w.n_wide = (int32_t)cs.h_scn_w.size(), w.n_narrow = (int32_t)cs.h_scn_n.size();
         w.len_n = cs.len_n.p, w.roff_n = cs.roff_n.p, w.lane_off_n = cs.lane_off_n.p;
         cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main, &w);
+    } else if (cs.mixed()) {   // several vehicle classes: scene_mixed_kernel, the views' state width the widest of them
+        cs.launches += launch_scene_mixed(cs.table.p, d_sets, c, e->d.ns, e->main);
     } else {
         cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main);
     }
@@ -784,5 +897,6 @@ int csf_scene_calib_clear(csf_engine *e) try {
     e->scene_calib.reset();
     rc = all.empty() ? CSF_OK : csf_remove_agents(e, (int64_t)all.size(), all.data());
     if (rc) e->scene_calib = std::move(cs);                            // (refused before it touched the mirror: the data set stays)
+    else if (cs->mixed()) e->d.ns = cs->ns_own;                        // (csf_scene_calib_classes: the state width is the engine's own again)
     return rc;                                                         // the buffers go with cs
 } catch (...) { return csf_caught(e); }

@@ -417,6 +417,7 @@ class Engine:
         R, _ = self._scene_calib
         if group is None:
             self._ck(self._lib.csf_scene_calib_groups(self._h, None, 0))
+            self.ns = int(self._lib.csf_num_states(self._h))
             return
         g = np.asarray(group)
         if g.shape != (R,) or g.dtype.kind not in "iub":
@@ -425,6 +426,7 @@ class Engine:
             raise ValueError("group: entries are 0 .. n_groups - 1")
         g8 = np.ascontiguousarray(g, dtype=np.uint8)
         self._ck(self._lib.csf_scene_calib_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+        self.ns = int(self._lib.csf_num_states(self._h))         # (the call replaces the classes of scene_calib_classes)
 
     def scene_calib_lane_groups(self, group, n_groups=None):
         """scene_calib_groups for a data set of scene_calib_load_shared / scene_calib_load_wide: group [R] per RIDER (integers
@@ -444,6 +446,36 @@ class Engine:
             raise ValueError("group: entries are 0 .. n_groups - 1")
         g8 = np.ascontiguousarray(g, dtype=np.uint8)
         self._ck(self._lib.csf_scene_calib_lane_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+
+    def scene_calib_classes(self, group, models=None, s0=None):
+        """Rider groups of DIFFERENT VEHICLE CLASSES on the loaded scenes (scene_calib_load only): group [R] (integers 0 .. G - 1), models
+        [G] the vehicle class of every group (the constants of _ffi: BICYCLE, TWOD, INVPEND, PLANARPOINT, PLANARBIKE, BALANCINGRIDER;
+        2 <= G <= 12) and s0 [R, <= 8] the start states in the widest layout (missing columns: 0).  `ns` becomes the widest state of the
+        loaded classes; rows a class lacks stay 0.  An evaluation is scene_calib_eval_groups with tuple entry g of class models[g].  The
+        call replaces the groups of scene_calib_groups and that call replaces these; None drops the classes."""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError("scene_calib_classes: no closed-loop data set (scene_calib_load first)")
+        R, _ = self._scene_calib
+        if group is None:
+            self._ck(self._lib.csf_scene_calib_classes(self._h, None, 0, None, None))
+            self.ns = int(self._lib.csf_num_states(self._h))
+            return
+        g = np.asarray(group)
+        if g.shape != (R,) or g.dtype.kind not in "iub":
+            raise ValueError("group must have one integer entry per rider of the data set")
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("group: entries are 0 .. n_groups - 1")
+        if models is None or s0 is None:
+            raise ValueError("models [n_groups] and s0 [R, <= 8] are needed with group")
+        g8 = np.ascontiguousarray(g, dtype=np.uint8)
+        m = np.ascontiguousarray(models, dtype=np.int32).reshape(-1)
+        s = np.asarray(s0, dtype=np.float64)
+        if s.ndim != 2 or s.shape[0] != R or not 4 <= s.shape[1] <= 8:
+            raise ValueError("s0 must be [sum(n_riders), 4 .. 8]: the start states in the widest layout")
+        wide = np.zeros((R, 8))
+        wide[:, : s.shape[1]] = s
+        self._ck(self._lib.csf_scene_calib_classes(self._h, _ptr(g8), int(m.size), _ptr(m), _ptr(wide)))
+        self.ns = int(self._lib.csf_num_states(self._h))
 
     def scene_calib_eval_groups(self, pods, road_F0=None, road_sigma=None, states=False, stride=1):
         """scene_calib_eval for riders in groups: `pods` is a sequence of n_groups-tuples of csf_params, tuple k the candidate k and
@@ -469,6 +501,7 @@ class Engine:
     def scene_calib_clear(self):
         self._ck(self._lib.csf_scene_calib_clear(self._h))
         self._scene_calib = None
+        self.ns = int(self._lib.csf_num_states(self._h))         # (scene_calib_classes: the engine's own width again)
 
     def scene_calib_launches(self):
         """kernel launches of scene_calib_eval since scene_calib_load: one per call (after scene_calib_load_wide: one per call and kind

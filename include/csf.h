@@ -582,7 +582,28 @@ int csf_calib_clear(csf_engine *e);
  * NULL or n_groups <= 1 drops the groups, and evaluations are then what they were, bit for bit.  The checks, the allocate-before-replace
  * order and the refusals are csf_scene_calib_groups's, but for the data set: CSF_E_STATE on a plain csf_scene_calib_load data set (that one
  * takes csf_scene_calib_groups), without a closed-loop data set and with csf_calib_load's; CSF_E_ARG for n_groups > 4 and for an entry
- * >= n_groups.  csf_scene_calib_clear frees the groups with the rest.  csf_scene_calib_groups keeps its refusal on such a data set. */
+ * >= n_groups.  csf_scene_calib_clear frees the groups with the rest.  csf_scene_calib_groups keeps its refusal on such a data set.
+ *
+ * csf_scene_calib_classes gives the riders of a csf_scene_calib_load data set groups of DIFFERENT VEHICLE CLASSES -
+ * a Bicycle among TwoDBicycles, a BalancingRiderBicycle among InvPendulumBicycles, all simulated: group [R] holds 0 .. n_groups - 1 per
+ * rider, 2 <= n_groups <= 12 (six classes x two kinds of rider), models [n_groups] the enum csf_model of every group (not
+ * CSF_UNCONTROLLED; the engine's own class need not be among them) and s0 [R][8] the start states in the WIDEST layout (x, y, psi, v,
+ * delta, theta, steer rate, roll rate) - the load kept the columns of the engine's class only.  The call rewrites the reset image per
+ * rider: the state rows its class has (the others 0), the integrator's side state of that class and the first row of the position ring,
+ * as csf_add_agents makes them for a fresh vehicle of that class.  While classes are held csf_num_states - and the layout of states_out
+ * and of the read-backs - is the widest of the LOADED classes, and rows a class lacks stay 0.  The evaluation is
+ * csf_scene_calib_eval_groups with params [n_sets][n_groups] and params[k * n_groups + g].model == models[g] (CSF_E_ARG names set, group
+ * and both classes): ONE launch, a rider is ticked by the per-agent tick of its class with its own record, restored with its limits, and
+ * acts as a source with the field of ITS class - the Bicycle's or the TwoD one - and its record's field of view (intersection.py:797-823);
+ * the priority rule of a candidate is record (k, 0)'s.  csf_scene_calib_eval / _eval_road are refused (CSF_E_STATE) as under groups.
+ * Replay (a replayed BalancingRider keeps its unwrapped yaw consistent as csf_push_state does), windows, roads and road parameters per
+ * candidate, loaded before or after, work as without classes.  The call replaces groups loaded by csf_scene_calib_groups, and that call
+ * replaces these; (NULL, 0, NULL, NULL) drops the classes - the data set is what it was after the load, evaluations bit for bit what
+ * they were.  Everything is validated and allocated before anything is replaced: a refused call leaves the held groups or classes in
+ * force.  CSF_E_STATE without a closed-loop data set and on a data set of csf_scene_calib_load_shared / _load_wide (mixed classes need
+ * csf_scene_calib_load); CSF_E_ARG for n_groups outside 2 .. 12, an entry of group >= n_groups, an entry of models outside the six classes,
+ * a NULL array.  csf_scene_calib_clear frees the classes with the rest. */
+int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0);
 int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
 int csf_scene_calib_lane_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
 int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params,

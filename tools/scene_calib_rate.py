@@ -45,7 +45,13 @@ are timed there.  With --presence --share the packed data set of that cell gets 
 `packed_groups_base_ms` - per (set, scene) one general-path engine that holds the G sets, stepped tick by tick, a rider added
 (add_agents, set_agent_class, set_dest_queue) at its entry and removed at its exit, the state read back after every tick.
 
-    python tools/scene_calib_rate.py [--groups 2 [--groups-base-max 16]] [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
+--mixed adds the legs of several vehicle classes in one scene on the plain data set (not with --riders), under "mixed":
+the same scenes with rider r in group r % 2 and BOTH groups of the cell's one class, once through csf_scene_calib_groups
+(`one_class_groups_ms`) and once through csf_scene_calib_classes (`one_class_classes_ms`) - the two alternate window by window, each
+behind a warm-up call, and `one_class_equal` says whether their sums are array_equal: the cost of the merged kernel -, then a two-class
+mix (twod, invpend: `two_classes_ms`) and a six-class mix (rider r of class r % 6: `six_classes_ms`), one launch per evaluation each.
+
+    python tools/scene_calib_rate.py [--mixed] [--groups 2 [--groups-base-max 16]] [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
                                      [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
                                      [--riders 40,96 [--wide-from 33]]
 """
@@ -109,10 +115,13 @@ def main():
     ap.add_argument("--wide-from", type=int, default=33)
     ap.add_argument("--groups", type=int, default=0)
     ap.add_argument("--groups-base-max", type=int, default=16)
+    ap.add_argument("--mixed", action="store_true")
     a = ap.parse_args()
     riders = [int(x) for x in a.riders.split(",")] if a.riders else None
     if riders and (a.replay or a.road or a.presence or min(riders) < 1 or max(riders) > 256):
         ap.error("--riders takes 1 .. 256 road users per scene and stands alone: not with --replay, --road or --presence")
+    if a.mixed and riders:
+        ap.error("--mixed runs on the plain load: not with --riders")
     if a.groups and not 2 <= a.groups <= 4:
         ap.error("--groups takes 2 .. 4")
     if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
@@ -382,6 +391,51 @@ def main():
                             groups_base_ms=dict(median=float(np.median(t_gold)), min=min(t_gold), max=max(t_gold)) if t_gold else None)
                 for t in gtwins:
                     t.close()
+            if a.mixed:
+                from cyclistsocialforce_amd.engine import MODEL_IDS
+                e.scene_calib_replay(None)
+                wide = np.zeros((R, 8))
+                wide[:, : s0.shape[1]] = s0
+                rider = np.concatenate([np.arange(n) for n in nr])
+
+                def class_tuples(classes):
+                    """candidate k: record g the default set of classes[g], its field scaled as pod_sets scales it and by 1 + 0.1 g"""
+                    out = []
+                    for k in range(n_sets):
+                        tup = []
+                        for g, m in enumerate(classes):
+                            c = parameters.default_pod(m)
+                            c.f_0, c.p_0 = c.f_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g), c.p_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g)
+                            tup.append(c)
+                        out.append(tuple(tup))
+                    return out
+
+                def ms(t):
+                    return dict(median=float(np.median(t)), min=min(t), max=max(t))
+
+                grp2 = (rider % 2).astype(np.uint8)
+                one = class_tuples([model, model])
+                t_grp, t_cls, equal = [], [], True
+                for _ in range(a.windows):
+                    e.scene_calib_groups(grp2, 2)
+                    ref = e.scene_calib_eval_groups(one)
+                    t0 = time.perf_counter(); e.scene_calib_eval_groups(one); t_grp.append((time.perf_counter() - t0) * 1e3)
+                    e.scene_calib_classes(grp2, [MODEL_IDS[model]] * 2, wide)
+                    equal = equal and bool(np.array_equal(ref, e.scene_calib_eval_groups(one)))
+                    t0 = time.perf_counter(); e.scene_calib_eval_groups(one); t_cls.append((time.perf_counter() - t0) * 1e3)
+                mixed = dict(one_class_groups_ms=ms(t_grp), one_class_classes_ms=ms(t_cls), one_class_equal=equal)
+                for name, classes in (("two_classes_ms", ("twod", "invpend")), ("six_classes_ms", ("twod", "bicycle", "invpend", "planarpoint", "planarbike", "balancingrider"))):
+                    tups = class_tuples(classes)
+                    e.scene_calib_classes((rider % len(classes)).astype(np.uint8), [MODEL_IDS[m] for m in classes], wide)
+                    before = e.scene_calib_launches()
+                    e.scene_calib_eval_groups(tups)
+                    assert e.scene_calib_launches() == before + 1
+                    t_mix = []
+                    for _ in range(a.windows):
+                        t0 = time.perf_counter(); e.scene_calib_eval_groups(tups); t_mix.append((time.perf_counter() - t0) * 1e3)
+                    mixed[name] = ms(t_mix)
+                e.scene_calib_classes(None)
+                line["mixed"] = mixed
             print(json.dumps(line), flush=True)
             if a.out:
                 with open(a.out, "a") as f:
