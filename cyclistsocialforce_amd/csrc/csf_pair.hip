@@ -130,7 +130,17 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     }
 
     float ax[RPW], ay[RPW];     // the receivers themselves stay in LDS (rrec); one at a time is held in registers
-    int qhead = 0, qlen = 0;    // wave-uniform ring state of the queue
+    // Wave-uniform ring state of the queue.  qx: BYTE offset of the head entry within `queue`, qlen: entries queued.  A visit starts
+    // with the head at the start of the wave's row and a full pass pops exactly CHUNK = QCAP / 2 entries, so the head only ever sits
+    // at entry 0 or CHUNK of the row: a pass reads 2 * CHUNK bytes from qx on without wrapping, and an entry L < QCAP places
+    // behind the head lies at byte qx ^ 2 L (head 0: + 2 L; head CHUNK: adding CHUNK modulo QCAP flips the one bit) - no mask, and
+    // the row's base is folded into the scalar.
+    static_assert(QCAP == 2 * CHUNK && (QCAP & (QCAP - 1)) == 0, "the head of the ring toggles between the halves of a row");
+    unsigned qx = (unsigned)wave * (unsigned)(QCAP * sizeof(unsigned short));
+    int qlen = 0;
+    auto qentry = [&](unsigned byte_off) -> unsigned short & { return *(unsigned short *)((char *)&queue[0][0] + byte_off); };
+    // entry `at` (< QCAP) places behind the head
+    auto qslot = [&](unsigned at) -> unsigned short & { return qentry(qx ^ (at << 1)); };
     unsigned evals = 0;         // pair evaluations of this wave (wave-uniform: scalar adds; written out for csf_count_pairs)
     unsigned tests = 0;         // ... sources put through the per-lane tests, and full | partial << 16 evaluation passes
     unsigned pops = 0;
@@ -156,22 +166,41 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         ndrop += nn > NCAP ? (unsigned)(nn - NCAP) : 0u;      // (reported once, at the end: csf_near_dropped - the tests assert 0)
         nlen = __builtin_amdgcn_readfirstlane(nn < NCAP ? nn : NCAP);
     };
+    // `m != 0` as a BRANCH on the scalar: joined to a per-lane condition it would only be and-ed into the lanes' mask, and the
+    // instructions behind it issue for an empty mask all the same (the empty statement keeps the two conditions apart)
+    auto any_lane = [](unsigned long long m) {
+        if (m == 0ull) return false;
+        asm volatile("");
+        return true;
+    };
+    // byte offset of the entry `lane` places behind the head.  (Written as the one instruction it is: from `qx + 2 * lane` the compiler
+    // keeps 2 * lane, with the queue's base, in a register of its own for the whole kernel and spills it to scratch memory.)
+    auto qhead_lane = [&]() {
+        unsigned qa;
+        asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(qa) : "v"(lane), "s"(qx));
+        return qa;
+    };
     // pop CHUNK (or, when draining, whatever is left) queued sources of receiver u; the field takes two per lane
     auto pop = [&](int u, auto full) {
         constexpr bool FULL = decltype(full)::value;
         const int n = FULL ? CHUNK : (qlen < CHUNK ? qlen : CHUNK);
-        int i0 = queue[wave][(qhead + lane) & (QCAP - 1)];
-        int i1 = queue[wave][(qhead + WAVE + lane) & (QCAP - 1)];
+        const unsigned qa = qhead_lane();      // (one address: the second half is a constant 2 * WAVE bytes behind)
+        int i0 = qentry(qa);
+        int i1 = qentry(qa + 2u * WAVE);
         const bool v0 = lane < n, v1 = lane + WAVE < n;
         if (!FULL) i0 = v0 ? i0 : 0, i1 = v1 ? i1 : 0;
         unsigned long long n0, n1;
         field_twod_x2<FULL, true>(k, ru, lds_pair_b(tx, i0, i1), lds_pair_b(ty, i0, i1), lds_pair_b(tc, i0, i1),
                                   lds_pair_b(ts, i0, i1), v0, v1, ax[u], ay[u], &n0, &n1);
         if (__builtin_expect((n0 | n1) != 0ull, 0)) {   // rare: a pair among the 128 to be corrected (the queue still holds their offsets)
-            near_note(((n0 >> lane) & 1ull) != 0ull, (int)queue[wave][(qhead + lane) & (QCAP - 1)] >> 2);
-            near_note(((n1 >> lane) & 1ull) != 0ull, (int)queue[wave][(qhead + WAVE + lane) & (QCAP - 1)] >> 2);
+            // (read again through an address formed here: taken from above, address and entries would stay in registers across the field)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const unsigned qb = qx + 2u * (unsigned)ln;
+            near_note(((n0 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb) >> 2);
+            near_note(((n1 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb + 2u * WAVE) >> 2);
         }
-        qhead = __builtin_amdgcn_readfirstlane((qhead + n) & (QCAP - 1));
+        if (FULL) qx ^= 2u * CHUNK;       // (a partial pass ends the visit, which puts the head back)
         qlen = __builtin_amdgcn_readfirstlane(qlen - n);
         if (FULL) pops += 1u;             // (the evaluations of the full passes are added at the end: 128 each)
         else evals += (unsigned)n, pops += 0x10000u;
@@ -180,7 +209,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     // instructions of a packed evaluation whose second half would be empty
     auto pop_tail = [&](int u) {
         const bool v = lane < qlen;
-        const int o = v ? (int)queue[wave][(qhead + lane) & (QCAP - 1)] : 0;
+        const int o = v ? (int)qentry(qhead_lane()) : 0;
         const float4 q = make_float4(*(const float *)((const char *)tx + o), *(const float *)((const char *)ty + o),
                                      *(const float *)((const char *)tc + o), *(const float *)((const char *)ts + o));
         const float dx = ru.x - q.x, dy = ru.y - q.y, r2 = dx * dx + dy * dy;
@@ -198,7 +227,6 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         ay[u] += F * gy;
         evals += (unsigned)qlen;
         pops += 0x10000u;
-        qhead = __builtin_amdgcn_readfirstlane((qhead + qlen) & (QCAP - 1));
         qlen = 0;
     };
 
@@ -486,7 +514,9 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 // (A single loop over both kinds of batch pairs with the records of the next pair requested ahead of the
                 // queue append was tried: the compiler spilled 30 registers into the loops and the kernel ran at 180 us.)
                 // test of the two batches whose records are in (sx, sy, sc, ss), append of what it keeps
-                auto sift2 = [&](int b1, int b2, bool two, auto fov, v2f sx, v2f sy, v2f sc, v2f ss) {
+                // (t1, t2: byte offsets of this lane's records of the two batches in the tile arrays - what the records were read
+                // through and what is queued)
+                auto sift2 = [&](int t1, int t2, bool two, auto fov, v2f sx, v2f sy, v2f sc, v2f ss) {
                     constexpr bool FOV = decltype(fov)::value;
                     bool k0, k1, mg0, mg1;
                     keep_x2<FOV, P2R>(k, ru, sx, sy, sc, ss, k0, k1, mg0, mg1);
@@ -497,26 +527,32 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                     // lives across the queue append
                     const unsigned long long g0 = FOV ? (ballot1(mg0) & m0) : 0ull, g1 = FOV ? (ballot1(mg1) & m1) : 0ull;
                     const int n0 = __builtin_popcountll(m0);
-                    if (k0) {                       // slot = (head + length) + kept lanes below this one: v_mbcnt adds onto its operand
-                        const int at = __builtin_amdgcn_mbcnt_hi((unsigned)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0, (unsigned)(qhead + qlen)));
-                        queue[wave][at & (QCAP - 1)] = (unsigned short)(4 * ((b1 << 6) + lane));
+                    // slot = length + kept lanes below this one, behind the head; the length joins as a scalar, formed out here for both
+                    // halves (inside the branches the second one reached the length's update through a vector register)
+                    int q1 = qlen + n0;
+                    asm volatile("" : "+s"(q1));
+                    // (a third of the halves keep nothing: a scalar branch around the append - short as it is now, the compiler
+                    // no longer skips it on an empty mask by itself, and four vector instructions and an LDS write would issue for no lane)
+                    if (any_lane(m0) && k0) {
+                        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m0, 0u));
+                        qslot(below + (unsigned)qlen) = (unsigned short)t1;
                     }
-                    if (k1) {
-                        const int at = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, (unsigned)(qhead + qlen + n0)));
-                        queue[wave][at & (QCAP - 1)] = (unsigned short)(4 * ((b2 << 6) + lane));
+                    if (any_lane(m1) && k1) {
+                        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m1, 0u));
+                        qslot(below + (unsigned)q1) = (unsigned short)t2;
                     }
-                    qlen = __builtin_amdgcn_readfirstlane(qlen + n0 + __builtin_popcountll(m1));
+                    qlen = __builtin_amdgcn_readfirstlane(q1 + __builtin_popcountll(m1));
                     if (FOV && __builtin_expect((g0 | g1) != 0ull, 0)) {     // ... noted: decided exactly where the noted pairs are corrected (near_drain)
-                        near_note(((g0 >> lane) & 1ull) != 0ull, (b1 << 6) + lane);
-                        near_note(((g1 >> lane) & 1ull) != 0ull, (b2 << 6) + lane);
+                        near_note(((g0 >> lane) & 1ull) != 0ull, t1 >> 2);
+                        near_note(((g1 >> lane) & 1ull) != 0ull, t2 >> 2);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     while (qlen >= CHUNK) pop(u, std::true_type{});
                 };
                 auto load2 = [&](int b1, int b2, bool two, auto fov) {
-                    const int i0 = (b1 << 6) + lane, i1 = (b2 << 6) + lane;
-                    sift2(b1, b2, two, fov, lds_pair(tx, i0, i1), lds_pair(ty, i0, i1), lds_pair(tc, i0, i1), lds_pair(ts, i0, i1));
+                    const int t1 = (b1 << 8) | (lane << 2), t2 = (b2 << 8) | (lane << 2);   // one address per batch: read through, then queued
+                    sift2(t1, t2, two, fov, lds_pair_b(tx, t1, t2), lds_pair_b(ty, t1, t2), lds_pair_b(tc, t1, t2), lds_pair_b(ts, t1, t2));
                 };
                 unsigned ins = inside;
                 while (__builtin_popcount(ins) >= 2) {
@@ -563,7 +599,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 cand &= cand - 1u;
                 const int tb = (b << 8) + 4 * lane;   // byte offset of this lane's record in the tile arrays
                 if ((inside >> b) & 1u) {
-                    queue[wave][(qhead + qlen + lane) & (QCAP - 1)] = (unsigned short)tb;
+                    qslot((unsigned)(qlen + lane)) = (unsigned short)tb;
                     qlen = __builtin_amdgcn_readfirstlane(qlen + WAVE);
                 } else {
                     const float dx = ru.x - *(const float *)((const char *)tx + tb), dy = ru.y - *(const float *)((const char *)ty + tb);
@@ -571,9 +607,9 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                     tracked_c<P2R>(k, ru, dx, dy, in, lt);
                     tests += (unsigned)WAVE;
                     const unsigned long long m = ballot1(in), mg = ballot1(lt) & m;
-                    if (in) {
-                        const int pre = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                        queue[wave][(qhead + qlen + pre) & (QCAP - 1)] = (unsigned short)tb;
+                    if (any_lane(m) && in) {
+                        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                        qslot(below + (unsigned)qlen) = (unsigned short)tb;
                     }
                     qlen = __builtin_amdgcn_readfirstlane(qlen + __builtin_popcountll(m));
                     if (__builtin_expect(mg != 0ull, 0)) near_note(((mg >> lane) & 1ull) != 0ull, (b << 6) + lane);
@@ -586,6 +622,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             while (qlen >= CHUNK) pop(u, std::true_type{});
             if (qlen > WAVE) pop(u, std::false_type{});
             else if (qlen > 0) pop_tail(u);
+            qx &= ~(2u * (unsigned)CHUNK);      // the queue is empty: the next visit starts at the head of the row
             if (DYN) {  // column sum of this receiver: x in the lower half of the wave, y in the upper, then within halves
                 float v = swap_add32(ax[0], ay[0]);
                 v += dpp<DPP_ROW_ROR8>(v);
