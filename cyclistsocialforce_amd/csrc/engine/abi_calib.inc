@@ -6,6 +6,7 @@
 // that inner loop for ONE replay - it allocates, uploads the forces, launches once per tick and copies every state back.  Here the
 // data set is uploaded once (csf_calib_load), and one call evaluates up to 256 candidate sets on all sequences in one launch
 // (csf_calib.hip: replay_eval_kernel) and returns two sums per (set, sequence), from which both error functions follow.
+// Also here, for this data set and the closed-loop one (engine/abi_scene.inc): remove_everybody, calib_undo_load, calib_load_refuses.
 
 extern "C++" {
 
@@ -27,6 +28,29 @@ struct CalibState {
     size_t tab_bytes() const { return pb_off() + (size_t)max_sets * 7 * sizeof(double); }
 };
 
+// every road user of the engine leaves: what the two data sets' loads take back when they fail, and their _clear calls
+static int remove_everybody(csf_engine *e) {
+    std::vector<int32_t> all(e->order.size());
+    for (size_t i = 0; i < all.size(); i++) all[i] = (int32_t)i;
+    return all.empty() ? CSF_OK : csf_remove_agents(e, (int64_t)all.size(), all.data());
+}
+
+// a load that fails behind add_agents_impl: the engine was empty, so what has been added goes again; the call's message and code stay
+static int calib_undo_load(csf_engine *e, int code) {
+    const std::string msg = e->err;
+    (void)remove_everybody(e);
+    e->err = msg;
+    return code;
+}
+
+// the engine states both loads refuse in the same words; what they say differently stays with them
+static int calib_load_refuses(csf_engine *e, const char *fn) {
+    if (!e->order.empty()) return fail(e, CSF_E_STATE, "%s: the engine is not empty (%lld road users)", fn, (long long)e->order.size());
+    if (e->batch) return fail(e, CSF_E_STATE, "%s: the engine belongs to a batch (csf_batch_leave first)", fn);
+    if (e->loopback) return fail(e, CSF_E_STATE, "%s: the engine is a member of a loopback group", fn);
+    return CSF_OK;
+}
+
 }  // extern "C++"
 
 int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *s0, const double *Fx, const double *Fy, const int32_t *lengths,
@@ -37,9 +61,7 @@ int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *
         return fail(e, CSF_E_ARG, "csf_calib_load: n_seq >= 1, 1 <= n_ticks <= 2e9, 1 <= n_feat <= %d, 1 <= max_sets <= 256", CALIB_MAX_FEAT);
     if (e->calib) return fail(e, CSF_E_STATE, "csf_calib_load: the engine holds a calibration data set already (csf_calib_clear first)");
     if (int crc = calib_refuses(e, "csf_calib_load")) return crc;      // (a closed-loop data set: engine/abi_scene.inc)
-    if (!e->order.empty()) return fail(e, CSF_E_STATE, "csf_calib_load: the engine is not empty (%lld road users)", (long long)e->order.size());
-    if (e->batch) return fail(e, CSF_E_STATE, "csf_calib_load: the engine belongs to a batch (csf_batch_leave first)");
-    if (e->loopback) return fail(e, CSF_E_STATE, "csf_calib_load: the engine is a member of a loopback group");
+    if (int irc = calib_load_refuses(e, "csf_calib_load")) return irc;
     if (e->world > 1 || e->nccl) return fail(e, CSF_E_STATE, "csf_calib_load: a sharded engine replays nothing");
     if (!e->h_road.empty()) return fail(e, CSF_E_STATE, "csf_calib_load: the engine has a road (a replay takes its forces from the data set)");
     if (e->d.hist != nullptr) return fail(e, CSF_E_STATE, "csf_calib_load: the engine records (csf_record / csf_enable_history); a replay writes its own samples");
@@ -57,50 +79,34 @@ int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *
     cs->n_seq = n_seq, cs->n_feat = n_feat, cs->max_sets = max_sets, cs->n_ticks = n_ticks;
     for (int32_t k = 0; k < n_feat; k++) cs->feat[k] = feat[k];
     const size_t cap = (size_t)e->cap, tn = (size_t)n_ticks * (size_t)n_seq;
-    hipError_t r = cs->Fx.alloc(tn);
-    if (r == hipSuccess) r = cs->Fy.alloc(tn);
-    if (r == hipSuccess) r = cs->obj.alloc(tn * (size_t)n_feat);
+    std::vector<int32_t> ls((size_t)n_seq), la(cap, 0);
+    std::vector<uint8_t> cl(cap, 0);
+    for (int32_t i = 0; i < n_seq; i++) ls[(size_t)i] = lengths ? lengths[i] : (int32_t)n_ticks;
+    for (int64_t a = 0; a < n; a++) la[(size_t)a] = ls[(size_t)(a % n_seq)], cl[(size_t)a] = (uint8_t)(a / n_seq);
+    hipError_t r = cs->Fx.upload(Fx, tn);
+    if (r == hipSuccess) r = cs->Fy.upload(Fy, tn);
+    if (r == hipSuccess) r = cs->obj.upload(objective, tn * (size_t)n_feat);
     if (r == hipSuccess) r = cs->img_s.alloc(STATE_ROWS * cap);
     if (r == hipSuccess) r = cs->img_lti.alloc(5 * cap);
     if (r == hipSuccess) r = cs->img_ppsi.alloc(cap);
     if (r == hipSuccess) r = cs->img_ti.alloc(cap);
     if (r == hipSuccess) r = cs->img_status.alloc(cap);
-    if (r == hipSuccess) r = cs->len_seq.alloc((size_t)n_seq);
-    if (r == hipSuccess) r = cs->len_slot.alloc(cap);
-    if (r == hipSuccess) r = cs->cls.alloc(cap);
+    if (r == hipSuccess) r = cs->len_seq.upload(ls);
+    if (r == hipSuccess) r = cs->len_slot.upload(la);
+    if (r == hipSuccess) r = cs->cls.upload(cl);
     if (r == hipSuccess) r = cs->tab.alloc(cs->tab_bytes());
     if (r == hipSuccess) r = cs->tab_pin.alloc(cs->tab_bytes());
     if (r == hipSuccess) r = cs->sums.alloc((size_t)n);
     if (r != hipSuccess) return fail(e, CSF_E_DEVICE, "csf_calib_load: no memory for the data set: %s", hipGetErrorString(r));
     std::memset(cs->tab_pin.p, 0, cs->tab_bytes());
-    {
-        std::vector<int32_t> ls((size_t)n_seq), la(cap, 0);
-        std::vector<uint8_t> cl(cap, 0);
-        for (int32_t i = 0; i < n_seq; i++) ls[(size_t)i] = lengths ? lengths[i] : (int32_t)n_ticks;
-        for (int64_t a = 0; a < n; a++) la[(size_t)a] = ls[(size_t)(a % n_seq)], cl[(size_t)a] = (uint8_t)(a / n_seq);
-        HIPCHK(e, hipMemcpy(cs->Fx.p, Fx, tn * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(cs->Fy.p, Fy, tn * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(cs->obj.p, objective, tn * (size_t)n_feat * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(cs->len_seq.p, ls.data(), ls.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(cs->len_slot.p, la.data(), la.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(e, hipMemcpy(cs->cls.p, cl.data(), cl.size(), hipMemcpyHostToDevice));
-    }
     // the max_sets x n_seq vehicles: every set starts every sequence from the sequence's first state (calibration.py:443-448)
     const int ns = e->d.ns;
     std::vector<double> s_all((size_t)n * (size_t)ns), vd((size_t)n, 0.0);
     for (int64_t a = 0; a < n; a++) std::memcpy(&s_all[(size_t)a * ns], s0 + (a % n_seq) * ns, (size_t)ns * sizeof(double));
     int rc = add_agents_impl(e, n, s_all.data(), vd.data(), nullptr, nullptr);
-    auto undo = [&](int code) {       // (the engine was empty: what has been added goes again)
-        std::vector<int32_t> all((size_t)e->order.size());
-        for (size_t i = 0; i < all.size(); i++) all[i] = (int32_t)i;
-        const std::string msg = e->err;
-        if (!all.empty()) (void)csf_remove_agents(e, (int64_t)all.size(), all.data());
-        e->err = msg;
-        return code;
-    };
     if (rc) return rc;
-    if ((rc = upload_all(e))) return undo(rc);
-    if ((rc = ensure_compact(e))) return undo(rc);             // slot == place in the population order: slot a is (a / n_seq, a % n_seq)
+    if ((rc = upload_all(e))) return calib_undo_load(e, rc);
+    if ((rc = ensure_compact(e))) return calib_undo_load(e, rc);             // slot == place in the population order: slot a is (a / n_seq, a % n_seq)
     // the image: what csf_add_agents made of the start states (the stream is idle: upload_all has waited)
     hipError_t c = hipStreamSynchronize(e->main);
     if (c == hipSuccess) c = hipMemcpy(cs->img_s.p, e->s.p, STATE_ROWS * cap * sizeof(double), hipMemcpyDeviceToDevice);
@@ -109,7 +115,7 @@ int csf_calib_load(csf_engine *e, int32_t n_seq, int64_t n_ticks, const double *
     if (c == hipSuccess) c = hipMemcpy(cs->img_ti.p, e->ti.p, cap * sizeof(int32_t), hipMemcpyDeviceToDevice);
     if (c == hipSuccess) c = hipMemcpy(cs->img_status.p, e->status.p, cap * sizeof(uint32_t), hipMemcpyDeviceToDevice);
     if (c == hipSuccess) c = hipDeviceSynchronize();
-    if (c != hipSuccess) return undo(fail(e, CSF_E_DEVICE, "csf_calib_load: the reset image: %s", hipGetErrorString(c)));
+    if (c != hipSuccess) return calib_undo_load(e, fail(e, CSF_E_DEVICE, "csf_calib_load: the reset image: %s", hipGetErrorString(c)));
     e->calib = std::move(cs);
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
@@ -206,7 +212,5 @@ int csf_calib_clear(csf_engine *e) try {
     HIPCHK(e, hipStreamSynchronize(e->main));
     std::shared_ptr<CalibState> cs = std::move(e->calib);      // (the population calls take the engine again; the buffers go with cs)
     e->calib.reset();
-    std::vector<int32_t> all(e->order.size());
-    for (size_t i = 0; i < all.size(); i++) all[i] = (int32_t)i;
-    return all.empty() ? CSF_OK : csf_remove_agents(e, (int64_t)all.size(), all.data());
+    return remove_everybody(e);
 } catch (...) { return csf_caught(e); }

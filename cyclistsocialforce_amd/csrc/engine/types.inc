@@ -109,6 +109,19 @@ struct DevBuf {
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         return e;
     }
+    // alloc(count) and the host's `count` elements copied in: one result for the chain of a call that stages several buffers
+    hipError_t upload(const T *src, size_t count) {
+        hipError_t e = alloc(count);
+        if (e == hipSuccess && count > 0) e = hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &src) { return upload(src.data(), src.size()); }
+    // device to device, into this buffer as it is allocated: `rows` rows of `count` elements from `src`, whose rows are `pitch` apart
+    hipError_t copy_rows(const DevBuf &src, size_t count, size_t pitch, size_t rows = 1) const {
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; e == hipSuccess && k < rows; k++) e = hipMemcpy(p + k * count, src.p + k * pitch, count * sizeof(T), hipMemcpyDeviceToDevice);
+        return e;
+    }
     // CSF_DEBUG_POISON: elements [from, n) become 0xFF bytes
     hipError_t poison_from(size_t from) {
         if (!g_poison || !p || from >= n) return hipSuccess;

@@ -330,24 +330,45 @@ class Engine:
         self._scene_load_lanes(self._lib.csf_scene_calib_load_wide, (int(wide_from),), n_riders, n_lanes, lane, enter, exit, s0, v_desired,
                                dest_offsets, dest_xyz_stop, objective, feat, lengths, max_sets)
 
+    def _scene_held(self, name, first="scene_calib_load"):
+        """(R, T) of the loaded closed-loop data set; without one, `name` is the call that is refused"""
+        if getattr(self, "_scene_calib", None) is None:
+            raise EngineError(f"{name}: no closed-loop data set ({first} first)")
+        return self._scene_calib
+
+    @staticmethod
+    def _scene_group8(group, R):
+        """the group of every rider, checked: uint8 [R]"""
+        g = np.asarray(group)
+        if g.shape != (R,) or g.dtype.kind not in "iub":
+            raise ValueError("group must have one integer entry per rider of the data set")
+        if g.size and (g.min() < 0 or g.max() > 255):
+            raise ValueError("group: entries are 0 .. n_groups - 1")
+        return np.ascontiguousarray(g, dtype=np.uint8)
+
+    @staticmethod
+    def _scene_road_sets(n_sets, road_F0, road_sigma):
+        """road_F0 and road_sigma per candidate set, [n_sets] each (None stays None)"""
+        return tuple(None if a is None else _f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (n_sets,))) for a in (road_F0, road_sigma))
+
+    def _scene_outputs(self, n_sets, R, T, states, stride):
+        """what an evaluation writes: sums [n_sets, R, 2] and, with states, the samples [T // stride, n_sets * R, n_states]"""
+        return np.zeros((n_sets, R, 2)), np.zeros((T // stride if stride >= 1 else 0, n_sets * R, self.ns)) if states else None
+
     def scene_calib_eval(self, pods, states=False, stride=1, road_F0=None, road_sigma=None):
         """Evaluate the parameter sets `pods` (a sequence of csf_params) on the loaded scenes in one launch: sums [n_sets, R, 2] =
         (sum d^2, sum |d|) per set and RIDER (the riders of a scene are added by the caller, in rider order), and with states=True
         the trajectories [T // stride, n_sets * R, n_states] as well (slot = set * R + rider).  road_F0 / road_sigma [n_sets] (or
         scalars; both or neither): F_0 and sigma of every road vertex of the scenes' roads (scene_calib_road) for that set."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_eval: no closed-loop data set (scene_calib_load first)")
-        R, T = self._scene_calib
+        R, T = self._scene_held("scene_calib_eval")
         pods = list(pods)
         tab = (Params * len(pods))(*pods)
-        sums = np.zeros((len(pods), R, 2))
-        out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * R, self.ns)) if states else None
+        sums, out = self._scene_outputs(len(pods), R, T, states, stride)
         if road_F0 is None and road_sigma is None:
             self._ck(self._lib.csf_scene_calib_eval(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION, _ptr(sums), int(stride),
                                                     None if out is None else _ptr(out)))
         else:
-            f0 = None if road_F0 is None else _f64(np.broadcast_to(np.asarray(road_F0, dtype=np.float64), (len(pods),)))
-            sg = None if road_sigma is None else _f64(np.broadcast_to(np.asarray(road_sigma, dtype=np.float64), (len(pods),)))
+            f0, sg = self._scene_road_sets(len(pods), road_F0, road_sigma)
             self._ck(self._lib.csf_scene_calib_eval_road(self._h, len(pods), tab, C.sizeof(Params), _ffi.ABI_VERSION,
                                                          None if f0 is None else _ptr(f0), None if sg is None else _ptr(sg), _ptr(sums),
                                                          int(stride), None if out is None else _ptr(out)))
@@ -356,8 +377,7 @@ class Engine:
     def scene_calib_road(self, edge_scene, offsets, verts, F0, sigma):
         """Road edges for scenes of the loaded data set, shared by all candidate sets: edge_scene [n_edges] the scene of every edge
         (non-decreasing), the rest as set_road takes it.  No edge (edge_scene empty or None) drops every road."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_road: no closed-loop data set (scene_calib_load first)")
+        self._scene_held("scene_calib_road")
         es = np.ascontiguousarray([] if edge_scene is None else edge_scene, dtype=np.int32).reshape(-1)
         if es.size == 0:
             self._ck(self._lib.csf_scene_calib_road(self._h, 0, None, None, None, None, None))
@@ -374,9 +394,7 @@ class Engine:
         """Riders of the loaded scenes that follow their recording: replayed [R] (bool), rows [T, n_rep, 4] = (x, y, psi, v) of the
         replayed riders, in rider order, after every tick.  They are sources of the field only; their sums are (0, 0).  None (or
         no rider marked) drops the replay."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_replay: no closed-loop data set (scene_calib_load first)")
-        R, T = self._scene_calib
+        R, T = self._scene_held("scene_calib_replay")
         if replayed is None:
             self._ck(self._lib.csf_scene_calib_replay(self._h, None, None))
             return
@@ -394,9 +412,7 @@ class Engine:
         """Presence windows of the riders of the loaded scenes: enter, exit [R] (int32), rider r is in its scene at the ticks
         enter[r] <= t < exit[r] (0 <= enter <= exit <= the length of its scene) and at every other tick neither a source nor a
         receiver of the field, not ticked, not put on its recording and not part of its sums.  None, None drops the windows."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_windows: no closed-loop data set (scene_calib_load first)")
-        R, _ = self._scene_calib
+        R, _ = self._scene_held("scene_calib_windows")
         if enter is None and exit is None:
             self._ck(self._lib.csf_scene_calib_windows(self._h, None, None))
             return
@@ -412,20 +428,12 @@ class Engine:
         """Rider GROUPS of the loaded scenes (scene_calib_load only), each with parameter sets of its own: group [R] (integers
         0 .. n_groups - 1), n_groups <= 4 (default: the largest entry + 1).  None, or n_groups <= 1, drops the groups.  With groups
         loaded an evaluation is scene_calib_eval_groups; scene_calib_eval is refused."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_groups: no closed-loop data set (scene_calib_load first)")
-        R, _ = self._scene_calib
+        R, _ = self._scene_held("scene_calib_groups")
         if group is None:
             self._ck(self._lib.csf_scene_calib_groups(self._h, None, 0))
-            self.ns = int(self._lib.csf_num_states(self._h))
-            return
-        g = np.asarray(group)
-        if g.shape != (R,) or g.dtype.kind not in "iub":
-            raise ValueError("group must have one integer entry per rider of the data set")
-        if g.size and (g.min() < 0 or g.max() > 255):
-            raise ValueError("group: entries are 0 .. n_groups - 1")
-        g8 = np.ascontiguousarray(g, dtype=np.uint8)
-        self._ck(self._lib.csf_scene_calib_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+        else:
+            g8 = self._scene_group8(group, R)
+            self._ck(self._lib.csf_scene_calib_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
         self.ns = int(self._lib.csf_num_states(self._h))         # (the call replaces the classes of scene_calib_classes)
 
     def scene_calib_lane_groups(self, group, n_groups=None):
@@ -433,18 +441,11 @@ class Engine:
         0 .. n_groups - 1), n_groups <= 4 (default: the largest entry + 1); a lane's parameters are those of the rider it carries and
         change at a takeover.  None, or n_groups <= 1, drops the groups.  With groups loaded an evaluation is scene_calib_eval_groups;
         scene_calib_eval is refused.  A scene_calib_load data set takes scene_calib_groups and refuses this call."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_lane_groups: no closed-loop data set (scene_calib_load_shared / scene_calib_load_wide first)")
-        R, _ = self._scene_calib
+        R, _ = self._scene_held("scene_calib_lane_groups", "scene_calib_load_shared / scene_calib_load_wide")
         if group is None:
             self._ck(self._lib.csf_scene_calib_lane_groups(self._h, None, 0))
             return
-        g = np.asarray(group)
-        if g.shape != (R,) or g.dtype.kind not in "iub":
-            raise ValueError("group must have one integer entry per rider of the data set")
-        if g.size and (g.min() < 0 or g.max() > 255):
-            raise ValueError("group: entries are 0 .. n_groups - 1")
-        g8 = np.ascontiguousarray(g, dtype=np.uint8)
+        g8 = self._scene_group8(group, R)
         self._ck(self._lib.csf_scene_calib_lane_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
 
     def scene_calib_classes(self, group, models=None, s0=None):
@@ -453,21 +454,14 @@ class Engine:
         2 <= G <= 12) and s0 [R, <= 8] the start states in the widest layout (missing columns: 0).  `ns` becomes the widest state of the
         loaded classes; rows a class lacks stay 0.  An evaluation is scene_calib_eval_groups with tuple entry g of class models[g].  The
         call replaces the groups of scene_calib_groups and that call replaces these; None drops the classes."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_classes: no closed-loop data set (scene_calib_load first)")
-        R, _ = self._scene_calib
+        R, _ = self._scene_held("scene_calib_classes")
         if group is None:
             self._ck(self._lib.csf_scene_calib_classes(self._h, None, 0, None, None))
             self.ns = int(self._lib.csf_num_states(self._h))
             return
-        g = np.asarray(group)
-        if g.shape != (R,) or g.dtype.kind not in "iub":
-            raise ValueError("group must have one integer entry per rider of the data set")
-        if g.size and (g.min() < 0 or g.max() > 255):
-            raise ValueError("group: entries are 0 .. n_groups - 1")
+        g8 = self._scene_group8(group, R)
         if models is None or s0 is None:
             raise ValueError("models [n_groups] and s0 [R, <= 8] are needed with group")
-        g8 = np.ascontiguousarray(g, dtype=np.uint8)
         m = np.ascontiguousarray(models, dtype=np.int32).reshape(-1)
         s = np.asarray(s0, dtype=np.float64)
         if s.ndim != 2 or s.shape[0] != R or not 4 <= s.shape[1] <= 8:
@@ -481,18 +475,14 @@ class Engine:
         """scene_calib_eval for riders in groups: `pods` is a sequence of n_groups-tuples of csf_params, tuple k the candidate k and
         its entry g what the riders of group g carry.  A rider is simulated with its own set and acts on the others with its own
         set's field and field of view; the priority rule of a candidate is its first entry's.  Returns what scene_calib_eval returns."""
-        if getattr(self, "_scene_calib", None) is None:
-            raise EngineError("scene_calib_eval_groups: no closed-loop data set (scene_calib_load first)")
-        R, T = self._scene_calib
+        R, T = self._scene_held("scene_calib_eval_groups")
         pods = [tuple(p) if isinstance(p, (tuple, list)) else (p,) for p in pods]
         if not pods or any(len(p) != len(pods[0]) or not p for p in pods):
             raise ValueError("pods: a non-empty sequence of tuples of one length, one csf_params per group")
         G = len(pods[0])
         tab = (Params * (len(pods) * G))(*[p for t in pods for p in t])
-        sums = np.zeros((len(pods), R, 2))
-        out = np.zeros((T // stride if stride >= 1 else 0, len(pods) * R, self.ns)) if states else None
-        f0 = None if road_F0 is None else _f64(np.broadcast_to(np.asarray(road_F0, dtype=np.float64), (len(pods),)))
-        sg = None if road_sigma is None else _f64(np.broadcast_to(np.asarray(road_sigma, dtype=np.float64), (len(pods),)))
+        sums, out = self._scene_outputs(len(pods), R, T, states, stride)
+        f0, sg = self._scene_road_sets(len(pods), road_F0, road_sigma)
         self._ck(self._lib.csf_scene_calib_eval_groups(self._h, len(pods), G, tab, C.sizeof(Params), _ffi.ABI_VERSION,
                                                        None if f0 is None else _ptr(f0), None if sg is None else _ptr(sg), _ptr(sums),
                                                        int(stride), None if out is None else _ptr(out)))

@@ -2,7 +2,7 @@
 """Sums and sampled states of a fixed set of tiny closed-loop calibration data sets (GPU box), for comparing two builds of the library
 BIT FOR BIT: the GPU tests hold the scene kernels to their twins at 2e-7, which does not see a changed rounding.  Everything goes
 through the Python Engine API, so the tool runs unchanged from the tools/ folder of any checkout that has the scene calibration of
-DESIGN.md 4.10 - 4.10h; run it in both, then compare:
+DESIGN.md 4.10 - 4.10i; run it in both, then compare:
 
     python tools/scene_eval_dump.py --out a.npz                    (in the one checkout)
     python tools/scene_eval_dump.py --out b.npz --compare a.npz    (in the other: evaluates, writes, compares; exit status 1 on a difference)
@@ -21,6 +21,12 @@ The data sets are the smallest that reach every piece the kernels of csf_scene.h
          per-set parameters: two launches                                          scene_wide_kernel + scene_lanes_kernel
     fg, gg   fr and g with the riders in two groups (csf_scene_calib_lane_groups; left out where the library lacks the call)
                                                                                    scene_lanes_groups_kernel, scene_wide_groups_kernel
+    m    a with the riders alternating between two groups of two vehicle classes - the model's and the next one's
+         (csf_scene_calib_classes; left out where the library lacks the call)      scene_mixed_kernel
+    mc, md   m with the windows of c and rider 4 replayed; m with the roads and the per-set road parameters of d.  (One engine, in the
+         order md, m, mc: md runs with the road of d still held, mc adds to m.  Reordering the cases changes what is dumped.)
+    k    csf_calib_load / csf_calib_eval of 3 sequences (the second 45 ticks long), with and without fix_speed: k1, k0
+                                                                                   replay_eval_kernel
 """
 import argparse
 import os
@@ -33,9 +39,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 os.environ.pop("CSF_PAIR_VARIANT", None)
 from cyclistsocialforce_amd.engine import Engine  # noqa: E402
+from cyclistsocialforce_amd.engine import MODEL_IDS  # noqa: E402
+from calib_common import data_set, pod_sets  # noqa: E402
 from scene_calib_common import MODELS, VDES, scenes  # noqa: E402
 from scene_groups_common import group_sets  # noqa: E402
 from scene_lanes_common import greedy_lanes, loaded_shared, roster  # noqa: E402
+from scene_mixed_common import mixed_sets  # noqa: E402
 from scene_wide_common import edge_below, loaded_wide, wide_crowd  # noqa: E402
 from scene_windows_common import FEAT, one_scene, sets3  # noqa: E402
 
@@ -88,6 +97,27 @@ def small_cases(model, out):
     out["ed"] = e.scene_calib_eval_groups(gsets, states=True, stride=STRIDE, **over)
     e.scene_calib_groups(None)
     out["d"] = e.scene_calib_eval(sets, states=True, stride=STRIDE, **over)
+    if hasattr(e._lib, "csf_scene_calib_classes"):               # (the road of d stays for md, then goes)
+        classes = (model, MODELS[(MODELS.index(model) + 1) % len(MODELS)])
+        msets = mixed_sets(3, classes)
+        e.scene_calib_classes(group, [MODEL_IDS[c] for c in classes], s0)
+        out["md"] = e.scene_calib_eval_groups(msets, states=True, stride=STRIDE, **over)
+        e.scene_calib_road(None, None, None, None, None)
+        out["m"] = e.scene_calib_eval_groups(msets, states=True, stride=STRIDE)
+        e.scene_calib_windows(ENTER, EXIT)
+        e.scene_calib_replay(mask, rec)
+        out["mc"] = e.scene_calib_eval_groups(msets, states=True, stride=STRIDE)
+    e.close()
+
+
+def replay_cases(model, out):
+    sets = pod_sets(model, 3)
+    s0, Fx, Fy = data_set(model, seed=7, n_seq=3, ticks=T)
+    obj = np.random.default_rng(14).normal(size=(T, 3, len(FEAT)))
+    e = Engine(sets[0], 3 * 3)
+    e.calib_load(s0, Fx, Fy, obj, FEAT, lengths=np.array([T, 45, T], dtype=np.int32), max_sets=3)
+    out["k1"] = e.calib_eval(sets, fix_speed=True, states=True, stride=STRIDE)
+    out["k0"] = e.calib_eval(sets, fix_speed=False, states=True, stride=STRIDE)
     e.close()
 
 
@@ -144,6 +174,7 @@ def main():
         small_cases(model, out)
         shared_cases(model, out)
         wide_cases(model, out)
+        replay_cases(model, out)
         for case, (sums, states) in out.items():
             assert np.isfinite(sums).all() and np.any(sums != 0.0) and np.isfinite(states).any(), (model, case)
             arrays[f"{model}.{case}.sums"], arrays[f"{model}.{case}.states"] = sums, states
