@@ -13,6 +13,8 @@ Two things are not the reference's:
     extracts: traj[:, 1 : i + 1]); the reference's `simulate_single` returns traj[:, :n], which leads with the start state;
   * `CalibrationData` is built from plain arrays (the reference's builds on the `trajdatamanager` package).
 """
+from types import SimpleNamespace as _Namespace
+
 import numpy as np
 
 from . import _ffi
@@ -252,7 +254,54 @@ class ReplayedVehicle:
         self.id = vid
 
 
-class DownhillSimplexCalibration:
+class _Calibration:
+    """What DownhillSimplexCalibration and InteractionCalibration share: the data sets loaded on first use and closed together, the
+    chunk loop of `evaluate`, and `run_many`.  A class says how a data set is loaded (`_load` -> a mapping with "engine", "sets" and
+    "objectives"), what a parameter vector becomes (`_candidates`), how a chunk of candidates is launched (`_launch`), how the
+    device's sums become errors (`_errors`) and its states trajectories (`_trajs`)."""
+
+    xtol = ftol = 1e-4                                            # (minimize_many's own defaults)
+
+    def close(self):
+        for ds in self._sets.values():
+            ds["engine"].close()
+        self._sets = {}
+
+    def _dataset(self, test=False):
+        """the engine that holds the training (test) data, loaded on first use"""
+        ds = self._sets.get(bool(test))
+        if ds is None:
+            ds = self._sets[bool(test)] = self._load(self.test_data if test else self.train_data)
+        return ds
+
+    def evaluate(self, params_vals, test=False):
+        """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them.  With calc_sse_timesteps or
+        calc_maesse_samples the error is formed from the sums the device returns; another error_func gets the trajectories."""
+        vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
+        ds = self._dataset(test)
+        cands = self._candidates(vals)
+        err = np.zeros(len(cands))
+        for at in range(0, len(cands), ds["sets"]):
+            chunk = cands[at:at + ds["sets"]]
+            if self.error_func is calc_sse_timesteps or self.error_func is calc_maesse_samples:
+                err[at:at + len(chunk)] = self._errors(ds, self._launch(ds, chunk))
+            else:
+                _, states = self._launch(ds, chunk, states=True)
+                for k in range(len(chunk)):
+                    err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
+        return err
+
+    def run_many(self, guesses):
+        """Independent calibrations from several guesses, in lockstep (minimize_many): every iteration of all live runs is one launch
+        (a shrink one more).  Returns a list of (xopt, fopt, iterations) - per guess what `run` finds from it - and keeps the best in
+        param_args_opt."""
+        res = minimize_many(self.evaluate, [np.asarray(g, dtype=float) for g in guesses], xtol=self.xtol, ftol=self.ftol, maxiter=self.maxiter)
+        best = min(res, key=lambda r: r[1])
+        self.param_args_opt = self._update_params_args_dict(best[0])
+        return res
+
+
+class DownhillSimplexCalibration(_Calibration):
     """Fit parameters of a vehicle class to recorded trajectories by downhill simplex (calibration.py:243-526).  Arguments as the
     reference's; `device` and `max_sets` (parameter sets per launch, at most 256) are this package's."""
 
@@ -277,11 +326,6 @@ class DownhillSimplexCalibration:
         self.device, self.max_sets = device, int(max_sets)
         self._sets = {}
 
-    def close(self):
-        for ds in self._sets.values():
-            ds["engine"].close()
-        self._sets = {}
-
     def _update_params_args_dict(self, params_vals):
         """the optimiser's vector -> keyword arguments of the vehicle class's parameter object: value k belongs to params_keys[k],
         or, with auxiliary functions, key k gets params_auxfuncs[k](params_vals, **params_auxfuncsargs[k])"""
@@ -292,12 +336,7 @@ class DownhillSimplexCalibration:
     def _pod(self, params_args):
         return self.vehicle_type.PARAMS_TYPE(**params_args).to_pod(self.vehicle_type.MODEL)
 
-    def _dataset(self, test=False):
-        """the engine that holds the training (test) data, loaded on first use"""
-        ds = self._sets.get(bool(test))
-        if ds is not None:
-            return ds
-        data = self.test_data if test else self.train_data
+    def _load(self, data):
         samples = [(s0, np.asarray(i, dtype=float), np.asarray(o, dtype=float)) for s0, i, o in data]
         feat = np.flatnonzero(self.objective_features_traj).astype(np.int32)
         n_seq = len(samples)
@@ -313,9 +352,19 @@ class DownhillSimplexCalibration:
         sets = max(1, min(self.max_sets, 256))
         engine = Engine(self._pod({}), sets * n_seq, device=self.device)
         engine.calib_load(s0s, Fx, Fy, obj, feat, lengths=lens, max_sets=sets)
-        ds = dict(engine=engine, lens=lens, feat=feat, n_seq=n_seq, sets=sets, s0=s0s, objectives=[o for _, _, o in samples])
-        self._sets[bool(test)] = ds
-        return ds
+        return dict(engine=engine, lens=lens, feat=feat, n_seq=n_seq, sets=sets, s0=s0s, objectives=[o for _, _, o in samples])
+
+    def _candidates(self, vals):
+        return [self._pod(self._update_params_args_dict(v)) for v in vals]
+
+    def _launch(self, ds, pods, **kw):
+        return ds["engine"].calib_eval(pods, fix_speed=self.fix_speed, **kw)
+
+    def _errors(self, ds, sums):
+        if self.error_func is calc_sse_timesteps:
+            return sums[:, :, 0].sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):       # (an empty sample: nan, as np.mean gives)
+            return ((sums[:, :, 1] / (ds["lens"] * float(ds["feat"].size))[None, :]) ** 2).sum(axis=1)
 
     def _trajs(self, ds, states, k):
         """the samples of parameter set k from the states of one evaluation: [len, n_feat] each (rows the class lacks: 0)"""
@@ -328,27 +377,6 @@ class DownhillSimplexCalibration:
                     tr[:, c] = states[: ds["lens"][q], k * ds["n_seq"] + q, f]
             out.append(tr)
         return out
-
-    def evaluate(self, params_vals, test=False):
-        """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them.  With calc_sse_timesteps or
-        calc_maesse_samples the error is formed from the sums the device returns; another error_func gets the trajectories."""
-        vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
-        ds = self._dataset(test)
-        pods = [self._pod(self._update_params_args_dict(v)) for v in vals]
-        err = np.zeros(len(pods))
-        for at in range(0, len(pods), ds["sets"]):
-            chunk = pods[at:at + ds["sets"]]
-            if self.error_func is calc_sse_timesteps:
-                err[at:at + len(chunk)] = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed)[:, :, 0].sum(axis=1)
-            elif self.error_func is calc_maesse_samples:
-                sums = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed)
-                with np.errstate(invalid="ignore", divide="ignore"):   # (an empty sample: nan, as np.mean gives)
-                    err[at:at + len(chunk)] = ((sums[:, :, 1] / (ds["lens"] * float(ds["feat"].size))[None, :]) ** 2).sum(axis=1)
-            else:
-                _, states = ds["engine"].calib_eval(chunk, fix_speed=self.fix_speed, states=True)
-                for k in range(len(chunk)):
-                    err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
-        return err
 
     def simulate_single(self, params_args, return_vehicles=False, test=False):
         """One parameter set on every sample of the training (test) data (calibration.py:397-470): the samples' trajectories
@@ -383,15 +411,6 @@ class DownhillSimplexCalibration:
         results.append(self.simulate_single(param_args, return_vehicles=True))
         self.param_args_opt = param_args
         return results
-
-    def run_many(self, guesses):
-        """Independent calibrations from several guesses, in lockstep: every iteration of all live runs is one launch (a shrink one
-        more).  Returns a list of (xopt, fopt, iterations) - per guess what `run` finds from it - and keeps the best in
-        param_args_opt."""
-        res = minimize_many(self.evaluate, [np.asarray(g, dtype=float) for g in guesses], maxiter=self.maxiter)
-        best = min(res, key=lambda r: r[1])
-        self.param_args_opt = self._update_params_args_dict(best[0])
-        return res
 
     def test(self, param_args_opt=None, plot_results=False, color="blue", axes=None, name=None, plot_inref=True):
         """Error of a parameter set - by default the one `run` / `run_many` found - on the TEST data; returns (error, vehicles).
@@ -455,35 +474,49 @@ class SceneData:
 
     def __init__(self, s0, v_desired, dest_offsets, dest_xyz_stop, traj, length=None, replayed=None, road=None, present=None, wide=False,
                  group=None):
-        self.s0 = np.asarray(s0, dtype=float)
+        # one step per layer, in the order that decides which message an input with two faults gets
         self.wide = bool(wide)
-        if self.wide:
-            if self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > self.WIDE_MAX and present is None):
-                raise ValueError(f"a wide scene has 1 .. {self.WIDE_MAX} road users, or more with presence windows that keep at most "
-                                 f"{self.WIDE_MAX} at once: s0 is [n, >= 4]")
-        elif self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > 32 and present is None):
-            raise ValueError("a scene has 1 .. 32 road users, or more with presence windows that keep at most 32 at once: s0 is [n, >= 4]")
-        n = self.s0.shape[0]
+        self._take_roster(s0, present is not None)
+        self._take_v_desired(v_desired)
+        self._take_group(group)
+        self._take_replayed(replayed)
+        self._take_queues(dest_offsets, dest_xyz_stop)
+        self._take_traj(traj, length)
+        self._take_windows(present)
+        self._check_peak()
+        self._check_replay()
+        self.road = None if road is None else self._checked_road(road, self.n if self.n <= 32 else self.lanes()[1],
+                                                                 p_min=64 if self.wide else 1)   # (a workgroup's P: never below a wave)
+
+    def _take_roster(self, s0, windows):
+        self.s0 = np.asarray(s0, dtype=float)
+        self._most = most = self.WIDE_MAX if self.wide else 32    # road users in the scene at once
+        if self.s0.ndim != 2 or self.s0.shape[1] < 4 or self.s0.shape[0] < 1 or (self.s0.shape[0] > most and not windows):
+            raise ValueError(f"a {'wide ' if self.wide else ''}scene has 1 .. {most} road users, or more with presence windows that keep at most "
+                             f"{most} at once: s0 is [n, >= 4]")
+
+    def _take_v_desired(self, v_desired):
         try:
-            self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (n,)))
+            self.v_desired = np.array(np.broadcast_to(np.asarray(v_desired, dtype=float), (self.n,)))
         except ValueError:
             raise ValueError("v_desired: one desired speed per road user, or a scalar") from None
+
+    def _take_group(self, group):
         self.grouped = group is not None
-        if group is None:
-            self.group = np.zeros(n, dtype=np.int32)
-        else:
-            g = np.asarray(group)
-            if g.shape != (n,) or g.dtype.kind not in "iu":
-                raise ValueError("group: one integer per road user")
-            if np.any(g < 0):
-                raise ValueError("group: entries are >= 0")
-            self.group = g.astype(np.int32)
-        if replayed is None:
-            self.replayed = np.zeros(n, dtype=bool)
-        else:
-            self.replayed = np.array(replayed, dtype=bool)
-            if self.replayed.shape != (n,):
-                raise ValueError("replayed: one flag per road user")
+        g = np.zeros(self.n, dtype=np.int32) if group is None else np.asarray(group)
+        if g.shape != (self.n,) or g.dtype.kind not in "iu":
+            raise ValueError("group: one integer per road user")
+        if np.any(g < 0):
+            raise ValueError("group: entries are >= 0")
+        self.group = g.astype(np.int32)
+
+    def _take_replayed(self, replayed):
+        self.replayed = np.zeros(self.n, dtype=bool) if replayed is None else np.array(replayed, dtype=bool)
+        if self.replayed.shape != (self.n,):
+            raise ValueError("replayed: one flag per road user")
+
+    def _take_queues(self, dest_offsets, dest_xyz_stop):
+        n = self.n
         self.dest_offsets = np.asarray(dest_offsets, dtype=np.int64)
         self.dest_xyz_stop = np.asarray(dest_xyz_stop, dtype=float).reshape(-1, 3)
         off = self.dest_offsets
@@ -497,47 +530,49 @@ class SceneData:
                 rows.append(own if own.shape[0] else np.array([[self.s0[i, 0], self.s0[i, 1], 0.0]]))
                 new.append(new[-1] + rows[-1].shape[0])
             self.dest_offsets, self.dest_xyz_stop = np.array(new, dtype=np.int64), np.concatenate(rows)
+
+    def _take_traj(self, traj, length):
         self.traj = np.asarray(traj, dtype=float)
-        if self.traj.ndim != 3 or self.traj.shape[1] != n or not 1 <= self.traj.shape[2] <= TRAJ_ROWS:
+        if self.traj.ndim != 3 or self.traj.shape[1] != self.n or not 1 <= self.traj.shape[2] <= TRAJ_ROWS:
             raise ValueError(f"traj is [n_t, n, 1 .. {TRAJ_ROWS}]: the state of every road user after every tick")
         self.length = self.traj.shape[0] if length is None else int(length)
         if not 0 <= self.length <= self.traj.shape[0]:
             raise ValueError("length: 0 .. the rows of traj")
-        if present is None:
-            self.enter, self.exit = np.zeros(n, dtype=np.int32), np.full(n, self.length, dtype=np.int32)
-        else:
-            try:
-                enter, exit_ = present
-                enter, exit_ = np.asarray(enter), np.asarray(exit_)
-            except (TypeError, ValueError):
-                raise ValueError("present is (enter [n], exit [n])") from None
-            if enter.shape != (n,) or exit_.shape != (n,) or enter.dtype.kind not in "iu" or exit_.dtype.kind not in "iu":
-                raise ValueError("present: one integer entry tick and one integer exit tick per road user")
-            if np.any(enter < 0) or np.any(enter > exit_) or np.any(exit_ > self.length):
-                raise ValueError("present: 0 <= enter <= exit <= length for every road user")
-            self.enter, self.exit = enter.astype(np.int32), exit_.astype(np.int32)
+
+    def _take_windows(self, present):
+        n = self.n
+        try:                                                      # (default: everybody over all of [0, length))
+            enter, exit_ = (np.zeros(n, dtype=np.int32), np.full(n, self.length, dtype=np.int32)) if present is None else present
+            enter, exit_ = np.asarray(enter), np.asarray(exit_)
+        except (TypeError, ValueError):
+            raise ValueError("present is (enter [n], exit [n])") from None
+        if enter.shape != (n,) or exit_.shape != (n,) or enter.dtype.kind not in "iu" or exit_.dtype.kind not in "iu":
+            raise ValueError("present: one integer entry tick and one integer exit tick per road user")
+        if np.any(enter < 0) or np.any(enter > exit_) or np.any(exit_ > self.length):
+            raise ValueError("present: 0 <= enter <= exit <= length for every road user")
+        self.enter, self.exit = enter.astype(np.int32), exit_.astype(np.int32)
         self.windowed = bool(np.any(self.enter != 0) or np.any(self.exit != self.length))
-        most = self.WIDE_MAX if self.wide else 32
-        if n > most:
+
+    def _check_peak(self):
+        """a roster above the bound: at no tick more road users in the scene than the bound"""
+        if self.n > self._most:
             count = self.inside.sum(axis=1) if self.length else np.zeros(1, dtype=int)
-            if count.max() > most:
-                raise ValueError(f"present: {int(count.max())} road users are in the scene at tick {int(count.argmax())}; at most {most} at once")
-        if self.replayed.any():
-            if self.traj.shape[2] < 4:
-                raise ValueError("a replayed road user needs (x, y, psi, v): traj has fewer than 4 columns")
-            if not self.windowed:
-                finite = np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()
-            else:
-                finite = all(np.isfinite(self.traj[self.enter[i]: self.exit[i], i, :4]).all() for i in np.flatnonzero(self.replayed))
-            if not finite:
-                raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over the rows of its window "
-                                 "(all `length` rows without one)")
-        if road is None:
-            self.road = None
-        elif self.wide:                                           # (the workgroup's P: never below a wave)
-            self.road = self._checked_road(road, n if n <= 32 else self.lanes()[1], p_min=64)
+            if count.max() > self._most:
+                raise ValueError(f"present: {int(count.max())} road users are in the scene at tick {int(count.argmax())}; at most {self._most} at once")
+
+    def _check_replay(self):
+        """a replayed road user has finite (x, y, psi, v) wherever it is put on its recording"""
+        if not self.replayed.any():
+            return
+        if self.traj.shape[2] < 4:
+            raise ValueError("a replayed road user needs (x, y, psi, v): traj has fewer than 4 columns")
+        if not self.windowed:
+            finite = np.isfinite(self.traj[: self.length][:, self.replayed, :4]).all()
         else:
-            self.road = self._checked_road(road, n if n <= 32 else self.lanes()[1])
+            finite = all(np.isfinite(self.traj[self.enter[i]: self.exit[i], i, :4]).all() for i in np.flatnonzero(self.replayed))
+        if not finite:
+            raise ValueError("a replayed road user needs finite (x, y, psi, v) - columns 0 .. 3 of traj - over the rows of its window "
+                             "(all `length` rows without one)")
 
     @classmethod
     def _checked_road(cls, road, n, p_min=1):
@@ -635,6 +670,11 @@ def _init_names(cls):
     return names
 
 
+def _has_road(data):
+    """a scene of the data set has a road with at least one vertex"""
+    return any(d.road is not None and d.road[0][-1] > 0 for d in data)
+
+
 def _riders_then_scenes(per_rider, roff):
     """[k, R] per-rider figures -> [k, n_scn]: the riders of a scene added in rider order (the order of the sum is fixed)"""
     out = np.zeros((per_rider.shape[0], len(roff) - 1))
@@ -651,7 +691,7 @@ def _scenes_in_order(per_scene):
     return acc
 
 
-class InteractionCalibration:
+class InteractionCalibration(_Calibration):
     """Fit parameters that act BETWEEN road users - the social-force field f_0, sigma_0..3, e_0, e_1, hfov, p_0, p_decay, the priority
     rule - to recorded scenes by downhill simplex.  A replay of recorded forces (DownhillSimplexCalibration) couples no two vehicles;
     here every candidate set simulates every scene with its road users together, on the device: the scenes are loaded once
@@ -711,6 +751,29 @@ class InteractionCalibration:
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
                  wide_from=33, group_params=None, lane_groups=False):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
+        self._take_groups(vehicle_type, group_params)
+        self._check_keys()
+        self.share_lanes, self.lane_groups, self.wide_from = bool(share_lanes), bool(lane_groups), int(wide_from)
+        if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
+            raise ValueError(f"wide_from: 1 .. {SceneData.WIDE_MAX + 1}")
+        self.train_data, self.test_data = list(train_data), list(test_data)
+        self._check_data()
+        self.objective_features_traj = _indicators(objective_features_traj, "objective_features_traj", TRAJ_ROWS)
+        if not self.objective_features_traj.any():
+            raise ValueError("objective_features_traj selects no row of vehicle.traj")
+        self.error_func, self.maxiter, self.xtol, self.ftol, self.verbose = error_func, maxiter, xtol, ftol, verbose
+        self.device, self.max_sets = device, max(1, min(int(max_sets), 256))
+        self.param_args_opt = None
+        self._factory = engine_factory
+        self._sets = {}
+        self._road_keys = [k for k in self.params_keys if k in self.ROAD_KEYS]
+        if self._road_keys:                                       # either road key needs a scene with a road
+            for name, data in (("train_data", self.train_data), ("test_data", self.test_data)):
+                if data and not _has_road(data):
+                    raise ValueError(f"params_keys names {self._road_keys}, and no scene of {name} has a road")
+
+    def _take_groups(self, vehicle_type, group_params):
+        """the vehicle classes (`_types`; None: one class), the groups' fixed arguments and their number `_G`"""
         self._types = list(vehicle_type) if isinstance(vehicle_type, (list, tuple)) else None      # several vehicle classes: one per group
         if self._types is not None:
             if not 2 <= len(self._types) <= 12:
@@ -726,6 +789,11 @@ class InteractionCalibration:
         self._G = 1 if self.group_params is None else len(self.group_params)
         if self._types is None and not 1 <= self._G <= 4:
             raise ValueError("group_params: 1 .. 4 dicts of keyword arguments of PARAMS_TYPE, one per group")
+
+    def _check_keys(self):
+        """the grammar of params_keys - "name" or ("name", group) - and, with several vehicle classes, that a key is a parameter of the
+        PARAMS_TYPE of every group it reaches.  A fault of the grammar in ANY key is named before a key that is no parameter: the
+        parameters are looked up once the grammar has been through."""
         for k in self.params_keys:
             if isinstance(k, str):
                 continue
@@ -738,21 +806,18 @@ class InteractionCalibration:
                 raise ValueError(f"params_keys: {k!r} names a group and there is no group_params")
             if not 0 <= k[1] < self._G:
                 raise ValueError(f"params_keys: {k!r} names group {k[1]}, group_params defines {self._G}")
-        if self._types is not None:                               # a key must be a parameter of the PARAMS_TYPE of every group it reaches
-            for k in self.params_keys:
-                name = k if isinstance(k, str) else k[0]
-                if name in self.ROAD_KEYS:
-                    continue
-                for g in (range(self._G) if isinstance(k, str) else (k[1],)):
-                    if name not in _init_names(self._types[g].PARAMS_TYPE):
-                        raise ValueError(f"params_keys: {k!r}: {name!r} is no parameter of {self._types[g].PARAMS_TYPE.__name__}, "
-                                         f"the PARAMS_TYPE of group {g} ({self._types[g].__name__})")
-        self.share_lanes = bool(share_lanes)
-        self.lane_groups = bool(lane_groups)
-        self.wide_from = int(wide_from)
-        if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
-            raise ValueError(f"wide_from: 1 .. {SceneData.WIDE_MAX + 1}")
-        self.train_data, self.test_data = list(train_data), list(test_data)
+        if self._types is None:
+            return
+        for k in self.params_keys:
+            name = k if isinstance(k, str) else k[0]
+            if name in self.ROAD_KEYS:
+                continue
+            for g in (range(self._G) if isinstance(k, str) else (k[1],)):
+                if name not in _init_names(self._types[g].PARAMS_TYPE):
+                    raise ValueError(f"params_keys: {k!r}: {name!r} is no parameter of {self._types[g].PARAMS_TYPE.__name__}, "
+                                     f"the PARAMS_TYPE of group {g} ({self._types[g].__name__})")
+
+    def _check_data(self):
         for d in self.train_data + self.test_data:
             if not isinstance(d, SceneData):
                 raise TypeError("train_data and test_data are lists of SceneData")
@@ -763,24 +828,6 @@ class InteractionCalibration:
                                      f"group{'s' if self._G > 1 else ''}")
         if not self.train_data:
             raise ValueError("no scenes to train on")
-        self.objective_features_traj = _indicators(objective_features_traj, "objective_features_traj", TRAJ_ROWS)
-        if not self.objective_features_traj.any():
-            raise ValueError("objective_features_traj selects no row of vehicle.traj")
-        self.error_func, self.maxiter, self.xtol, self.ftol, self.verbose = error_func, maxiter, xtol, ftol, verbose
-        self.device, self.max_sets = device, max(1, min(int(max_sets), 256))
-        self.param_args_opt = None
-        self._factory = engine_factory
-        self._sets = {}
-        self._road_keys = [k for k in self.params_keys if k in self.ROAD_KEYS]
-        if self._road_keys:
-            for name, data in (("train_data", self.train_data), ("test_data", self.test_data)):
-                if data and not any(d.road is not None and d.road[0][-1] > 0 for d in data):
-                    raise ValueError(f"params_keys names {self._road_keys}, and no scene of {name} has a road")
-
-    def close(self):
-        for ds in self._sets.values():
-            ds["engine"].close()
-        self._sets = {}
 
     def _update_params_args_dict(self, params_vals):
         return dict(zip(self.params_keys, params_vals))
@@ -820,22 +867,25 @@ class InteractionCalibration:
         rp = [RoadElementParameters(**{self.ROAD_KEYS[k]: float(a[k]) for k in self._road_keys}) for a in args_list]
         return dict(road_F0=np.array([r.F_0 for r in rp], dtype=float), road_sigma=np.array([r.sigma for r in rp], dtype=float))
 
-    def _dataset(self, test=False):
-        """the engine that holds the training (test) scenes, loaded on first use"""
-        ds = self._sets.get(bool(test))
-        if ds is not None:
-            return ds
-        data = self.test_data if test else self.train_data
+    # ---- loading a data set: one step per layer of the host library (SceneImage, SceneLanes, SceneGroups, SceneReplay,
+    # SceneRoad, SceneWindows), in the order the engine is called, and the host's own bookkeeping last
+    def _load(self, data):
         if not data:
             raise ValueError("no test scenes")
-        feat = np.flatnonzero(self.objective_features_traj).astype(np.int32)
+        img = self._image(data, np.flatnonzero(self.objective_features_traj).astype(np.int32))
+        engine, shared = self._load_image(data, img)
+        self._load_replay(engine, data, img)
+        self._load_road(engine, data)
+        inside = self._load_windows(engine, data, img, shared)
+        return self._bookkeeping(engine, data, img, inside)
+
+    def _image(self, data, feat):
+        """IMAGE: the scenes refused one by one, in scene order, and their arrays concatenated in rider order - each once"""
         nr = np.array([d.n for d in data], dtype=np.int32)
         roff = np.r_[0, np.cumsum(nr)].astype(np.int64)
         R, T = int(roff[-1]), max(1, max(d.traj.shape[0] for d in data))
-        lens = np.array([d.length for d in data], dtype=np.int32)
         s0, vd, obj = np.zeros((R, 8)), np.zeros(R), np.zeros((T, R, feat.size))
         off, rows = [0], []
-        rep = np.concatenate([d.replayed for d in data])
         for q, d in enumerate(data):
             if d.replayed.all():
                 raise ValueError(f"scene {q}: every road user is replayed - there is nothing to fit")
@@ -850,70 +900,82 @@ class InteractionCalibration:
             obj[: d.traj.shape[0], sl] = d.traj[:, :, feat]
             off.extend((d.dest_offsets[1:] + len(rows)).tolist())
             rows.extend(d.dest_xyz_stop.tolist())
+        per_rider = {name: np.concatenate([getattr(d, name) for d in data]) for name in ("enter", "exit", "group", "replayed")}
+        return _Namespace(feat=feat, nr=nr, roff=roff, R=R, T=T, lens=np.array([d.length for d in data], dtype=np.int32), s0=s0, vd=vd,
+                          off=np.array(off, dtype=np.int64), rows=np.array(rows, dtype=float).reshape(-1, 3), obj=obj, **per_rider)
+
+    def _load_image(self, data, img):
+        """LOAD: which of the three load calls the data set needs - refused before any engine is made where groups or classes cannot
+        go with it -, the engine, that one load call and at most one call that hands over groups or classes; -> (engine, shared)"""
         wide = any(d.wide for d in data)
         shared = wide or self.share_lanes or any(d.n > 32 for d in data)
+        needs = "this data set needs shared lanes" + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)"
         if self._types is not None and shared:
-            raise ValueError("mixed classes run on Engine.scene_calib_load only, and this data set needs shared lanes"
-                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)")
+            raise ValueError("mixed classes run on Engine.scene_calib_load only, and " + needs)
         if self._G > 1 and shared and not self.lane_groups:
-            raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and this data set needs shared lanes"
-                             + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True); or pass lane_groups=True")
+            raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and " + needs + "; or pass lane_groups=True")
         pod0 = self._pods({})[0] if self._G > 1 else self._pod({})
+        image = (img.s0, img.vd, img.off, img.rows, img.obj, img.feat)
         if shared:                                               # every scene on its lanes; the windows go with the load
             packed = [d.lanes() for d in data]
             nl = np.array([p[1] for p in packed], dtype=np.int32)
-            engine = self._factory(pod0, max(R, self.max_sets * int(nl.sum())), device=self.device)
+            engine = self._factory(pod0, max(img.R, self.max_sets * int(nl.sum())), device=self.device)
             load = engine.scene_calib_load_wide if wide else engine.scene_calib_load_shared
-            load(nr, nl, np.concatenate([p[0] for p in packed]), np.concatenate([d.enter for d in data]),
-                 np.concatenate([d.exit for d in data]), s0, vd, np.array(off, dtype=np.int64),
-                 np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens, max_sets=self.max_sets,
+            load(img.nr, nl, np.concatenate([p[0] for p in packed]), img.enter, img.exit, *image, lengths=img.lens, max_sets=self.max_sets,
                  **(dict(wide_from=self.wide_from) if wide else {}))
             if self._G > 1:                                      # (lane_groups=True: the group goes with the rider a lane carries)
-                engine.scene_calib_lane_groups(np.concatenate([d.group for d in data]), self._G)
+                engine.scene_calib_lane_groups(img.group, self._G)
         else:
-            engine = self._factory(pod0, self.max_sets * R, device=self.device)
-            engine.scene_calib_load(nr, s0, vd, np.array(off, dtype=np.int64), np.array(rows, dtype=float).reshape(-1, 3), obj, feat, lengths=lens,
-                                    max_sets=self.max_sets)
+            engine = self._factory(pod0, self.max_sets * img.R, device=self.device)
+            engine.scene_calib_load(img.nr, *image, lengths=img.lens, max_sets=self.max_sets)
             if self._types is not None:
-                engine.scene_calib_classes(np.concatenate([d.group for d in data]), [t.MODEL for t in self._types], s0)
+                engine.scene_calib_classes(img.group, [t.MODEL for t in self._types], img.s0)
             elif self._G > 1:
-                engine.scene_calib_groups(np.concatenate([d.group for d in data]), self._G)
-        if rep.any():                                            # the recorded (x, y, psi, v) of the replayed riders, in rider order
-            rec = np.zeros((T, int(rep.sum()), 4))
-            at = 0
-            for d in data:
-                k = int(d.replayed.sum())
-                if k:
-                    rec[: d.traj.shape[0], at: at + k] = d.replay_rows()
-                at += k
-            engine.scene_calib_replay(rep, rec)
-        if any(d.road is not None and d.road[0][-1] > 0 for d in data):
-            es, ro, vs, f0, sg = [], [0], [], [], []
-            for q, d in enumerate(data):
-                if d.road is None:
-                    continue
-                eoff, verts, F0, sigma = d.road
-                for k in range(eoff.size - 1):
-                    es.append(q)
-                    vs.append(verts[eoff[k]: eoff[k + 1]])
-                    ro.append(ro[-1] + vs[-1].shape[0])
-                    f0.append(F0[k])
-                    sg.append(sigma[k])
-            engine.scene_calib_road(np.array(es, dtype=np.int32), np.array(ro, dtype=np.int64), np.concatenate(vs), np.array(f0), np.array(sg))
-        objectives = [d.traj[: d.length][:, ~d.replayed][:, :, feat] for d in data]
-        inside = None
-        if shared or any(d.windowed for d in data):             # (no scene has a window: nothing is passed, the calls are today's)
-            if not shared:
-                engine.scene_calib_windows(np.concatenate([d.enter for d in data]), np.concatenate([d.exit for d in data]))
-            inside = [d.inside for d in data]
+                engine.scene_calib_groups(img.group, self._G)
+        return engine, shared
+
+    def _load_replay(self, engine, data, img):
+        """REPLAY: the recorded (x, y, psi, v) of the replayed riders, in rider order - where anybody is replayed"""
+        if not img.replayed.any():
+            return
+        rec = np.zeros((img.T, int(img.replayed.sum()), 4))
+        at = 0
+        for d in data:
+            k = int(d.replayed.sum())
+            if k:
+                rec[: d.traj.shape[0], at: at + k] = d.replay_rows()
+            at += k
+        engine.scene_calib_replay(img.replayed, rec)
+
+    def _load_road(self, engine, data):
+        """ROAD: the edges of all scenes in one CSR, every edge with its scene - where a scene has a road"""
+        if not _has_road(data):
+            return
+        edges = [(q, d.road[1][a:b], f0, sigma) for q, d in enumerate(data) if d.road is not None     # (scene, vertices, F0, sigma) per edge
+                 for a, b, f0, sigma in zip(d.road[0][:-1], d.road[0][1:], d.road[2], d.road[3])]
+        es, vs, f0, sg = zip(*edges)
+        ro = np.r_[0, np.cumsum([v.shape[0] for v in vs])].astype(np.int64)
+        engine.scene_calib_road(np.array(es, dtype=np.int32), ro, np.concatenate(vs), np.array(f0), np.array(sg))
+
+    def _load_windows(self, engine, data, img, shared):
+        """WINDOWS: where a scene has one, or the riders share lanes - the load call has taken them then; -> who is inside when, per
+        scene (None: no scene has a window, nothing is passed and nothing is masked)"""
+        if not (shared or any(d.windowed for d in data)):
+            return None
+        if not shared:
+            engine.scene_calib_windows(img.enter, img.exit)
+        return [d.inside for d in data]
+
+    def _bookkeeping(self, engine, data, img, inside):
+        """what `evaluate` and `_trajs` need on the host: the objectives of the simulated riders (NaN outside a window) and, per scene,
+        who is simulated and how many present (rider, tick) cells they have - length x simulated riders without windows"""
+        objectives = [d.traj[: d.length][:, ~d.replayed][:, :, img.feat] for d in data]
+        if inside is not None:
             for q, d in enumerate(data):
                 objectives[q][~inside[q][:, ~d.replayed]] = np.nan
-        # present (rider, tick) cells of the simulated riders of every scene: length x simulated riders without windows
         cells = np.array([int((d.exit - d.enter)[~d.replayed].sum()) for d in data])
-        ds = dict(engine=engine, lens=lens, feat=feat, nr=nr, roff=roff, R=R, sets=self.max_sets, sim=[~d.replayed for d in data],
-                  nsim=np.array([int((~d.replayed).sum()) for d in data]), cells=cells, inside=inside, objectives=objectives)
-        self._sets[bool(test)] = ds
-        return ds
+        return dict(engine=engine, lens=img.lens, feat=img.feat, nr=img.nr, roff=img.roff, R=img.R, sets=self.max_sets, sim=[~d.replayed for d in data],
+                    nsim=np.array([int((~d.replayed).sum()) for d in data]), cells=cells, inside=inside, objectives=objectives)
 
     def _trajs(self, ds, states, k):
         """the scenes of parameter set k from the states of one evaluation: [length, simulated riders, n_feat] each (rows the class
@@ -929,35 +991,26 @@ class InteractionCalibration:
             out.append(tr if ds["sim"][q].all() else tr[:, ds["sim"][q]])
         return out
 
-    def evaluate(self, params_vals, test=False):
-        """Errors of many parameter vectors, [k, n_params] -> [k]: one launch per max_sets of them."""
-        vals = np.atleast_2d(np.asarray(params_vals, dtype=float))
-        ds = self._dataset(test)
-        args = [self._update_params_args_dict(v) for v in vals]
-        err = np.zeros(len(args))
-        for at in range(0, len(args), ds["sets"]):
-            chunk = args[at:at + ds["sets"]]
-            road = self._road_over(chunk)
-            if self.error_func is calc_sse_timesteps:
-                sums = self._eval(ds, chunk, **road)
-                err[at:at + len(chunk)] = _scenes_in_order(_riders_then_scenes(sums[:, :, 0], ds["roff"]))
-            elif self.error_func is calc_maesse_samples:
-                sums = self._eval(ds, chunk, **road)
-                with np.errstate(invalid="ignore", divide="ignore"):   # (an empty scene: nan, as np.mean gives)
-                    mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["cells"] * float(ds["feat"].size))[None, :]
-                err[at:at + len(chunk)] = _scenes_in_order(mae ** 2)
-            else:
-                _, states = self._eval(ds, chunk, states=True, **road)
-                for k in range(len(chunk)):
-                    err[at + k] = self.error_func(self._trajs(ds, states, k), ds["objectives"])
-        return err
+    def _candidates(self, vals):
+        return [self._update_params_args_dict(v) for v in vals]
+
+    def _launch(self, ds, args_list, **kw):
+        return self._eval(ds, args_list, **kw, **self._road_over(args_list))
+
+    def _errors(self, ds, sums):
+        """per-rider sums -> errors: the riders of a scene added in rider order, then the scenes in scene order"""
+        if self.error_func is calc_sse_timesteps:
+            return _scenes_in_order(_riders_then_scenes(sums[:, :, 0], ds["roff"]))
+        with np.errstate(invalid="ignore", divide="ignore"):       # (an empty scene: nan, as np.mean gives)
+            mae = _riders_then_scenes(sums[:, :, 1], ds["roff"]) / (ds["cells"] * float(ds["feat"].size))[None, :]
+        return _scenes_in_order(mae ** 2)
 
     def simulate(self, params_vals, test=False):
         """The trajectories of one parameter vector on the training (test) scenes: ([length, simulated riders, n_feat] per scene -
         the state after each tick -, the objectives)."""
         ds = self._dataset(test)
         args = self._update_params_args_dict(np.asarray(params_vals, dtype=float))
-        _, states = self._eval(ds, [args], states=True, **self._road_over([args]))
+        _, states = self._launch(ds, [args], states=True)
         return self._trajs(ds, states, 0), list(ds["objectives"])
 
     def run(self, params_vals_guess):
@@ -970,14 +1023,6 @@ class InteractionCalibration:
         self.param_args_opt = self._update_params_args_dict(results[0])
         results.append(self.simulate(results[0]))
         return results
-
-    def run_many(self, guesses):
-        """Independent calibrations from several guesses, in lockstep (minimize_many): every iteration of all live runs is one launch.
-        Returns a list of (xopt, fopt, iterations) - per guess what `run` finds from it - and keeps the best in param_args_opt."""
-        res = minimize_many(self.evaluate, [np.asarray(g, dtype=float) for g in guesses], xtol=self.xtol, ftol=self.ftol, maxiter=self.maxiter)
-        best = min(res, key=lambda r: r[1])
-        self.param_args_opt = self._update_params_args_dict(best[0])
-        return res
 
     def test(self, params_vals=None):
         """Error of a parameter vector - by default the one `run` / `run_many` found - on the TEST scenes."""
