@@ -1,5 +1,6 @@
 // csf_field.h — the repulsive force fields and the field-of-view test as device functions (fp32, trig-free): TwoDBicycle
-// field (vehicle.py:1560-1648) one pair per lane and two pairs per lane on packed arithmetic, the reach test, the Bicycle
+// field (vehicle.py:1560-1648) one pair per lane and two pairs per lane - on packed arithmetic, and as two plain halves that
+// return the packed form's bits (pair_cull_kernel takes those: csf_pair.hip, header) -, the reach test in both forms, the Bicycle
 // field (vehicle.py:1054-1147); the rare paths that make the field-of-view decision exact.  Used by the pair kernels
 // (csf_pair.hip).
 #pragma once
@@ -192,15 +193,78 @@ __device__ __forceinline__ void field_twod(const PairConsts &k, const Recv &r, c
     F = P * ig;                                       // :1644-1646: |F| = P
 }
 
+// ONE source of field_twod_x2 on plain f32 instructions: the arithmetic of one half of the packed form, operation for operation -
+// an explicit fma where the packed form issues v_pk_fma_f32, a plain product where it issues v_pk_mul_f32 (read off its
+// disassembly: of a sum of two products the first is fused onto the second), nothing left to the compiler's contraction - so
+// that a half of a packed evaluation and this function return the same bits.  (cx, cy): the source's contribution.
+// CAUTION: the pairing is PINNED here and LEFT TO THE COMPILER in the packed form (field_twod_x2 below, which csf_mid.hip, the
+// csf_scene*.hip kernels, plain_pair_sums and the pair_cull_kernel variants without the reach test still use).  A compiler that
+// contracts the packed expressions differently makes the two forms - and so those kernels and this one - diverge in the last bit;
+// nothing but the recorded fixtures (tests/test_gpu_sift_bookkeeping.py, tests/test_gpu_pair_plain_f32.py) catches that.  Read the
+// pairing off the packed form's disassembly again after a compiler upgrade.
+template <bool FULL, bool NEARFLAG>
+__device__ __forceinline__ void field_twod_half(const PairConsts &k, const Recv &r, float qx, float qy, float qc, float qs, bool valid,
+                                                float &cx, float &cy, unsigned long long *near) {
+#pragma clang fp contract(off)
+    const float dx = r.x - qx, dy = r.y - qy;         // vehicle.py:1615-1616
+    float r2 = __builtin_fmaf(dx, dx, dy * dy);
+    if (NEARFLAG) {
+        *near = __builtin_amdgcn_ballot_w64(r2 < k.rnear2);
+        if (!FULL) *near &= __builtin_amdgcn_ballot_w64(valid);
+    }
+    if (!FULL) r2 = fmaxf(r2, 1e-30f);
+    const float inv = fast_rsq(r2), rho = r2 * inv;
+    const float srel = __builtin_fmaf(qs, r.c, -(qc * r.s));   // :1595
+    const float s2 = srel * srel;
+    const float sga = __builtin_fmaf(k.sg1, s2, k.sg0), sgb = __builtin_fmaf(k.sg3, s2, k.sg2), e = __builtin_fmaf(-k.e1, s2, k.e0);
+    const float cphi = __builtin_fmaf(qc, dx, qs * dy) * inv, sphi = __builtin_fmaf(qc, dy, -(qs * dx)) * inv;   // :1618-1621
+    const float a = __builtin_fmaf(__builtin_fabsf(cphi), 0.5f, 0.5f);
+    const float rs = fast_rsq(a);
+    const float big = a * rs, hrs = 0.5f * rs;
+    const float al = sphi * hrs;
+    if (NEARFLAG) {   // (np.sign(phi) within rounding of phi = 0: field_twod_x2)
+        const float Ts = k.fovT0 + k.fovT1;
+        unsigned long long s = __builtin_amdgcn_ballot_w64(__builtin_fabsf(al) <= Ts);
+        if (!FULL) s &= __builtin_amdgcn_ballot_w64(valid);
+        *near |= s;
+    }
+    const float bs = __builtin_copysignf(big, sphi);
+    const bool p = cphi >= 0.0f;
+    const float h1 = p ? __builtin_fabsf(al) : big, h2s = p ? bs : al;
+    const float sigma = __builtin_fmaf(-sgb, h1, sga);
+    const float hd = (0.5f * sgb) * h2s;
+    const float ec = e * cphi;
+    const float q2 = __builtin_fmaf(-ec, ec, 1.0f);
+    const float grho = q2 * sigma;
+    const float gphi = __builtin_fmaf(q2, hd, (e * ec) * (sphi * sigma));
+    const float gx = __builtin_fmaf(grho, dx, -(gphi * dy)), gy = __builtin_fmaf(grho, dy, gphi * dx);
+    const float ig = fast_rsq(__builtin_fmaf(gx, gx, gy * gy));
+    const float qos = q2 * fast_rsq(grho * sigma);
+    const float ex = __builtin_fmaf(-k.kexp, rho * qos, k.lf0);
+    float F = fast_exp2(ex) * ig;
+    if (!FULL) F = valid ? F : 0.0f;
+    cx = F * gx;
+    cy = F * gy;
+}
+
 // The same field for TWO sources per lane (components .x / .y), float2 arithmetic -> v_pk_* instructions.
 // FULL: both sources of every lane are real, tracked pairs (rho > 0); otherwise valid0 / valid1 mask the lanes
 // of a partial batch, whose dummy record may coincide with the receiver.  Accumulates into (ax, ay).
 // NEARFLAG: near0 / near1 (wave masks) report the pairs closer than k.rnear (pair_cull_kernel corrects them from the precise
 // records).
-template <bool FULL, bool NEARFLAG = false>
+// PLAIN: the same two sources per lane, each half through field_twod_half - plain f32 instructions, the same bits.
+template <bool FULL, bool NEARFLAG = false, bool PLAIN = false>
 __device__ __forceinline__ void field_twod_x2(const PairConsts &k, const Recv &r, const v2f qx, const v2f qy,
                                               const v2f qc, const v2f qs, bool valid0, bool valid1, float &ax,
                                               float &ay, unsigned long long *near0 = nullptr, unsigned long long *near1 = nullptr) {
+    if (PLAIN) {
+        float cx0, cy0, cx1, cy1;
+        field_twod_half<FULL, NEARFLAG>(k, r, qx.x, qy.x, qc.x, qs.x, valid0, cx0, cy0, near0);
+        field_twod_half<FULL, NEARFLAG>(k, r, qx.y, qy.y, qc.y, qs.y, valid1, cx1, cy1, near1);
+        ax += cx0 + cx1;
+        ay += cy0 + cy1;
+        return;
+    }
     v2f dx = r.x - qx, dy = r.y - qy;                 // vehicle.py:1615-1616
     v2f r2 = dx * dx + dy * dy;
     if (NEARFLAG) {   // (every mask the result of ONE compare: csf_pair.hip ballot1)
@@ -249,15 +313,55 @@ __device__ __forceinline__ void field_twod_x2(const PairConsts &k, const Recv &r
     ay += cy.x + cy.y;
 }
 
+// ONE source of keep_x2 on plain f32 instructions (as field_twod_half: the fma / product pairing of the packed form, pinned -
+// and the same CAUTION: the packed keep_x2 is contracted by the compiler, so a compiler upgrade can make the two forms differ in
+// the last bit, i.e. in the kept set; the packed form is measured by tools/packed_vs_plain_ubench.hip only, no kernel runs it).
+template <bool FOV, bool P2R>
+__device__ __forceinline__ void keep_half(const PairConsts &k, const Recv &r, float qx, float qy, float qc, float qs, bool &kept, bool &m) {
+#pragma clang fp contract(off)
+    const float dx = r.x - qx, dy = r.y - qy;
+    const float r2 = __builtin_fmaf(dx, dx, dy * dy);
+    const float X = __builtin_fmaf(qc, dx, qs * dy);
+    const float srel = __builtin_fmaf(qs, r.c, -(qc * r.s));
+    const float s2 = srel * srel;
+    const float e = __builtin_fmaf(-k.e1, s2, k.e0), A = __builtin_fmaf(k.tA1, s2, k.tA0), B = __builtin_fmaf(k.tB1, s2, k.tB0);
+    const float inv = fast_rsq(r2);
+    const float c = X * inv;
+    const float S = __builtin_fmaf(B, c, A);
+    const float eX = e * X;
+    const float f = __builtin_fmaf(-S, S, __builtin_fmaf(-eX, eX, r2));
+    m = false;
+    if (!FOV) {
+        kept = !(f > 0.0f);
+    } else {
+        const float tt = __builtin_fmaf(dx, r.c, dy * r.s);      // (- t)
+        const float T = __builtin_fmaf(k.fovT1, inv, k.fovT0);
+        const float dc = __builtin_fmaf(-tt, inv, -k.chk);
+        const float z = dc + T;
+        if (!P2R) kept = __builtin_fminf(-f, z) > 0.0f;
+        m = dc < T;
+        if (P2R) {
+            const float ss = __builtin_fmaf(r.s, dx, -(r.c * dy)) * inv;
+            kept = (!(f > 0.0f)) & (z > 0.0f) & !(ss > T);
+            m = m | (ss > -T);
+        }
+    }
+}
+
 // Reach test for TWO sources per lane (csf_engine.hip: update_far_radius): keep a pair unless its contribution is provably
 // below far_eps f_0 / n,
 //     rho^2 - e^2 X^2 > T^2 (sigma_a - sigma_b / 2 + (sigma_b / 2) X / rho)^2,   X = rho cos(phi) = (dx, dy) . (cos psi0, sin psi0),
 // which needs the three pair scalars (rho^2, X, s2) and one rsq: ~40 % of the cost of the field (vehicle.py:1604-1628),
 // and removes three of four pairs inside the field of view.  FOV adds the exact mask of intersection.py:690-745 for
-// batches that are not wholly inside the field of view.
-template <bool FOV, bool P2R>
+// batches that are not wholly inside the field of view.  PLAIN: each half through keep_half - plain f32 instructions, the same bits.
+template <bool FOV, bool P2R, bool PLAIN = false>
 __device__ __forceinline__ void keep_x2(const PairConsts &k, const Recv &r, const v2f qx, const v2f qy, const v2f qc,
                                         const v2f qs, bool &k0, bool &k1, bool &m0, bool &m1) {
+    if (PLAIN) {
+        keep_half<FOV, P2R>(k, r, qx.x, qy.x, qc.x, qs.x, k0, m0);
+        keep_half<FOV, P2R>(k, r, qx.y, qy.y, qc.y, qs.y, k1, m1);
+        return;
+    }
     const v2f dx = r.x - qx, dy = r.y - qy;
     const v2f r2 = dx * dx + dy * dy;
     const v2f X = dx * qc + dy * qs;

@@ -5,22 +5,44 @@
 // 1054-1147) and the column sum of intersection.py:841-843;  RoadEdge.calcRepulsiveForce
 // (intersection.py:226-242) for the static-obstacle term.
 //
-// Mapping (CDNA4, 64-wide waves): SOURCES sit in the lanes, RECEIVERS are wave-uniform.  A workgroup owns 16 or 32
+// Mapping (CDNA4, 64-wide waves): SOURCES sit in the lanes, RECEIVERS are wave-uniform.  A workgroup owns 8, 16 or 32
 // receivers and streams the fp32 source records (x, y, cos psi, sin psi) of one chunk through an LDS tile that its four
-// waves share; the waves take the receivers one at a time (an LDS counter), each lane accumulates its sources'
+// or - the headline - eight waves share (1024 or 2048 sources; eight waves per SIMD are resident); the waves take the
+// receivers one at a time (an LDS counter), each lane accumulates its sources'
 // contribution, and gfx950 lane exchanges (v_permlane32/16_swap, DPP adds) form the column sum of a receiver, which is
 // added to an LDS accumulator in a fixed order.  No atomics on the sums: the result is bit-reproducible.
 //
-// The kernel is VALU-issue bound (tools/valu_ubench.hip: ~3-4.5 cycles per wave64 fp32 instruction, ~8.3 per
-// transcendental, v_pk_* at ~4.7 for two results), so the work is organised to issue as little as possible:
-//   1. CULL FIRST.  The field-of-view test costs ~12 instructions, the field itself ~70.  With the
+// The kernel is VALU-issue bound, so the work is organised to hold the vector pipe as briefly as possible.  What an
+// instruction holds it for AT THIS KERNEL'S OCCUPANCY, 8 waves per SIMD (tools/packed_vs_plain_ubench.hip ->
+// profiles/packed_vs_plain_ubench.txt, shader-clock ticks per PAIR of f32 results; tools/valu_ubench.hip has the rates of a
+// wave that is almost alone, where a packed instruction looks almost twice as good as two plain ones - it is 9 % better):
+//     v_pk_fma / v_pk_mul / v_pk_add_f32, VGPR, SGPR-pair or inline-constant operands   2.64 - 2.67   (one instruction)
+//     two v_fma / v_mul / v_add_f32, VGPR or inline-constant operands                   2.87 - 2.97
+//     two of them with an SGPR operand                                                   5.27 - 5.29   (!)
+//     with one v_rsq_f32 per eight instructions                                          3.25 packed, 4.6 - 4.8 plain
+//     the chains themselves (csf_field.h), per pass of two sources per lane              keep_x2 54 / 81 packed, 55 / 85 plain
+//                                                                                        field_twod_x2 204 packed, 238 plain
+//   Packed f32 is at or below two plain instructions in every row, and in isolation the packed chains win.  IN THIS KERNEL the
+//   plain forms win all the same (profiles/pair_plain_f32_ab.txt, FINAL: 151.3 -> 158.0 M agent-steps/s, + 4.4 %, the launch 103.7 -> 98.8 us):
+//   every constant of the field is ONE register instead of a duplicated pair, the kernel drops from 64 VGPRs with 12 bytes of
+//   scratch to 63 without, and the scheduler interleaves the two halves where the packed form stood behind its s_nop.  The price list
+//   above says how: no plain instruction of the two loops may read an SGPR - receiver, band and edge of the field of view sit
+//   in VGPRs (session 2 of that file: with the receiver left in scalar registers the plain forms gain 0.6 %, with it in VGPRs
+//   2.1 %, with the band as well 4.3 %; session 1: sift or field pass alone in plain form loses - 0.9 % and, spilling 48 bytes,
+//   a factor 2.5).
+//   1. CULL FIRST.  The reach and field-of-view test costs 24 - 32 vector instructions per source, the field itself 58
+//      (profiles/pair_plain_f32_isa_counts.txt).  With the
 //      reference's default 120 degree field of view two thirds of all pairs are masked.  Every lane tests its
 //      source, the wave ballots, and the lanes that pass append their tile index to a per-receiver queue in
 //      LDS (prefix = v_mbcnt of the ballot).  The field is evaluated only on full batches popped from the
 //      queue, so all 64 lanes do useful work there.
-//   2. TWO PAIRS PER LANE in the field evaluation, written on float2 so that hipcc emits v_pk_fma_f32 /
-//      v_pk_mul_f32 / v_pk_add_f32.
-//   3. Wave-uniform operands are kept in VGPRs (an SGPR operand makes a VALU instruction slower here).
+//   2. TWO PAIRS PER LANE in the test and in the field evaluation: two independent chains for the scheduler to interleave.
+//      In pair_cull_kernel they are plain f32 instructions with the packed form's pairing of products and fused multiply-adds
+//      (csf_field.h: keep_half, field_twod_half - the same bits).  The variants WITHOUT the reach test (every pair evaluated:
+//      the field is nearly all their work) and the other kernels (csf_mid.hip, csf_scene*.hip, plain_pair_sums) keep the float2
+//      form, v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32, with the receiver in scalar registers.
+//   3. Wave-uniform operands of PLAIN instructions are kept in VGPRs (an SGPR operand doubles what they cost, above);
+//      packed instructions take them as SGPR pairs at no cost.
 //   4. WHOLE BATCHES of 64 spatially binned records are classified first from their bounding circle (csf_bin.hip):
 //      outside the field of view or beyond the far-field radius -> skipped, inside -> evaluated without the test.
 // The math is trig-free: every angle of the reference enters only through sin/cos, which are dot and cross
@@ -30,7 +52,7 @@
 namespace csf {
 
 
-// ---- culling kernel (TwoD field): classify batches -> test -> ballot -> LDS queue -> packed field ---------
+// ---- culling kernel (TwoD field): classify batches -> test -> ballot -> LDS queue -> field, two sources per lane ---------
 // CLASSIFY: the records are streamed in spatially binned order (csf_bin.hip) and every batch of 64 carries a
 // bounding circle.  Per receiver and tile, lane b classifies batch b against the field-of-view cone:
 //   outside (smallest bearing in the circle > hfov/2)  -> skipped without touching its records,
@@ -54,7 +76,7 @@ namespace csf {
 // receivers shortens that wave.  At full size the SIMDs are issue-bound either way and the variant is not used.
 // RPB: receivers of a workgroup, 16, or 32 where the grid stays large enough (DYN only: with dynamic hand-out a
 // workgroup of twice the receivers shares one tile fill and one start-up between them: 146 -> 141 us at N = 16 384)
-// REACH (with the far-field cull on): every candidate batch goes through the packed reach test keep_x2, two batches at a
+// REACH (with the far-field cull on): every candidate batch goes through the reach test keep_x2 (two sources per lane), two batches at a
 // time, and only the sources it keeps are queued for the field.
 // CW: waves of a workgroup, 4, or 8 (DYN, RPB 32: launch_cull_dyn): a workgroup of 8 waves holds a
 // tile of 2048 sources (32 batches), so a visit - one receiver against one tile - covers twice the sources: half the visits
@@ -90,6 +112,10 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     static_assert(RPB == WPB * RPW || (DYN && (RPB % (WPB * RPW) == 0 || RPB == 2 * RPW) && RPB <= WAVE), "other workgroup sizes need the dynamic hand-out");
     static_assert(CW == WPB || (CW == 2 * WPB && DYN && CLASSIFY && (RPB == 32 || RPB == 16)), "the wide workgroup is built into the variants with 16 / 32 receivers");
     constexpr int BLOCKW = CW * WAVE;             // threads of a workgroup
+    // the sift and the field pass as plain f32 instructions, receiver and field-of-view band in vector registers (header, item 2) -
+    // in the variants with the reach test.  Without it (CSF_FAR_EPS=0) nearly all the work is the field, where the packed form is the
+    // faster one (204 against 238 cycles per pass): plain, that kernel lost 1 - 4 % (profiles/pair_plain_f32_ab.txt) and stays packed.
+    constexpr bool PLAIN = REACH;
     constexpr int TL = TILE2 / WPB * CW;          // sources of a tile
     constexpr int NBT = TL / WAVE;                // batches of a tile: 16 or 32
     constexpr int RPP = WAVE / NBT;               // receivers one classification pass of a wave covers: 4 or 2
@@ -151,6 +177,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     asm volatile("" : "+v"(k.sg0), "+v"(k.sg1), "+v"(k.sg2), "+v"(k.sg3), "+v"(k.e0), "+v"(k.e1), "+v"(k.lf0),
                  "+v"(k.kexp), "+v"(k.chs));
     if (REACH) asm volatile("" : "+v"(k.tA0), "+v"(k.tA1), "+v"(k.tB0), "+v"(k.tB1));
+    if (PLAIN) asm volatile("" : "+v"(k.fovT0), "+v"(k.fovT1), "+v"(k.chk));    // (the band and the edge of the field-of-view test: read by plain instructions)
 
     // Near pairs (precise_delta): what the field evaluation meets closer than k.rnear is noted here - receiver << 16 |
     // tile index - and corrected once per wave and tile (near_drain, in the tile loop).
@@ -190,8 +217,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         const bool v0 = lane < n, v1 = lane + WAVE < n;
         if (!FULL) i0 = v0 ? i0 : 0, i1 = v1 ? i1 : 0;
         unsigned long long n0, n1;
-        field_twod_x2<FULL, true>(k, ru, lds_pair_b(tx, i0, i1), lds_pair_b(ty, i0, i1), lds_pair_b(tc, i0, i1),
-                                  lds_pair_b(ts, i0, i1), v0, v1, ax[u], ay[u], &n0, &n1);
+        field_twod_x2<FULL, true, PLAIN>(k, ru, lds_pair_b(tx, i0, i1), lds_pair_b(ty, i0, i1), lds_pair_b(tc, i0, i1),
+                                         lds_pair_b(ts, i0, i1), v0, v1, ax[u], ay[u], &n0, &n1);
         if (__builtin_expect((n0 | n1) != 0ull, 0)) {   // rare: a pair among the 128 to be corrected (the queue still holds their offsets)
             // (read again through an address formed here: taken from above, address and entries would stay in registers across the field)
             int ln = lane;
@@ -497,19 +524,28 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             cur_recv = ur;
             {
                 const float4 q = rrec[ur];
-                // the receiver in SCALAR registers (round 3): every packed instruction of the test and of the field takes at most
-                // one of its four numbers, which the constant bus allows; as vector registers (rounds 1 and 2, when the compiler
-                // answered scalar operands with copies) they were four register PAIRS - with them gone the kernel fits 64 VGPRs
-                ru.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.x)));
-                ru.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.y)));
-                ru.c = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.z)));
-                ru.s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.w)));
+                if (PLAIN) {
+                    // the receiver in VECTOR registers: the sift and the field pass are plain f32 instructions (csf_field.h: keep_half,
+                    // field_twod_half), and a plain instruction that reads a scalar register holds the pipe about twice as long as one
+                    // that reads vector registers only (profiles/packed_vs_plain_ubench.txt: 5.3 against 2.9 cycles per pair of results
+                    // at 8 waves per SIMD)
+                    ru.x = q.x, ru.y = q.y, ru.c = q.z, ru.s = q.w;
+                    asm volatile("" : "+v"(ru.x), "+v"(ru.y), "+v"(ru.c), "+v"(ru.s));
+                } else {
+                    // the receiver in SCALAR registers: every packed instruction of the field takes at most one of its four numbers,
+                    // which the constant bus allows, and takes a scalar pair at no cost; as vector registers they would be four
+                    // register PAIRS
+                    ru.x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.x)));
+                    ru.y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.y)));
+                    ru.c = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.z)));
+                    ru.s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.w)));
+                }
             }
             unsigned cand = ((DYN && CLASSIFY) ? (NBT > 16 ? bm : (bm & 0xFFFFu)) : (unsigned)(cand_all >> (16 * u))) & live;
             const unsigned inside = ((DYN && CLASSIFY) ? (NBT > 16 ? bm_in : (bm >> 16)) : (unsigned)(inside_all >> (16 * u))) & live;
             if (REACH) {
                 tests += (unsigned)WAVE * (unsigned)__builtin_popcount(cand | inside);   // every candidate batch goes through the per-lane test
-                // two candidate batches at a time through the packed reach test (+ the exact field-of-view test unless
+                // two candidate batches at a time through the reach test, two sources per lane (+ the exact field-of-view test unless
                 // both are wholly inside); what it keeps is appended to the queue, first batch first.
                 // (A single loop over both kinds of batch pairs with the records of the next pair requested ahead of the
                 // queue append was tried: the compiler spilled 30 registers into the loops and the kernel ran at 180 us.)
@@ -519,7 +555,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 auto sift2 = [&](int t1, int t2, bool two, auto fov, v2f sx, v2f sy, v2f sc, v2f ss) {
                     constexpr bool FOV = decltype(fov)::value;
                     bool k0, k1, mg0, mg1;
-                    keep_x2<FOV, P2R>(k, ru, sx, sy, sc, ss, k0, k1, mg0, mg1);
+                    keep_x2<FOV, P2R, PLAIN>(k, ru, sx, sy, sc, ss, k0, k1, mg0, mg1);
                     // (wave masks straight from the compares: a ballot of `k1 & two` would go through a vector register)
                     const unsigned long long m0 = ballot1(k0), m1 = ballot1(k1) & (0ull - (unsigned long long)two);
                     k1 = k1 & two;
