@@ -42,6 +42,7 @@ SYMBOLS = (
     "csf_scene_calib_groups", "csf_scene_calib_eval_groups",
     "csf_scene_calib_lane_groups",
     "csf_scene_calib_classes",
+    "csf_handout_ranks",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -164,6 +165,8 @@ def load():
     L.csf_set_incremental.argtypes = [vp, i32]
     L.csf_set_script.argtypes = [vp, i64, vp, vp, dp]
     L.csf_near_dropped.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_handout_ranks"):
+        L.csf_handout_ranks.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.csf_comm_stream_order.argtypes = [vp, C.POINTER(i32), dp]
     L.csf_small_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]

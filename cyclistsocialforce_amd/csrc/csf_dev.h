@@ -269,6 +269,7 @@ struct Dev {
     uint64_t *atrace;  // CSF_TRACE_AGENT: eight time stamps (wall_clock64, 100 MHz) of every wave of the last per-agent launch, else NULL:
                        // entry, own scalars loaded, destination force done, partial sums loaded, combine done, integrate done, stores
                        // issued, stores done
+    int32_t index_order;   // CSF_HANDOUT=index: a workgroup of pair_cull_kernel hands its receivers out in index order, not heaviest first (csf_handout.h)
     uint64_t *trace;   // CSF_TRACE_BLOCKS: (start, end, hw id) of every pair-kernel workgroup of the last tick, else NULL
 };
 

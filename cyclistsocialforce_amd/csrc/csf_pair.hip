@@ -74,6 +74,14 @@ namespace csf {
 // handed to its waves one at a time through an LDS counter instead of four per wave.  With few workgroups the kernel
 // ends with its longest single wave (a lone wave issues one dependent instruction every ~8 cycles); sharing the
 // receivers shortens that wave.  At full size the SIMDs are issue-bound either way and the variant is not used.
+// HEAVIEST FIRST (receivers in slot order; csf_handout.h): a workgroup's ~16 non-empty visits to a tile take 1 to 16 sift passes each,
+// known from the batch masks, and handed out in index order a wave that claims a long visit last holds the workgroup - 39.6 KB of
+// LDS, eight wave slots - while its siblings wait at the last barrier: at the headline 12.1 % of a workgroup's wave-slot time passed
+// behind a wave's last receiver (mean 2.8 us between the average wave's end and the last one's, of 23 us).  The receivers are
+// ranked by weight class (3 per pair of inside batches, 4 per pair of the others; classes >= 32, >= 16, >= 8, rest; index order
+// within a class) and claim k takes rank k: 6.0 % and 1.35 us, pair launch 99.6 -> 97.8 us, 157.5 -> 159.9 M agent-steps/s
+// (profiles/handout_order_trace.txt, handout_order_ab.txt; classes >= 48 / 32 / 16 measure the same, >= 24 / 12 / 6 half the gain).
+// No sum depends on the order: a receiver's visit to a tile is one wave's, and so are its noted corrections (near_drain).
 // RPB: receivers of a workgroup, 16, or 32 where the grid stays large enough (DYN only: with dynamic hand-out a
 // workgroup of twice the receivers shares one tile fill and one start-up between them: 146 -> 141 us at N = 16 384)
 // REACH (with the far-field cull on): every candidate batch goes through the reach test keep_x2 (two sources per lane), two batches at a
@@ -511,11 +519,36 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         // loaded) an empty visit is just left at once.
         constexpr bool COMPACT = DYN && CLASSIFY && !BINR;
         const unsigned live = nb >= NBT ? NBMASK : ((1u << (nb & 31)) - 1u);
-        unsigned mymask = 0u;
+        // HEAVIEST FIRST (csf_handout.h): a visit's sift passes are known from its masks, 1 to 16 of them, and a wave that claims a
+        // long visit last keeps the workgroup - its LDS, its eight wave slots - while its siblings wait at the barrier.  Lane r ranks
+        // receiver r: by weight class (three compares, whose wave masks are the ballots), within a class by index; the k-th claim is
+        // the receiver of rank k.  Every wave forms the same ranks from the same masks.  The rank is what a lane keeps across the
+        // visits - the masks of the claimed receiver come from LDS with its record.  Dev::index_order: the ranks of the index order.
+        unsigned myrank = 0u;
         unsigned long long wanted = 0ull;
         if (COMPACT) {
-            mymask = bmask[ln & (RPB - 1)];
-            wanted = ballot1((mymask & live) != 0u) & (RPB >= 64 ? ~0ull : ((1ull << (RPB & 63)) - 1ull));
+            const unsigned mymask = bmask[ln & (RPB - 1)];
+            const unsigned cd = (NBT > 16 ? mymask : (mymask & 0xFFFFu)) & live;
+            wanted = ballot1(cd != 0u) & (RPB >= 64 ? ~0ull : ((1ull << (RPB & 63)) - 1ull));
+            // set bits of a wave mask below this lane, + n (receivers sit in the lanes below RPB <= 32: the lower half is all of it)
+            auto below = [&](unsigned long long m, int n) {
+                const unsigned lo = __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)n);
+                return RPB > 32 ? __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), lo) : lo;
+            };
+            if (d.index_order) {
+                myrank = below(wanted, 0);
+            } else {
+                const unsigned in = (NBT > 16 ? bmask_in[ln & (RPB - 1)] : (mymask >> 16)) & cd;
+                const unsigned w = handout_weight(cd, in);
+                const bool g0 = w >= HANDOUT_T0, g1 = w >= HANDOUT_T1, g2 = w >= HANDOUT_T2;
+                const unsigned long long ge0 = ballot1(g0), ge1 = ballot1(g1), ge2 = ballot1(g2);
+                const unsigned long long m0 = ge0 & wanted, m1 = ge1 & ~ge0 & wanted, m2 = ge2 & ~ge1 & wanted, m3 = wanted & ~ge2;
+                const int n0 = __builtin_popcountll(m0), n1 = n0 + __builtin_popcountll(m1), n2 = n1 + __builtin_popcountll(m2);
+                myrank = below(m3, n2);
+                myrank = g2 ? below(m2, n1) : myrank;
+                myrank = g1 ? below(m1, n0) : myrank;
+                myrank = g0 ? below(m0, 0) : myrank;
+            }
         }
         const int n_wanted = COMPACT ? __builtin_popcountll(wanted) : RPB;
         // one VISIT: receiver ur of the workgroup (batch masks bm / bm_in) against this tile
@@ -682,14 +715,13 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 if (lane == 0) got = atomicAdd(&next_recv, 1);
                 int ur = __builtin_amdgcn_readfirstlane(got);
                 bool skip = false;
-                if (COMPACT) {                        // the ur-th set bit of `wanted`: the lane whose bit it is has `ur` set bits below it
+                if (COMPACT) {                        // the receiver of rank ur: the one wanted lane that holds this rank
                     more = ur < n_wanted;
                     if (more) {
-                        const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(wanted >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wanted, 0u));
-                        const unsigned long long hit = ballot1(below == ur) & wanted;   // (the lanes from the ur-th set bit up to the next one, masked)
+                        const unsigned long long hit = ballot1(myrank == (unsigned)ur) & wanted;   // (lanes that are not wanted hold ranks of no meaning)
                         ur = __builtin_ctzll(hit);
-                        bm = (unsigned)__builtin_amdgcn_readlane((int)mymask, ur);
-                        if (NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);   // (with the receiver's record: one round trip)
+                        bm = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask[ur]);             // (with the receiver's record: one round trip)
+                        if (NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);
                     }
                 } else {
                     more = ur < RPB;
@@ -707,6 +739,11 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             for (int uu = 0; uu < RPW; uu++) visit(wave * RPW + uu, 0u, 0u, uu);
             near_drain();
         }
+    }
+    if (d.trace && lane == 0) {   // tools/handout_trace.py: this wave has no receiver left to claim - from here it waits for its siblings
+        // (stored at once, not kept for the record below: across the barrier the stamp cost four spilled scalar registers)
+        uint32_t *o = (uint32_t *)(d.trace + 3 * (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CW + wave));
+        o[5] = (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xFu) | ((uint32_t)wall_clock64() << 4);   // HW_REG_XCC_ID | 28 bits of the clock
     }
     if (DYN) {
         const float4 *const chase = cold_args().part4;   // (uniform; NULL but for the launches the per-agent kernel runs beside)
@@ -746,8 +783,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         uint64_t *o = d.trace + 3 * (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CW + wave);
         o[0] = t_start;
         o[1] = wall_clock64();
-        o[2] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11))                 // HW_REG_HW_ID
-               | ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);  // HW_REG_XCC_ID
+        *(uint32_t *)(o + 2) = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_REG_HW_ID (the upper half: above)
     }
 }
 

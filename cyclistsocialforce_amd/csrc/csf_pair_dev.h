@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "csf_field.h"
+#include "csf_handout.h"
 
 namespace csf {
 

@@ -121,6 +121,13 @@ int csf_near_dropped(csf_engine *e, int64_t *n_dropped) try {
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 
+int csf_handout_ranks(const uint32_t *cand, const uint32_t *inside, int32_t n, int32_t *rank, int32_t *weight) try {
+    if (!cand || !inside || !rank || n < 0 || n > 64) return -1;
+    if (weight)
+        for (int r = 0; r < n; r++) weight[r] = (int32_t)csf::handout_weight(cand[r], inside[r] & cand[r]);
+    return csf::handout_ranks(cand, inside, n, rank);
+} catch (...) { return -1; }
+
 int csf_comm_stream_order(const csf_engine *e, int32_t *second_stream, double us_per_tick[2]) try {
     if (!e || !second_stream) return CSF_E_ARG;
     *second_stream = e->comm_second ? 1 : 0;

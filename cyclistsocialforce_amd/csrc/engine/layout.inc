@@ -148,6 +148,7 @@ int alloc_all(csf_engine *e) {
         HIPCHK(e, e->atrace.alloc(8 * ((size_t)cap / 64 + 2) + 16 * ((size_t)cap / 4 + 2)));   // (csf_mid.hip: 16 words per workgroup)
         d.atrace = e->atrace.p;
     }
+    d.index_order = e->knobs.handout_index;
     d.trace = nullptr;
     if (!e->knobs.trace_blocks.empty()) {  // 3 words per wave: the grid is at most (cap/16) x MAX_SPLIT workgroups of 4 waves
         e->trace_words = 3 * 4 * ((size_t)cap / 16 + 1) * MAX_SPLIT;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "csf_dev.h"
+#include "csf_handout.h"
 #include "csf_calib.h"
 #include "csf_scene.h"
 
@@ -198,6 +199,7 @@ struct Knobs {
     int chase_gate_pct = 85;                  // CSF_CHASE_GATE: per cent of the pair workgroups through before the per-agent kernel is let go
     int fused_small = 1;                      // CSF_FUSED_SMALL=0: a handful of road users take the general path too (csf_agent.hip: small_tick_kernel)
     int segments = -1;                        // CSF_SEGMENTS
+    int handout_index = 0;                    // CSF_HANDOUT=index: the pair kernel's workgroups hand their receivers out in index order (0, default: heaviest first, csf_handout.h)
     int seg_grid = 1;                         // CSF_SEG_GRID=0: one launch per parameter set (class-segmented order) instead of one grid
     int far_tight = 1;                        // CSF_FAR_TIGHT=0: the far-field radius prices all n sources at the cut (ln(n / eps) / kappa) also where candidate lists say how many a receiver can meet
     int clist = 1;                            // CSF_CLIST=0: receivers in binned order walk every tile of their chunk (no candidate lists)
@@ -250,6 +252,7 @@ struct Knobs {
         clist = geti("CSF_CLIST", 1);
         far_tight = geti("CSF_FAR_TIGHT", 1);
         seg_grid = gete("CSF_SEG_GRID", 1);
+        if (const char *v = getenv("CSF_HANDOUT")) handout_index = expert && std::string(v) == "index" ? 1 : 0;
         rebin_churn = std::max(1, geti("CSF_REBIN_CHURN", 4000));
         hole_reuse = geti("CSF_HOLE_REUSE", 1);
         hole_lazy = geti("CSF_HOLE_LAZY", 1);

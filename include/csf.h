@@ -382,6 +382,12 @@ int csf_count_pairs(csf_engine *e, int64_t counts[4], const char **kernel_name);
  * found its list full, or a hand-over ring that overflowed within one tick, is counted here; such a pair keeps the fp32
  * result. */
 int csf_near_dropped(csf_engine *e, int64_t *n_dropped);
+/* The order in which a workgroup of the pair kernel hands its receivers to its waves, computed on the host exactly as the kernel
+ * computes it (csrc/csf_handout.h; needs no engine and no device): cand[r] / inside[r] are the candidate batches of receiver r in
+ * the tile and those of them wholly inside its field of view, n <= 64.  rank[r]: the claim that takes receiver r - heavier
+ * visits first, within a weight class by index - or -1 where cand[r] is empty; weight[r] (may be NULL): the visit's weight.
+ * Returns the number of receivers ranked, -1 on bad arguments. */
+int csf_handout_ranks(const uint32_t *cand, const uint32_t *inside, int32_t n, int32_t *rank, int32_t *weight);
 /* Where a sharded engine issues the all-gather of a tick: 0 in stream order on its main stream, 1 on a second stream beside
  * the destination-force phase of the next tick.  Unless CSF_COMM_STREAM=main|second says which, the communicator times both
  * orders itself on its first tick - 32 launches each of the pair kernel + the collective on the records as they are, the
