@@ -42,6 +42,7 @@ SYMBOLS = (
     "csf_scene_calib_groups", "csf_scene_calib_eval_groups",
     "csf_scene_calib_lane_groups",
     "csf_scene_calib_classes",
+    "csf_small_classes",
     "csf_handout_ranks",
 )
 ABI_VERSION = 9
@@ -216,6 +217,8 @@ def load():
         L.csf_scene_calib_lane_groups.argtypes = [vp, vp, i32]
     if hasattr(L, "csf_scene_calib_classes"):       # (the same)
         L.csf_scene_calib_classes.argtypes = [vp, vp, i32, vp, dp]
+    if hasattr(L, "csf_small_classes"):             # (the same)
+        L.csf_small_classes.argtypes = [vp, i32]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

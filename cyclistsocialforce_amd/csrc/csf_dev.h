@@ -306,6 +306,10 @@ void launch_small_tick(const Dev &d, int n_ticks, hipStream_t st, hipEvent_t t0 
 // csf_step_batch: `count` scenes of vehicle class `model`, one wave each, their Dev records in `table` (device memory); the road of
 // each is staged in max_nv_pad float4 of LDS; pack: the read-back into every member's Dev::snap behind the last tick
 void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, int n_ticks, bool pack, hipStream_t st);
+// csf_small_classes.hip: the same two for a handful of road users of several parameter sets or vehicle classes, the
+// UncontrolledVehicle's among them - d.ptab / pctab / pbtab / cls are read; one batched launch serves members of any classes
+void launch_small_classes(const Dev &d, int n_ticks, hipStream_t st);
+void launch_small_classes_batch(const Dev *table, int count, int max_nv_pad, int n_ticks, bool pack, hipStream_t st);
 // csf_mid.hip: one tick of a mid-size population (plain pair sums + per-agent tick) in one launch; d.rec_w / recg_w / rec2_w /
 // src64_w point at the halves of the double buffers this tick does not read, d.mid_group = slots per workgroup
 bool launch_mid_tick(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);

@@ -1,5 +1,5 @@
 // csf_small_body.inc - the one-wave tick of a handful of road users (DESIGN.md 4.6): included by csf_agent.hip (small_tick_kernel,
-// small_batch_kernel), by csf_scene.hip (scene_eval_kernel) and by csf_scene_mixed.hip (scene_mixed_kernel) inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
+// small_batch_kernel), by csf_scene.hip (scene_eval_kernel), by csf_scene_mixed.hip (scene_mixed_kernel) and by csf_small_classes.hip inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
 // include and not a __device__ function of a translation unit of its own, as csf_mid_body.inc is (DESIGN.md 4.6d): the kernels of
 // csf_agent.hip keep the instruction stream they had when the body stood in that file.
 //
@@ -39,7 +39,18 @@
 //   per-agent tick   inside the uniform loop over the groups a uniform switch on the group's class to agent_body<M>; no barrier,
 //                    shuffle or ballot stands under a divergent condition.
 // Every line of it stands under `if constexpr (MIXED)`: an instance of a real class is the one it was.
+//
+// HOOK::BY_CLASS (DESIGN.md 4.6e; csf_small_classes.hip: the stepping engine's own mixed populations): a SMALL_MIXED hook whose cells are
+// indexed by the road user, not by a group, and whose per-agent tick runs on the engine's tables - one pass per vehicle CLASS present, the
+// loop uniform over the bits of Dev::model_mask (a kernel argument), agent_body<M, HET = true> picking the lane's own row of Dev::ptab / pbtab
+// and returning for a lane of another class; the UncontrolledVehicle's class is among them.  A hook without the member has it false
+// (HookByClass), and every line of it stands under that condition.
 constexpr int SMALL_MIXED = -1;   // (no enum csf_model)
+
+template <class H, class = void>
+struct HookByClass { static constexpr bool value = false; };
+template <class H>
+struct HookByClass<H, decltype((void)H::BY_CLASS)> { static constexpr bool value = H::BY_CLASS; };
 
 struct NoTickHook {
     static constexpr bool MASKED = false;
@@ -210,7 +221,23 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             if (mine) d.froad[lane] = make_float2(qx, qy);        // (agent_body reads it back: the same lane, program order)
         }
         __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
-        if constexpr (HOOK::GROUPS) {
+        if constexpr (HookByClass<HOOK>::value) {
+            constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
+#pragma nounroll
+            for (int m = 0; m < 7; m++) {                          // (uniform: the classes of the population, a kernel argument)
+                if (((d.model_mask >> m) & 1) == 0) continue;
+                switch (m) {                                        // (agent_body<M, true>: a lane of another class returns at once)
+                case CSF_BICYCLE: if (mine) agent_body<CSF_BICYCLE, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_TWOD: if (mine) agent_body<CSF_TWOD, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_INVPEND: if (mine) agent_body<CSF_INVPEND, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_PLANARPOINT: if (mine) agent_body<CSF_PLANARPOINT, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_PLANARBIKE: if (mine) agent_body<CSF_PLANARBIKE, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_BALANCINGRIDER: if (mine) agent_body<CSF_BALANCINGRIDER, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                case CSF_UNCONTROLLED: if (mine) agent_body<CSF_UNCONTROLLED, true, true>(d, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
+                default: break;
+                }
+            }
+        } else if constexpr (HOOK::GROUPS) {
             Dev dg = d;
 #pragma nounroll
             for (int g = 0; g < hook.n_groups; g++) {               // (uniform; the body of agent_body is emitted once, here)

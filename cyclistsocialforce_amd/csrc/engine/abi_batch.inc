@@ -4,8 +4,9 @@
 // A junction of a SUMO network or one run of a parameter sweep is a handful of road users: one wave of the one-wave tick
 // (csf_agent.hip: small_tick_kernel), and its launch is nearly all latency.  The members of a batch that this tick takes
 // (small_fused_ok) are stepped by small_batch_kernel instead - one launch per vehicle class present, workgroup b ticking the scene
-// of table[b] - and every other member by step_impl in turn.  The table holds the members' Dev records in device memory; it is
-// renewed in stream order, and only where a member's Dev changed since it was last copied (a host shadow, memcmp).  Per-call
+// of table[b], and with csf_small_classes on one further launch of small_classes_batch_kernel (csf_small_classes.hip) for all members
+// of several parameter sets or classes - and every other member by step_impl in turn.  The table holds the members' Dev records in
+// device memory; it is renewed in stream order, and only where a member's Dev changed since it was last copied (a host shadow, memcmp).  Per-call
 // values stay out of it: whether the read-back is packed is a kernel argument, and Dev::tick - what the samples of a recording
 // (csf_record) are numbered from - is 0 in the table: a recording member's count is a word of its own in device memory
 // (Dev::rec_tick) that the launch reads and moves on itself.  The host knows what the word holds (csf_engine::rec_tick_dev) and
@@ -470,17 +471,18 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
     if (!b.small.empty()) {
         // table slots: the one-wave members by vehicle class, in join order within a class - one launch per class
         b.slot_member.clear();
-        int cls_beg[8] = {0}, cls_nv[7] = {0};
-        for (int m = 0; m < 7; m++) {
+        // (... and behind them the members of several sets or classes, csf_small_classes: ONE further launch whatever their classes)
+        int cls_beg[9] = {0}, cls_nv[8] = {0};
+        for (int m = 0; m < 8; m++) {
             cls_beg[m] = (int)b.slot_member.size();
             for (int32_t i : b.small) {
                 const Dev &d = engines[i]->d;
-                if (d.p.model != m) continue;
+                if ((small_takes_classes(engines[i]) ? 7 : d.p.model) != m) continue;
                 b.slot_member.push_back(i);
                 if (d.nv > 0) cls_nv[m] = std::max(cls_nv[m], (int)d.nv_pad);
             }
         }
-        cls_beg[7] = (int)b.slot_member.size();
+        cls_beg[8] = (int)b.slot_member.size();
         if ((rc = batch_table(b, e0->main))) return rc;
         for (int32_t i : b.small) {                               // a recording member's tick word, where it is not current
             csf_engine *e = engines[i];
@@ -493,10 +495,11 @@ static int step_batch_impl(csf_engine *const *engines, int32_t count, int64_t n_
         for (int64_t t = 0; t < n_ticks;) {
             const int k = small_launch_ticks(n_ticks - t);
             const bool pack = want_snap && t + k == n_ticks;
-            for (int m = 0; m < 7; m++) {
+            for (int m = 0; m < 8; m++) {
                 const int cnt = cls_beg[m + 1] - cls_beg[m];
                 if (cnt == 0) continue;
-                launch_small_batch(m, b.table.p + cls_beg[m], cnt, cls_nv[m], k, pack, e0->main);
+                if (m == 7) launch_small_classes_batch(b.table.p + cls_beg[m], cnt, cls_nv[m], k, pack, e0->main);
+                else launch_small_batch(m, b.table.p + cls_beg[m], cnt, cls_nv[m], k, pack, e0->main);
                 b.launches++;
                 HIPCHK(e0, hipGetLastError());
             }

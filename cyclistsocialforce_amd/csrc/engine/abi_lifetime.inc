@@ -44,6 +44,7 @@ csf_engine *csf_create(const csf_params *params, int64_t n_capacity, int32_t dev
     // every SoA array - fresh slots are handed out up to n_pad (csf_add_agents)
     e->cap = (e->cap + 63) / 64 * 64;
     e->knobs.read();
+    e->small_classes = e->knobs.small_classes != 0;
     e->time_pop = getenv("CSF_TIME_POP") != nullptr;
     e->d.p = *params;
     derive_consts(e);

@@ -141,6 +141,14 @@ int csf_small_ticks(const csf_engine *e, int64_t *n_ticks) try {
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 
+// (refused like csf_step while a calibration data set is held; a refused call changes nothing)
+int csf_small_classes(csf_engine *e, int32_t on) try {
+    if (!e || (on != 0 && on != 1)) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_small_classes")) return crc;
+    e->small_classes = on == 1;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
 int csf_mid_ticks(const csf_engine *e, int64_t *n_ticks) try {
     if (!e || !n_ticks) return CSF_E_ARG;
     *n_ticks = e->mid_ticks;

@@ -605,7 +605,8 @@ static int loopback_exchange(csf_engine *const *g, int world) {
     return CSF_OK;
 }
 
-// A handful of road users of one class (not the UncontrolledVehicle's) on one device, nothing sampled per tick and no history ring but
+// A handful of road users of one class (not the UncontrolledVehicle's; with csf_small_classes on: of any sets and classes) on one
+// device, nothing sampled per tick and no history ring but
 // csf_record's (the engine's rec_fast; the ring of csf_enable_history keeps the general path): the whole tick in one
 // wave, all ticks of the call in one launch (csf_agent.hip: small_tick_kernel).  A pinned pair-kernel variant (the test suite's
 // CSF_PAIR_VARIANT) keeps the general path.
@@ -616,14 +617,20 @@ static bool small_road_ok(const Dev &d) {   // no road, or a small one: staged i
     return d.rg_nx == 0 && d.nv_pad <= SMALL_ROAD_MAX && d.nv_pad * P <= 256 * WAVE;
 }
 
+// A population of several parameter sets (any classes), or of the UncontrolledVehicle's class: small_tick_kernel does not take it.
+static bool small_is_classes(const csf_engine *e) { return e->classes.size() > 1 || e->d.p.model == CSF_UNCONTROLLED; }
+
 static bool small_fused_ok(const csf_engine *e) {
     const Dev &d = e->d;
-    const int m = d.p.model;
     return e->knobs.fused_small != 0 && e->knobs.pair_variant < 0 && d.n >= 1 && d.n <= SMALL_MAX && d.n_live == d.n &&
-           e->classes.size() == 1 && m != CSF_UNCONTROLLED && small_road_ok(d) &&
+           (!small_is_classes(e) || e->small_classes) && small_road_ok(d) &&
            e->world == 1 && !e->nccl && !e->loopback && e->knobs.fake_world <= 1 && (d.hist == nullptr || e->rec_fast) && e->profile <= 0 &&
            d.atrace == nullptr && d.lo == 0 && d.hi == d.n && e->pend.empty() && !e->dirty;
 }
+
+// ... and which of the two kernels a population that small_fused_ok admits takes: small_classes_kernel (csf_small_classes.hip; DESIGN.md
+// 4.6e) with the switch of csf_small_classes on; a single set of a rider class keeps small_tick_kernel, switch or no switch.
+static bool small_takes_classes(const csf_engine *e) { return e->small_classes && small_is_classes(e); }
 
 // the bytes of the packed read-back (csf_get_tick: state rows, Fx, Fy, destination pointers, one-hot navigation state)
 static size_t snap_need(const csf_engine *e) {
@@ -684,7 +691,8 @@ static int step_impl(csf_engine *e, int64_t n_ticks, bool want_snap, bool *snapp
             const int k = small_launch_ticks(n_ticks - t);
             Dev dd = e->d;
             dd.snap = (snap && t + k == n_ticks) ? (double *)e->snap.dev : nullptr;
-            launch_small_tick(dd, k, e->main);
+            if (small_takes_classes(e)) launch_small_classes(dd, k, e->main);
+            else launch_small_tick(dd, k, e->main);
             HIPCHK(e, hipGetLastError());
             small_ticked(e, k, false);
             t += k;

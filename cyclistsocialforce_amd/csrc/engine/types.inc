@@ -198,6 +198,7 @@ struct Knobs {
     int debug_throw = 0;                      // CSF_DEBUG_THROW: csf_sync throws (1 std::bad_alloc, 2 std::runtime_error) - the test of the boundary (consts.inc: csf_caught)
     int chase_gate_pct = 85;                  // CSF_CHASE_GATE: per cent of the pair workgroups through before the per-agent kernel is let go
     int fused_small = 1;                      // CSF_FUSED_SMALL=0: a handful of road users take the general path too (csf_agent.hip: small_tick_kernel)
+    int small_classes = 0;                    // CSF_SMALL_CLASSES=1: csf_small_classes is on from csf_create (csf_small_classes.hip; DESIGN.md 4.6e)
     int segments = -1;                        // CSF_SEGMENTS
     int handout_index = 0;                    // CSF_HANDOUT=index: the pair kernel's workgroups hand their receivers out in index order (0, default: heaviest first, csf_handout.h)
     int seg_grid = 1;                         // CSF_SEG_GRID=0: one launch per parameter set (class-segmented order) instead of one grid
@@ -242,6 +243,7 @@ struct Knobs {
         if (const char *v = getenv("CSF_CHASE_CLOCK")) chase_clock = v;
         chase_gate_pct = std::max(0, std::min(100, geti("CSF_CHASE_GATE", 85)));
         fused_small = geti("CSF_FUSED_SMALL", 1);
+        small_classes = geti("CSF_SMALL_CLASSES", 0) == 1 ? 1 : 0;
         fused_mid = geti("CSF_FUSED_MID", 1);
         mid_below = geti("CSF_MID_BELOW", 0);
         batch_mid = geti("CSF_BATCH_MID", 1);
@@ -501,6 +503,7 @@ struct csf_engine {
     HostBuf<double, false> bound_pin;   // where the positions land when that bound is measured again (set_fov_band)
     int64_t moves = 0;
     int64_t small_ticks = 0;         // ticks run by the one-wave kernel (csf_small_ticks)
+    bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     int64_t slab_rewrites = 0;       // compact_slab calls (upload_queues sizes the slab by them)
     bool bound_stale = false;        // positions moved without a speed clamp (csf_replay_forces with fix_speed): measure them
     uint32_t edge_stamp = 0;

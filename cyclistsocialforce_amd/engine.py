@@ -881,6 +881,11 @@ class Engine:
         self._ck(self._lib.csf_small_ticks(self._h, C.byref(n)))
         return n.value
 
+    def small_classes(self, on=True):
+        """several parameter sets, several vehicle classes or an UncontrolledVehicle population of up to 32 road users take the one-wave
+        tick and the batched launch too (csf.h: csf_small_classes; off by default, or what CSF_SMALL_CLASSES said at creation)"""
+        self._ck(self._lib.csf_small_classes(self._h, 1 if on else 0))
+
     def mid_ticks(self):
         """ticks run as one launch each (csf_mid.hip: mid-size populations)"""
         v = C.c_int64()

@@ -168,6 +168,7 @@ class SocialForceIntersection:
         self._capacity = capacity
         self._track_params = track_params
         self._engine = None
+        self._small_classes = None   # set_small_classes: what the engine is told once it exists (None: the engine's own default)
         self._S = None            # host mirror [capacity, n_states]; vehicle.s are row views
         self._shadow = None       # device's view of the mirror after the last pull / push, kept once a vehicle.s has been handed out
         self._s_watched = False   # some vehicle.s has been handed out: the mirror is compared with the shadow before every tick
@@ -439,6 +440,8 @@ class SocialForceIntersection:
         if self._engine is None:
             cap = self._capacity or max(256, 4 * len(self.vehicles))
             self._engine = Engine(v0._pod(PRIORITY_RULES[self.priority_rule]), cap, device=self._device)
+            if self._small_classes is not None:
+                self._engine.small_classes(self._small_classes)
             self._capacity = cap
             ns = max(type(v).N_STATES for v in self.vehicles)
             self._S = np.zeros((cap, ns))
@@ -974,6 +977,14 @@ class SocialForceIntersection:
         if self._S.shape[1] != e.ns:
             return None
         return e, self._live()
+
+    def set_small_classes(self, on=True):
+        """Engine.small_classes for this intersection's engine, now or when it is made: up to 32 road users with their own `params=`, of
+        several vehicle classes or with UncontrolledVehicles among them take the one-wave tick - through step, step_n, step_together
+        and advance_together (off by default)"""
+        self._small_classes = bool(on)
+        if self._engine is not None:
+            self._engine.small_classes(self._small_classes)
 
     def set_animated(self, animated):
         """intersection.py:899-915: switch every drawing between blitted (animated) and ordinary artists."""

@@ -304,7 +304,9 @@ int csf_step_group(csf_engine *const *engines, int32_t world, int64_t n_ticks);
  * not sharded, not in a loopback group and not in another batch; otherwise the call is refused and nothing changes.  The
  * members then share one HIP stream (each member's own stream is waited for first).  csf_step_batch steps every member by
  * n_ticks: the members the one-wave tick takes (see csf_small_ticks) run in ONE launch per vehicle class present - one wave
- * per scene, all ticks of the call -; the members the one-launch tick takes (see csf_mid_ticks: 33 ... 2 175 road users of one
+ * per scene, all ticks of the call - and, with csf_small_classes on, those of several parameter sets or classes in ONE further launch
+ * whatever their classes (a small member of several sets or of the UncontrolledVehicle's class is stepped in turn otherwise);
+ * the members the one-launch tick takes (see csf_mid_ticks: 33 ... 2 175 road users of one
  * parameter set), where the batch has at least two of them, run tick by tick in ONE launch per vehicle class and priority rule
  * present; every other member is stepped by csf_step in turn - among them a mid-size member with road edges (its road term is
  * a launch of its own per tick), with several parameter sets, a BalancingRider or UncontrolledVehicle population above 32 road
@@ -403,6 +405,18 @@ int csf_profile_gather(const csf_engine *e, double *gather_ms);
  * the two positions, inside the band of fp32 rounding by the reference's own fp64 chain, intersection.py:690-745,
  * vehicle.py:1617-1625), instead of a pair launch and a per-agent launch per tick.  CSF_FUSED_SMALL=0 or a pinned CSF_PAIR_VARIANT keep the general path. */
 int csf_small_ticks(const csf_engine *e, int64_t *n_ticks);
+/* The one-wave tick and the batched launch for populations of SEVERAL PARAMETER SETS AND VEHICLE CLASSES (no change
+ * of CSF_ABI_VERSION or csf_params: bind it where the library exports it).  on = 1: a population that meets every other condition of
+ * csf_small_ticks and has more than one parameter set (csf_set_param_classes: any sets of any classes, up to one per road user) or is of
+ * class CSF_UNCONTROLLED is ticked by small_classes_kernel - one wave, all ticks of csf_step in one launch, the constants of the field
+ * staged per road user and one pass of the per-agent tick per vehicle class present - instead of a pair launch and one per-agent launch
+ * per class and tick; inside a batch, csf_step_batch steps all such members in ONE further launch whatever their classes.  csf_small_ticks
+ * and csf_batch_ticks count these ticks; csf_record and csf_step_get_tick work as on the one-wave path.  A single set of a rider class
+ * keeps its kernel bit for bit, switch or no switch.  on = 0 (the default; CSF_SMALL_CLASSES=1 in the environment of csf_create turns it
+ * on from the start): every call takes the kernels it took before there was a switch.  The results agree with the general path's within
+ * the rounding of the pair sum (2e-5 m over 40 ticks), not bit for bit.  CSF_E_ARG for e == NULL or on outside 0 / 1; refused like
+ * csf_step while a calibration data set is held; a refused call changes nothing. */
+int csf_small_classes(csf_engine *e, int32_t on);
 /* Ticks this engine has run as ONE launch each (ABI 7; csf_mid.hip).  Between 33 and ~3 000 road users of one parameter set on
  * one device - BASELINE config 2, and what the reference runs under SUMO - a tick is launch latency, not work: the pair sums
  * of a receiver group (intersection.py:690-745, 814-843) and the per-agent tick of its road users (:841-862, 891-892) share
