@@ -6,7 +6,8 @@
 // (intersection.py:226-242) for the static-obstacle term.
 //
 // Mapping (CDNA4, 64-wide waves): SOURCES sit in the lanes, RECEIVERS are wave-uniform.  A workgroup owns 8, 16 or 32
-// receivers and streams the fp32 source records (x, y, cos psi, sin psi) of one chunk through an LDS tile that its four
+// receivers and streams the fp32 source records (x, y, cos psi, sin psi) of one chunk through an LDS tile (one 16-byte record per
+// source where the loops are plain f32, four arrays where they are packed: see `tile` below) that its four
 // or - the headline - eight waves share (1024 or 2048 sources; eight waves per SIMD are resident); the waves take the
 // receivers one at a time (an LDS counter), each lane accumulates its sources'
 // contribution, and gfx950 lane exchanges (v_permlane32/16_swap, DPP adds) form the column sum of a receiver, which is
@@ -129,10 +130,18 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     constexpr int RPP = WAVE / NBT;               // receivers one classification pass of a wave covers: 4 or 2
     constexpr unsigned NBMASK = NBT >= 32 ? 0xFFFFFFFFu : ((1u << (NBT & 31)) - 1u);
     static_assert(!REACH || (CLASSIFY && DYN), "the reach test is built into the classified, dynamically handed-out variant");
-    __shared__ float tx[TL], ty[TL], tc[TL], ts[TL];              // SoA: the two records of a lane load straight
-    __shared__ float4 tbnd[NBT];                                   // into the halves of a packed register pair
+    // The tile, 16 TL bytes, in one of two layouts over the same storage:
+    //   packed form (no reach test): SoA, tx | ty | tc | ts - the two records of a lane load straight into the halves of a packed
+    //     register pair, four ds_read_b32 per record;
+    //   PLAIN: AoS, one float4 record per source - the plain instructions take single registers, so nothing is gained by the split,
+    //     and one ds_read_b128 per record moves the same bytes in half the LDS cycles and a quarter of the LDS instructions
+    //     (a lane's record of batch b lies at byte (b << 10) | (lane << 4): 64 consecutive quads, conflict-free).
+    __shared__ float4 tile[TL];
+    float *const tx = (float *)tile, *const ty = tx + TL, *const tc = ty + TL, *const ts = tc + TL;
+    constexpr int OSH = PLAIN ? 4 : 2;                             // log2 of the bytes between two sources of a tile array
+    __shared__ float4 tbnd[NBT];
     __shared__ unsigned short queue[CW][QCAP];  // one queue per wave, drained after each receiver; holds BYTE offsets
-                                                 // into the tile arrays (4 x index <= 4092)
+                                                 // into the tile: 4 x index <= 8 188 (SoA), 16 x index <= 32 752 (AoS)
     __shared__ float4 rrec[RPB];
     __shared__ int ragent[RPB];              // slot of every receiver of the workgroup (-1: none)
     __shared__ unsigned bmask[DYN ? RPB : 1];   // DYN: candidate (| inside << 16, 16 batches) batch masks of every receiver
@@ -225,15 +234,20 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         const bool v0 = lane < n, v1 = lane + WAVE < n;
         if (!FULL) i0 = v0 ? i0 : 0, i1 = v1 ? i1 : 0;
         unsigned long long n0, n1;
-        field_twod_x2<FULL, true, PLAIN>(k, ru, lds_pair_b(tx, i0, i1), lds_pair_b(ty, i0, i1), lds_pair_b(tc, i0, i1),
-                                         lds_pair_b(ts, i0, i1), v0, v1, ax[u], ay[u], &n0, &n1);
+        if (PLAIN) {       // one gathered 16-byte read per source
+            const v4f q0 = lds_rec_b(tile, i0), q1 = lds_rec_b(tile, i1);
+            field_twod_x2<FULL, true, true>(k, ru, v2f{q0.x, q1.x}, v2f{q0.y, q1.y}, v2f{q0.z, q1.z}, v2f{q0.w, q1.w}, v0, v1, ax[u], ay[u], &n0, &n1);
+        } else {
+            field_twod_x2<FULL, true, false>(k, ru, lds_pair_b(tx, i0, i1), lds_pair_b(ty, i0, i1), lds_pair_b(tc, i0, i1),
+                                             lds_pair_b(ts, i0, i1), v0, v1, ax[u], ay[u], &n0, &n1);
+        }
         if (__builtin_expect((n0 | n1) != 0ull, 0)) {   // rare: a pair among the 128 to be corrected (the queue still holds their offsets)
             // (read again through an address formed here: taken from above, address and entries would stay in registers across the field)
             int ln = lane;
             asm volatile("" : "+v"(ln));
             const unsigned qb = qx + 2u * (unsigned)ln;
-            near_note(((n0 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb) >> 2);
-            near_note(((n1 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb + 2u * WAVE) >> 2);
+            near_note(((n0 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb) >> OSH);
+            near_note(((n1 >> lane) & 1ull) != 0ull, (int)*(volatile unsigned short *)&qentry(qb + 2u * WAVE) >> OSH);
         }
         if (FULL) qx ^= 2u * CHUNK;       // (a partial pass ends the visit, which puts the head back)
         qlen = __builtin_amdgcn_readfirstlane(qlen - n);
@@ -245,8 +259,14 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     auto pop_tail = [&](int u) {
         const bool v = lane < qlen;
         const int o = v ? (int)qentry(qhead_lane()) : 0;
-        const float4 q = make_float4(*(const float *)((const char *)tx + o), *(const float *)((const char *)ty + o),
-                                     *(const float *)((const char *)tc + o), *(const float *)((const char *)ts + o));
+        float4 q;
+        if (PLAIN) {
+            const v4f qq = lds_rec_b(tile, o);
+            q = make_float4(qq.x, qq.y, qq.z, qq.w);
+        } else {
+            q = make_float4(*(const float *)((const char *)tx + o), *(const float *)((const char *)ty + o),
+                            *(const float *)((const char *)tc + o), *(const float *)((const char *)ts + o));
+        }
         const float dx = ru.x - q.x, dy = ru.y - q.y, r2 = dx * dx + dy * dy;
         float F, gx, gy;
         field_twod<false>(k, ru, q, dx, dy, fmaxf(r2, 1e-30f), F, gx, gy);
@@ -255,7 +275,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             const float inv1 = fast_rsq(fmaxf(r2, 1e-30f));
             const unsigned long long nm = (ballot1(r2 < k.rnear2) | ballot1(__builtin_fabsf((dy * q.z - dx * q.w) * inv1) <= k.fovT0 + k.fovT1)) &
                                           (qlen >= WAVE ? ~0ull : ((1ull << qlen) - 1ull));
-            if (__builtin_expect(nm != 0ull, 0)) near_note(((nm >> lane) & 1ull) != 0ull, o >> 2);
+            if (__builtin_expect(nm != 0ull, 0)) near_note(((nm >> lane) & 1ull) != 0ull, o >> OSH);
         }
         F = v ? F : 0.0f;
         ax[u] += F * gx;
@@ -282,10 +302,14 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 q = d.rec[a];
                 q.x += o.x, q.y += o.y;
             }
-            tx[t] = q.x;
-            ty[t] = q.y;
-            tc[t] = q.z;
-            ts[t] = q.w;
+            if (PLAIN) {
+                lds_rec_store(tile, t, q);            // (one 16-byte store)
+            } else {
+                tx[t] = q.x;
+                ty[t] = q.y;
+                tc[t] = q.z;
+                ts[t] = q.w;
+            }
         }
         if (CLASSIFY && tid < (cnt >> 6)) {
             float4 bb = d.bnd[(base >> 6) + tid];             // (scene coordinates)
@@ -487,8 +511,15 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             F = seen ? F : 0.0f;
             float fx = F * hx, fy = F * hy;
             {   // ... minus what the fast path added for it (every noted pair was kept and evaluated there)
-                const float sx = rr.x - tx[idx], sy = rr.y - ty[idx];
-                field_twod<false>(k, rr, make_float4(0.f, 0.f, tc[idx], ts[idx]), sx, sy, fmaxf(sx * sx + sy * sy, 1e-30f), F, hx, hy);
+                float4 qt;
+                if (PLAIN) {
+                    const v4f qq = lds_rec_b(tile, idx << 4);
+                    qt = make_float4(qq.x, qq.y, qq.z, qq.w);
+                } else {
+                    qt = make_float4(tx[idx], ty[idx], tc[idx], ts[idx]);
+                }
+                const float sx = rr.x - qt.x, sy = rr.y - qt.y;
+                field_twod<false>(k, rr, make_float4(0.f, 0.f, qt.z, qt.w), sx, sy, fmaxf(sx * sx + sy * sy, 1e-30f), F, hx, hy);
                 F = act ? F : 0.0f;
                 fx -= F * hx;
                 fy -= F * hy;
@@ -582,13 +613,26 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 // both are wholly inside); what it keeps is appended to the queue, first batch first.
                 // (A single loop over both kinds of batch pairs with the records of the next pair requested ahead of the
                 // queue append was tried: the compiler spilled 30 registers into the loops and the kernel ran at 180 us.)
-                // test of the two batches whose records are in (sx, sy, sc, ss), append of what it keeps
-                // (t1, t2: byte offsets of this lane's records of the two batches in the tile arrays - what the records were read
+                // test of the two batches whose records are in `rec` - PLAIN: two 16-byte records, else the four packed pairs
+                // (x, y, cos, sin) -, append of what it keeps
+                // (t1, t2: byte offsets of this lane's records of the two batches in the tile - what the records were read
                 // through and what is queued)
-                auto sift2 = [&](int t1, int t2, bool two, auto fov, v2f sx, v2f sy, v2f sc, v2f ss) {
+                // (KEEP THIS SHAPE: with the test moved out of this lambda and its results passed in, the compiler and-ed `any_lane`
+                // into the lanes' mask again - the append issued for empty masks, + 2.8 % vector and + 18 % scalar instructions per
+                // launch, and the kernel was 1.2 % slower than the parent: profiles/pair_tile_aos_ab.txt, session 1)
+                auto sift2 = [&](int t1, int t2, bool two, auto fov, auto rec) {
                     constexpr bool FOV = decltype(fov)::value;
                     bool k0, k1, mg0, mg1;
-                    keep_x2<FOV, P2R, PLAIN>(k, ru, sx, sy, sc, ss, k0, k1, mg0, mg1);
+                    if constexpr (PLAIN) {
+                        // (a last pass of ONE batch - two == false, about one visit in two - still tests the first batch twice: the second
+                        // half behind a scalar branch, two-batch and one-batch form side by side, measured 1.2 % SLOWER than the parent
+                        // where this form is 2.1 % faster, profiles/pair_tile_aos_ab.txt - the kept flag then reaches the append through a
+                        // vector register)
+                        const v4f ra = rec[0], rb = rec[1];
+                        keep_x2<FOV, P2R, true>(k, ru, v2f{ra.x, rb.x}, v2f{ra.y, rb.y}, v2f{ra.z, rb.z}, v2f{ra.w, rb.w}, k0, k1, mg0, mg1);
+                    } else {
+                        keep_x2<FOV, P2R, false>(k, ru, rec[0], rec[1], rec[2], rec[3], k0, k1, mg0, mg1);
+                    }
                     // (wave masks straight from the compares: a ballot of `k1 & two` would go through a vector register)
                     const unsigned long long m0 = ballot1(k0), m1 = ballot1(k1) & (0ull - (unsigned long long)two);
                     k1 = k1 & two;
@@ -612,16 +656,24 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                     }
                     qlen = __builtin_amdgcn_readfirstlane(q1 + __builtin_popcountll(m1));
                     if (FOV && __builtin_expect((g0 | g1) != 0ull, 0)) {     // ... noted: decided exactly where the noted pairs are corrected (near_drain)
-                        near_note(((g0 >> lane) & 1ull) != 0ull, t1 >> 2);
-                        near_note(((g1 >> lane) & 1ull) != 0ull, t2 >> 2);
+                        near_note(((g0 >> lane) & 1ull) != 0ull, t1 >> OSH);
+                        near_note(((g1 >> lane) & 1ull) != 0ull, t2 >> OSH);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     while (qlen >= CHUNK) pop(u, std::true_type{});
                 };
                 auto load2 = [&](int b1, int b2, bool two, auto fov) {
-                    const int t1 = (b1 << 8) | (lane << 2), t2 = (b2 << 8) | (lane << 2);   // one address per batch: read through, then queued
-                    sift2(t1, t2, two, fov, lds_pair_b(tx, t1, t2), lds_pair_b(ty, t1, t2), lds_pair_b(tc, t1, t2), lds_pair_b(ts, t1, t2));
+                    // one address per batch: read through, then queued
+                    if constexpr (PLAIN) {   // one 16-byte read per batch
+                        const int t1 = (b1 << 10) | (lane << 4), t2 = (b2 << 10) | (lane << 4);
+                        const v4f rec[2] = {lds_rec_b(tile, t1), lds_rec_b(tile, t2)};
+                        sift2(t1, t2, two, fov, rec);
+                    } else {
+                        const int t1 = (b1 << 8) | (lane << 2), t2 = (b2 << 8) | (lane << 2);
+                        const v2f rec[4] = {lds_pair_b(tx, t1, t2), lds_pair_b(ty, t1, t2), lds_pair_b(tc, t1, t2), lds_pair_b(ts, t1, t2)};
+                        sift2(t1, t2, two, fov, rec);
+                    }
                 };
                 unsigned ins = inside;
                 while (__builtin_popcount(ins) >= 2) {

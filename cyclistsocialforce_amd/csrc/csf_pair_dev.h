@@ -141,6 +141,17 @@ __device__ __forceinline__ v2f lds_pair_b(const float *a, int o0, int o1) {
     return v2f{*(lds_vfp)((const char *)a + o0), *(lds_vfp)((const char *)a + o1)};
 }
 
+// One record (x, y, cos psi, sin psi) of an AoS tile at BYTE offset o: one ds_read_b128 (the tile is 16-byte aligned, and so is o)
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) v4f *lds_v4fp;
+__device__ __forceinline__ v4f lds_rec_b(const float4 *tile, int o) {
+    return *(lds_v4fp)((const char *)tile + o);
+}
+
+__device__ __forceinline__ void lds_rec_store(float4 *tile, int i, const float4 q) {
+    *(__attribute__((address_space(3))) v4f *)(tile + i) = v4f{q.x, q.y, q.z, q.w};
+}
+
 // Classification of one batch of 64 binned source records (bounding circle bb = centre, radius) against one receiver rl
 // = (x, y, cos psi, sin psi).  out: no source of the batch can be tracked (or all are beyond the far-field radius);
 // in: every source is tracked and none is far.  Both keep a 1e-4 margin and need the receiver outside the circle, so
