@@ -42,6 +42,7 @@ SYMBOLS = (
     "csf_scene_calib_groups", "csf_scene_calib_eval_groups",
     "csf_scene_calib_lane_groups",
     "csf_scene_calib_classes",
+    "csf_scene_calib_lane_classes",
     "csf_small_classes",
     "csf_handout_ranks",
 )
@@ -217,6 +218,8 @@ def load():
         L.csf_scene_calib_lane_groups.argtypes = [vp, vp, i32]
     if hasattr(L, "csf_scene_calib_classes"):       # (the same)
         L.csf_scene_calib_classes.argtypes = [vp, vp, i32, vp, dp]
+    if hasattr(L, "csf_scene_calib_lane_classes"):  # (the same)
+        L.csf_scene_calib_lane_classes.argtypes = [vp, vp, i32, vp, dp]
     if hasattr(L, "csf_small_classes"):             # (the same)
         L.csf_small_classes.argtypes = [vp, i32]
     if L.csf_abi_version() != ABI_VERSION:

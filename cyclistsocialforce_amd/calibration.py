@@ -741,7 +741,9 @@ class InteractionCalibration(_Calibration):
     vehicle_type[g].MODEL); the data set is loaded by `Engine.scene_calib_load` and then `Engine.scene_calib_classes`, and everything
     else - both built-in errors, a custom error_func, `simulate`, `run`, `run_many`, `test`, replay, windows, roads and the road keys -
     works as with groups.  Mixed classes run on Engine.scene_calib_load only: a data set that needs shared lanes or a wide scene raises
-    ValueError.  With a single vehicle_type nothing changes and no new call is made.
+    ValueError - unless lane_classes=True, which loads such a data set on its lanes as above and then hands groups,
+    classes and start states to `Engine.scene_calib_lane_classes`: a lane then carries the class of the rider it holds and changes it
+    at a takeover.  With a single vehicle_type, or on a plain load, nothing changes and no new call is made.
 
     train_data, test_data: lists of SceneData; objective_features_traj: six indicators over the rows of vehicle.traj."""
 
@@ -749,11 +751,12 @@ class InteractionCalibration(_Calibration):
 
     def __init__(self, vehicle_type, params_keys, train_data, test_data, objective_features_traj, error_func=calc_sse_timesteps,
                  max_sets=256, maxiter=100, xtol=1e-4, ftol=1e-4, verbose=False, device=0, engine_factory=Engine, share_lanes=False,
-                 wide_from=33, group_params=None, lane_groups=False):
+                 wide_from=33, group_params=None, lane_groups=False, lane_classes=False):
         self.vehicle_type, self.params_keys = vehicle_type, list(params_keys)
         self._take_groups(vehicle_type, group_params)
         self._check_keys()
         self.share_lanes, self.lane_groups, self.wide_from = bool(share_lanes), bool(lane_groups), int(wide_from)
+        self.lane_classes = bool(lane_classes)
         if not 1 <= self.wide_from <= SceneData.WIDE_MAX + 1:
             raise ValueError(f"wide_from: 1 .. {SceneData.WIDE_MAX + 1}")
         self.train_data, self.test_data = list(train_data), list(test_data)
@@ -910,9 +913,9 @@ class InteractionCalibration(_Calibration):
         wide = any(d.wide for d in data)
         shared = wide or self.share_lanes or any(d.n > 32 for d in data)
         needs = "this data set needs shared lanes" + (" and a wide scene" if wide else "") + " (a roster above 32, share_lanes or wide=True)"
-        if self._types is not None and shared:
+        if self._types is not None and shared and not self.lane_classes:
             raise ValueError("mixed classes run on Engine.scene_calib_load only, and " + needs)
-        if self._G > 1 and shared and not self.lane_groups:
+        if self._types is None and self._G > 1 and shared and not self.lane_groups:
             raise ValueError("group_params: rider groups run on Engine.scene_calib_load only, and " + needs + "; or pass lane_groups=True")
         pod0 = self._pods({})[0] if self._G > 1 else self._pod({})
         image = (img.s0, img.vd, img.off, img.rows, img.obj, img.feat)
@@ -923,7 +926,9 @@ class InteractionCalibration(_Calibration):
             load = engine.scene_calib_load_wide if wide else engine.scene_calib_load_shared
             load(img.nr, nl, np.concatenate([p[0] for p in packed]), img.enter, img.exit, *image, lengths=img.lens, max_sets=self.max_sets,
                  **(dict(wide_from=self.wide_from) if wide else {}))
-            if self._G > 1:                                      # (lane_groups=True: the group goes with the rider a lane carries)
+            if self._types is not None:                          # (lane_classes=True: the class goes with the rider a lane carries)
+                engine.scene_calib_lane_classes(img.group, [t.MODEL for t in self._types], img.s0)
+            elif self._G > 1:                                    # (lane_groups=True: the group goes with the rider a lane carries)
                 engine.scene_calib_lane_groups(img.group, self._G)
         else:
             engine = self._factory(pod0, self.max_sets * img.R, device=self.device)

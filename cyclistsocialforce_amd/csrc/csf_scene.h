@@ -84,7 +84,7 @@ struct SceneDev {
     // DESIGN.md 4.10h), by scene_lanes_groups_kernel / scene_wide_groups_kernel - only: the group of every rider, and the sets are
     // [n_sets][n_groups] records.  NULL: no groups - every rider carries record `set` of [n_sets], and the launch is today's.
     const uint8_t *group;        // [R] 0 .. n_groups - 1
-    int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group` (scene_mixed_kernel: 2 .. SCENE_CLASS_GROUPS_MAX), else 0
+    int32_t n_groups;            // 2 .. SCENE_GROUPS_MAX with `group` (the kernels of csf_scene_mixed.hip: 2 .. SCENE_CLASS_GROUPS_MAX), else 0
 };
 
 // Wide scenes (csf_scene_calib_load_wide): a data set on shared lanes whose scenes with n_lanes >= wide_from run on
@@ -105,8 +105,9 @@ struct SceneWideDev {
 // `table` holds the narrow scenes and up to two kernels are launched on `st`, the narrow scenes first.  Returns the kernels launched.
 int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w = nullptr);
 
-// One evaluation with vehicle classes loaded (csf_scene_calib_classes): scene_mixed_kernel on a csf_scene_calib_load data set, `ns` the
-// widest state of the loaded classes.  Returns the kernels launched (1).
-int launch_scene_mixed(const Dev *table, const SceneSet *sets, const SceneDev &c, int ns, hipStream_t st);
+// One evaluation with vehicle classes loaded: scene_mixed_kernel on a csf_scene_calib_load data set (csf_scene_calib_classes), `ns` the
+// widest state of the loaded classes; scene_lanes_mixed_kernel on shared lanes (csf_scene_calib_lane_classes: c.lane_off is set) and, with
+// `w` (a wide load), the narrow scenes on it and then the wide ones on scene_wide_mixed_kernel.  Returns the kernels launched (0 .. 2).
+int launch_scene_mixed(const Dev *table, const SceneSet *sets, const SceneDev &c, int ns, hipStream_t st, const SceneWideDev *w = nullptr);
 
 }  // namespace csf

@@ -59,8 +59,14 @@
 // scene_rider_step branches on the rider's class at run time.  The image the restore reads was rewritten per rider and class by the host
 // (abi_scene.inc), and the views' state width is the call's widest class.  A data set without classes launches what it launched before.
 //
+// Vehicle classes on shared lanes and on wide scenes (csf_scene_calib_lane_classes): scene_lanes_mixed_kernel and
+// scene_wide_mixed_kernel in csf_scene_mixed.hip - scene_lanes_groups_kernel / scene_wide_groups_kernel with the class a property of the
+// group, so of the rider a lane carries: SceneLaneHook<SMALL_MIXED, true>::seat also makes the lane's class the newcomer's, the tick stages
+// the Bicycle cell and picks agent_body<M> by it (csf_small_body.inc, csf_wide_body.inc: SMALL_MIXED), and the replay write-back is that of
+// the rider's class.  SceneLaneHook stands in csf_scene_hook.inc for that; no kernel of this file changed.
+//
 // What exists once ("Folded"): scene_rider_step - the replay write-back or the error terms behind a tick, called by both
-// hooks -, and for_vehicle_class, which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
+// hooks (csf_scene_hook.inc) -, and for_vehicle_class, which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
 // slot becomes a fresh vehicle from the image - serves scene_groups_kernel and SceneLaneHook::seat; scene_eval_kernel has the same lines
 // written out.  The per-set prologue is written out in all four kernels, and scene_groups_kernel / scene_wide_kernel repeat the skeleton
 // of scene_eval_kernel / scene_lanes_kernel: with one function for either, sums and states were no longer the parent's bit for bit.
@@ -214,103 +220,6 @@ __global__ __launch_bounds__(64) void scene_groups_kernel(const Dev *__restrict_
     if (hook.smp != nullptr)
         while (hook.taken < c.n_samples) hook.sample(d, lane);
 }
-
-// what SceneLaneHook holds of the rider groups beside SceneGroupPart: the staged table of the lanes' groups once more, to write to - a
-// lane's group changes with its rider
-template <bool GRP>
-struct SceneLaneGroupPart : SceneGroupPart<GRP> {};
-template <>
-struct SceneLaneGroupPart<true> : SceneGroupPart<true> {
-    uint8_t *w_grp = nullptr;     // l_grp, writable: a lane stores to its own cell only
-};
-
-// behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment.  GRP (csf_scene_calib_lane_groups;
-// DESIGN.md 4.10h): the riders are in groups, and the lane's group is its rider's - `grp` and the lane's cell of the staged table are
-// renewed by seat.  A lane nobody rides yet has group 0 and is never present.
-template <int MODEL, bool GRP = false>
-struct SceneLaneHook : SceneLaneGroupPart<GRP> {
-    static constexpr bool MASKED = true;
-    static constexpr bool SHARED = true;
-    static constexpr bool GROUPS = GRP;
-    const SceneDev &c;
-    const int64_t row0;           // set * R: first row of the set in sums and in a sample
-    int cur = -1;                 // the rider this lane carries (0 .. R - 1), -1: nobody yet
-    int nxt = -1;                 // who takes over next, -1: nobody
-    int nxt_in = 0x7fffffff;      // ... and the tick it enters at
-    int t_in = 0, t_out = 0;      // the window of cur (nobody: never present)
-    const double *obj = nullptr;  // objective of cur at tick 0
-    const double *rep = nullptr;  // recorded (x, y, psi, v) of cur after tick 0; NULL: it is simulated
-    int wait;                     // ticks until the next sampled one
-    int taken = 0;                // sampled ticks so far
-    double sse = 0.0, sae = 0.0;
-    __device__ __forceinline__ SceneLaneHook(const SceneDev &c_, int64_t row0_) : c(c_), row0(row0_), wait(c_.stride - 1) {}
-    __device__ __forceinline__ void follower(int r) {
-        nxt = r;
-        nxt_in = r >= 0 ? c.win_enter[r] : 0x7fffffff;
-    }
-    // the lane's slot becomes rider r's fresh vehicle - what scene_eval_kernel restores at its head, and what was constant per slot
-    // there - and the lane's registers become r's
-    __device__ __forceinline__ void seat(const Dev &d, int lane, int r) {
-        const int64_t a = lane;
-        if constexpr (GRP) {
-            // the lane's group becomes r's (an entry the host has checked, clamped all the same: it indexes LDS), the restore takes the
-            // limits of r's own record.  The store goes to the lane's OWN cell of the staged table and to no other; the other lanes
-            // read it in the pair loop of this tick, and what orders the two is what orders the takeover's stores to the slot:
-            //   one-wave tick   the takeover stands at the head of the tick, in front of the staging stores and their fence + wave
-            //                   barrier; the pair loop of the tick before ended in front of the wave barrier at that tick's foot
-            //   wide tick       the takeover stands behind barrier 2 of the tick before - its pair loop has ended - and in front of
-            //                   barrier 1 of its own tick, behind which the pair loop reads the table
-            int g = (int)c.group[r];
-            g = g < this->n_groups ? g : this->n_groups - 1;
-            this->grp = g;
-            this->w_grp[lane] = (uint8_t)g;
-            scene_restore(d, c, a, r, this->rec[g].p.v_max_walk, this->rec[g].p.delta_max_walk);
-        } else {
-            scene_restore(d, c, a, r, d.p.v_max_walk, d.p.delta_max_walk);
-        }
-        // (what scene_eval_kernel's riders keep from the load of the data set: a slot is theirs alone there)
-        d.vdes[a] = c.img_vdes[r];
-        d.qbeg[a] = c.img_qbeg[r];
-        d.qlen[a] = c.img_qlen[r];
-        cur = r;
-        t_in = c.win_enter[r], t_out = c.win_exit[r];
-        obj = c.obj + (int64_t)r * c.n_feat;
-        const int rcol = c.rep != nullptr ? c.rep_index[r] : -1;
-        rep = rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr;
-        follower(c.rider_next[r]);
-    }
-    // the sums of the rider the lane has carried go to its row
-    __device__ __forceinline__ void flush() {
-        if (cur >= 0) c.sums[row0 + cur] = make_double2(sse, sae);
-        sse = sae = 0.0;
-    }
-    // head of tick t (csf_small_body.inc: HOOK::SHARED): no shuffle, no ballot, no barrier; stores to this lane's own slot and rows
-    __device__ __forceinline__ void takeover(const Dev &d, int t, int lane) {
-        while (nxt_in <= t) {
-            flush();
-            seat(d, lane, nxt);
-        }
-    }
-    // (wide_tick_body: the flag of this lane alone - 256 lanes have no ballot)
-    __device__ __forceinline__ bool here(int t) const { return t_in <= t && t < t_out; }
-    __device__ __forceinline__ uint64_t present(int t) const { return __ballot(t_in <= t && t < t_out); }
-    __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
-        if (lane >= n) return;
-        const bool here = t_in <= t && t < t_out;
-        if (here) scene_rider_step<MODEL>(d, c, t, lane, rep, obj, sse, sae);   // (else: the lane is empty at this tick)
-        if (c.states != nullptr) {
-            if (wait == 0) {
-                if (here) {
-                    double *smp = c.states + ((int64_t)taken * c.n_sets * c.R + row0 + cur) * d.ns;
-                    for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
-                }
-                taken++;
-                wait = c.stride;
-            }
-            wait--;
-        }
-    }
-};
 
 template <int MODEL>
 __global__ __launch_bounds__(64) void scene_lanes_kernel(const Dev *__restrict__ table, const SceneSet *__restrict__ sets, const SceneDev c) {

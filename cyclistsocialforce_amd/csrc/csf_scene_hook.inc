@@ -1,5 +1,5 @@
 // csf_scene_hook.inc - what the closed-loop calibration kernels share behind a tick of the one-wave tick: the restore of a slot from the
-// image, the rider step and SceneHook.  Included by csf_scene.hip and by csf_scene_mixed.hip inside namespace csf, behind csf_small_body.inc:
+// image, the rider step, SceneHook and SceneLaneHook.  Included by csf_scene.hip and by csf_scene_mixed.hip inside namespace csf, behind csf_small_body.inc:
 // an include and not a translation unit of its own, for the reason given at csf_small_body.inc.
 
 // slot `slot` of the block becomes the fresh vehicle of rider `rider` (row of the image): Vehicle.__init__ (vehicle.py:64-204,
@@ -135,6 +135,114 @@ struct SceneHook : std::conditional_t<MODEL == SMALL_MIXED, SceneMixedPart, Scen
         if (smp != nullptr) {
             if (wait == 0) {
                 sample(d, lane);
+                wait = c.stride;
+            }
+            wait--;
+        }
+    }
+};
+
+// what SceneLaneHook holds of the rider groups beside SceneGroupPart: the staged table of the lanes' groups once more, to write to - a
+// lane's group changes with its rider (DESIGN.md 4.10h)
+template <bool GRP>
+struct SceneLaneGroupPart : SceneGroupPart<GRP> {};
+template <>
+struct SceneLaneGroupPart<true> : SceneGroupPart<true> {
+    uint8_t *w_grp = nullptr;     // l_grp, writable: a lane stores to its own cell only
+};
+// ... and beside SceneMixedPart (csf_scene_calib_lane_classes; DESIGN.md 4.10j): the same cell, the class goes with the group
+struct SceneLaneMixedPart : SceneMixedPart {
+    uint8_t *w_grp = nullptr;
+};
+
+// behind every tick, and at its head: lane = LANE of the scene and the rider it carries at the moment.  GRP (csf_scene_calib_lane_groups;
+// DESIGN.md 4.10h): the riders are in groups, and the lane's group is its rider's - `grp` and the lane's cell of the staged table are
+// renewed by seat.  A lane nobody rides yet has group 0 and is never present.  MODEL == SMALL_MIXED (csf_scene_calib_lane_classes; DESIGN.md
+// 4.10j; always with GRP): the groups are of several vehicle classes, and `model` - what small_tick_body / wide_tick_body stage the Bicycle
+// cell by and what the replay write-back branches on - becomes the class of the newcomer's group in seat as well.
+template <int MODEL, bool GRP = false>
+struct SceneLaneHook : std::conditional_t<MODEL == SMALL_MIXED, SceneLaneMixedPart, SceneLaneGroupPart<GRP>> {
+    static constexpr bool MASKED = true;
+    static constexpr bool SHARED = true;
+    static constexpr bool GROUPS = GRP;
+    const SceneDev &c;
+    const int64_t row0;           // set * R: first row of the set in sums and in a sample
+    int cur = -1;                 // the rider this lane carries (0 .. R - 1), -1: nobody yet
+    int nxt = -1;                 // who takes over next, -1: nobody
+    int nxt_in = 0x7fffffff;      // ... and the tick it enters at
+    int t_in = 0, t_out = 0;      // the window of cur (nobody: never present)
+    const double *obj = nullptr;  // objective of cur at tick 0
+    const double *rep = nullptr;  // recorded (x, y, psi, v) of cur after tick 0; NULL: it is simulated
+    int wait;                     // ticks until the next sampled one
+    int taken = 0;                // sampled ticks so far
+    double sse = 0.0, sae = 0.0;
+    __device__ __forceinline__ SceneLaneHook(const SceneDev &c_, int64_t row0_) : c(c_), row0(row0_), wait(c_.stride - 1) {}
+    __device__ __forceinline__ void follower(int r) {
+        nxt = r;
+        nxt_in = r >= 0 ? c.win_enter[r] : 0x7fffffff;
+    }
+    // the lane's slot becomes rider r's fresh vehicle - what scene_eval_kernel restores at its head, and what was constant per slot
+    // there - and the lane's registers become r's
+    __device__ __forceinline__ void seat(const Dev &d, int lane, int r) {
+        const int64_t a = lane;
+        if constexpr (GRP) {
+            // the lane's group becomes r's (an entry the host has checked, clamped all the same: it indexes LDS), the restore takes the
+            // limits of r's own record.  The store goes to the lane's OWN cell of the staged table and to no other; the other lanes
+            // read it in the pair loop of this tick, and what orders the two is what orders the takeover's stores to the slot:
+            //   one-wave tick   the takeover stands at the head of the tick, in front of the staging stores and their fence + wave
+            //                   barrier; the pair loop of the tick before ended in front of the wave barrier at that tick's foot
+            //   wide tick       the takeover stands behind barrier 2 of the tick before - its pair loop has ended - and in front of
+            //                   barrier 1 of its own tick, behind which the pair loop reads the table
+            int g = (int)c.group[r];
+            g = g < this->n_groups ? g : this->n_groups - 1;
+            this->grp = g;
+            this->w_grp[lane] = (uint8_t)g;
+            if constexpr (MODEL == SMALL_MIXED) this->model = this->l_model[g];   // (staged before the first seat, never written again)
+            scene_restore(d, c, a, r, this->rec[g].p.v_max_walk, this->rec[g].p.delta_max_walk);
+        } else {
+            scene_restore(d, c, a, r, d.p.v_max_walk, d.p.delta_max_walk);
+        }
+        // (what scene_eval_kernel's riders keep from the load of the data set: a slot is theirs alone there)
+        d.vdes[a] = c.img_vdes[r];
+        d.qbeg[a] = c.img_qbeg[r];
+        d.qlen[a] = c.img_qlen[r];
+        cur = r;
+        t_in = c.win_enter[r], t_out = c.win_exit[r];
+        obj = c.obj + (int64_t)r * c.n_feat;
+        const int rcol = c.rep != nullptr ? c.rep_index[r] : -1;
+        rep = rcol >= 0 ? c.rep + (int64_t)rcol * 4 : nullptr;
+        follower(c.rider_next[r]);
+    }
+    // the sums of the rider the lane has carried go to its row
+    __device__ __forceinline__ void flush() {
+        if (cur >= 0) c.sums[row0 + cur] = make_double2(sse, sae);
+        sse = sae = 0.0;
+    }
+    // head of tick t (csf_small_body.inc: HOOK::SHARED): no shuffle, no ballot, no barrier; stores to this lane's own slot and rows
+    __device__ __forceinline__ void takeover(const Dev &d, int t, int lane) {
+        while (nxt_in <= t) {
+            flush();
+            seat(d, lane, nxt);
+        }
+    }
+    // (wide_tick_body: the flag of this lane alone - 256 lanes have no ballot)
+    __device__ __forceinline__ bool here(int t) const { return t_in <= t && t < t_out; }
+    __device__ __forceinline__ uint64_t present(int t) const { return __ballot(t_in <= t && t < t_out); }
+    __device__ __forceinline__ void operator()(const Dev &d, int t, int lane, int n) {
+        if (lane >= n) return;
+        const bool here = t_in <= t && t < t_out;
+        if constexpr (MODEL == SMALL_MIXED) {                                    // (the write-back of a replayed rider is that of ITS class)
+            if (here) scene_rider_step<MODEL>(d, c, t, lane, rep, obj, sse, sae, this->model == CSF_BALANCINGRIDER);
+        } else {
+            if (here) scene_rider_step<MODEL>(d, c, t, lane, rep, obj, sse, sae);   // (else: the lane is empty at this tick)
+        }
+        if (c.states != nullptr) {
+            if (wait == 0) {
+                if (here) {
+                    double *smp = c.states + ((int64_t)taken * c.n_sets * c.R + row0 + cur) * d.ns;
+                    for (int r = 0; r < d.ns; r++) smp[r] = d.s[(int64_t)r * d.cap + lane];
+                }
+                taken++;
                 wait = c.stride;
             }
             wait--;

@@ -1,5 +1,5 @@
 // csf_small_body.inc - the one-wave tick of a handful of road users (DESIGN.md 4.6): included by csf_agent.hip (small_tick_kernel,
-// small_batch_kernel), by csf_scene.hip (scene_eval_kernel), by csf_scene_mixed.hip (scene_mixed_kernel) and by csf_small_classes.hip inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
+// small_batch_kernel), by csf_scene.hip (scene_eval_kernel), by csf_scene_mixed.hip (scene_mixed_kernel, scene_lanes_mixed_kernel) and by csf_small_classes.hip inside namespace csf, behind csf_agent_dev.h and csf_field.h.  An
 // include and not a __device__ function of a translation unit of its own, as csf_mid_body.inc is (DESIGN.md 4.6d): the kernels of
 // csf_agent.hip keep the instruction stream they had when the body stood in that file.
 //

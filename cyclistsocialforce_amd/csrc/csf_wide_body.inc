@@ -1,5 +1,6 @@
 // csf_wide_body.inc - the tick of csf_small_body.inc for ONE WORKGROUP of 256 threads: 33 .. WIDE_MAX road users present at once
-// (DESIGN.md 4.10f).  Included by csf_scene.hip (scene_wide_kernel) inside namespace csf, behind csf_small_body.inc.
+// (DESIGN.md 4.10f).  Included by csf_scene.hip (scene_wide_kernel) and by csf_scene_mixed.hip (scene_wide_mixed_kernel) inside namespace
+// csf, behind csf_small_body.inc.
 //
 // Thread = (receiver, source group) as in the one-wave tick, over four waves: with P the power of two that holds the lanes - 64, 128
 // or 256, never less than a wave - and G = 256 / P, thread tid has receiver i = tid & (P - 1) and source group grp = tid / P; source j
@@ -33,10 +34,18 @@
 // for the Bicycle se entry, and the loop over the groups around agent_body.  A lane's cell of the staged group table is written by
 // hook.takeover - behind barrier 2 of the tick before, in front of barrier 1 of its own - and read in the pair loop between the two
 // barriers of the tick.  The skip ballot of the group loop is per wave; groups gate work, never a barrier.
+//
+// MODEL == SMALL_MIXED (DESIGN.md 4.10j; csf_scene_mixed.hip: scene_wide_mixed_kernel): the parts of small_tick_body of that name, all behind
+// `if constexpr (MIXED)` - `se` has a cell per lane, staged by the owners whose rider is a Bicycle (hook.own_model(), renewed by the takeover
+// at the head of the tick: the model cell, se and shere are all staged between the takeover and barrier 1); a source acts with the field of
+// ITS class (hook.src_model(j), LDS); and inside the per-wave loop over the groups a uniform switch on the group's class leads to
+// agent_body<M>.  Classes gate work, never a barrier, and the order of a receiver's sum does not depend on them.  An instance of a real class
+// is the one it was.
 template <int MODEL, class HOOK>
 __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, float4 *const srv, HOOK &hook) {
     __shared__ double sx[WIDE_MAX], sy[WIDE_MAX], spsi[WIDE_MAX], scs[WIDE_MAX], ssn[WIDE_MAX];
-    __shared__ float2 se[MODEL == CSF_BICYCLE ? WIDE_MAX : 1];   // Bicycle field: (e, 1 / sqrt(1 - e^2)) of every source
+    constexpr bool MIXED = MODEL == SMALL_MIXED;
+    __shared__ float2 se[MODEL == CSF_BICYCLE || MIXED ? WIDE_MAX : 1];   // Bicycle field: (e, 1 / sqrt(1 - e^2)) of every source
     __shared__ int shere[WIDE_MAX];                              // lane j holds a road user at this tick (a 64-bit ballot cannot hold 256 lanes)
     __shared__ double2 part[WIDE_MAX];                           // [G][P] the groups' partial sums of the pair term
     __shared__ float2 rpart[WIDE_MAX];                           // [G][P] ... and of the road term
@@ -63,7 +72,9 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
             sincos(psi, &sp, &cp);
             sx[tid] = x, sy[tid] = y, spsi[tid] = psi, scs[tid] = cp, ssn[tid] = sp;
             shere[tid] = own_here ? 1 : 0;
-            if (MODEL == CSF_BICYCLE) {
+            bool bike = MODEL == CSF_BICYCLE;
+            if constexpr (MIXED) bike = hook.own_model() == CSF_BICYCLE;   // (the class of the rider the takeover above has seated)
+            if (bike) {
                 const double v = d.s[3 * cap + tid];
                 double vref = d.p.v_max_riding[1];
                 if constexpr (HOOK::GROUPS) vref = hook.v_ref(tid);   // (the lane's own set, as in small_tick_body)
@@ -98,7 +109,9 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
             if (!seen) continue;
             int sg = 1;
             float F, gx, gy;
-            if (MODEL == CSF_BICYCLE) {                             // vehicle.py:1054-1147: no jump at phi = 0
+            bool bike_src = MODEL == CSF_BICYCLE;
+            if constexpr (MIXED) bike_src = hook.src_model(j) == CSF_BICYCLE;
+            if (bike_src) {                                         // vehicle.py:1054-1147: no jump at phi = 0
                 field_bicycle(ks, q, se[j], dx, dy, r2, F, gx, gy);
             } else {
                 float sgf = 0.0f;                                   // 0: the sign of the fp32 sine
@@ -181,7 +194,20 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
                 const bool turn = mine && hook.grp == g;
                 if (__ballot(turn) == 0ull) continue;
                 hook.select(dg, g);
-                if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, tid, nullptr, 0u, rx, ry, -1);
+                if constexpr (MIXED) {
+                    constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
+                    switch (hook.group_model(g)) {                  // (uniform: the class of the group, from its record)
+                    case CSF_BICYCLE: if (turn) agent_body<CSF_BICYCLE, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    case CSF_TWOD: if (turn) agent_body<CSF_TWOD, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    case CSF_INVPEND: if (turn) agent_body<CSF_INVPEND, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    case CSF_PLANARPOINT: if (turn) agent_body<CSF_PLANARPOINT, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    case CSF_PLANARBIKE: if (turn) agent_body<CSF_PLANARBIKE, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    case CSF_BALANCINGRIDER: if (turn) agent_body<CSF_BALANCINGRIDER, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
+                    default: break;                                 // (the host admits the six classes only)
+                    }
+                } else {
+                    if (turn) agent_body<MODEL, false, true>(dg, PH_DEST | PH_COMBINE | PH_INTEGRATE, tid, nullptr, 0u, rx, ry, -1);
+                }
             }
         }
         hook(d, t, tid, n);

@@ -115,7 +115,7 @@ struct SceneLanes {
 };
 
 // csf_scene_calib_groups / _lane_groups (DESIGN.md 4.10g, 4.10h): rider groups with parameter sets of their own; the call's table is
-// [n_sets][n] records in `sets`.  csf_scene_calib_classes (4.10i): class_models [n] the vehicle class of every group.  Dev::ns of the engine
+// [n_sets][n] records in `sets`.  csf_scene_calib_classes / _lane_classes (4.10i, 4.10j): class_models [n] the vehicle class of every group.  Dev::ns of the engine
 // is the widest of them while they are held - ns_own is what it was -, and an evaluation restores from the class image: state rows, side
 // state and first ring row as a fresh vehicle of the rider's OWN class has them (abi_population.inc: add_agents_impl, side_state)
 struct SceneGroups {
@@ -567,11 +567,15 @@ static int scene_eval_impl(csf_engine *e, int32_t n_sets, const csf_params *para
     cs.groups.fill(c);
     // one copy of the table, one or two launches, one wait
     HIPCHK(e, hipMemcpyAsync(d_sets, pin, (size_t)n_sets * (size_t)G * sizeof(SceneSet), hipMemcpyHostToDevice, e->main));
-    if (cs.lanes.wide()) {   // the narrow scenes on scene_lanes_kernel, the wide ones on scene_wide_kernel: one stream, one wait
+    if (cs.groups.mixed() && cs.lanes.wide()) {   // (csf_scene_calib_lane_classes: scene_lanes_mixed_kernel, then scene_wide_mixed_kernel)
+        SceneWideDev w{};
+        cs.lanes.fill(w);
+        cs.launches += launch_scene_mixed(cs.table.p, d_sets, c, e->d.ns, e->main, &w);
+    } else if (cs.lanes.wide()) {   // the narrow scenes on scene_lanes_kernel, the wide ones on scene_wide_kernel: one stream, one wait
         SceneWideDev w{};
         cs.lanes.fill(w);
         cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main, &w);
-    } else if (cs.groups.mixed()) {   // several vehicle classes: scene_mixed_kernel, the views' state width the widest of them
+    } else if (cs.groups.mixed()) {   // several vehicle classes: scene_mixed_kernel (shared lanes: scene_lanes_mixed_kernel), the views' state width the widest of them
         cs.launches += launch_scene_mixed(cs.table.p, d_sets, c, e->d.ns, e->main);
     } else {
         cs.launches += launch_scene_eval(e->d.p.model, cs.table.p, d_sets, c, e->main);
@@ -656,13 +660,17 @@ static int scene_groups_impl(csf_engine *e, const char *fn, bool lanes, const ui
     return CSF_OK;
 }
 
-int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0) try {
-    if (!e) return CSF_E_ARG;
-    const char *fn = "csf_scene_calib_classes";
+// csf_scene_calib_classes (lanes == false: a csf_scene_calib_load data set, one slot per rider) and csf_scene_calib_lane_classes (lanes ==
+// true: a data set of csf_scene_calib_load_shared / _load_wide, the class goes with the rider a lane carries; DESIGN.md 4.10j).  `fn` names
+// the call in the messages
+static int scene_classes_impl(csf_engine *e, const char *fn, bool lanes, const uint8_t *group, int32_t n_groups, const int32_t *models,
+                              const double *s0) {
     if (!e->scene_calib) return scene_none(e, fn, "whose candidate sets are whole populations already");
     SceneCalibState &cs = *e->scene_calib;
-    if (cs.lanes.held())
+    if (!lanes && cs.lanes.held())
         return fail(e, CSF_E_STATE, "%s: the data set shares its lanes (csf_scene_calib_load_shared / _load_wide): mixed classes need csf_scene_calib_load - one slot per rider, at most %d riders per scene", fn, SMALL_MAX);
+    if (lanes && !cs.lanes.held())
+        return fail(e, CSF_E_STATE, "%s: the data set has one slot per rider (csf_scene_calib_load): its classes are loaded by csf_scene_calib_classes", fn);
     const bool drop = group == nullptr && n_groups == 0 && models == nullptr && s0 == nullptr;
     HIPCHK(e, hipSetDevice(e->device));
     if (drop) {                                                // the data set is what it was after the load (groups of either call go)
@@ -715,6 +723,16 @@ int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_group
     cs.groups = std::move(fresh);
     e->d.ns = ns;                                              // csf_num_states: the widest class while the classes are held
     return CSF_OK;
+}
+
+int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0) try {
+    if (!e) return CSF_E_ARG;
+    return scene_classes_impl(e, "csf_scene_calib_classes", false, group, n_groups, models, s0);
+} catch (...) { return csf_caught(e); }
+
+int csf_scene_calib_lane_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0) try {
+    if (!e) return CSF_E_ARG;
+    return scene_classes_impl(e, "csf_scene_calib_lane_classes", true, group, n_groups, models, s0);
 } catch (...) { return csf_caught(e); }
 
 int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups) try {

@@ -444,9 +444,10 @@ class Engine:
         R, _ = self._scene_held("scene_calib_lane_groups", "scene_calib_load_shared / scene_calib_load_wide")
         if group is None:
             self._ck(self._lib.csf_scene_calib_lane_groups(self._h, None, 0))
-            return
-        g8 = self._scene_group8(group, R)
-        self._ck(self._lib.csf_scene_calib_lane_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+        else:
+            g8 = self._scene_group8(group, R)
+            self._ck(self._lib.csf_scene_calib_lane_groups(self._h, _ptr(g8), int(g8.max()) + 1 if n_groups is None else int(n_groups)))
+        self.ns = int(self._lib.csf_num_states(self._h))         # (the call replaces the classes of scene_calib_lane_classes)
 
     def scene_calib_classes(self, group, models=None, s0=None):
         """Rider groups of DIFFERENT VEHICLE CLASSES on the loaded scenes (scene_calib_load only): group [R] (integers 0 .. G - 1), models
@@ -454,9 +455,22 @@ class Engine:
         2 <= G <= 12) and s0 [R, <= 8] the start states in the widest layout (missing columns: 0).  `ns` becomes the widest state of the
         loaded classes; rows a class lacks stay 0.  An evaluation is scene_calib_eval_groups with tuple entry g of class models[g].  The
         call replaces the groups of scene_calib_groups and that call replaces these; None drops the classes."""
-        R, _ = self._scene_held("scene_calib_classes")
+        self._scene_classes("scene_calib_classes", self._lib.csf_scene_calib_classes, None, group, models, s0)
+
+    def scene_calib_lane_classes(self, group, models=None, s0=None):
+        """scene_calib_classes for a data set of scene_calib_load_shared / scene_calib_load_wide: the same arguments, and the vehicle
+        class is a property of the RIDER a lane carries - a lane changes its class when another rider takes it over.  An evaluation is
+        scene_calib_eval_groups.  The call replaces the groups of scene_calib_lane_groups and that call replaces these; None drops the
+        classes.  A scene_calib_load data set takes scene_calib_classes and refuses this call."""
+        if not hasattr(self._lib, "csf_scene_calib_lane_classes"):
+            raise EngineError("libcsf_hip.so has no csf_scene_calib_lane_classes: rebuild the library")
+        self._scene_classes("scene_calib_lane_classes", self._lib.csf_scene_calib_lane_classes, "scene_calib_load_shared / scene_calib_load_wide",
+                            group, models, s0)
+
+    def _scene_classes(self, name, call, loader, group, models, s0):
+        R, _ = self._scene_held(name, loader) if loader else self._scene_held(name)
         if group is None:
-            self._ck(self._lib.csf_scene_calib_classes(self._h, None, 0, None, None))
+            self._ck(call(self._h, None, 0, None, None))
             self.ns = int(self._lib.csf_num_states(self._h))
             return
         g8 = self._scene_group8(group, R)
@@ -468,7 +482,7 @@ class Engine:
             raise ValueError("s0 must be [sum(n_riders), 4 .. 8]: the start states in the widest layout")
         wide = np.zeros((R, 8))
         wide[:, : s.shape[1]] = s
-        self._ck(self._lib.csf_scene_calib_classes(self._h, _ptr(g8), int(m.size), _ptr(m), _ptr(wide)))
+        self._ck(call(self._h, _ptr(g8), int(m.size), _ptr(m), _ptr(wide)))
         self.ns = int(self._lib.csf_num_states(self._h))
 
     def scene_calib_eval_groups(self, pods, road_F0=None, road_sigma=None, states=False, stride=1):

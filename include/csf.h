@@ -622,8 +622,19 @@ int csf_calib_clear(csf_engine *e);
  * they were.  Everything is validated and allocated before anything is replaced: a refused call leaves the held groups or classes in
  * force.  CSF_E_STATE without a closed-loop data set and on a data set of csf_scene_calib_load_shared / _load_wide (mixed classes need
  * csf_scene_calib_load); CSF_E_ARG for n_groups outside 2 .. 12, an entry of group >= n_groups, an entry of models outside the six classes,
- * a NULL array.  csf_scene_calib_clear frees the classes with the rest. */
+ * a NULL array.  csf_scene_calib_clear frees the classes with the rest.
+ *
+ * csf_scene_calib_lane_classes is csf_scene_calib_classes for a data set of csf_scene_calib_load_shared /
+ * csf_scene_calib_load_wide: the same arguments and limits, the same rewritten image, and the class is a property of the RIDER a lane
+ * carries - at a takeover the lane's slot becomes the newcomer's fresh vehicle of ITS class (rows that class lacks are 0), from that tick
+ * on the lane is ticked by that class's per-agent tick, acts as a source with that class's field and, replayed, takes that class's
+ * write-back.  A lane nobody rides yet has group 0 and is never present.  The evaluation is csf_scene_calib_eval_groups on
+ * scene_lanes_mixed_kernel / scene_wide_mixed_kernel: one launch, or up to two after csf_scene_calib_load_wide.  The call replaces the
+ * groups of csf_scene_calib_lane_groups, and that call replaces these; (NULL, 0, NULL, NULL) drops the classes.  CSF_E_STATE on a plain
+ * csf_scene_calib_load data set (that one takes csf_scene_calib_classes), without a closed-loop data set and with csf_calib_load's;
+ * CSF_E_ARG as csf_scene_calib_classes.  A refused call changes nothing.  csf_scene_calib_classes keeps its refusal on such a data set. */
 int csf_scene_calib_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0);
+int csf_scene_calib_lane_classes(csf_engine *e, const uint8_t *group, int32_t n_groups, const int32_t *models, const double *s0);
 int csf_scene_calib_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
 int csf_scene_calib_lane_groups(csf_engine *e, const uint8_t *group, int32_t n_groups);
 int csf_scene_calib_eval_groups(csf_engine *e, int32_t n_sets, int32_t n_groups, const csf_params *params,

@@ -45,11 +45,15 @@ are timed there.  With --presence --share the packed data set of that cell gets 
 `packed_groups_base_ms` - per (set, scene) one general-path engine that holds the G sets, stepped tick by tick, a rider added
 (add_agents, set_agent_class, set_dest_queue) at its entry and removed at its exit, the state read back after every tick.
 
---mixed adds the legs of several vehicle classes in one scene on the plain data set (not with --riders), under "mixed":
+--mixed adds the legs of several vehicle classes in one scene on the plain data set, under "mixed":
 the same scenes with rider r in group r % 2 and BOTH groups of the cell's one class, once through csf_scene_calib_groups
 (`one_class_groups_ms`) and once through csf_scene_calib_classes (`one_class_classes_ms`) - the two alternate window by window, each
 behind a warm-up call, and `one_class_equal` says whether their sums are array_equal: the cost of the merged kernel -, then a two-class
 mix (twod, invpend: `two_classes_ms`) and a six-class mix (rider r of class r % 6: `six_classes_ms`), one launch per evaluation each.
+With --riders the same legs run on the wide data set through csf_scene_calib_lane_groups / csf_scene_calib_lane_classes,
+one launch per kind of scene; with --presence --share on the packed data set of that cell (under "share" -> "mixed"), where a lane changes
+its class with its rider, and at 1 set `two_classes_host_stepped_ms` is what the two-class mix costs on one host-stepped general-path
+engine per scene - riders added and removed between 1-tick steps - for scale.
 
     python tools/scene_calib_rate.py [--mixed] [--groups 2 [--groups-base-max 16]] [--sets 1,4,16,64,256] [--scenes 16] [--ticks 1000] [--windows 5] [--base-max 256] [--out FILE]
                                      [--replay [--replay-base-max 4]] [--road [--road-verts 200]] [--presence [--share [--share-roster 20] [--share-peak 6]]]
@@ -94,6 +98,57 @@ def pod_sets(base, n):
     return out
 
 
+SIX = ("twod", "bicycle", "invpend", "planarpoint", "planarbike", "balancingrider")
+
+
+def class_tuples(n_sets, classes):
+    """candidate k: record g the default set of classes[g], its field scaled as pod_sets scales it and by 1 + 0.1 g"""
+    out = []
+    for k in range(n_sets):
+        tup = []
+        for g, m in enumerate(classes):
+            c = parameters.default_pod(m)
+            c.f_0, c.p_0 = c.f_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g), c.p_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g)
+            tup.append(c)
+        out.append(tuple(tup))
+    return out
+
+
+def ms(t):
+    return dict(median=float(np.median(t)), min=min(t), max=max(t))
+
+
+def mixed_legs(eng, lanes, rider, wide, n_sets, model, windows, launches):
+    """the --mixed legs on the data set `eng` holds - lanes: it is on shared lanes or wide (csf_scene_calib_lane_groups / _lane_classes),
+    else a plain load (csf_scene_calib_groups / _classes); rider [R]: the index of every rider in its scene; launches: per evaluation"""
+    from cyclistsocialforce_amd.engine import MODEL_IDS
+    groups, classes_call = (eng.scene_calib_lane_groups, eng.scene_calib_lane_classes) if lanes else (eng.scene_calib_groups, eng.scene_calib_classes)
+    grp2 = (rider % 2).astype(np.uint8)
+    one = class_tuples(n_sets, [model, model])
+    t_grp, t_cls, equal = [], [], True
+    for _ in range(windows):
+        groups(grp2, 2)
+        ref = eng.scene_calib_eval_groups(one)
+        t0 = time.perf_counter(); eng.scene_calib_eval_groups(one); t_grp.append((time.perf_counter() - t0) * 1e3)
+        classes_call(grp2, [MODEL_IDS[model]] * 2, wide)
+        equal = equal and bool(np.array_equal(ref, eng.scene_calib_eval_groups(one)))
+        t0 = time.perf_counter(); eng.scene_calib_eval_groups(one); t_cls.append((time.perf_counter() - t0) * 1e3)
+    mixed = dict(one_class_groups_ms=ms(t_grp), one_class_classes_ms=ms(t_cls), one_class_equal=equal,
+                 one_class_classes_over_groups=float(np.median(t_cls) / np.median(t_grp)))
+    for name, classes in (("two_classes_ms", ("twod", "invpend")), ("six_classes_ms", SIX)):
+        tups = class_tuples(n_sets, classes)
+        classes_call((rider % len(classes)).astype(np.uint8), [MODEL_IDS[m] for m in classes], wide)
+        before = eng.scene_calib_launches()
+        eng.scene_calib_eval_groups(tups)
+        assert eng.scene_calib_launches() == before + launches
+        t_mix = []
+        for _ in range(windows):
+            t0 = time.perf_counter(); eng.scene_calib_eval_groups(tups); t_mix.append((time.perf_counter() - t0) * 1e3)
+        mixed[name] = ms(t_mix)
+    classes_call(None)
+    return mixed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="1,4,16,64,256")
@@ -120,8 +175,6 @@ def main():
     riders = [int(x) for x in a.riders.split(",")] if a.riders else None
     if riders and (a.replay or a.road or a.presence or min(riders) < 1 or max(riders) > 256):
         ap.error("--riders takes 1 .. 256 road users per scene and stands alone: not with --replay, --road or --presence")
-    if a.mixed and riders:
-        ap.error("--mixed runs on the plain load: not with --riders")
     if a.groups and not 2 <= a.groups <= 4:
         ap.error("--groups takes 2 .. 4")
     if a.share and not (a.presence and 1 <= a.share_peak <= a.share_roster <= 32):
@@ -314,6 +367,36 @@ def main():
                     line["share"].update(groups=G, packed_groups_rel_gap=l_gap,
                                          packed_groups_ms=dict(median=float(np.median(t_l)), min=min(t_l), max=max(t_l)),
                                          packed_groups_base_ms=dict(median=float(np.median(t_lold)), min=min(t_lold), max=max(t_lold)) if t_lold else None)
+                if a.mixed:                                      # vehicle classes on the packed data set: a lane's class changes with its rider
+                    from cyclistsocialforce_amd.engine import MODEL_IDS
+                    wb = np.zeros((Rb, 8))
+                    wb[:, : sb.shape[1]] = sb
+                    riderb = np.tile(np.arange(ro), a.scenes)
+                    line["share"]["mixed"] = mixed_legs(packed, True, riderb, wb, n_sets, model, a.windows, 1)
+                    if n_sets == 1:                              # for scale: the host-stepped twin of the two-class mix, one general-path engine per scene
+                        two = class_tuples(1, ("twod", "invpend"))[0]
+                        t0 = time.perf_counter()
+                        for q, (sq, oq, dq) in enumerate(big):
+                            t = Engine(two[0], ro)
+                            t.set_param_classes(list(two))
+                            ids = []
+                            for tick in range(a.ticks):
+                                gone = [i for i, r in enumerate(ids) if ex1[r] == tick]
+                                if gone:
+                                    t.remove_agents(gone)
+                                    ids = [r for r in ids if ex1[r] != tick]
+                                come = [r for r in range(ro) if en1[r] == tick and ex1[r] > tick]
+                                if come:
+                                    t.add_agents(wb[q * ro + np.array(come)], 5.0)
+                                    where = np.arange(len(ids), len(ids) + len(come))
+                                    t.set_agent_class(where, (np.array(come) % 2).astype(np.uint8))
+                                    t.set_dest_queue(where, np.arange(len(come) + 1) * 5, np.concatenate([dq[oq[r]: oq[r + 1]] for r in come]), reset=True)
+                                    ids += come
+                                if ids:
+                                    t.step(1)
+                                    t.state()
+                            t.close()
+                        line["share"]["mixed"]["two_classes_host_stepped_ms"] = (time.perf_counter() - t0) * 1e3
                 plain.close()
                 packed.close()
             if a.replay:
@@ -391,51 +474,13 @@ def main():
                             groups_base_ms=dict(median=float(np.median(t_gold)), min=min(t_gold), max=max(t_gold)) if t_gold else None)
                 for t in gtwins:
                     t.close()
-            if a.mixed:
-                from cyclistsocialforce_amd.engine import MODEL_IDS
+            if a.mixed:                                          # (--riders: the data set is on lanes - DESIGN.md 4.10j)
                 e.scene_calib_replay(None)
                 wide = np.zeros((R, 8))
                 wide[:, : s0.shape[1]] = s0
                 rider = np.concatenate([np.arange(n) for n in nr])
-
-                def class_tuples(classes):
-                    """candidate k: record g the default set of classes[g], its field scaled as pod_sets scales it and by 1 + 0.1 g"""
-                    out = []
-                    for k in range(n_sets):
-                        tup = []
-                        for g, m in enumerate(classes):
-                            c = parameters.default_pod(m)
-                            c.f_0, c.p_0 = c.f_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g), c.p_0 * (1.0 + 0.002 * k) * (1.0 + 0.1 * g)
-                            tup.append(c)
-                        out.append(tuple(tup))
-                    return out
-
-                def ms(t):
-                    return dict(median=float(np.median(t)), min=min(t), max=max(t))
-
-                grp2 = (rider % 2).astype(np.uint8)
-                one = class_tuples([model, model])
-                t_grp, t_cls, equal = [], [], True
-                for _ in range(a.windows):
-                    e.scene_calib_groups(grp2, 2)
-                    ref = e.scene_calib_eval_groups(one)
-                    t0 = time.perf_counter(); e.scene_calib_eval_groups(one); t_grp.append((time.perf_counter() - t0) * 1e3)
-                    e.scene_calib_classes(grp2, [MODEL_IDS[model]] * 2, wide)
-                    equal = equal and bool(np.array_equal(ref, e.scene_calib_eval_groups(one)))
-                    t0 = time.perf_counter(); e.scene_calib_eval_groups(one); t_cls.append((time.perf_counter() - t0) * 1e3)
-                mixed = dict(one_class_groups_ms=ms(t_grp), one_class_classes_ms=ms(t_cls), one_class_equal=equal)
-                for name, classes in (("two_classes_ms", ("twod", "invpend")), ("six_classes_ms", ("twod", "bicycle", "invpend", "planarpoint", "planarbike", "balancingrider"))):
-                    tups = class_tuples(classes)
-                    e.scene_calib_classes((rider % len(classes)).astype(np.uint8), [MODEL_IDS[m] for m in classes], wide)
-                    before = e.scene_calib_launches()
-                    e.scene_calib_eval_groups(tups)
-                    assert e.scene_calib_launches() == before + 1
-                    t_mix = []
-                    for _ in range(a.windows):
-                        t0 = time.perf_counter(); e.scene_calib_eval_groups(tups); t_mix.append((time.perf_counter() - t0) * 1e3)
-                    mixed[name] = ms(t_mix)
-                e.scene_calib_classes(None)
-                line["mixed"] = mixed
+                kinds = len({n >= a.wide_from for n in nr}) if riders else 1
+                line["mixed"] = mixed_legs(e, bool(riders), rider, wide, n_sets, model, a.windows, kinds)
             print(json.dumps(line), flush=True)
             if a.out:
                 with open(a.out, "a") as f:

@@ -2,7 +2,7 @@
 """Sums and sampled states of a fixed set of tiny closed-loop calibration data sets (GPU box), for comparing two builds of the library
 BIT FOR BIT: the GPU tests hold the scene kernels to their twins at 2e-7, which does not see a changed rounding.  Everything goes
 through the Python Engine API, so the tool runs unchanged from the tools/ folder of any checkout that has the scene calibration of
-DESIGN.md 4.10 - 4.10i; run it in both, then compare:
+DESIGN.md 4.10 - 4.10j; run it in both, then compare:
 
     python tools/scene_eval_dump.py --out a.npz                    (in the one checkout)
     python tools/scene_eval_dump.py --out b.npz --compare a.npz    (in the other: evaluates, writes, compares; exit status 1 on a difference)
@@ -21,6 +21,9 @@ The data sets are the smallest that reach every piece the kernels of csf_scene.h
          per-set parameters: two launches                                          scene_wide_kernel + scene_lanes_kernel
     fg, gg   fr and g with the riders in two groups (csf_scene_calib_lane_groups; left out where the library lacks the call)
                                                                                    scene_lanes_groups_kernel, scene_wide_groups_kernel
+    fm, gm   fr and g with the riders alternating between two groups of two vehicle classes - the model's and the next one's
+         (csf_scene_calib_lane_classes; left out where the library lacks the call: a lane changes its class at a handover)
+                                                                                   scene_lanes_mixed_kernel, scene_wide_mixed_kernel
     m    a with the riders alternating between two groups of two vehicle classes - the model's and the next one's
          (csf_scene_calib_classes; left out where the library lacks the call)      scene_mixed_kernel
     mc, md   m with the windows of c and rider 4 replayed; m with the roads and the per-set road parameters of d.  (One engine, in the
@@ -71,6 +74,11 @@ def recording(e, sets, riders, n):
     return np.ascontiguousarray(np.nan_to_num(st[:, n + np.asarray(riders), :4]))
 
 
+def next_class(model):
+    """the two classes of the mixed cases: the model's and the next one's"""
+    return model, MODELS[(MODELS.index(model) + 1) % len(MODELS)]
+
+
 def small_cases(model, out):
     sets, gsets = sets3(model), group_sets(model, 3, 2)
     s0, off, rows, _ = scenes(model, N_RIDERS, seed=5)
@@ -98,7 +106,7 @@ def small_cases(model, out):
     e.scene_calib_groups(None)
     out["d"] = e.scene_calib_eval(sets, states=True, stride=STRIDE, **over)
     if hasattr(e._lib, "csf_scene_calib_classes"):               # (the road of d stays for md, then goes)
-        classes = (model, MODELS[(MODELS.index(model) + 1) % len(MODELS)])
+        classes = next_class(model)
         msets = mixed_sets(3, classes)
         e.scene_calib_classes(group, [MODEL_IDS[c] for c in classes], s0)
         out["md"] = e.scene_calib_eval_groups(msets, states=True, stride=STRIDE, **over)
@@ -138,6 +146,10 @@ def shared_cases(model, out):
     if hasattr(e._lib, "csf_scene_calib_lane_groups"):           # (riders 0 and 3 share lane 0: its group changes at the handover)
         e.scene_calib_lane_groups((np.arange(6) % 2).astype(np.uint8), 2)
         out["fg"] = e.scene_calib_eval_groups(group_sets(model, 3, 2), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
+    if hasattr(e._lib, "csf_scene_calib_lane_classes"):          # (riders 0 and 3 share lane 0: its class changes at the handover)
+        classes = next_class(model)
+        e.scene_calib_lane_classes((np.arange(6) % 2).astype(np.uint8), [MODEL_IDS[c] for c in classes], part[0])
+        out["fm"] = e.scene_calib_eval_groups(mixed_sets(3, classes), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
     e.close()
 
 
@@ -159,6 +171,12 @@ def wide_cases(model, out):
         e.scene_calib_lane_groups((np.arange(53) % 3 % 2).astype(np.uint8), 2)
         out["gg"] = e.scene_calib_eval_groups(group_sets(model, 3, 2), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
         assert e.scene_calib_launches() == before + 4
+    if hasattr(e._lib, "csf_scene_calib_lane_classes"):
+        classes = next_class(model)
+        at = e.scene_calib_launches()
+        e.scene_calib_lane_classes((np.arange(53) % 3 % 2).astype(np.uint8), [MODEL_IDS[c] for c in classes], np.concatenate([p[0][:, :4] for p in parts]))
+        out["gm"] = e.scene_calib_eval_groups(mixed_sets(3, classes), states=True, stride=STRIDE, road_F0=ROAD_F0, road_sigma=ROAD_SIGMA)
+        assert e.scene_calib_launches() == at + 2
     e.close()
 
 
@@ -183,9 +201,12 @@ def main():
         np.savez(a.out, **arrays)
     if a.compare:
         other = np.load(a.compare)
-        differ = sorted(set(arrays) ^ set(other.files))
+        differ = sorted(set(other.files) - set(arrays))
         for name in differ:
-            print(f"{name}: in one of the two only")
+            print(f"{name}: in {a.compare} only")
+        extra = sorted(set(arrays) - set(other.files))           # (cases the other build's library lacks the call for: nothing to compare)
+        if extra:
+            print(f"{len(extra)} arrays in this build only: {' '.join(sorted({n.split('.')[1] for n in extra}))}")
         for name in sorted(set(arrays) & set(other.files)):
             x, y = arrays[name], other[name]
             if x.shape == y.shape and np.array_equal(x, y, equal_nan=True):
@@ -195,7 +216,8 @@ def main():
                 print(f"{name}: shapes {x.shape} / {y.shape}, or another NaN pattern")
             else:
                 print(f"{name}: largest |difference| {np.nanmax(np.abs(x - y)):.3e} in {int(np.sum(~((x == y) | np.isnan(x))))} of {x.size}")
-        print(f"compared with {a.compare}: {len(arrays) - len(differ)} of {len(arrays)} arrays identical" + ("" if differ else ": ALL IDENTICAL"))
+        n_both = len(set(arrays) & set(other.files))
+        print(f"compared with {a.compare}: {n_both + len(set(other.files) - set(arrays)) - len(differ)} of {len(other.files)} arrays identical" + ("" if differ else ": ALL IDENTICAL"))
         if differ:
             sys.exit(1)
 
