@@ -45,6 +45,7 @@ SYMBOLS = (
     "csf_scene_calib_lane_classes",
     "csf_small_classes",
     "csf_handout_ranks",
+    "csf_wg_order_ranks", "csf_wg_order_tables",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -169,6 +170,9 @@ def load():
     L.csf_near_dropped.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "csf_handout_ranks"):
         L.csf_handout_ranks.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if hasattr(L, "csf_wg_order_ranks"):
+        L.csf_wg_order_ranks.argtypes = [C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32)]
+        L.csf_wg_order_tables.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), vp, vp, i64]
     L.csf_comm_stream_order.argtypes = [vp, C.POINTER(i32), dp]
     L.csf_small_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]

@@ -16,6 +16,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "csf_dev.h"
+#include "csf_wg_order.h"
 
 namespace csf {
 
@@ -371,6 +372,39 @@ void launch_mid_batch_rebin(const Dev *table, const MidTick *ticks, int slots, i
     if (slots <= 0 || max_n_pad <= 0) return;
     hipLaunchKernelGGL(identity_perm_batch_kernel, dim3((unsigned)((max_n_pad + 255) / 256), (unsigned)slots), dim3(256), 0, st, table, ticks);
     hipLaunchKernelGGL(rebase_batch_kernel, dim3((unsigned)((max_n_pad / 64 + 3) / 4), (unsigned)slots), dim3(256), 0, st, table, ticks);
+}
+
+// The order of a chunk's receiver groups for pair_cull_kernel (csf_wg_order.h).  A workgroup ranks 64 groups of one source chunk:
+// lane r of every wave holds group 64 y + r, the chunk's costs pass through LDS 512 at a time, and wave w counts its 64 of them -
+// the groups that are heavier, or as heavy with a lower index - so a thread compares 64 keys per pass, not 512 (one workgroup per
+// chunk with a thread per group took 18 us at the headline's 512 groups: a chain of 512 dependent LDS reads per thread).  The
+// eight partial counts meet in LDS, and order[rank] = group.  Correct for any group count: more passes, more workgroups.
+constexpr int WGO_THREADS = 512, WGO_ROWS = 64;
+__global__ __launch_bounds__(WGO_THREADS) void wg_order_kernel(const uint32_t *cost, int32_t *order, int groups) {
+    __shared__ __attribute__((aligned(16))) uint32_t keys[WGO_THREADS];
+    __shared__ int rank[WGO_ROWS];
+    const int lane = (int)threadIdx.x & (WGO_ROWS - 1), wave = (int)threadIdx.x / WGO_ROWS;
+    const uint32_t *const c = cost + (int64_t)blockIdx.x * groups;
+    int32_t *const o = order + (int64_t)blockIdx.x * groups;
+    const int i = (int)blockIdx.y * WGO_ROWS + lane;
+    const uint32_t mine = i < groups ? c[i] : 0u;
+    if (threadIdx.x < WGO_ROWS) rank[threadIdx.x] = 0;
+    int part = 0;
+    for (int j0 = 0; j0 < groups; j0 += WGO_THREADS) {           // (uniform bounds: every thread meets every barrier)
+        const int j = j0 + (int)threadIdx.x;
+        __syncthreads();
+        keys[threadIdx.x] = j < groups ? c[j] : 0u;               // (behind the last group: zeros with an index >= groups - they come before nobody)
+        __syncthreads();
+        part += wg_rank_count(keys + wave * WGO_ROWS, WGO_ROWS, j0 + wave * WGO_ROWS, mine, i);
+    }
+    if (i < groups) atomicAdd(&rank[lane], part);
+    __syncthreads();
+    if (wave == 0 && i < groups) o[rank[lane]] = i;              // (a permutation whatever the costs: rank < groups, no two alike)
+}
+
+void launch_wg_order(const uint32_t *cost, int32_t *order, int64_t groups, int chunks, hipStream_t st) {
+    if (groups <= 0 || chunks <= 0) return;
+    hipLaunchKernelGGL(wg_order_kernel, dim3((unsigned)chunks, (unsigned)((groups + WGO_ROWS - 1) / WGO_ROWS)), dim3(WGO_THREADS), 0, st, cost, order, (int)groups);
 }
 
 void launch_bounds(const Dev &d, hipStream_t st) {

@@ -271,6 +271,12 @@ struct Dev {
                        // issued, stores done
     int32_t index_order;   // CSF_HANDOUT=index: a workgroup of pair_cull_kernel hands its receivers out in index order, not heaviest first (csf_handout.h)
     uint64_t *trace;   // CSF_TRACE_BLOCKS: (start, end, hw id) of every pair-kernel workgroup of the last tick, else NULL
+    // pair_cull_kernel with receivers in slot order, one grid (csf_wg_order.h): workgroup blockIdx.x of source chunk `by` serves receiver
+    // group wg_order[by * groups + blockIdx.x] (a permutation of the groups per chunk; NULL: blockIdx.x itself) and leaves what the
+    // group cost, 28 x tests + 58 x evaluations of its waves, in wg_cost[by * groups + group] (NULL: not stored)
+    const int32_t *wg_order;
+    uint32_t *wg_cost;
+    int32_t wg_groups;   // groups per chunk the two tables are laid out for: a launch whose gridDim.x is another takes index order and stores nothing
 };
 
 enum : int { PH_DEST = 1, PH_COMBINE = 2, PH_INTEGRATE = 4, PH_FIXSPEED = 8 };
@@ -279,6 +285,10 @@ enum : int { PH_DEST = 1, PH_COMBINE = 2, PH_INTEGRATE = 4, PH_FIXSPEED = 8 };
 // t0 / t1 (may be NULL): HIP events that receive the start / end time stamp of the kernel itself (hipExtLaunchKernelGGL:
 // taken from the dispatch packet, no extra barrier packet in the stream as with hipEventRecord)
 void launch_pair(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// receiver groups of launch_pair's grid where it takes a kernel that reads Dev::wg_order / writes Dev::wg_cost, else 0
+int64_t pair_order_groups(const Dev &d);
+// csf_bin.hip: order[c * groups + rank] = group for every source chunk c, heaviest first by cost[c * groups + group] (csf_wg_order.h)
+void launch_wg_order(const uint32_t *cost, int32_t *order, int64_t groups, int chunks, hipStream_t st);
 void launch_pair_segments(const Dev &d, int total_by, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 void launch_road(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // csf_road.hip: the road term over a lattice (Dev::rg_*).  launch_road_far: the far field of every cell at its 8 x 8

@@ -83,6 +83,14 @@ namespace csf {
 // within a class) and claim k takes rank k: 6.0 % and 1.35 us, pair launch 99.6 -> 97.8 us, 157.5 -> 159.9 M agent-steps/s
 // (profiles/handout_order_trace.txt, handout_order_ab.txt; classes >= 48 / 32 / 16 measure the same, >= 24 / 12 / 6 half the gain).
 // No sum depends on the order: a receiver's visit to a tile is one wave's, and so are its noted corrections (near_drain).
+// HEAVIEST GROUP FIRST (receivers in slot order, one grid; csf_wg_order.h, engine/tick.inc: wg_order_apply): the launch is dispatched
+// chunk by chunk, 512 receiver groups per source chunk at the headline, and from 76 % of it on nothing is left to dispatch - the SIMDs
+// end up to 17 us apart.  Every workgroup leaves what its group cost in vector instructions, 28 x tests + 58 x evaluations, in
+// Dev::wg_cost; every CSF_WG_ORDER_TICKS ticks wg_order_kernel (csf_bin.hip) ranks each chunk's groups by it, and workgroup
+// blockIdx.x of a chunk serves group Dev::wg_order[chunk][blockIdx.x]: a chunk's heavy groups start first, its light ones fill the
+// tail.  No sum depends on it - a group's sums go to part[(part_base + by) * cap + agent], whoever computes them - and any
+// permutation will do, which is all the order kernel guarantees (profiles/wg_order_estimate.txt, wg_order_experiment.txt, wg_order_ab.txt).
+// The circles of the next tick, the trace record and the through-counter stay on blockIdx.x.
 // RPB: receivers of a workgroup, 16, or 32 where the grid stays large enough (DYN only: with dynamic hand-out a
 // workgroup of twice the receivers shares one tile fill and one start-up between them: 146 -> 141 us at N = 16 384)
 // REACH (with the far-field cull on): every candidate batch goes through the reach test keep_x2 (two sources per lane), two batches at a
@@ -93,8 +101,11 @@ namespace csf {
 // SEG (several parameter sets in the class-segmented order, csf_engine.hip: rebin): ONE grid for the runs of all sets whose
 // field is the TwoD one - blockIdx.y counts the source chunks of all runs, and a workgroup takes its run's constants, source
 // range and partial-sum slots from Dev::segtab (a launch per run left the device idle while each run's last workgroups ended).
-template <bool P2R, bool CLASSIFY, bool BINR, bool DYN, int RPB = WPB * RPW, bool REACH = false, int CW = WPB, bool SEG = false>
+// ORD (heaviest group first, below): the instances that read Dev::wg_order and leave Dev::wg_cost.  launch_cull takes them only for a
+// launch that was given the tables; every other launch runs the instance without a single instruction of it.
+template <bool P2R, bool CLASSIFY, bool BINR, bool DYN, int RPB = WPB * RPW, bool REACH = false, int CW = WPB, bool SEG = false, bool ORD = false>
 __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(const Dev dk) {
+    static_assert(!ORD || (DYN && CLASSIFY && !BINR && !SEG), "the order tables are built into the classified variants with receivers in slot order, one grid");
     static_assert(!SEG || (DYN && CLASSIFY && !BINR), "the segmented grid is built into the classified variants with receivers in slot order");
     Dev dseg;
     int by = (int)blockIdx.y;
@@ -156,6 +167,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     const int64_t j0 = d.lo + ((int64_t)blockIdx.x * CW + wave) * RPW;
     int64_t ibeg, iend;
     source_chunk(d, ibeg, iend, by);
+    constexpr bool ORDERED = ORD;   // HEAVIEST GROUP FIRST (csf_wg_order.h)
     const uint64_t t_start = d.trace ? wall_clock64() : 0;
     if (cold_args().chase_clock != nullptr && lane == 0 && wave == 0)      // (measurement aid: when did this launch's first wave start?)
         atomicMin(cold_args().chase_clock + 8 * cold_args().chase_slot + 0, (unsigned long long)wall_clock64());
@@ -338,8 +350,13 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     // first tile and the workgroup's receiver records travel together: one global round trip, not two
     if (!uselist && ibeg >= iend) return;  // (uniform) nothing to do for this chunk
     if (!BINR) fill_tile(ibeg, (int)((iend - ibeg) < TL ? (iend - ibeg) : TL), (int)threadIdx.x);
+    // HEAVIEST GROUP FIRST (csf_wg_order.h): which receiver group this workgroup serves - by the table, a permutation of the chunk's
+    // groups, where the engine has one for this grid.  A uniform load, asked for BEHIND the tile's loads: scalar loads return in any
+    // order, so the wait for any kernel argument in front of the fill would have waited for this round trip as well.
+    int group = (int)blockIdx.x;
+    if (ORDERED && d.wg_order != nullptr && d.wg_groups == (int)gridDim.x) group = d.wg_order[(int64_t)by * gridDim.x + blockIdx.x];
     if (threadIdx.x < RPB) {
-        const int64_t j = d.lo + (int64_t)blockIdx.x * RPB + threadIdx.x;
+        const int64_t j = d.lo + (ORDERED ? (int64_t)group : (int64_t)blockIdx.x) * RPB + threadIdx.x;
         const int64_t jc = j < d.hi ? j : d.hi - 1;          // clamp: results of the duplicates are not stored
         if (BINR) {  // receiver slot jc - lo of this rank -> place of the binned order -> slot
             const int64_t p = d.rlist ? (int64_t)d.rlist[jc - d.lo] : jc;
@@ -800,8 +817,25 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     if (DYN) {
         const float4 *const chase = cold_args().part4;   // (uniform; NULL but for the launches the per-agent kernel runs beside)
         if (chase != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's hand-over stores have landed (edge_handover)
+        // what this wave's visits cost in vector instructions (profiles/pair_plain_f32_isa_counts.txt: 28 per source tested, 58 per
+        // pair evaluated), left in the first word of its list of noted pairs - drained, and nobody else's
+        // (the table and the block's first slot: asked for in front of the barrier, like the pointer above - behind it the round trip
+        // to the argument block would be the workgroup's last act, with its slot and its LDS held.  A launch without tables - NULL, or
+        // laid out for another grid - pays these loads and nothing else)
+        uint32_t *const wcost = ORDERED && cold_args().wg_groups == (int)gridDim.x ? cold_args().wg_cost : nullptr;
+        const int64_t wlo = ORDERED ? cold_args().lo : 0;
+        if (ORDERED && wcost != nullptr && lane == 0) nlist[wave][0] = 28u * tests + 58u * (evals + (unsigned)CHUNK * (pops & 0xFFFFu));
         __syncthreads();
         const int te = (wave << 6) | lane;     // (threadIdx.x, not kept alive across the kernel)
+        if (ORDERED && wave == 0 && wcost != nullptr) {   // the workgroup's cost, for the order of a later launch (counts, not clocks: a run reproduces its orders)
+            unsigned c = lane < CW ? nlist[lane][0] : 0u;
+            c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR1, 0xf, 0xf, false);
+            c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR2, 0xf, 0xf, false);
+            c += __builtin_amdgcn_update_dpp(0u, c, DPP_HALF_MIRROR, 0xf, 0xf, false);   // lane 0: waves 0 .. 3 + waves 4 .. 7
+            static_assert(CW <= 8, "three exchanges within eight lanes sum the waves' costs");
+            // (the group it served: its first receiver's slot - never a clamped one - is RPB x group places behind the block's first)
+            if (lane == 0) wcost[(int64_t)by * gridDim.x + (((int64_t)ragent[0] - wlo) / RPB)] = c;
+        }
         if (te < RPB) {
             const int64_t a = ragent[te];
             if (a >= 0) {
@@ -1135,30 +1169,30 @@ static dim3 recv_grid(const Dev &d, int split, int per_block_recv = WPB * RPW) {
 // every launch of this file: optional events take the kernel's own start / end time stamps (csf_dev.h)
 #define CSF_LAUNCH(kernel, grid) hipExtLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, st, t0, t1, 0, d)
 
-template <bool P2R, bool CLASSIFY, bool BINR>
+template <bool P2R, bool CLASSIFY, bool BINR, bool ORD = false>
 static void launch_cull_dyn(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
     if (CLASSIFY && d.dyn_recv && d.pc.reach) {      // the default: per-pair reach test in front of the field
         if (d.rpb == 16 && d.wide && CLASSIFY) {
-            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 16, CLASSIFY, CLASSIFY ? 2 * WPB : WPB>), recv_grid(d, d.n_split, 16),
+            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 16, CLASSIFY, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 16),
                                   dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
         } else if (d.rpb == 32 && d.wide && CLASSIFY) {   // 8 waves, tiles of 2048 sources (csf_engine.hip set_chunks: chunks of 32 batches)
-            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY, CLASSIFY ? 2 * WPB : WPB>), recv_grid(d, d.n_split, 32),
+            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 32),
                                   dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
-        } else if (d.rpb == 32) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY>), recv_grid(d, d.n_split, 32));
-        else if (d.rpb == 8) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 8, CLASSIFY>), recv_grid(d, d.n_split, 8));
-        else CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, WPB * RPW, CLASSIFY>), recv_grid(d, d.n_split));
+        } else if (d.rpb == 32) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split, 32));
+        else if (d.rpb == 8) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 8, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split, 8));
+        else CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, WPB * RPW, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split));
         return;
     }
     if (CLASSIFY && d.dyn_recv && d.rpb == 32 && d.wide) {   // every pair evaluated (CSF_FAR_EPS=0): the wide workgroup as well
-        hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, false, CLASSIFY ? 2 * WPB : WPB>), recv_grid(d, d.n_split, 32),
+        hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, false, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 32),
                               dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
         return;
     }
     if (d.dyn_recv && d.rpb == 32) {
-        CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32>), recv_grid(d, d.n_split, 32));
+        CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, false, WPB, false, ORD>), recv_grid(d, d.n_split, 32));
         return;
     }
-    if (d.dyn_recv) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true>), recv_grid(d, d.n_split));
+    if (d.dyn_recv) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, WPB * RPW, false, WPB, false, ORD>), recv_grid(d, d.n_split));
     else CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, false>), recv_grid(d, d.n_split));
 }
 
@@ -1184,6 +1218,9 @@ static void launch_cull(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t 
     if (d.classify && d.recv_binned) {
         if (p2r) launch_cull_dyn<true, true, true>(d, st, t0, t1);
         else launch_cull_dyn<false, true, true>(d, st, t0, t1);
+    } else if (d.classify && d.dyn_recv && d.wg_cost != nullptr) {   // (tick.inc: wg_order_apply gave this launch its tables)
+        if (p2r) launch_cull_dyn<true, true, false, true>(d, st, t0, t1);
+        else launch_cull_dyn<false, true, false, true>(d, st, t0, t1);
     } else if (d.classify) {
         if (p2r) launch_cull_dyn<true, true, false>(d, st, t0, t1);
         else launch_cull_dyn<false, true, false>(d, st, t0, t1);
@@ -1191,6 +1228,14 @@ static void launch_cull(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t 
         if (p2r) launch_cull_dyn<true, false, false>(d, st, t0, t1);
         else launch_cull_dyn<false, false, false>(d, st, t0, t1);
     }
+}
+
+// (launch_pair and launch_cull_dyn, read backwards: one parameter set, TwoD field, the cull-first kernel on classified batches,
+// receivers in slot order and handed out dynamically; 32, 8 or 16 receivers per workgroup)
+int64_t pair_order_groups(const Dev &d) {
+    if (d.hi <= d.lo || d.n_classes > 1 || d.p.model == CSF_BICYCLE || d.pair_variant == 1 || !d.classify || d.recv_binned || !d.dyn_recv) return 0;
+    const int per = d.rpb == 32 ? 32 : (d.rpb == 8 && d.pc.reach) ? 8 : WPB * RPW;
+    return (d.hi - d.lo + per - 1) / per;
 }
 
 void launch_pair(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {

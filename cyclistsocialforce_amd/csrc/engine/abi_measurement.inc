@@ -128,6 +128,27 @@ int csf_handout_ranks(const uint32_t *cand, const uint32_t *inside, int32_t n, i
     return csf::handout_ranks(cand, inside, n, rank);
 } catch (...) { return -1; }
 
+int csf_wg_order_ranks(const uint32_t *cost, int32_t n, int32_t *order) try {
+    if (!cost || !order || n < 0) return -1;
+    csf::wg_order_host(cost, n, order);
+    return n;
+} catch (...) { return -1; }
+
+int csf_wg_order_tables(csf_engine *e, int64_t *groups, int32_t *chunks, int32_t *ordered, uint32_t *cost, int32_t *order, int64_t capacity) try {
+    if (!e || !groups || !chunks || !ordered || capacity < 0) return e ? fail(e, CSF_E_ARG, "csf_wg_order_tables: bad arguments") : CSF_E_ARG;
+    int rc = csf_sync(e);
+    if (rc) return rc;
+    const csf_engine::WgOrder &w = e->wgo;
+    *groups = 0, *chunks = 0, *ordered = 0;
+    if (w.last < 0) return CSF_OK;
+    const int64_t words = w.groups * w.chunks;
+    if ((cost || order) && words > capacity) return fail(e, CSF_E_ARG, "csf_wg_order_tables: %lld words, room for %lld", (long long)words, (long long)capacity);
+    *groups = w.groups, *chunks = w.chunks, *ordered = w.last_ordered ? 1 : 0;
+    if (cost) HIPCHK(e, hipMemcpy(cost, w.cost[w.last].p, (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (order && w.last_ordered) HIPCHK(e, hipMemcpy(order, w.order[w.last].p, (size_t)words * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
 int csf_comm_stream_order(const csf_engine *e, int32_t *second_stream, double us_per_tick[2]) try {
     if (!e || !second_stream) return CSF_E_ARG;
     *second_stream = e->comm_second ? 1 : 0;

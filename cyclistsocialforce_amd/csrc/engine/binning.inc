@@ -335,6 +335,7 @@ int rebin(csf_engine *e) {
     // (one read-back of the positions; where every slot's state is on this device).
     if (e->moves >= 4096 && e->world <= 1 && !e->loopback) e->bound_stale = true;
     e->ticks_since_rebin = 0;
+    e->wgo.forget();            // (new tiles: what a group cost against the old ones says little)
     e->moved_unbinned = 0;
     e->churn = 0;
     e->bounds_fresh = true;                                          // (rebase_kernel wrote the circles of the records as they are)

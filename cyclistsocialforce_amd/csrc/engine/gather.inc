@@ -111,5 +111,6 @@ int prepare_mutation(csf_engine *e, bool calib_ok = false) {
     rc = download_all(e);
     if (rc) return rc;
     e->dirty = true;
+    e->wgo.forget();
     return CSF_OK;
 }

@@ -149,6 +149,9 @@ int alloc_all(csf_engine *e) {
         d.atrace = e->atrace.p;
     }
     d.index_order = e->knobs.handout_index;
+    d.wg_order = nullptr;   // (set around a tick's own pair launch only: tick.inc wg_order_apply)
+    d.wg_cost = nullptr;
+    d.wg_groups = 0;
     d.trace = nullptr;
     if (!e->knobs.trace_blocks.empty()) {  // 3 words per wave: the grid is at most (cap/16) x MAX_SPLIT workgroups of 4 waves
         e->trace_words = 3 * 4 * ((size_t)cap / 16 + 1) * MAX_SPLIT;
@@ -199,6 +202,7 @@ void set_shard(csf_engine *e) {
 // the source chunks of the pair kernel's grid, for the d.n_src places of the source order that can hold road users
 void set_chunks(csf_engine *e) {
     Dev &d = e->d;
+    e->wgo.forget();
     int64_t nloc = d.hi - d.lo;
     int64_t blocks = (nloc + 15) / 16;
     int64_t units = std::max<int64_t>(1, d.n_src / 64);

@@ -9,6 +9,48 @@
 // The pair term of a tick: one launch, or - class-segmented order, several parameter sets - one launch of the culling kernel
 // per set's run of places, with that set's constants, field (vehicle class) and far-field radius; `base` carries what the
 // caller wants of every launch (counters, next tick's circles or not).  The optional time stamps bracket the first launch.
+// Heaviest group first (csf_wg_order.h; csf_engine::WgOrder has the hand-off): the tables of a tick's own pair launch on stream `st`,
+// k the parity that picks them.  The order is formed again every CSF_WG_ORDER_TICKS ticks and as soon as a launch of this grid and
+// these tiles has left its costs - the order kernel sits directly in front of the launch, in its stream; until then the launch
+// takes the groups in index order (NULL).  Every other launch of the pair kernel (the warm launch, csf_count_pairs, calibration,
+// the copies of Dev the scene and measurement calls make) leaves both pointers NULL: Dev holds them only from here to wg_order_done.
+static int wg_order_apply(csf_engine *e, Dev &dd, int k, hipStream_t st) {
+    dd.wg_order = nullptr;
+    dd.wg_cost = nullptr;
+    dd.wg_groups = 0;
+    e->wgo.last = -1;
+    if (e->knobs.wg_order == 0 || !e->segs.empty()) return CSF_OK;
+    const int64_t groups = pair_order_groups(dd);
+    const int chunks = (int)dd.n_split;
+    if (groups <= 0 || chunks <= 0 || groups * chunks < e->knobs.wg_order_min) return CSF_OK;
+    csf_engine::WgOrder &w = e->wgo;
+    const size_t words = (size_t)groups * (size_t)chunks;
+    if (w.groups != groups || w.chunks != chunks || w.cost[0].n < words) {   // another grid: nothing known about it
+        w.forget();
+        w.groups = groups, w.chunks = chunks;
+        for (int t = 0; t < 2; t++) {   // (grow-only; an allocation waits for the device: no launch still reads what is freed)
+            HIPCHK(e, w.cost[t].reserve(words));
+            HIPCHK(e, w.order[t].reserve(words));
+        }
+    }
+    if (w.cost_ok[k] && (!w.order_ok[k] || 2 * w.used[k] >= e->knobs.wg_order_ticks)) {
+        launch_wg_order(w.cost[k].p, w.order[k].p, groups, chunks, st);
+        w.order_ok[k] = true;
+        w.used[k] = 0;
+    }
+    if (w.order_ok[k] && e->knobs.wg_order == 1) dd.wg_order = w.order[k].p;
+    // (a workgroup whose source chunk is empty stores no cost: the first launch after the costs were forgotten starts from zeros,
+    // so that no word of another grid or of older tiles is left in the table)
+    if (!w.cost_ok[k]) HIPCHK(e, hipMemsetAsync(w.cost[k].p, 0, words * sizeof(uint32_t), st));
+    dd.wg_cost = w.cost[k].p;
+    dd.wg_groups = (int32_t)groups;
+    w.cost_ok[k] = true;          // (for whatever follows this launch in its stream)
+    w.used[k]++;
+    w.last = k, w.last_ordered = dd.wg_order != nullptr;
+    return CSF_OK;
+}
+static void wg_order_done(Dev &dd) { dd.wg_order = nullptr, dd.wg_cost = nullptr, dd.wg_groups = 0; }
+
 static void launch_pair_all(csf_engine *e, const Dev &base, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
     if (e->segs.empty()) {
         launch_pair(base, e->main, t0, t1);
@@ -490,7 +532,9 @@ static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engin
     // previous tick's per-agent kernel in its stream, so a workgroup of it through means that kernel has ended - whose state this
     // tick's per-agent kernel reads from its first instruction on)
     dd.chase_gate = (uint32_t)((int64_t)(e->chase_round - 1) * wgs + std::max<int64_t>(1, wgs * e->knobs.chase_gate_pct / 100));
+    if ((rc = wg_order_apply(e, dd, e->chase_parity ? 1 : 0, P))) return rc;
     launch_pair(dd, P, ps ? ps->ev[0] : nullptr, ps ? ps->ev[1] : nullptr);
+    wg_order_done(dd);
     if (ps) ps->pair = true;
     bounds_after_pair(e, true);
     if (!launch_agent_chase(dd, Q, po ? po->ev[4] : nullptr, po ? po->ev[5] : nullptr))
@@ -559,7 +603,9 @@ static int enqueue_two_launch_tick(csf_engine *e, bool bounds_done) {
     }
     if ((rc = set_fov_band(e))) return rc;
     if (d.n_live > 1 && d.hi > d.lo) {
+        if ((rc = wg_order_apply(e, d, (int)(d.tick & 1), e->main))) return rc;
         launch_pair_all(e, d, ps ? ps->ev[0] : nullptr, ps ? ps->ev[1] : nullptr);
+        wg_order_done(d);
         if (ps) ps->pair = true;
     }
     bounds_after_pair(e, true);

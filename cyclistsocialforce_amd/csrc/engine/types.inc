@@ -24,6 +24,7 @@
 
 #include "csf_dev.h"
 #include "csf_handout.h"
+#include "csf_wg_order.h"
 #include "csf_calib.h"
 #include "csf_scene.h"
 
@@ -201,6 +202,9 @@ struct Knobs {
     int small_classes = 0;                    // CSF_SMALL_CLASSES=1: csf_small_classes is on from csf_create (csf_small_classes.hip; DESIGN.md 4.6e)
     int segments = -1;                        // CSF_SEGMENTS
     int handout_index = 0;                    // CSF_HANDOUT=index: the pair kernel's workgroups hand their receivers out in index order (0, default: heaviest first, csf_handout.h)
+    int wg_order = 1;                         // CSF_WG_ORDER=1 (default): the receiver groups of a source chunk are handed to the pair kernel's workgroups heaviest first (csf_wg_order.h); 0: in index order; index (CSF_EXPERT=1): costs and orders are kept, the launches take index order
+    int wg_order_ticks = 64;                  // CSF_WG_ORDER_TICKS: an order is formed again every this many ticks
+    int wg_order_min = 2048;                  // CSF_WG_ORDER_MIN: ... for grids of at least this many workgroups (two rounds of the device's 1 024 slots: in a single round every workgroup starts at once, and a rank's block of an 8-way shard - 64 groups x 16 chunks - lost 2.9 us to the order)
     int seg_grid = 1;                         // CSF_SEG_GRID=0: one launch per parameter set (class-segmented order) instead of one grid
     int far_tight = 1;                        // CSF_FAR_TIGHT=0: the far-field radius prices all n sources at the cut (ln(n / eps) / kappa) also where candidate lists say how many a receiver can meet
     int clist = 1;                            // CSF_CLIST=0: receivers in binned order walk every tile of their chunk (no candidate lists)
@@ -254,6 +258,9 @@ struct Knobs {
         clist = geti("CSF_CLIST", 1);
         far_tight = geti("CSF_FAR_TIGHT", 1);
         seg_grid = gete("CSF_SEG_GRID", 1);
+        if (const char *v = getenv("CSF_WG_ORDER")) wg_order = std::string(v) == "index" ? (expert ? 2 : 0) : (atoi(v) == 1 ? 1 : 0);
+        wg_order_ticks = std::max(1, geti("CSF_WG_ORDER_TICKS", 64));
+        wg_order_min = std::max(0, geti("CSF_WG_ORDER_MIN", 2048));
         if (const char *v = getenv("CSF_HANDOUT")) handout_index = expert && std::string(v) == "index" ? 1 : 0;
         rebin_churn = std::max(1, geti("CSF_REBIN_CHURN", 4000));
         hole_reuse = geti("CSF_HOLE_REUSE", 1);
@@ -515,6 +522,23 @@ struct csf_engine {
     bool ev_gather_recorded = false;
     HostBuf<char> snap;       // csf_get_tick: the packed read-back (snap_need bytes), written by the kernels themselves
     DevBuf<uint64_t> trace;   // CSF_TRACE_BLOCKS (measurement aid)
+    // Heaviest group first (csf_wg_order.h, tick.inc: wg_order_apply): two cost tables and two order tables of chunks x groups words.
+    // A pair launch uses table k - the parity of its tick; side by side: of its stream, which is the same thing - so whatever
+    // touches table k sits in one stream, in order: the launch two ticks back wrote cost[k], the order kernel in front of this
+    // launch reads it and writes order[k], this launch reads order[k] and writes cost[k] again; the launch of the tick between,
+    // which may still run on the other stream, has the other pair of tables.
+    struct WgOrder {
+        DevBuf<uint32_t> cost[2];
+        DevBuf<int32_t> order[2];
+        int64_t groups = 0;                  // the grid the tables are laid out for (a launch of another grid gets none of them)
+        int chunks = 0;
+        bool cost_ok[2] = {false, false};    // cost[k] was written by a launch of this grid and these tiles
+        bool order_ok[2] = {false, false};   // order[k] holds a permutation per chunk of this grid
+        int64_t used[2] = {0, 0};            // launches since order[k] was formed
+        int last = -1;                       // the tables of the last tick's pair launch (-1: it kept none), and whether it took an order
+        bool last_ordered = false;
+        void forget() { cost_ok[0] = cost_ok[1] = order_ok[0] = order_ok[1] = false; }   // grid or tiles changed: index order until costs of the new ones are in
+    } wgo;
     DevBuf<uint64_t> atrace;  // CSF_TRACE_AGENT (measurement aid)
     size_t trace_words = 0;
 

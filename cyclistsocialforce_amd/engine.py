@@ -906,6 +906,18 @@ class Engine:
         self._ck(self._lib.csf_mid_ticks(self._h, C.byref(v)))
         return v.value
 
+    def wg_order_tables(self):
+        """(groups, chunks, ordered, cost [chunks, groups] uint32, order [chunks, groups] int32 or None) of the last tick's pair
+        launch (include/csf.h: csf_wg_order_tables); None where that launch kept no tables"""
+        g, c, o = C.c_int64(), C.c_int32(), C.c_int32()
+        self._ck(self._lib.csf_wg_order_tables(self._h, C.byref(g), C.byref(c), C.byref(o), None, None, 0))
+        if g.value == 0:
+            return None
+        cost = np.zeros((c.value, g.value), dtype=np.uint32)
+        order = np.full((c.value, g.value), -1, dtype=np.int32)
+        self._ck(self._lib.csf_wg_order_tables(self._h, C.byref(g), C.byref(c), C.byref(o), _ptr(cost), _ptr(order), cost.size))
+        return g.value, c.value, bool(o.value), cost, (order if o.value else None)
+
     def chase_ticks(self):
         """ticks whose per-agent launch ran beside the pair launch (include/csf.h: csf_chase_ticks)"""
         v = C.c_int64()

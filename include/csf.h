@@ -390,6 +390,16 @@ int csf_near_dropped(csf_engine *e, int64_t *n_dropped);
  * visits first, within a weight class by index - or -1 where cand[r] is empty; weight[r] (may be NULL): the visit's weight.
  * Returns the number of receivers ranked, -1 on bad arguments. */
 int csf_handout_ranks(const uint32_t *cand, const uint32_t *inside, int32_t n, int32_t *rank, int32_t *weight);
+/* The order in which the receiver groups of one source chunk are handed to the pair kernel's workgroups, computed on the host
+ * exactly as the order kernel computes it (csrc/csf_wg_order.h; needs no engine and no device): order[rank] = group, heavier
+ * groups first, equal costs in index order - a permutation of 0 .. n - 1 whatever the costs are.  Returns n, -1 on bad arguments. */
+int csf_wg_order_ranks(const uint32_t *cost, int32_t n, int32_t *order);
+/* Read-back of the tables the last tick's pair launch used (measurement and tests; waits for the device): *groups x *chunks words
+ * each; *ordered: 1 where that launch took its groups by an order table - then order[c * groups + k] is the group workgroup k of chunk
+ * c served -, 0 where it took them in index order (order is left alone); cost[c * groups + g]: what the launch left for group g of
+ * chunk c, 28 x tests + 58 x evaluations.  *groups = 0: that launch kept no tables (another kernel, CSF_WG_ORDER=0, no tick yet).
+ * cost / order may be NULL; both hold `capacity` words, and a grid of more words is CSF_E_ARG. */
+int csf_wg_order_tables(csf_engine *e, int64_t *groups, int32_t *chunks, int32_t *ordered, uint32_t *cost, int32_t *order, int64_t capacity);
 /* Where a sharded engine issues the all-gather of a tick: 0 in stream order on its main stream, 1 on a second stream beside
  * the destination-force phase of the next tick.  Unless CSF_COMM_STREAM=main|second says which, the communicator times both
  * orders itself on its first tick - 32 launches each of the pair kernel + the collective on the records as they are, the

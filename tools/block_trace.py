@@ -3,6 +3,7 @@
 
     CSF_TRACE_BLOCKS=/tmp/trace.bin python3 tools/block_trace.py run      # GPU box: 60 ticks of the bench population
     python3 tools/block_trace.py show gpurun_out/trace.bin                # anywhere: summarise
+    COSTS=/tmp/costs.npy ... run                                           # also the cost table of the last launch (csf_wg_order_tables)
 
 Every wave of pair_cull_kernel stores wall_clock64() (100 MHz) at entry and exit plus HW_ID / XCC_ID; the engine
 writes the records of the LAST launch to the file when it is destroyed.
@@ -27,6 +28,10 @@ def run():
     eng.add_agents(s0, 5.0)
     eng.set_dest_queue(np.arange(n), off, dq, reset=True)
     eng.step(int(os.environ.get("TICKS", "60")), sync=True)
+    if os.environ.get("COSTS"):      # what every workgroup of the last launch left in Dev::wg_cost, [chunks, groups] (tools/wg_order_estimate.py --costs)
+        t = eng.wg_order_tables()
+        if t is not None:
+            np.save(os.environ["COSTS"], t[3])
     eng.close()
 
 
