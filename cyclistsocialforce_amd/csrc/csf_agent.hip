@@ -145,30 +145,16 @@ void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, 
     if (n_ticks <= 0 || count <= 0) return;
     const size_t lds = (size_t)max_nv_pad * sizeof(float4);
     const int pk = pack ? 1 : 0;
-#define CSF_BATCH(MODEL) hipLaunchKernelGGL((small_batch_kernel<MODEL>), dim3((unsigned)count), dim3(64), lds, st, table, count, n_ticks, pk)
-    switch (model) {
-    case CSF_BICYCLE: CSF_BATCH(CSF_BICYCLE); break;
-    case CSF_TWOD: CSF_BATCH(CSF_TWOD); break;
-    case CSF_INVPEND: CSF_BATCH(CSF_INVPEND); break;
-    case CSF_PLANARBIKE: CSF_BATCH(CSF_PLANARBIKE); break;
-    case CSF_BALANCINGRIDER: CSF_BATCH(CSF_BALANCINGRIDER); break;
-    default: CSF_BATCH(CSF_PLANARPOINT); break;
-    }
-#undef CSF_BATCH
+    for_vehicle_class(model, [&](auto m) {
+        hipLaunchKernelGGL((small_batch_kernel<decltype(m)::value>), dim3((unsigned)count), dim3(64), lds, st, table, count, n_ticks, pk);
+    });
 }
 
 void launch_small_tick(const Dev &d, int n_ticks, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
     if (n_ticks <= 0 || d.n <= 0) return;
-#define CSF_SMALL(MODEL) hipExtLaunchKernelGGL((small_tick_kernel<MODEL>), dim3(1), dim3(64), 0, st, t0, t1, 0, d, n_ticks)
-    switch (d.p.model) {
-    case CSF_BICYCLE: CSF_SMALL(CSF_BICYCLE); break;
-    case CSF_TWOD: CSF_SMALL(CSF_TWOD); break;
-    case CSF_INVPEND: CSF_SMALL(CSF_INVPEND); break;
-    case CSF_PLANARBIKE: CSF_SMALL(CSF_PLANARBIKE); break;
-    case CSF_BALANCINGRIDER: CSF_SMALL(CSF_BALANCINGRIDER); break;
-    default: CSF_SMALL(CSF_PLANARPOINT); break;
-    }
-#undef CSF_SMALL
+    for_vehicle_class(d.p.model, [&](auto m) {
+        hipExtLaunchKernelGGL((small_tick_kernel<decltype(m)::value>), dim3(1), dim3(64), 0, st, t0, t1, 0, d, n_ticks);
+    });
 }
 
 // (re)build the fp32 records, the short position ring and the model side-state from the fp64 state:

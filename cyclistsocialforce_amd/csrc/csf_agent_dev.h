@@ -2,7 +2,10 @@
 // state machine, destination force (straight line / spline planner), controller + kinematics of the five rider models,
 // ring-buffer bookkeeping and the fp32 source record, for agent_kernel (csf_agent.hip).  Reference lines are cited at every
 // function.
+// At the end, one piece of HOST code for the translation units that launch these bodies per vehicle class: for_vehicle_class.
 #pragma once
+#include <type_traits>
+
 #include "csf_dev.h"
 #define CSF_HD __device__ __forceinline__
 #include "csf_math64.h"
@@ -1296,6 +1299,20 @@ __device__ __forceinline__ void agent_body(const Dev &d, const int phases, const
     }
     if (tr != nullptr && (threadIdx.x & 63) == 0) tr[6] = wall_clock64();
     stamp(7);
+}
+
+// f(std::integral_constant<int, MODEL>) for the vehicle class of a call (host): turns the class into the template argument of whatever
+// is launched for the six simulated classes, the PlanarPoint's for anything else
+template <class F>
+static void for_vehicle_class(int model, F &&f) {
+    switch (model) {
+    case CSF_BICYCLE: f(std::integral_constant<int, CSF_BICYCLE>{}); break;
+    case CSF_TWOD: f(std::integral_constant<int, CSF_TWOD>{}); break;
+    case CSF_INVPEND: f(std::integral_constant<int, CSF_INVPEND>{}); break;
+    case CSF_PLANARBIKE: f(std::integral_constant<int, CSF_PLANARBIKE>{}); break;
+    case CSF_BALANCINGRIDER: f(std::integral_constant<int, CSF_BALANCINGRIDER>{}); break;
+    default: f(std::integral_constant<int, CSF_PLANARPOINT>{}); break;
+    }
 }
 
 }  // namespace csf

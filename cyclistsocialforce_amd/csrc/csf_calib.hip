@@ -73,16 +73,7 @@ __global__ __launch_bounds__(64) void replay_eval_kernel(const Dev d0, const int
 void launch_replay_eval(const Dev &d, int phases, const CalibDev &c, hipStream_t st) {
     if (d.hi <= 0) return;
     const dim3 g((unsigned)((d.hi + 63) / 64)), b(64);
-#define CSF_CALIB(MODEL) hipLaunchKernelGGL((replay_eval_kernel<MODEL>), g, b, 0, st, d, phases, c)
-    switch (d.p.model) {
-    case CSF_BICYCLE: CSF_CALIB(CSF_BICYCLE); break;
-    case CSF_TWOD: CSF_CALIB(CSF_TWOD); break;
-    case CSF_INVPEND: CSF_CALIB(CSF_INVPEND); break;
-    case CSF_PLANARBIKE: CSF_CALIB(CSF_PLANARBIKE); break;
-    case CSF_BALANCINGRIDER: CSF_CALIB(CSF_BALANCINGRIDER); break;
-    default: CSF_CALIB(CSF_PLANARPOINT); break;
-    }
-#undef CSF_CALIB
+    for_vehicle_class(d.p.model, [&](auto m) { hipLaunchKernelGGL((replay_eval_kernel<decltype(m)::value>), g, b, 0, st, d, phases, c); });
 }
 
 }  // namespace csf

@@ -211,14 +211,7 @@
                 }
                 if (qlen > 0) pass(std::false_type{});
             }
-            // column sum: x in the lower half of the wave, y in the upper, then within the halves (csf_pair.hip)
-            float v = swap_add32(ax, ay);
-            v += dpp<DPP_ROW_ROR8>(v);
-            v += dpp<DPP_XOR1>(v);
-            v += dpp<DPP_XOR2>(v);
-            v += dpp<DPP_HALF_MIRROR>(v);
-            const auto rr = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-            v = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
+            const float v = column_sum_xy(ax, ay);             // (csf_pair_dev.h: x in lanes < 32, y beyond)
             if ((lane & 31) == 0) (&psum[0][0])[2 * item + (lane >> 5)] = v;
             item = nxt;
         }

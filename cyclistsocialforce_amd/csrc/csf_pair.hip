@@ -761,14 +761,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             if (qlen > WAVE) pop(u, std::false_type{});
             else if (qlen > 0) pop_tail(u);
             qx &= ~(2u * (unsigned)CHUNK);      // the queue is empty: the next visit starts at the head of the row
-            if (DYN) {  // column sum of this receiver: x in the lower half of the wave, y in the upper, then within halves
-                float v = swap_add32(ax[0], ay[0]);
-                v += dpp<DPP_ROW_ROR8>(v);
-                v += dpp<DPP_XOR1>(v);
-                v += dpp<DPP_XOR2>(v);
-                v += dpp<DPP_HALF_MIRROR>(v);                              // every lane: the sum of its row of 16
-                const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-                v = __uint_as_float(r[0]) + __uint_as_float(r[1]);          // rows 0+1 (x) in lanes < 32, rows 2+3 (y) beyond
+            if (DYN) {  // column sum of this receiver (csf_pair_dev.h): x in lanes < 32, y beyond
+                const float v = column_sum_xy(ax[0], ay[0]);
                 if ((lane & 31) == 0) racc[lane >> 5][ur] += v;  // one wave per receiver and tile: fixed order, no atomics
                 ax[0] = ay[0] = 0.0f;
             }

@@ -56,6 +56,18 @@ __device__ __forceinline__ float dpp(float x) {
 }
 constexpr int DPP_ROW_ROR8 = 0x128, DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141;
 
+// column sum of ONE receiver's two per-lane accumulators: x in the lower half of the wave, y in the upper, then within the halves.
+// Lanes < 32 end with the sum of ax over the wave, lanes >= 32 with that of ay.  For the kernels that finish one receiver at a time:
+// pair_cull_kernel with receivers handed out (csf_pair.hip) and the mid-size tick (csf_mid_body.inc).
+__device__ __forceinline__ float column_sum_xy(float ax, float ay) {
+    float v = swap_add32(ax, ay);
+    v += dpp<DPP_ROW_ROR8>(v);
+    v += dpp<DPP_XOR1>(v);
+    v += dpp<DPP_XOR2>(v);
+    v += dpp<DPP_HALF_MIRROR>(v);                                  // every lane: the sum of its row of 16
+    return swap_add16(v, v);                                       // rows 0+1 (x) in lanes < 32, rows 2+3 (y) beyond
+}
+
 // reduce8: the butterfly itself - every lane of a group of 8 ends with value `idx` = 4 bit5 + 2 bit4 + bit3 of its lane number
 // (2 u + component: receiver u of the wave, x or y) summed over the wave
 __device__ __forceinline__ float reduce8(int lane, const float (&ax)[RPW], const float (&ay)[RPW], int &idx) {

@@ -66,7 +66,7 @@
 // the rider's class.  SceneLaneHook stands in csf_scene_hook.inc for that; no kernel of this file changed.
 //
 // What exists once ("Folded"): scene_rider_step - the replay write-back or the error terms behind a tick, called by both
-// hooks (csf_scene_hook.inc) -, and for_vehicle_class, which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
+// hooks (csf_scene_hook.inc) -, and for_vehicle_class (csf_agent_dev.h), which turns the class of the call into the template argument of whatever is launched.  scene_restore - a
 // slot becomes a fresh vehicle from the image - serves scene_groups_kernel and SceneLaneHook::seat; scene_eval_kernel has the same lines
 // written out.  The per-set prologue is written out in all four kernels, and scene_groups_kernel / scene_wide_kernel repeat the skeleton
 // of scene_eval_kernel / scene_lanes_kernel: with one function for either, sums and states were no longer the parent's bit for bit.
@@ -423,19 +423,6 @@ __global__ __launch_bounds__(256) void scene_wide_groups_kernel(const Dev *__res
     for (int r = c.roff[scn] + lane; r < c.roff[scn + 1]; r += (int)blockDim.x)
         if (c.win_enter[r] >= c.win_exit[r]) c.sums[row0 + r] = make_double2(0.0, 0.0);
     if (lane < n) hook.flush();
-}
-
-// f(std::integral_constant<int, MODEL>) for the vehicle class of the call (host)
-template <class F>
-static void for_vehicle_class(int model, F &&f) {
-    switch (model) {
-    case CSF_BICYCLE: f(std::integral_constant<int, CSF_BICYCLE>{}); break;
-    case CSF_TWOD: f(std::integral_constant<int, CSF_TWOD>{}); break;
-    case CSF_INVPEND: f(std::integral_constant<int, CSF_INVPEND>{}); break;
-    case CSF_PLANARBIKE: f(std::integral_constant<int, CSF_PLANARBIKE>{}); break;
-    case CSF_BALANCINGRIDER: f(std::integral_constant<int, CSF_BALANCINGRIDER>{}); break;
-    default: f(std::integral_constant<int, CSF_PLANARPOINT>{}); break;
-    }
 }
 
 int launch_scene_eval(int model, const Dev *table, const SceneSet *sets, const SceneDev &c, hipStream_t st, const SceneWideDev *w) {

@@ -3,6 +3,10 @@
 // include and not a __device__ function of a translation unit of its own, as csf_mid_body.inc is (DESIGN.md 4.6d): the kernels of
 // csf_agent.hip keep the instruction stream they had when the body stood in that file.
 //
+// wide_tick_body (csf_wide_body.inc) is this body for a workgroup.  What the two share as functions stands in csf_tick_terms.h, included
+// below: the Bicycle field's entry of a lane.  The pair loop, the road loop and the switch to agent_body<M> are still written out in both -
+// marked TWIN COPY or with a note: a change in one is made in the other.
+//
 // HOOK: what a caller does behind every tick - hook(d, t, lane, n) is called by all 64 lanes once the tick's stores are issued
 // (lanes 0 .. n - 1 have just written their road user's state: their own stores, program order).  NoTickHook is empty and
 // compiles to nothing; csf_scene.hip sums an error there.
@@ -46,6 +50,8 @@
 // and returning for a lane of another class; the UncontrolledVehicle's class is among them.  A hook without the member has it false
 // (HookByClass), and every line of it stands under that condition.
 constexpr int SMALL_MIXED = -1;   // (no enum csf_model)
+
+#include "csf_tick_terms.h"   // bicycle_se: shared with csf_wide_body.inc
 
 template <class H, class = void>
 struct HookByClass { static constexpr bool value = false; };
@@ -133,16 +139,18 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         bool bike = MODEL == CSF_BICYCLE;
         if constexpr (MIXED) bike = hook.own_model() == CSF_BICYCLE;
         if (bike && lane < n) {                                    // (what write_record keeps in rec2 for the pair kernels)
-            const double v = d.s[3 * cap + a];
             double vref = d.p.v_max_riding[1];
             if constexpr (HOOK::GROUPS) vref = hook.v_ref(lane);   // (the lane's own set: what write_record takes for rec2)
-            const double e = v > 0.0 ? fmin(pow(v / vref, 0.1), 0.7) : 0.0;
-            se[lane] = make_float2((float)e, (float)(1.0 / sqrt(1.0 - e * e)));
+            se[lane] = bicycle_se(d.s[3 * cap + a], vref);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const Recv r{0.f, 0.f, (float)cp, (float)sp};
         double rx = 0.0, ry = 0.0;
+        // (TRIED: the body of this loop from `ex = x - xs` to `ry += wy` as exact_pair_term(...) of csf_tick_terms.h, for both bodies.  In the
+        // shape that kept the parent's bits - the sum in and out by value - it kept every resource figure and opcode count too, but over five
+        // rounds 6 of 92 figures were slower than the parent by more than its spread, scene_eval_kernel<TwoD> at 256 sets by 0.7 %:
+        // profiles/tick_terms_ab.txt, 1. and 3.  So the loop stays written out twice.)
         // (TWIN COPY: the pair loop of wide_tick_body, csf_wide_body.inc, is this loop for a workgroup; a change here is made there too)
         for (int j = grp; j < n; j += G) {                         // (lanes of one group: the same j)
             const double xs = sx[j], ys = sy[j], ps = spsi[j];
@@ -191,6 +199,9 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
             ry += __shfl_xor(ry, o, WAVE);
         }
         if (nvp > 0) {
+            // (TRIED: this loop as road_term_share(d, srv, nvp, x, y, grp, G) of csf_tick_terms.h, for both bodies - the same bits and the same
+            // resource figures, but figures of the scene kernels slower than the parent's by more than its spread: profiles/tick_terms_ab.txt, 4.
+            // The loop of wide_tick_body, csf_wide_body.inc, is the other copy: a change here is made there too.)
             // vertices as offsets from the origin of their tile of 1 024 (csf_dev.h: rv, rvo): the receiver's offset from it is formed
             // in fp64; the sum as road_kernel forms it (fp32, r^-(sigma+1) as a power of rsq(r^2) where every edge shares an integer sigma)
             float qx = 0.f, qy = 0.f;
@@ -222,6 +233,7 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
         }
         __builtin_amdgcn_wave_barrier();                          // (the staged snapshot is read by every lane before it is renewed)
         if constexpr (HookByClass<HOOK>::value) {
+            // (TRIED: one agent_body_of_class<HET, WITH_UNCONTROLLED> for this switch and its two twins - SGPR spills and AGPRs of all six kernels that hold it moved: profiles/tick_terms_resource_usage.txt, 3.)
             constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
 #pragma nounroll
             for (int m = 0; m < 7; m++) {                          // (uniform: the classes of the population, a kernel argument)
@@ -246,6 +258,7 @@ __device__ __forceinline__ void small_tick_body(const Dev &d, const int n_ticks,
                 hook.select(dg, g);
                 if constexpr (MIXED) {
                     constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
+                    // (the switch of BY_CLASS above without the UncontrolledVehicle, and the one of csf_wide_body.inc: see the note there)
                     switch (hook.group_model(g)) {                  // (uniform: the class of the group, from its record)
                     case CSF_BICYCLE: if (turn) agent_body<CSF_BICYCLE, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;
                     case CSF_TWOD: if (turn) agent_body<CSF_TWOD, false, true>(dg, PH, lane, nullptr, ka_lines, rx, ry, rec_slot); break;

@@ -1,6 +1,7 @@
 // csf_wide_body.inc - the tick of csf_small_body.inc for ONE WORKGROUP of 256 threads: 33 .. WIDE_MAX road users present at once
 // (DESIGN.md 4.10f).  Included by csf_scene.hip (scene_wide_kernel) and by csf_scene_mixed.hip (scene_wide_mixed_kernel) inside namespace
-// csf, behind csf_small_body.inc.
+// csf, behind csf_small_body.inc - and so behind csf_tick_terms.h (bicycle_se).  The pair loop, the road loop and the switch to
+// agent_body<M> are second copies of small_tick_body's, marked below.
 //
 // Thread = (receiver, source group) as in the one-wave tick, over four waves: with P the power of two that holds the lanes - 64, 128
 // or 256, never less than a wave - and G = 256 / P, thread tid has receiver i = tid & (P - 1) and source group grp = tid / P; source j
@@ -75,11 +76,9 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
             bool bike = MODEL == CSF_BICYCLE;
             if constexpr (MIXED) bike = hook.own_model() == CSF_BICYCLE;   // (the class of the rider the takeover above has seated)
             if (bike) {
-                const double v = d.s[3 * cap + tid];
                 double vref = d.p.v_max_riding[1];
                 if constexpr (HOOK::GROUPS) vref = hook.v_ref(tid);   // (the lane's own set, as in small_tick_body)
-                const double e = v > 0.0 ? fmin(pow(v / vref, 0.1), 0.7) : 0.0;
-                se[tid] = make_float2((float)e, (float)(1.0 / sqrt(1.0 - e * e)));
+                se[tid] = bicycle_se(d.s[3 * cap + tid], vref);
             }
         }
         __syncthreads();                                          // barrier 1: the staging of this tick is complete
@@ -135,6 +134,7 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
         if (nvp > 0) {
             // the road term as small_tick_body forms it (vertices as offsets from the origin of their tile of 1 024, fp32 sum), the
             // vertices of a tile shared between the groups
+            // (the second copy of that loop: see the note there; a change there is made here too)
             float qx = 0.f, qy = 0.f;
             const double bx = x - d.ox, by = y - d.oy;
             for (int base = 0; base < nvp; base += 1024) {
@@ -196,6 +196,7 @@ __device__ __forceinline__ void wide_tick_body(const Dev &d, const int n_ticks, 
                 hook.select(dg, g);
                 if constexpr (MIXED) {
                     constexpr int PH = PH_DEST | PH_COMBINE | PH_INTEGRATE;
+                    // (the switch of small_tick_body, csf_small_body.inc - written out a third time: see the note there)
                     switch (hook.group_model(g)) {                  // (uniform: the class of the group, from its record)
                     case CSF_BICYCLE: if (turn) agent_body<CSF_BICYCLE, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;
                     case CSF_TWOD: if (turn) agent_body<CSF_TWOD, false, true>(dg, PH, tid, nullptr, 0u, rx, ry, -1); break;

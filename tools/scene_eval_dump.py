@@ -30,6 +30,11 @@ The data sets are the smallest that reach every piece the kernels of csf_scene.h
          order md, m, mc: md runs with the road of d still held, mc adds to m.  Reordering the cases changes what is dumped.)
     k    csf_calib_load / csf_calib_eval of 3 sequences (the second 45 ticks long), with and without fix_speed: k1, k0
                                                                                    replay_eval_kernel
+    x    a wide scene of 40 riders at once whose start reaches the two rare branches of the exact pair term (the pair loops of csf_small_body.inc / csf_wide_body.inc): riders 0
+         and 1 on the very same spot (receiver - source = (0, 0): no term), and rider 3 exactly on the heading line of rider 2 - source
+         at (10, 10) with psi = 0, receiver at (15, 10) looking back at it -, so the sign of phi is undecided in fp32, exactly 0 in fp64, and the term is
+         projected on the line.  (The last case of every model: the dumps of the cases above stay what they were.)
+                                                                                   scene_wide_kernel
 """
 import argparse
 import os
@@ -48,7 +53,7 @@ from scene_calib_common import MODELS, VDES, scenes  # noqa: E402
 from scene_groups_common import group_sets  # noqa: E402
 from scene_lanes_common import greedy_lanes, loaded_shared, roster  # noqa: E402
 from scene_mixed_common import mixed_sets  # noqa: E402
-from scene_wide_common import edge_below, loaded_wide, wide_crowd  # noqa: E402
+from scene_wide_common import always, edge_below, loaded_wide, wide_crowd  # noqa: E402
 from scene_windows_common import FEAT, one_scene, sets3  # noqa: E402
 
 T, STRIDE = 60, 10
@@ -180,6 +185,23 @@ def wide_cases(model, out):
     e.close()
 
 
+def exact_cases(model, out):
+    # (that the start takes the two branches rests on the geometry and on the conditions in the source, not on a counter: see
+    # tools/small_tick_dump.py, exact())
+    sets = sets3(model)
+    s0, off, dq = wide_crowd(model, 40)
+    s0 = s0.copy()
+    s0[1, :2] = s0[0, :2]                                         # the very same spot
+    s0[2, :3] = 10.0, 10.0, 0.0                                   # cos = 1, sin = 0 exactly
+    s0[3, :3] = 15.0, 10.0, -3.0                                  # 5 m straight ahead of rider 2 (phi = 0), facing it: rider 2 is in its view,
+                                                                  # and to its right, so under the priority rule as well
+    lanes, enter, exit_ = always(40, T)
+    obj = np.random.default_rng(15).normal(size=(T, 40, len(FEAT)))
+    e = loaded_wide(sets, [(s0, off, dq)], [lanes], enter, exit_, obj)
+    out["x"] = e.scene_calib_eval(sets, states=True, stride=STRIDE)
+    e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -193,6 +215,7 @@ def main():
         shared_cases(model, out)
         wide_cases(model, out)
         replay_cases(model, out)
+        exact_cases(model, out)
         for case, (sums, states) in out.items():
             assert np.isfinite(sums).all() and np.any(sums != 0.0) and np.isfinite(states).any(), (model, case)
             arrays[f"{model}.{case}.sums"], arrays[f"{model}.{case}.states"] = sums, states
