@@ -46,6 +46,7 @@ SYMBOLS = (
     "csf_small_classes",
     "csf_handout_ranks",
     "csf_wg_order_ranks", "csf_wg_order_tables",
+    "csf_pair_shape_of", "csf_pair_shape_words",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -91,6 +92,21 @@ class EngineError(RuntimeError):
 
 
 _lib = None
+
+# csf_pair_shape_of (include/csf.h): the input words and the words of the answer, in order
+PAIR_SHAPE_IN, PAIR_SHAPE_OUT = 16, 15
+PAIR_SHAPE_INPUTS = ("p2r", "n_classes", "has_bike", "model_mask", "model", "classify", "recs_valid", "pair_variant", "recv_binned", "rpb", "wide",
+                     "reach", "tables", "segments", "nloc")
+PAIR_SHAPE_FIELDS = ("family", "field", "rw", "p2r", "classify", "binr", "ord", "reach", "rpb", "cw", "per_group", "threads", "tile", "grid_x", "order_groups")
+
+
+def pair_shape_of(lib, words):
+    """the answer of csf_pair_shape_of for PAIR_SHAPE_IN int32 input words (a ctypes array), as a dict with the kernel's name"""
+    out = (C.c_int32 * PAIR_SHAPE_OUT)()
+    name = C.c_char_p()
+    if lib.csf_pair_shape_of(words, out, C.byref(name)) != PAIR_SHAPE_OUT:
+        raise EngineError("csf_pair_shape_of refused its arguments")
+    return dict(zip(PAIR_SHAPE_FIELDS, out), name=name.value.decode())
 
 
 def load():
@@ -173,6 +189,9 @@ def load():
     if hasattr(L, "csf_wg_order_ranks"):
         L.csf_wg_order_ranks.argtypes = [C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_int32)]
         L.csf_wg_order_tables.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), vp, vp, i64]
+    if hasattr(L, "csf_pair_shape_of"):
+        L.csf_pair_shape_of.argtypes = [C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_char_p)]
+        L.csf_pair_shape_words.argtypes = [vp, C.POINTER(i32)]
     L.csf_comm_stream_order.argtypes = [vp, C.POINTER(i32), dp]
     L.csf_small_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]

@@ -116,8 +116,8 @@ struct Dev {
     int32_t back;      // int(1 / t_s) — vehicle.py:1487
     int32_t n_split;   // source chunks of the pair kernel (every one of them holds sources: csf_engine.hip set_shard)
     int32_t chunk_units;  // batches of 64 records per source chunk
-    int32_t dyn_recv;  // cull kernel: receivers handed to the waves of a workgroup dynamically
-    int32_t rpb;       // ... and receivers per workgroup then: 16 or 32
+    int32_t spare0;    // (unused: keeps the offsets of the members behind it - once dyn_recv)
+    int32_t rpb;       // cull kernel: receivers per workgroup, 16 or 32
     int32_t wide;      // rpb 32, receivers in slot order: workgroups of 8 waves on tiles of 2048 sources (chunk_units is then 32)
     int32_t pair_variant;  // 0: cull-first kernel on binned records (default), 1: evaluate-then-mask, 2: cull-first, unbinned
     int32_t classify;      // the records are binned and every batch of 64 carries a bounding circle
@@ -285,6 +285,24 @@ enum : int { PH_DEST = 1, PH_COMBINE = 2, PH_INTEGRATE = 4, PH_FIXSPEED = 8 };
 // t0 / t1 (may be NULL): HIP events that receive the start / end time stamp of the kernel itself (hipExtLaunchKernelGGL:
 // taken from the dispatch packet, no extra barrier packet in the stream as with hipEventRecord)
 void launch_pair(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// What a pair launch takes (csf_pair.hip: pair_shape, the one place that reads pair_variant, classify, recv_binned, recs_valid,
+// rpb, wide, pc.reach, n_classes, has_bike, model_mask, p.model and wg_cost for this): kernel and template arguments, grid unit, name.
+struct PairShape {
+    enum : int32_t { NONE, HET, PLAIN, BIKE, CULL, CULL_SEG };   // nothing to launch / pair_kernel, the source's own set per pair /
+                                                                 // pair_kernel / pair_bike_kernel / pair_cull_kernel / ... one grid for all runs
+    int32_t family;
+    int32_t field;       // HET: 0 TwoD, 1 Bicycle, 2 the source's class; PLAIN: 0, 1
+    int32_t rw;          // BIKE: receivers per wave, 4 or 8
+    int32_t p2r;
+    int32_t classify, binr, ord, reach;   // cull family: template arguments of the same names
+    int32_t rpb, cw;     // ... 16 or 32 receivers, 4 or 8 waves (whatever the family: what the candidate lists are built for)
+    int32_t per_group;   // receivers per workgroup of the launch: gridDim.x = ceil(receivers / per_group)
+    int32_t threads;     // threads per workgroup
+    const char *name;    // for profiles and the bench line
+    int32_t tile() const { return cw * 256; }   // sources of an LDS tile of the cull family: 1024 or 2048
+    int64_t groups(int64_t receivers) const { return receivers > 0 ? (receivers + per_group - 1) / per_group : 0; }   // gridDim.x
+};
+PairShape pair_shape(const Dev &d, bool segments = false);   // segments: the one-grid launch of launch_pair_segments
 // receiver groups of launch_pair's grid where it takes a kernel that reads Dev::wg_order / writes Dev::wg_cost, else 0
 int64_t pair_order_groups(const Dev &d);
 // csf_bin.hip: order[c * groups + rank] = group for every source chunk c, heaviest first by cost[c * groups + group] (csf_wg_order.h)

@@ -52,6 +52,22 @@
 
 namespace csf {
 
+// Column sums and store of a wave's four receivers (pair_kernel, pair_bike_kernel).  agent_of: the receivers' slots (LDS), NULL: j0 + u.
+// No caller passes one since the static hand-out went; it stays, and the function stays visible (`used`: one uncalled
+// copy in the code object), because with NULL at every call site the compiler folds the argument BEFORE inlining, and the same source
+// then gives both kernels another register allocation - pair_bike_kernel<false, 8> 82 VGPRs for 79, 5 waves per SIMD for 6, - 5.5 % at
+// 16 384 Bicycle riders (profiles/pair_shape_ab.txt, session 1).  Visible, it is folded at inlining as ever: the parent's instructions.
+__attribute__((used)) __device__ __forceinline__ void reduce_store(const Dev &d, int64_t j0, int lane, const float (&ax)[RPW],
+                                                                    const float (&ay)[RPW], const int *agent_of = nullptr) {
+    int idx;
+    const float z = reduce8(lane, ax, ay, idx);
+    const int u = idx >> 1;
+    const int64_t a = agent_of ? (int64_t)agent_of[u] : (j0 + u < d.hi ? j0 + u : -1);
+    if ((lane & 7) == 0 && a >= 0) {
+        float *dst = (float *)&d.part[(int64_t)(d.part_base + blockIdx.y) * d.cap + a];
+        dst[idx & 1] = z;
+    }
+}
 
 // ---- culling kernel (TwoD field): classify batches -> test -> ballot -> LDS queue -> field, two sources per lane ---------
 // CLASSIFY: the records are streamed in spatially binned order (csf_bin.hip) and every batch of 64 carries a
@@ -71,10 +87,9 @@ namespace csf {
 // of the scene - 6e-5 m would be the resolution of scene coordinates in the 1 600 m of config 5.  (Smaller populations take their
 // receivers in slot order: a workgroup then holds a random sample of receivers and every workgroup carries the same
 // load - with neighbours the few workgroups whose tile lies in front of ALL their receivers end the kernel 10 % later.)
-// DYN (small receiver blocks, i.e. shards of a small population: launch_pair): the 16 receivers of the workgroup are
-// handed to its waves one at a time through an LDS counter instead of four per wave.  With few workgroups the kernel
-// ends with its longest single wave (a lone wave issues one dependent instruction every ~8 cycles); sharing the
-// receivers shortens that wave.  At full size the SIMDs are issue-bound either way and the variant is not used.
+// HAND-OUT: the receivers of the workgroup are handed to its waves one at a time through an LDS counter.  With few workgroups
+// the kernel ends with its longest single wave (a lone wave issues one dependent instruction every ~8 cycles); sharing the
+// receivers shortens that wave.  (Four fixed receivers per wave was the alternative until DESIGN.md A.3 retired it.)
 // HEAVIEST FIRST (receivers in slot order; csf_handout.h): a workgroup's ~16 non-empty visits to a tile take 1 to 16 sift passes each,
 // known from the batch masks, and handed out in index order a wave that claims a long visit last holds the workgroup - 39.6 KB of
 // LDS, eight wave slots - while its siblings wait at the last barrier: at the headline 12.1 % of a workgroup's wave-slot time passed
@@ -91,22 +106,23 @@ namespace csf {
 // tail.  No sum depends on it - a group's sums go to part[(part_base + by) * cap + agent], whoever computes them - and any
 // permutation will do, which is all the order kernel guarantees (profiles/wg_order_estimate.txt, wg_order_experiment.txt, wg_order_ab.txt).
 // The circles of the next tick, the trace record and the through-counter stay on blockIdx.x.
-// RPB: receivers of a workgroup, 16, or 32 where the grid stays large enough (DYN only: with dynamic hand-out a
-// workgroup of twice the receivers shares one tile fill and one start-up between them: 146 -> 141 us at N = 16 384)
+// RPB: receivers of a workgroup, 16, or 32 where the grid stays large enough (a workgroup of twice the receivers
+// shares one tile fill and one start-up between them: 146 -> 141 us at N = 16 384)
 // REACH (with the far-field cull on): every candidate batch goes through the reach test keep_x2 (two sources per lane), two batches at a
 // time, and only the sources it keeps are queued for the field.
-// CW: waves of a workgroup, 4, or 8 (DYN, RPB 32: launch_cull_dyn): a workgroup of 8 waves holds a
+// CW: waves of a workgroup, 4, or 8 (classified batches; pair_shape has the sizes): a workgroup of 8 waves holds a
 // tile of 2048 sources (32 batches), so a visit - one receiver against one tile - covers twice the sources: half the visits
 // (each with its claim, record, column sum), and twice the sources to evaluate per visit, i.e. fuller evaluation passes.
 // SEG (several parameter sets in the class-segmented order, csf_engine.hip: rebin): ONE grid for the runs of all sets whose
 // field is the TwoD one - blockIdx.y counts the source chunks of all runs, and a workgroup takes its run's constants, source
 // range and partial-sum slots from Dev::segtab (a launch per run left the device idle while each run's last workgroups ended).
-// ORD (heaviest group first, below): the instances that read Dev::wg_order and leave Dev::wg_cost.  launch_cull takes them only for a
-// launch that was given the tables; every other launch runs the instance without a single instruction of it.
-template <bool P2R, bool CLASSIFY, bool BINR, bool DYN, int RPB = WPB * RPW, bool REACH = false, int CW = WPB, bool SEG = false, bool ORD = false>
+// ORD (heaviest group first, below): the instances that read Dev::wg_order and leave Dev::wg_cost.  pair_shape takes them only for a
+// launch that was given the tables; every other launch runs the instance without a single instruction of it.  (pair_shape, below,
+// decides which of all these a launch takes; launch_cull lists the instances that exist.)
+template <bool P2R, bool CLASSIFY, bool BINR, int RPB, bool REACH, int CW, bool SEG, bool ORD>
 __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(const Dev dk) {
-    static_assert(!ORD || (DYN && CLASSIFY && !BINR && !SEG), "the order tables are built into the classified variants with receivers in slot order, one grid");
-    static_assert(!SEG || (DYN && CLASSIFY && !BINR), "the segmented grid is built into the classified variants with receivers in slot order");
+    static_assert(!ORD || (CLASSIFY && !BINR && !SEG), "the order tables are built into the classified variants with receivers in slot order, one grid");
+    static_assert(!SEG || (CLASSIFY && !BINR), "the segmented grid is built into the classified variants with receivers in slot order");
     Dev dseg;
     int by = (int)blockIdx.y;
     double seg_hfov = 0.0;
@@ -129,8 +145,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         seg_hfov = t.hfov;
     }
     const Dev &d = SEG ? (const Dev &)dseg : dk;
-    static_assert(RPB == WPB * RPW || (DYN && (RPB % (WPB * RPW) == 0 || RPB == 2 * RPW) && RPB <= WAVE), "other workgroup sizes need the dynamic hand-out");
-    static_assert(CW == WPB || (CW == 2 * WPB && DYN && CLASSIFY && (RPB == 32 || RPB == 16)), "the wide workgroup is built into the variants with 16 / 32 receivers");
+    static_assert(RPB == 16 || RPB == 32, "a workgroup serves 16 or 32 receivers: one lane each in the hand-out's ranks");
+    static_assert(CW == WPB || (CW == 2 * WPB && CLASSIFY), "the wide workgroup is built into the classified variants");
     constexpr int BLOCKW = CW * WAVE;             // threads of a workgroup
     // the sift and the field pass as plain f32 instructions, receiver and field-of-view band in vector registers (header, item 2) -
     // in the variants with the reach test.  Without it (CSF_FAR_EPS=0) nearly all the work is the field, where the packed form is the
@@ -140,7 +156,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
     constexpr int NBT = TL / WAVE;                // batches of a tile: 16 or 32
     constexpr int RPP = WAVE / NBT;               // receivers one classification pass of a wave covers: 4 or 2
     constexpr unsigned NBMASK = NBT >= 32 ? 0xFFFFFFFFu : ((1u << (NBT & 31)) - 1u);
-    static_assert(!REACH || (CLASSIFY && DYN), "the reach test is built into the classified, dynamically handed-out variant");
+    static_assert(!REACH || CLASSIFY, "the reach test is built into the classified variants");
     // The tile, 16 TL bytes, in one of two layouts over the same storage:
     //   packed form (no reach test): SoA, tx | ty | tc | ts - the two records of a lane load straight into the halves of a packed
     //     register pair, four ds_read_b32 per record;
@@ -155,16 +171,15 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                                                  // into the tile: 4 x index <= 8 188 (SoA), 16 x index <= 32 752 (AoS)
     __shared__ float4 rrec[RPB];
     __shared__ int ragent[RPB];              // slot of every receiver of the workgroup (-1: none)
-    __shared__ unsigned bmask[DYN ? RPB : 1];   // DYN: candidate (| inside << 16, 16 batches) batch masks of every receiver
-    __shared__ unsigned bmask_in[DYN && NBT > 16 ? RPB : 1];   // 32 batches: the inside masks
+    __shared__ unsigned bmask[RPB];          // candidate (| inside << 16, 16 batches) batch masks of every receiver
+    __shared__ unsigned bmask_in[NBT > 16 ? RPB : 1];   // 32 batches: the inside masks
     constexpr int NCAP = 32;                           // near pairs noted by one wave and tile: receiver << 16 | tile index (32, not
                                                        // 64: with 256 bytes less a workgroup fits 20 KB of LDS, eight to a CU)
     __shared__ unsigned nlist[CW][NCAP];
-    __shared__ float racc[2][DYN ? RPB : 1];    // DYN: column sums of the workgroup's receivers
+    __shared__ float racc[2][RPB];           // column sums of the workgroup's receivers
     __shared__ int next_recv;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t j0 = d.lo + ((int64_t)blockIdx.x * CW + wave) * RPW;
     int64_t ibeg, iend;
     source_chunk(d, ibeg, iend, by);
     constexpr bool ORDERED = ORD;   // HEAVIEST GROUP FIRST (csf_wg_order.h)
@@ -184,7 +199,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             batch_circle(d, b, lane, d.bnd_margin, d.bnd_next, d.part4 != nullptr);
     }
 
-    float ax[RPW], ay[RPW];     // the receivers themselves stay in LDS (rrec); one at a time is held in registers
+    float ax[RPW], ay[RPW];     // slot 0: this lane's share of the receiver being worked on (the receivers themselves stay in LDS, rrec;
+                                // arrays, and the slot handed down as `u`: as two scalars the compiler orders the kernel differently)
     // Wave-uniform ring state of the queue.  qx: BYTE offset of the head entry within `queue`, qlen: entries queued.  A visit starts
     // with the head at the start of the wave's row and a full pass pops exactly CHUNK = QCAP / 2 entries, so the head only ever sits
     // at entry 0 or CHUNK of the row: a pass reads 2 * CHUNK bytes from qx on without wrapping, and an entry L < QCAP places
@@ -236,7 +252,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(qa) : "v"(lane), "s"(qx));
         return qa;
     };
-    // pop CHUNK (or, when draining, whatever is left) queued sources of receiver u; the field takes two per lane
+    // pop CHUNK (or, when draining, whatever is left) queued sources of the receiver (accumulator slot u); the field takes two per lane
     auto pop = [&](int u, auto full) {
         constexpr bool FULL = decltype(full)::value;
         const int n = FULL ? CHUNK : (qlen < CHUNK ? qlen : CHUNK);
@@ -328,7 +344,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             if (BINR) bb.x -= og.x, bb.y -= og.y;
             tbnd[tid] = bb;
         }
-        if (DYN && tid == BLOCKW - 1) next_recv = 0;
+        if (tid == BLOCKW - 1) next_recv = 0;
     };
     // BINR: the tiles this receiver group can meet before the next re-binning are listed (csf_dev.h: Dev::clist) - the workgroup
     // takes its share of the list (source chunk c of n: entries [c L / n, (c + 1) L / n)) and of the tiles of the sentinel
@@ -376,7 +392,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             }
             ragent[threadIdx.x] = j < d.hi ? (int)jc : -1;
         }
-        if (DYN) racc[0][threadIdx.x] = racc[1][threadIdx.x] = 0.0f;
+        racc[0][threadIdx.x] = racc[1][threadIdx.x] = 0.0f;
     }
     __syncthreads();
     float gx = 0.f, gy = 0.f, gr = 0.f;   // BINR: bounding circle of the workgroup's receivers (the same in every wave)
@@ -451,22 +467,20 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             fill_tile(base, cnt, tid);
             __syncthreads();
         }
-        // classification of the tile's (at most 16) batches for all four receivers in one pass:
+        // classification of the tile's (at most 16) batches for four receivers in one pass of a wave:
         // lanes 16u .. 16u+15 hold receiver u, lane & 15 selects the batch
-        static_assert((NBT == 16 || NBT == 32) && RPW == 4, "one classification pass covers 4 receivers x 16 batches, or 2 x 32");
-        unsigned long long cand_all = ~0ull, inside_all = 0ull;
+        static_assert(NBT == 16 || NBT == 32, "one classification pass covers 4 receivers x 16 batches, or 2 x 32");
         if (CLASSIFY) {
-            constexpr int PASSES = RPB >= CW * RPP ? RPB / (CW * RPP) : 1;   // four receivers x 16 batches per pass (two x 32)
+            static_assert(RPB % (CW * RPP) == 0, "every wave classifies the same number of receivers");
+            constexpr int PASSES = RPB / (CW * RPP);     // four receivers x 16 batches per pass (two x 32)
 #pragma unroll
             for (int ps = 0; ps < PASSES; ps++) {
-                if (RPB < CW * RPP && wave * RPP >= RPB) break;   // (8 receivers: two waves classify)
                 const int r0 = (wave * PASSES + ps) * RPP;   // first receiver of this pass
                 bool out, in;
                 classify_batch<P2R>(k, rrec[r0 + ln / NBT], tbnd[ln & (NBT - 1)], out, in);
                 const bool valid = (ln & (NBT - 1)) < nb;
-                cand_all = ballot1(valid & !out);
-                inside_all = ballot1(valid & in);
-                if (DYN && ln < RPP) {
+                const unsigned long long cand_all = ballot1(valid & !out), inside_all = ballot1(valid & in);
+                if (ln < RPP) {
                     if (NBT > 16) {
                         bmask[r0 + ln] = (unsigned)(cand_all >> ((NBT & 63) * ln)) & NBMASK;
                         bmask_in[r0 + ln] = (unsigned)(inside_all >> ((NBT & 63) * ln)) & NBMASK;
@@ -476,7 +490,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                     }
                 }
             }
-            if (DYN) __syncthreads();
+            __syncthreads();
         }
         // The near pairs this wave has noted in this tile (receiver, tile index), one per lane: the pair from the precise
         // records (precise_delta: two levels of global loads - once per wave and tile, not per receiver), field of view
@@ -545,16 +559,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                 const int ui = __builtin_amdgcn_readlane(urn, i);
                 const float vx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(fx), i));
                 const float vy = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(fy), i));
-                if (DYN) {
-                    if (lane == 0) racc[0][ui] += vx, racc[1][ui] += vy;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < RPW; q++) {
-                        const bool mine = (lane == 0) & (ui == wave * RPW + q);
-                        ax[q] += mine ? vx : 0.0f;
-                        ay[q] += mine ? vy : 0.0f;
-                    }
-                }
+                if (lane == 0) racc[0][ui] += vx, racc[1][ui] += vy;
             }
             evals += (unsigned)nlen;
             nlen = 0;
@@ -565,7 +570,7 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         // receiver r) and only the receivers some batch can act on are handed out: the k-th claim is the k-th such receiver.
         // With receivers in binned order (neighbours: a tile concerns all of them or, mostly, none - and then it was never
         // loaded) an empty visit is just left at once.
-        constexpr bool COMPACT = DYN && CLASSIFY && !BINR;
+        constexpr bool COMPACT = CLASSIFY && !BINR;
         const unsigned live = nb >= NBT ? NBMASK : ((1u << (nb & 31)) - 1u);
         // HEAVIEST FIRST (csf_handout.h): a visit's sift passes are known from its masks, 1 to 16 of them, and a wave that claims a
         // long visit last keeps the workgroup - its LDS, its eight wave slots - while its siblings wait at the barrier.  Lane r ranks
@@ -600,8 +605,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
         }
         const int n_wanted = COMPACT ? __builtin_popcountll(wanted) : RPB;
         // one VISIT: receiver ur of the workgroup (batch masks bm / bm_in) against this tile
-        auto visit = [&](int ur, unsigned bm, unsigned bm_in, int uu) {
-            const int u = DYN ? 0 : uu;               // accumulator slot
+        auto visit = [&](int ur, unsigned bm, unsigned bm_in) {
+            constexpr int u = 0;                      // accumulator slot
             cur_recv = ur;
             {
                 const float4 q = rrec[ur];
@@ -622,8 +627,8 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
                     ru.s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(q.w)));
                 }
             }
-            unsigned cand = ((DYN && CLASSIFY) ? (NBT > 16 ? bm : (bm & 0xFFFFu)) : (unsigned)(cand_all >> (16 * u))) & live;
-            const unsigned inside = ((DYN && CLASSIFY) ? (NBT > 16 ? bm_in : (bm >> 16)) : (unsigned)(inside_all >> (16 * u))) & live;
+            unsigned cand = (CLASSIFY ? (NBT > 16 ? bm : (bm & 0xFFFFu)) : ~0u) & live;      // (unclassified: every batch is a candidate)
+            const unsigned inside = (CLASSIFY ? (NBT > 16 ? bm_in : (bm >> 16)) : 0u) & live;
             if (REACH) {
                 tests += (unsigned)WAVE * (unsigned)__builtin_popcount(cand | inside);   // every candidate batch goes through the per-lane test
                 // two candidate batches at a time through the reach test, two sources per lane (+ the exact field-of-view test unless
@@ -761,96 +766,85 @@ __global__ __launch_bounds__(CW * WAVE, CSF_CULL_WAVES) void pair_cull_kernel(co
             if (qlen > WAVE) pop(u, std::false_type{});
             else if (qlen > 0) pop_tail(u);
             qx &= ~(2u * (unsigned)CHUNK);      // the queue is empty: the next visit starts at the head of the row
-            if (DYN) {  // column sum of this receiver (csf_pair_dev.h): x in lanes < 32, y beyond
-                const float v = column_sum_xy(ax[0], ay[0]);
-                if ((lane & 31) == 0) racc[lane >> 5][ur] += v;  // one wave per receiver and tile: fixed order, no atomics
-                ax[0] = ay[0] = 0.0f;
-            }
+            // column sum of this receiver (csf_pair_dev.h): x in lanes < 32, y beyond
+            const float v = column_sum_xy(ax[0], ay[0]);
+            if ((lane & 31) == 0) racc[lane >> 5][ur] += v;  // one wave per receiver and tile: fixed order, no atomics
+            ax[0] = ay[0] = 0.0f;
         };
-        if (DYN) {
-            // receivers are claimed from the workgroup's counter until none is left; the wave's list of noted pairs is
-            // corrected when the tile is done - or, in a crowd, as soon as it is half full, between two receivers (every
-            // noted pair then belongs to a receiver whose column sum has been added: the order of the additions is fixed)
-            bool more = true;
-            do {
-                unsigned bm = 0u, bm_in = 0u;
-                int got = 0;
-                if (lane == 0) got = atomicAdd(&next_recv, 1);
-                int ur = __builtin_amdgcn_readfirstlane(got);
-                bool skip = false;
-                if (COMPACT) {                        // the receiver of rank ur: the one wanted lane that holds this rank
-                    more = ur < n_wanted;
-                    if (more) {
-                        const unsigned long long hit = ballot1(myrank == (unsigned)ur) & wanted;   // (lanes that are not wanted hold ranks of no meaning)
-                        ur = __builtin_ctzll(hit);
-                        bm = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask[ur]);             // (with the receiver's record: one round trip)
-                        if (NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);
-                    }
-                } else {
-                    more = ur < RPB;
-                    if (more && CLASSIFY) {
-                        bm = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask[ur]);
-                        skip = (bm & live) == 0u;     // no batch of this tile can act on this receiver: nothing to add
-                        if (!skip && NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);
-                    }
+        // receivers are claimed from the workgroup's counter until none is left; the wave's list of noted pairs is
+        // corrected when the tile is done - or, in a crowd, as soon as it is half full, between two receivers (every
+        // noted pair then belongs to a receiver whose column sum has been added: the order of the additions is fixed)
+        bool more = true;
+        do {
+            unsigned bm = 0u, bm_in = 0u;
+            int got = 0;
+            if (lane == 0) got = atomicAdd(&next_recv, 1);
+            int ur = __builtin_amdgcn_readfirstlane(got);
+            bool skip = false;
+            if (COMPACT) {                        // the receiver of rank ur: the one wanted lane that holds this rank
+                more = ur < n_wanted;
+                if (more) {
+                    const unsigned long long hit = ballot1(myrank == (unsigned)ur) & wanted;   // (lanes that are not wanted hold ranks of no meaning)
+                    ur = __builtin_ctzll(hit);
+                    bm = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask[ur]);             // (with the receiver's record: one round trip)
+                    if (NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);
                 }
-                if (more && !skip) visit(ur, bm, bm_in, 0);
-                if (!more || nlen >= NCAP / 2) near_drain();
-            } while (more);
-        } else {
-#pragma unroll
-            for (int uu = 0; uu < RPW; uu++) visit(wave * RPW + uu, 0u, 0u, uu);
-            near_drain();
-        }
+            } else {
+                more = ur < RPB;
+                if (more && CLASSIFY) {
+                    bm = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask[ur]);
+                    skip = (bm & live) == 0u;     // no batch of this tile can act on this receiver: nothing to add
+                    if (!skip && NBT > 16) bm_in = (unsigned)__builtin_amdgcn_readfirstlane((int)bmask_in[ur]);
+                }
+            }
+            if (more && !skip) visit(ur, bm, bm_in);
+            if (!more || nlen >= NCAP / 2) near_drain();
+        } while (more);
     }
     if (d.trace && lane == 0) {   // tools/handout_trace.py: this wave has no receiver left to claim - from here it waits for its siblings
         // (stored at once, not kept for the record below: across the barrier the stamp cost four spilled scalar registers)
         uint32_t *o = (uint32_t *)(d.trace + 3 * (((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CW + wave));
         o[5] = (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xFu) | ((uint32_t)wall_clock64() << 4);   // HW_REG_XCC_ID | 28 bits of the clock
     }
-    if (DYN) {
-        const float4 *const chase = cold_args().part4;   // (uniform; NULL but for the launches the per-agent kernel runs beside)
-        if (chase != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's hand-over stores have landed (edge_handover)
-        // what this wave's visits cost in vector instructions (profiles/pair_plain_f32_isa_counts.txt: 28 per source tested, 58 per
-        // pair evaluated), left in the first word of its list of noted pairs - drained, and nobody else's
-        // (the table and the block's first slot: asked for in front of the barrier, like the pointer above - behind it the round trip
-        // to the argument block would be the workgroup's last act, with its slot and its LDS held.  A launch without tables - NULL, or
-        // laid out for another grid - pays these loads and nothing else)
-        uint32_t *const wcost = ORDERED && cold_args().wg_groups == (int)gridDim.x ? cold_args().wg_cost : nullptr;
-        const int64_t wlo = ORDERED ? cold_args().lo : 0;
-        if (ORDERED && wcost != nullptr && lane == 0) nlist[wave][0] = 28u * tests + 58u * (evals + (unsigned)CHUNK * (pops & 0xFFFFu));
-        __syncthreads();
-        const int te = (wave << 6) | lane;     // (threadIdx.x, not kept alive across the kernel)
-        if (ORDERED && wave == 0 && wcost != nullptr) {   // the workgroup's cost, for the order of a later launch (counts, not clocks: a run reproduces its orders)
-            unsigned c = lane < CW ? nlist[lane][0] : 0u;
-            c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR1, 0xf, 0xf, false);
-            c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR2, 0xf, 0xf, false);
-            c += __builtin_amdgcn_update_dpp(0u, c, DPP_HALF_MIRROR, 0xf, 0xf, false);   // lane 0: waves 0 .. 3 + waves 4 .. 7
-            static_assert(CW <= 8, "three exchanges within eight lanes sum the waves' costs");
-            // (the group it served: its first receiver's slot - never a clamped one - is RPB x group places behind the block's first)
-            if (lane == 0) wcost[(int64_t)by * gridDim.x + (((int64_t)ragent[0] - wlo) / RPB)] = c;
-        }
-        if (te < RPB) {
-            const int64_t a = ragent[te];
-            if (a >= 0) {
-                if (chase != nullptr) {
-                    // a per-agent wave of another XCD reads it within this launch: ONE 16-byte write-through store, the tick's tag
-                    // beside the sums - nobody waits for it here and nobody signals (a wave that waited for its stores before an
-                    // arrival counter kept its workgroup's slot ~1.5 us longer: + 2 us on the launch)
-                    const Dev &dc = cold_args();
-                    st_granule16(&dc.part4[(int64_t)(d.part_base + by) * d.cap + a], racc[0][te], racc[1][te], __uint_as_float(dc.chase_tag), 0.0f);
-                } else {
-                    d.part[(int64_t)(d.part_base + by) * d.cap + a] = make_float2(racc[0][te], racc[1][te]);
-                }
+    const float4 *const chase = cold_args().part4;   // (uniform; NULL but for the launches the per-agent kernel runs beside)
+    if (chase != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's hand-over stores have landed (edge_handover)
+    // what this wave's visits cost in vector instructions (profiles/pair_plain_f32_isa_counts.txt: 28 per source tested, 58 per
+    // pair evaluated), left in the first word of its list of noted pairs - drained, and nobody else's
+    // (the table and the block's first slot: asked for in front of the barrier, like the pointer above - behind it the round trip
+    // to the argument block would be the workgroup's last act, with its slot and its LDS held.  A launch without tables - NULL, or
+    // laid out for another grid - pays these loads and nothing else)
+    uint32_t *const wcost = ORDERED && cold_args().wg_groups == (int)gridDim.x ? cold_args().wg_cost : nullptr;
+    const int64_t wlo = ORDERED ? cold_args().lo : 0;
+    if (ORDERED && wcost != nullptr && lane == 0) nlist[wave][0] = 28u * tests + 58u * (evals + (unsigned)CHUNK * (pops & 0xFFFFu));
+    __syncthreads();
+    const int te = (wave << 6) | lane;     // (threadIdx.x, not kept alive across the kernel)
+    if (ORDERED && wave == 0 && wcost != nullptr) {   // the workgroup's cost, for the order of a later launch (counts, not clocks: a run reproduces its orders)
+        unsigned c = lane < CW ? nlist[lane][0] : 0u;
+        c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR1, 0xf, 0xf, false);
+        c += __builtin_amdgcn_update_dpp(0u, c, DPP_XOR2, 0xf, 0xf, false);
+        c += __builtin_amdgcn_update_dpp(0u, c, DPP_HALF_MIRROR, 0xf, 0xf, false);   // lane 0: waves 0 .. 3 + waves 4 .. 7
+        static_assert(CW <= 8, "three exchanges within eight lanes sum the waves' costs");
+        // (the group it served: its first receiver's slot - never a clamped one - is RPB x group places behind the block's first)
+        if (lane == 0) wcost[(int64_t)by * gridDim.x + (((int64_t)ragent[0] - wlo) / RPB)] = c;
+    }
+    if (te < RPB) {
+        const int64_t a = ragent[te];
+        if (a >= 0) {
+            if (chase != nullptr) {
+                // a per-agent wave of another XCD reads it within this launch: ONE 16-byte write-through store, the tick's tag
+                // beside the sums - nobody waits for it here and nobody signals (a wave that waited for its stores before an
+                // arrival counter kept its workgroup's slot ~1.5 us longer: + 2 us on the launch)
+                const Dev &dc = cold_args();
+                st_granule16(&dc.part4[(int64_t)(d.part_base + by) * d.cap + a], racc[0][te], racc[1][te], __uint_as_float(dc.chase_tag), 0.0f);
+            } else {
+                d.part[(int64_t)(d.part_base + by) * d.cap + a] = make_float2(racc[0][te], racc[1][te]);
             }
         }
-        if (chase != nullptr && wave == 0 && lane == 0) {
-            const Dev &dc = cold_args();
-            atomicAdd(&dc.chase_misc[0], 1u);                                      // (the gate of the per-agent launch: a count, no hand-off)
-            if (dc.chase_clock != nullptr) atomicMax(dc.chase_clock + 8 * dc.chase_slot + 1, (unsigned long long)wall_clock64());
-        }
-    } else {
-        reduce_store(d, j0, lane, ax, ay, &ragent[wave * RPW]);
+    }
+    if (chase != nullptr && wave == 0 && lane == 0) {
+        const Dev &dc = cold_args();
+        atomicAdd(&dc.chase_misc[0], 1u);                                      // (the gate of the per-agent launch: a count, no hand-off)
+        if (dc.chase_clock != nullptr) atomicMax(dc.chase_clock + 8 * dc.chase_slot + 1, (unsigned long long)wall_clock64());
     }
     if (ndrop != 0u && lane == 0) atomicAdd(cold_args().near_dropped, ndrop);
     if (d.pair_count != nullptr && lane == 0) {
@@ -1154,127 +1148,132 @@ void launch_untracked(const Dev &d, uint8_t *out, hipStream_t st) {
     hipLaunchKernelGGL(untracked_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, d, out);
 }
 
-static dim3 recv_grid(const Dev &d, int split, int per_block_recv = WPB * RPW) {
-    int64_t nloc = d.hi - d.lo;
-    int64_t per_block = per_block_recv;
-    return dim3((unsigned)((nloc + per_block - 1) / per_block), (unsigned)split, 1);
+// ---- which kernel a pair launch takes: THE one reader of the words of Dev that decide it (csf_dev.h: PairShape) ----------------
+// The launches below, the order tables, the gate of the per-agent launch and the candidate lists (engine/tick.inc, binning.inc)
+// take its answer.  The sizes that set those words - set_chunks, pair_variant_for, rebin - are not its business.
+PairShape pair_shape(const Dev &d, bool segments) {
+    PairShape s{};
+    s.p2r = d.pc.p2r != 0;
+    s.rpb = d.rpb == 32 ? 32 : 16;
+    s.cw = WPB;
+    s.per_group = WPB * RPW;
+    s.threads = BLOCK;
+    s.name = "pair_kernel";
+    if (segments) {                                // the runs of all TwoD-field sets in one grid: classified, slot order, reach test, 8 waves
+        s.family = PairShape::CULL_SEG;
+        s.classify = s.reach = 1;
+    } else if (d.n_classes > 1) {                  // several parameter sets: the source's own row for every pair
+        if (d.n_classes > MAX_CLASSES) return s;   // (csf_set_param_classes refuses more: nothing to launch)
+        s.family = PairShape::HET;
+        s.field = d.has_bike ? ((d.model_mask & ~1) ? 2 : 1) : 0;   // Bicycle and other classes together: the field of the source's class
+        return s;
+    } else if (d.p.model == CSF_BICYCLE) {
+        if (!(d.classify && d.recs_valid)) {       // no binned records: every pair evaluated
+            s.family = PairShape::PLAIN;
+            s.field = 1;
+            return s;
+        }
+        s.family = PairShape::BIKE;
+        s.name = "pair_bike_kernel";
+        s.rw = s.rpb == 32 ? 8 : 4;                // receivers per wave
+        s.per_group = WPB * s.rw;
+        return s;
+    } else if (d.pair_variant == 1) {
+        s.family = PairShape::PLAIN;
+        return s;
+    } else {
+        s.family = PairShape::CULL;
+        s.classify = d.classify != 0;
+        s.binr = s.classify && d.recv_binned;
+        s.ord = s.classify && !s.binr && d.wg_cost != nullptr;      // (tick.inc: wg_order_apply gave this launch its tables)
+        s.reach = s.classify && d.pc.reach;        // the default: per-pair reach test in front of the field
+    }
+    s.name = "pair_cull_kernel";
+    if (segments || (s.classify && d.wide && (s.reach || s.rpb == 32))) s.cw = 2 * WPB;   // tiles of 2048 sources - with 16 receivers only in front of the reach test
+    s.per_group = s.rpb;
+    s.threads = s.cw * WAVE;
+    return s;
 }
 
 // every launch of this file: optional events take the kernel's own start / end time stamps (csf_dev.h)
-#define CSF_LAUNCH(kernel, grid) hipExtLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, st, t0, t1, 0, d)
+#define CSF_LAUNCH_AS(kernel, grid, threads) hipExtLaunchKernelGGL(kernel, grid, dim3(threads), 0, st, t0, t1, 0, d)
+#define CSF_LAUNCH(kernel, grid) CSF_LAUNCH_AS(kernel, grid, BLOCK)
+static dim3 recv_grid(const Dev &d, int split) { return dim3((unsigned)((d.hi - d.lo + WPB * RPW - 1) / (WPB * RPW)), (unsigned)split, 1); }   // (the road term)
 
-template <bool P2R, bool CLASSIFY, bool BINR, bool ORD = false>
-static void launch_cull_dyn(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
-    if (CLASSIFY && d.dyn_recv && d.pc.reach) {      // the default: per-pair reach test in front of the field
-        if (d.rpb == 16 && d.wide && CLASSIFY) {
-            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 16, CLASSIFY, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 16),
-                                  dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
-        } else if (d.rpb == 32 && d.wide && CLASSIFY) {   // 8 waves, tiles of 2048 sources (csf_engine.hip set_chunks: chunks of 32 batches)
-            hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 32),
-                                  dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
-        } else if (d.rpb == 32) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split, 32));
-        else if (d.rpb == 8) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 8, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split, 8));
-        else CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, WPB * RPW, CLASSIFY, WPB, false, ORD>), recv_grid(d, d.n_split));
-        return;
+// The instances of pair_cull_kernel that exist, listed once: (receivers, reach test, waves) of a classified launch - the segmented
+// grid has the first two -, and of an unclassified one.  A shape outside the list is a bug in pair_shape, not a reason for another kernel.
+template <bool P2R, bool CLASSIFY, bool BINR, bool SEG, bool ORD>
+static void launch_cull(const PairShape &s, const Dev &d, const dim3 g, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+#define CSF_CULL_ROW(RPB_, REACH_, CW_) \
+    if (s.rpb == RPB_ && (s.reach != 0) == REACH_ && s.cw == CW_) {                                                       \
+        CSF_LAUNCH_AS((pair_cull_kernel<P2R, CLASSIFY, BINR, RPB_, REACH_, CW_, SEG, ORD>), g, CW_ * WAVE);                \
+        return;                                                                                                            \
     }
-    if (CLASSIFY && d.dyn_recv && d.rpb == 32 && d.wide) {   // every pair evaluated (CSF_FAR_EPS=0): the wide workgroup as well
-        hipExtLaunchKernelGGL((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, false, CLASSIFY ? 2 * WPB : WPB, false, ORD>), recv_grid(d, d.n_split, 32),
-                              dim3(2 * BLOCK), 0, st, t0, t1, 0, d);
-        return;
+    if constexpr (CLASSIFY) {
+        CSF_CULL_ROW(16, true, 2 * WPB);
+        CSF_CULL_ROW(32, true, 2 * WPB);
+        if constexpr (!SEG) {
+            CSF_CULL_ROW(16, true, WPB);
+            CSF_CULL_ROW(32, true, WPB);
+            CSF_CULL_ROW(32, false, 2 * WPB);      // every pair evaluated (CSF_FAR_EPS=0): the wide workgroup as well
+        }
     }
-    if (d.dyn_recv && d.rpb == 32) {
-        CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, 32, false, WPB, false, ORD>), recv_grid(d, d.n_split, 32));
-        return;
+    if constexpr (!SEG) {
+        CSF_CULL_ROW(16, false, WPB);
+        CSF_CULL_ROW(32, false, WPB);
     }
-    if (d.dyn_recv) CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, true, WPB * RPW, false, WPB, false, ORD>), recv_grid(d, d.n_split));
-    else CSF_LAUNCH((pair_cull_kernel<P2R, CLASSIFY, BINR, false>), recv_grid(d, d.n_split));
+#undef CSF_CULL_ROW
+    fprintf(stderr, "csf: no pair_cull_kernel for %d receivers, reach %d, %d waves\n", s.rpb, s.reach, s.cw);
+    abort();
 }
 
-// the runs of all TwoD-field parameter sets in one grid (Dev::segtab; receivers per workgroup and tile as launch_cull_dyn chooses)
+#define CSF_P2R(call_true, call_false) do { if (s.p2r) { call_true; } else { call_false; } } while (0)
+#define CSF_CULL(CLASSIFY_, BINR_, SEG_, ORD_) \
+    CSF_P2R((launch_cull<true, CLASSIFY_, BINR_, SEG_, ORD_>(s, d, g, st, t0, t1)), (launch_cull<false, CLASSIFY_, BINR_, SEG_, ORD_>(s, d, g, st, t0, t1)))
+static void launch_shape(const PairShape &s, const Dev &d, int split, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+    if (d.hi <= d.lo || s.family == PairShape::NONE) return;
+    const dim3 g((unsigned)s.groups(d.hi - d.lo), (unsigned)split, 1);
+    switch (s.family) {
+    case PairShape::HET:
+        if (s.field == 2) CSF_P2R(CSF_LAUNCH((pair_kernel<2, true, true>), g), CSF_LAUNCH((pair_kernel<2, false, true>), g));
+        else if (s.field == 1) CSF_P2R(CSF_LAUNCH((pair_kernel<1, true, true>), g), CSF_LAUNCH((pair_kernel<1, false, true>), g));
+        else CSF_P2R(CSF_LAUNCH((pair_kernel<0, true, true>), g), CSF_LAUNCH((pair_kernel<0, false, true>), g));
+        break;
+    case PairShape::BIKE:
+        if (s.rw == 8) CSF_P2R(CSF_LAUNCH((pair_bike_kernel<true, 8>), g), CSF_LAUNCH((pair_bike_kernel<false, 8>), g));
+        else CSF_P2R(CSF_LAUNCH((pair_bike_kernel<true, 4>), g), CSF_LAUNCH((pair_bike_kernel<false, 4>), g));
+        break;
+    case PairShape::PLAIN:
+        if (s.field == 1) CSF_P2R(CSF_LAUNCH((pair_kernel<1, true>), g), CSF_LAUNCH((pair_kernel<1, false>), g));
+        else CSF_P2R(CSF_LAUNCH((pair_kernel<0, true>), g), CSF_LAUNCH((pair_kernel<0, false>), g));
+        break;
+    case PairShape::CULL_SEG: CSF_CULL(true, false, true, false); break;
+    default:   // PairShape::CULL
+        if (s.binr) CSF_CULL(true, true, false, false);
+        else if (s.ord) CSF_CULL(true, false, false, true);
+        else if (s.classify) CSF_CULL(true, false, false, false);
+        else CSF_CULL(false, false, false, false);
+        break;
+    }
+}
+#undef CSF_CULL
+#undef CSF_P2R
+
+void launch_pair(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) { launch_shape(pair_shape(d), d, d.n_split, st, t0, t1); }
+
+// the runs of all TwoD-field parameter sets in one grid (Dev::segtab)
 void launch_pair_segments(const Dev &d, int total_by, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
-    if (d.hi <= d.lo || total_by <= 0) return;
-    const bool p2r = d.pc.p2r != 0;
-    const int rpb = d.rpb == 32 ? 32 : 16;
-    const dim3 g = recv_grid(d, total_by, rpb);
-#define CSF_SEG_LAUNCH(P2R_, RPB_) hipExtLaunchKernelGGL((pair_cull_kernel<P2R_, true, false, true, RPB_, true, 2 * WPB, true>), g, dim3(2 * BLOCK), 0, st, t0, t1, 0, d)
-    if (rpb == 32) {
-        if (p2r) CSF_SEG_LAUNCH(true, 32);
-        else CSF_SEG_LAUNCH(false, 32);
-    } else {
-        if (p2r) CSF_SEG_LAUNCH(true, 16);
-        else CSF_SEG_LAUNCH(false, 16);
-    }
-#undef CSF_SEG_LAUNCH
+    if (total_by > 0) launch_shape(pair_shape(d, true), d, total_by, st, t0, t1);
 }
 
-static void launch_cull(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
-    const bool p2r = d.pc.p2r != 0;
-    if (d.classify && d.recv_binned) {
-        if (p2r) launch_cull_dyn<true, true, true>(d, st, t0, t1);
-        else launch_cull_dyn<false, true, true>(d, st, t0, t1);
-    } else if (d.classify && d.dyn_recv && d.wg_cost != nullptr) {   // (tick.inc: wg_order_apply gave this launch its tables)
-        if (p2r) launch_cull_dyn<true, true, false, true>(d, st, t0, t1);
-        else launch_cull_dyn<false, true, false, true>(d, st, t0, t1);
-    } else if (d.classify) {
-        if (p2r) launch_cull_dyn<true, true, false>(d, st, t0, t1);
-        else launch_cull_dyn<false, true, false>(d, st, t0, t1);
-    } else {
-        if (p2r) launch_cull_dyn<true, false, false>(d, st, t0, t1);
-        else launch_cull_dyn<false, false, false>(d, st, t0, t1);
-    }
-}
-
-// (launch_pair and launch_cull_dyn, read backwards: one parameter set, TwoD field, the cull-first kernel on classified batches,
-// receivers in slot order and handed out dynamically; 32, 8 or 16 receivers per workgroup)
 int64_t pair_order_groups(const Dev &d) {
-    if (d.hi <= d.lo || d.n_classes > 1 || d.p.model == CSF_BICYCLE || d.pair_variant == 1 || !d.classify || d.recv_binned || !d.dyn_recv) return 0;
-    const int per = d.rpb == 32 ? 32 : (d.rpb == 8 && d.pc.reach) ? 8 : WPB * RPW;
-    return (d.hi - d.lo + per - 1) / per;
-}
-
-void launch_pair(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
-    if (d.hi <= d.lo) return;
-    const dim3 g = recv_grid(d, d.n_split);
-    const bool p2r = d.pc.p2r != 0;
-    if (d.n_classes > 1) {                         // several parameter sets: the source's own row for every pair
-        if (d.n_classes > MAX_CLASSES) return;     // (csf_set_param_classes refuses more)
-        if (d.has_bike && (d.model_mask & ~1)) {   // Bicycle and other classes together: the field of the source's class
-            if (p2r) CSF_LAUNCH((pair_kernel<2, true, true>), g);
-            else CSF_LAUNCH((pair_kernel<2, false, true>), g);
-        } else if (d.has_bike) {
-            if (p2r) CSF_LAUNCH((pair_kernel<1, true, true>), g);
-            else CSF_LAUNCH((pair_kernel<1, false, true>), g);
-        } else {
-            if (p2r) CSF_LAUNCH((pair_kernel<0, true, true>), g);
-            else CSF_LAUNCH((pair_kernel<0, false, true>), g);
-        }
-    } else if (d.p.model == CSF_BICYCLE && d.classify && d.recs_valid) {
-        if (d.rpb == 32) {
-            const dim3 g8 = recv_grid(d, d.n_split, 32);
-            if (p2r) CSF_LAUNCH((pair_bike_kernel<true, 8>), g8);
-            else CSF_LAUNCH((pair_bike_kernel<false, 8>), g8);
-        } else {
-            if (p2r) CSF_LAUNCH((pair_bike_kernel<true, 4>), g);
-            else CSF_LAUNCH((pair_bike_kernel<false, 4>), g);
-        }
-    } else if (d.p.model == CSF_BICYCLE) {
-        if (p2r) CSF_LAUNCH((pair_kernel<1, true>), g);
-        else CSF_LAUNCH((pair_kernel<1, false>), g);
-    } else if (d.pair_variant == 1) {
-        if (p2r) CSF_LAUNCH((pair_kernel<0, true>), g);
-        else CSF_LAUNCH((pair_kernel<0, false>), g);
-    } else {
-        launch_cull(d, st, t0, t1);
-    }
+    const PairShape s = pair_shape(d);
+    // (asked before the launch has its tables: the instance it WOULD take with them - classified, slot order, one parameter set)
+    return s.family == PairShape::CULL && s.classify && !s.binr ? s.groups(d.hi - d.lo) : 0;
 }
 
 // which pair kernel launch_pair() takes for this engine (profiles and the bench line name it)
-const char *pair_kernel_name(const Dev &d) {
-    if (d.n_classes > 1) return "pair_kernel";
-    if (d.p.model == CSF_BICYCLE) return (d.classify && d.recs_valid) ? "pair_bike_kernel" : "pair_kernel";
-    if (d.pair_variant == 1) return "pair_kernel";
-    return "pair_cull_kernel";
-}
+const char *pair_kernel_name(const Dev &d) { return pair_shape(d).name; }
 
 void launch_road(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
     if (d.hi <= d.lo || d.nv == 0) return;

@@ -87,19 +87,6 @@ __device__ __forceinline__ float reduce8(int lane, const float (&ax)[RPW], const
     return z;
 }
 
-__device__ __forceinline__ void reduce_store(const Dev &d, int64_t j0, int lane, const float (&ax)[RPW],
-                                             const float (&ay)[RPW], const int *agent_of = nullptr) {
-    int idx;
-    const float z = reduce8(lane, ax, ay, idx);
-    const int u = idx >> 1;
-    // agent_of: slot of each of the wave's receivers, -1 for none (LDS); else the receivers are the slots j0 + u
-    const int64_t a = agent_of ? (int64_t)agent_of[u] : (j0 + u < d.hi ? j0 + u : -1);
-    if ((lane & 7) == 0 && a >= 0) {
-        float *dst = (float *)&d.part[(int64_t)(d.part_base + blockIdx.y) * d.cap + a];
-        dst[idx & 1] = z;
-    }
-}
-
 __device__ __forceinline__ void source_chunk(const Dev &d, int64_t &ibeg, int64_t &iend, int by = (int)blockIdx.y) {
     const int64_t per = d.chunk_units;  // `by` (blockIdx.y) selects a chunk of sources, in units of 64 records
     ibeg = d.src_beg + (int64_t)by * per * WAVE;

@@ -134,6 +134,46 @@ int csf_wg_order_ranks(const uint32_t *cost, int32_t n, int32_t *order) try {
     return n;
 } catch (...) { return -1; }
 
+// pair_shape on bare words (tests/test_pair_shape_host.py: the whole lattice against the recorded table, no device)
+static Dev pair_shape_dev(const int32_t *in) {
+    Dev d{};
+    d.pc.p2r = in[0], d.n_classes = in[1], d.has_bike = in[2], d.model_mask = in[3], d.p.model = in[4], d.classify = in[5], d.recs_valid = in[6];
+    d.pair_variant = in[7], d.recv_binned = in[8], d.rpb = in[9], d.wide = in[10], d.pc.reach = in[11];
+    static uint32_t given;
+    d.wg_cost = in[12] ? &given : nullptr;      // (compared with NULL, never read)
+    d.hi = in[14];
+    return d;
+}
+
+int csf_pair_shape_of(const int32_t *in, int32_t *out, const char **name) try {
+    if (!in || !out) return -1;
+    const Dev d = pair_shape_dev(in);
+    const PairShape s = pair_shape(d, in[13] != 0);
+    const int32_t w[CSF_PAIR_SHAPE_OUT] = {s.family, s.field, s.rw, s.p2r, s.classify, s.binr, s.ord, s.reach, s.rpb, s.cw, s.per_group, s.threads,
+                                           s.tile(), (int32_t)s.groups(d.hi - d.lo), (int32_t)pair_order_groups(d)};
+    std::copy(w, w + CSF_PAIR_SHAPE_OUT, out);
+    if (name) *name = s.name;
+    return CSF_PAIR_SHAPE_OUT;
+} catch (...) { return -1; }
+
+int csf_pair_shape_words(csf_engine *e, int32_t *in) try {
+    if (!e || !in) return e ? fail(e, CSF_E_ARG, "csf_pair_shape_words: NULL output") : CSF_E_ARG;
+    HIPCHK(e, hipSetDevice(e->device));
+    int rc = upload_all(e);
+    if (rc) return rc;
+    Dev d = e->d;
+    const bool one_grid = !e->segs.empty() && e->seg_total_by > 0 && e->knobs.seg_grid != 0;
+    if (!e->segs.empty()) {                      // the first launch of launch_pair_all: the grid of all runs, or the first set's run
+        d.n_classes = 1, d.recv_binned = 0;
+        if (!one_grid) d.p = e->classes[(size_t)e->segs[0].cls], d.pc = e->segs[0].pc;
+    }
+    const int32_t w[CSF_PAIR_SHAPE_IN] = {d.pc.p2r != 0, d.n_classes, d.has_bike, d.model_mask, d.p.model, d.classify, d.recs_valid, d.pair_variant,
+                                          d.recv_binned, d.rpb, d.wide, d.pc.reach, e->wgo.last >= 0, one_grid,
+                                          (int32_t)std::min<int64_t>(d.hi - d.lo, INT32_MAX), 0};
+    std::copy(w, w + CSF_PAIR_SHAPE_IN, in);
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
 int csf_wg_order_tables(csf_engine *e, int64_t *groups, int32_t *chunks, int32_t *ordered, uint32_t *cost, int32_t *order, int64_t capacity) try {
     if (!e || !groups || !chunks || !ordered || capacity < 0) return e ? fail(e, CSF_E_ARG, "csf_wg_order_tables: bad arguments") : CSF_E_ARG;
     int rc = csf_sync(e);

@@ -278,9 +278,10 @@ int rebin(csf_engine *e) {
     d.clist = nullptr;
     d.ccount = nullptr;
     if (d.recv_binned && e->knobs.clist != 0) {   // which tiles can matter to which receiver group until the next re-binning
-        d.clist_tile = d.wide ? 2048 : 1024;
-        d.clist_rpb = d.rpb;
-        const int64_t nloc = d.hi - d.lo, groups = (nloc + d.rpb - 1) / d.rpb;
+        const PairShape sh = pair_shape(d);           // (the instance that reads the lists checks both words against its own)
+        d.clist_tile = sh.tile();
+        d.clist_rpb = sh.rpb;
+        const int64_t nloc = d.hi - d.lo, groups = (nloc + sh.rpb - 1) / sh.rpb;
         const int64_t ntiles = (d.n_src + d.clist_tile - 1) / d.clist_tile;
         if (groups > 0 && ntiles > 0 && ntiles < 65536) {
             HIPCHK(e, e->tcirc.reserve((size_t)ntiles + 1));

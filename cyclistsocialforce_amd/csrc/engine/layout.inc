@@ -231,7 +231,7 @@ void set_chunks(csf_engine *e) {
     // 32 receivers per workgroup where that still leaves thousands of workgroups (N = 16 384 unsharded: 8192): measured
     // better from 8192 receivers up, worse for the few workgroups of small populations and 4-way shards
     d.rpb = (nloc >= 8192 || (nloc >= 4096 && d.n_src >= 16384)) ? 32 : 16;   // (4-way shard of 16 384: 38.9 -> 36.6 us with the wide workgroups below)
-    if (e->knobs.rpb > 0) d.rpb = e->knobs.rpb == 32 ? 32 : e->knobs.rpb == 8 ? 8 : 16;
+    if (e->knobs.rpb > 0) d.rpb = e->knobs.rpb == 32 ? 32 : 16;
     // ... and then workgroups of 8 waves on tiles of 2048 sources (csf_pair.hip: CW); below 65 536 places in chunks of 32 batches
     // (with 16 receivers for the shards of a large population: 8-way shard of 16 384 26.3 -> 25.1 us; unsharded 115 against 101)
     d.wide = (d.rpb == 32 || (d.rpb == 16 && (e->knobs.wide > 0 || d.n_src >= 16384))) && d.p.model != CSF_BICYCLE &&
@@ -240,8 +240,6 @@ void set_chunks(csf_engine *e) {
     split = (units + per - 1) / per;
     d.n_split = (int32_t)split;
     d.chunk_units = (int32_t)per;
-    d.dyn_recv = 1;   // receivers handed to the waves of a workgroup one at a time (csf_pair.hip, DYN; 0: four per wave)
-    if (e->knobs.dyn_recv >= 0) d.dyn_recv = e->knobs.dyn_recv != 0;
 }
 
 constexpr int64_t BIN_MIN_AGENTS = 1024;

@@ -56,7 +56,7 @@ static void launch_pair_all(csf_engine *e, const Dev &base, hipEvent_t t0 = null
         launch_pair(base, e->main, t0, t1);
         return;
     }
-    const bool one_grid = e->seg_total_by > 0 && base.pair_count == nullptr && base.dyn_recv && e->knobs.seg_grid != 0;
+    const bool one_grid = e->seg_total_by > 0 && base.pair_count == nullptr && e->knobs.seg_grid != 0;
     if (one_grid) {      // the runs of all TwoD-field sets in one grid
         Dev dd = base;
         dd.n_classes = 1;
@@ -348,7 +348,7 @@ static bool chase_shape(const csf_engine *e) {
 // partial block only under CSF_FAKE_SHARD.
 static bool chase_eligible(const csf_engine *e, int64_t ticks_left) {
     const Dev &d = e->d;
-    return chase_shape(e) && d.n_classes == 1 && d.recs_valid && d.dyn_recv && (d.rpb == 32 || d.rpb == 16 || d.rpb == 8) && d.n_split <= 16 &&
+    return chase_shape(e) && d.n_classes == 1 && d.recs_valid && pair_shape(d).family == PairShape::CULL && d.n_split <= 16 &&
            d.part_base == 0 && d.pair_count == nullptr && e->segs.empty() && e->state_all_current &&   // (wave traces allowed: tools/chase_timeline.py)
            e->pend.empty() && !e->bound_stale && e->bounds_fresh && d.n_live > 1 && d.hi > d.lo && (d.lo & 63) == 0 && d.replay_len == nullptr &&
            ((d.lo == 0 && d.hi == d.n) || e->knobs.fake_world > 1) && (e->chase_prev || ticks_left >= 4);
@@ -508,7 +508,7 @@ static int enqueue_chase_tick(csf_engine *e, csf_engine::ProfSlot *ps, csf_engin
     }
     hipStream_t P = e->chase_parity ? e->comm : e->main, Q = e->chase_parity ? e->main : e->comm;
     const OtherHalves o = other_halves(e);
-    const int64_t groups = (d.hi - d.lo + d.rpb - 1) / d.rpb, wgs = groups * d.n_split;
+    const int64_t groups = pair_shape(d).groups(d.hi - d.lo), wgs = groups * d.n_split;   // (the grid launch_pair takes below)
     e->chase_round++;
     Dev dd = d;
     write_other_halves(dd, o, true);

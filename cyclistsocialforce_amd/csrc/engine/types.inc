@@ -186,7 +186,7 @@ struct Knobs {
     std::string trace_agent;                  // CSF_TRACE_AGENT=<file>: eight time stamps per wave of the last per-agent launch
     int fake_rank = 0, fake_world = 1;        // CSF_FAKE_SHARD=r/w: only rank r's receiver block of w (timing aid)
     int nsplit = 0;                           // CSF_NSPLIT: source chunks of the pair grid (0: the engine's choice)
-    int dyn_recv = -1, rpb = 0;               // CSF_DYN_RECV, CSF_RPB
+    int rpb = 0;                              // CSF_RPB: 32 or 16 receivers per workgroup of the cull kernel (0: the engine's choice)
     int wide = -1;                            // CSF_WIDE: workgroups of 8 waves on tiles of 2048 sources (-1: the engine's choice)
     int pair_variant = -1;                    // CSF_PAIR_VARIANT (-1: by population size)
     int64_t rebin_ticks = 64;                 // CSF_REBIN_TICKS: ticks between two re-binnings (1 .. 120; the tests that step 40 - 48 ticks "across a re-binning" pin 32)
@@ -238,7 +238,6 @@ struct Knobs {
         const bool expert = geti("CSF_EXPERT", 0) != 0;
         auto gete = [&](const char *name, int dflt) { return expert ? geti(name, dflt) : dflt; };
         nsplit = gete("CSF_NSPLIT", 0);
-        dyn_recv = gete("CSF_DYN_RECV", -1);
         rpb = gete("CSF_RPB", 0);
         wide = gete("CSF_WIDE", -1);
         pair_variant = geti("CSF_PAIR_VARIANT", -1);

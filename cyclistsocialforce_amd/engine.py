@@ -918,6 +918,13 @@ class Engine:
         self._ck(self._lib.csf_wg_order_tables(self._h, C.byref(g), C.byref(c), C.byref(o), _ptr(cost), _ptr(order), cost.size))
         return g.value, c.value, bool(o.value), cost, (order if o.value else None)
 
+    def pair_shape(self):
+        """what this engine's next pair launch takes (include/csf.h: csf_pair_shape_of), as a dict: family, field, rw, p2r, classify, binr,
+        ord, reach, rpb, cw, per_group, threads, tile, grid_x, order_groups, name"""
+        words = (C.c_int32 * _ffi.PAIR_SHAPE_IN)()
+        self._ck(self._lib.csf_pair_shape_words(self._h, words))
+        return _ffi.pair_shape_of(self._lib, words)
+
     def chase_ticks(self):
         """ticks whose per-agent launch ran beside the pair launch (include/csf.h: csf_chase_ticks)"""
         v = C.c_int64()

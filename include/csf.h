@@ -394,6 +394,18 @@ int csf_handout_ranks(const uint32_t *cand, const uint32_t *inside, int32_t n, i
  * exactly as the order kernel computes it (csrc/csf_wg_order.h; needs no engine and no device): order[rank] = group, heavier
  * groups first, equal costs in index order - a permutation of 0 .. n - 1 whatever the costs are.  Returns n, -1 on bad arguments. */
 int csf_wg_order_ranks(const uint32_t *cost, int32_t n, int32_t *order);
+/* Which kernel a pair launch takes, decided on the host by the function every launch asks (csrc/csf_pair.hip: pair_shape; tests).
+ * csf_pair_shape_of needs no engine and no device.  in[CSF_PAIR_SHAPE_IN]: priority to the right, parameter sets, has_bike, model_mask,
+ * vehicle class (enum csf_model), classify, recs_valid, pair_variant, recv_binned, rpb, wide, reach, order tables given, the segmented
+ * one-grid launch, receivers of the launch, 0.  out[CSF_PAIR_SHAPE_OUT]: family (0 none, 1 pair_kernel with the source's own set per
+ * pair, 2 pair_kernel, 3 pair_bike_kernel, 4 pair_cull_kernel, 5 pair_cull_kernel on the segmented grid), field, receivers per wave
+ * (Bicycle), priority to the right, classify, binr, ord, reach, rpb, waves (cull family), receivers per workgroup, threads per
+ * workgroup, sources per tile, gridDim.x, groups of the order tables (0: none); *name (may be NULL): the kernel's name in profiles.  Returns CSF_PAIR_SHAPE_OUT, -1 on bad
+ * arguments.  csf_pair_shape_words fills `in` with the words of this engine's next pair launch (uploads what is pending). */
+#define CSF_PAIR_SHAPE_IN 16
+#define CSF_PAIR_SHAPE_OUT 15
+int csf_pair_shape_of(const int32_t *in, int32_t *out, const char **name);
+int csf_pair_shape_words(csf_engine *e, int32_t *in);
 /* Read-back of the tables the last tick's pair launch used (measurement and tests; waits for the device): *groups x *chunks words
  * each; *ordered: 1 where that launch took its groups by an order table - then order[c * groups + k] is the group workgroup k of chunk
  * c served -, 0 where it took them in index order (order is left alone); cost[c * groups + g]: what the launch left for group g of

@@ -30,7 +30,7 @@ CASES = {
                   contrast={"CSF_EXPERT": "1", "CSF_RPB": "16", "CSF_WIDE": "1"}),
     "nsplit2": dict(n=8192, box=141.0, seed=33, env={"CSF_EXPERT": "1", "CSF_NSPLIT": "2"}, contrast={}),
 }
-KNOBS = ("CSF_RECV_BINNED", "CSF_EXPERT", "CSF_WIDE", "CSF_NSPLIT", "CSF_RPB", "CSF_SEGMENTS", "CSF_FAR_EPS", "CSF_CLIST", "CSF_DYN_RECV")
+KNOBS = ("CSF_RECV_BINNED", "CSF_EXPERT", "CSF_WIDE", "CSF_NSPLIT", "CSF_RPB", "CSF_SEGMENTS", "CSF_FAR_EPS", "CSF_CLIST")
 digest = sb.digest
 
 
