@@ -28,6 +28,11 @@ def _ptr(a):
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
 
+    # what intersection.py keeps on an engine.  Declared on the class, not assigned in __init__: two more entries in every instance's
+    # dictionary cost the batched calls over 256 engines 8 % of their host time (profiles/mirror_refactor_ab.txt)
+    _together = None      # the engines of the batch this one was last joined to (_batch_of)
+    _dense_for = None     # the population size its dense record ring was made for (SocialForceIntersection._dense_engine)
+
     def __init__(self, params, capacity, device=0):
         self._lib = _ffi.load()
         self._h = None

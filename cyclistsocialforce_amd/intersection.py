@@ -25,11 +25,15 @@ import numpy as np
 
 from . import _ffi, parameters
 from .engine import Engine
+from .mirror import PopulationMirror
 from .parameters import RoadElementParameters
 from .utils import angleSFMtoSUMO, generateSplinePrototype
-from .vehicle import Vehicle
+from .vehicle import QUEUE_APPENDED, QUEUE_EDITED, QUEUE_RANK, QUEUE_REPLACED, Vehicle
 
 PRIORITY_RULES = {"unregulated": _ffi.UNREGULATED, "p2r": _ffi.P2R}
+DENSE_CHUNK = 512        # ticks per call of the dense paths = samples of the engines' rings (DESIGN 4.6c: the bytes per member)
+# why every tick of an intersection passes the host (SocialForceIntersection._host_reason)
+EMPTY, HOOKS, POLES, DRAWN, FIRST_DRAWINGS = "empty", "force hooks", "drawn poles", "drawings or SUMO", "drawings on the first tick"
 
 
 # ----------------------------------------------------------------------------- road elements
@@ -163,40 +167,21 @@ class SocialForceIntersection:
         self._vx = np.zeros((0, 1))       # vehicleX / vehicleY / vehicleTheta (intersection.py:660-677): refreshed when read
         self._vy = np.zeros((0, 1))
         self._vth = np.zeros((0, 1))
-        self._pos_stale = False
         self._device = device
         self._capacity = capacity
         self._track_params = track_params
         self._engine = None
         self._small_classes = None   # set_small_classes: what the engine is told once it exists (None: the engine's own default)
-        self._S = None            # host mirror [capacity, n_states]; vehicle.s are row views
-        self._shadow = None       # device's view of the mirror after the last pull / push, kept once a vehicle.s has been handed out
-        self._s_watched = False   # some vehicle.s has been handed out: the mirror is compared with the shadow before every tick
+        self._mirror = PopulationMirror()   # the bulk host arrays of the per-vehicle attributes the device produces, and their books
         self._scripted = []       # live UncontrolledVehicles (their traj may be rewritten while they run)
-        self._vd = None
         self._rule_on_device = None
-        self._pod_bytes = None
         self._class_table = None
-        self._cls = None
         self._road_sig = None
         self._pending = []        # vehicles waiting to be added to the engine
-        # bulk mirror of the per-vehicle attributes the device produces (Vehicle properties read these): one
-        # read-back per tick refreshes every vehicle, with no Python loop over the population
-        self._ptr = None          # destpointer [capacity]
-        self._zn = None           # znav [capacity, 3]; vehicle.znav are row views
-        self._fx = self._fy = None
-        self._have_force = False
         self._hooked = False      # some vehicle carries a custom rep_force_func / dest_force_func: forces are formed on the host (_hooked_forces)
         self._field_engines = {}  # ... engines for the class fields of the others, by parameter set
         self._stoch, self._stoch_for, self._stoch_epoch = [], -1, 0   # riders with stochastic_control_behavior (cache)
-        self._ti = None           # vehicle.i [capacity]
-        self._traj = None         # vehicle.traj, stored [traj_len, rows, n_states] (a tick writes one contiguous slab);
-                                  # vehicle.traj are transposed views [n_states, traj_len]
-        self._dirty_queues = {}   # vehicle -> None (rows appended) | -1 (queue replaced) | -2 (rows edited in place)
-        self._drawn = []          # vehicles with a drawing / saveForces (the only per-tick Python loop)
-        self._drawn_stale = True
-        self._flog = []           # |F| of every evaluated tick since the last fold (vehicle.F)
-        self._flog_base = 0
+        self._dirty_queues = {}   # vehicle -> QUEUE_APPENDED | QUEUE_REPLACED | QUEUE_EDITED
         self._params_seen = -1
         if self.activate_sumo_cosimulation:
             self._init_sumo(net)
@@ -290,14 +275,12 @@ class SocialForceIntersection:
             v._solo = None
         v._owner = self
         v._index = len(self.vehicles)
-        v._live = False
         v._queue_synced = -1
-        v._f_seen = self._flog_base + len(self._flog)
-        self._dirty_queues[v] = -1
+        self._dirty_queues[v] = QUEUE_REPLACED
         self.vehicles.append(v)
         self._pending.append(v)
         self.n_bikes = len(self.vehicles)
-        self._pos_stale = True                                         # intersection.py:531-538: vehicleX ... grow by a row
+        self._mirror.pos_stale = True                                         # intersection.py:531-538: vehicleX ... grow by a row
 
     def _param_classes(self, vehicles=None):
         """The parameter sets of the population.  Every reference vehicle owns its params object: the field vehicle i
@@ -339,17 +322,14 @@ class SocialForceIntersection:
         if table != self._class_table:
             if self._class_table is not None and len(table) < len(self._class_table) and n_on_device:
                 e.set_agent_class(np.arange(n_on_device), cls[:n_on_device])      # rows first: none may point beyond the new table
-                self._cls[:n_on_device] = cls[:n_on_device]
+                self._mirror.update_classes(cls[:n_on_device])
             e.set_param_classes(pods)
             self._class_table = table
-            self._pod_bytes = table[0]
 
     def _sync_param_rows(self, cls):
-        n = len(self.vehicles)
-        ch = np.where(cls != self._cls[:n])[0]
+        ch = self._mirror.update_classes(cls)
         if ch.size:
             self._engine.set_agent_class(ch, cls[ch])
-            self._cls[:n] = cls
 
     def add_road_user(self, user):
         """intersection.py:458-539"""
@@ -387,47 +367,21 @@ class SocialForceIntersection:
         if self._engine is not None:
             self._flush_pending()
             self._engine.remove_agents(idx)
-        self._fold_all_force_logs()                  # indices are about to change
         gone = set(idx)
         keep = [k for k in range(len(self.vehicles)) if k not in gone]
+        self._mirror.compact(keep)                   # (the leavers take private copies of what they saw through it)
         for k in idx:
             v = self.vehicles[k]
-            self._detach(v)
+            v._owner, v._index = None, -1
             if v in self._pending:
                 self._pending.remove(v)
             self._dirty_queues.pop(v, None)
         self.vehicles = [self.vehicles[k] for k in keep]
-        m = len(keep)
-        if self._S is not None:
-            for a in (self._S, self._shadow, self._vd, self._ptr, self._zn, self._fx, self._fy, self._ti, self._cls):
-                a[:m] = a[keep]
-        if self._traj is not None and m:
-            self._traj[:, :m] = self._traj[:, keep]
         for new, v in enumerate(self.vehicles):
             v._index = new
-            if v._live:
-                self._bind(v)
-        self._drawn_stale = True
         self._scripted = [v for v in self._scripted if v._owner is self]
         self.n_bikes = len(self.vehicles)
-        self._pos_stale = True
-
-    def _bind(self, v):
-        """vehicle attributes that are views of the bulk mirror"""
-        k, w = v._index, type(v).N_STATES       # (a mixed population: the bulk rows are as wide as the widest class)
-        v._s = self._S[k, :w]
-        v.znav = self._zn[k]
-        if not getattr(v, "uncontrolled", False):             # (an UncontrolledVehicle's traj is its prescription: vehicle.py:958-960)
-            v.traj = self._traj[:, k, :w].T
-
-    def _detach(self, v):
-        """the vehicle leaves with private copies of everything it saw through the mirror"""
-        if v._live:
-            st = dict(i=v.i, destpointer=v.destpointer, force=v.force)
-            v._s, v.znav, v.traj = v._s.copy(), v.znav.copy(), v.traj.copy()
-            v._live = False
-            v.i, v.destpointer, v.force = st["i"], st["destpointer"], st["force"]
-        v._owner, v._index = None, -1
+        self._mirror.pos_stale = True
 
     def addEdge(self, roadEdge):
         self.road_elements.append(roadEdge)
@@ -436,342 +390,174 @@ class SocialForceIntersection:
     def _engine_ready(self):
         if not self.vehicles:
             raise RuntimeError("the intersection is empty")
-        v0 = self.vehicles[0]
         if self._engine is None:
+            pod = self.vehicles[0]._pod(PRIORITY_RULES[self.priority_rule])
             cap = self._capacity or max(256, 4 * len(self.vehicles))
-            self._engine = Engine(v0._pod(PRIORITY_RULES[self.priority_rule]), cap, device=self._device)
+            self._engine = Engine(pod, cap, device=self._device)
             if self._small_classes is not None:
                 self._engine.small_classes(self._small_classes)
             self._capacity = cap
-            ns = max(type(v).N_STATES for v in self.vehicles)
-            self._S = np.zeros((cap, ns))
-            self._shadow = np.zeros((cap, ns))
-            self._vd = np.zeros(cap)
-            self._ptr = np.zeros(cap, dtype=np.int32)
-            self._zn = np.zeros((cap, 3), dtype=bool)
-            self._fx = np.zeros(cap)
-            self._fy = np.zeros(cap)
-            self._ti = np.zeros(cap, dtype=np.int64)
+            self._mirror.allocate(cap, max(type(v).N_STATES for v in self.vehicles))
             self._rule_on_device = self.priority_rule
-            self._pod_bytes = bytes(v0._pod(PRIORITY_RULES[self.priority_rule]))
-            self._class_table = (self._pod_bytes,)
-            self._cls = np.zeros(cap, dtype=np.int32)
+            self._class_table = (bytes(pod),)
         self._flush_pending()
         return self._engine
 
     def _flush_pending(self):
         if not self._pending:
             return
-        e = self._engine
+        e, m = self._engine, self._mirror
         if len(self.vehicles) > self._capacity:
             raise RuntimeError(f"intersection capacity {self._capacity} exceeded; pass capacity= at construction")
         new = self._pending
         self._pending = []
         pods, cls = self._param_classes()                      # of everyone, the arrivals included
-        ns = max(self._S.shape[1], max(type(v).N_STATES for v in new))
-        if ns > self._S.shape[1]:                              # a wider vehicle class joins: wider rows
-            self._widen(ns)
+        ns = max(m.ns, max(type(v).N_STATES for v in new))
+        if ns > m.ns:                                          # a wider vehicle class joins: wider rows
+            m.widen(ns)
         self._sync_param_table(pods, cls, len(self.vehicles) - len(new))   # first: it decides the engine's state layout
         s0 = np.zeros((len(new), ns))
         for k, v in enumerate(new):
             s0[k, : v._s.size] = v._s
         vd = np.array([float(getattr(v.params, "v_desired_default", 0.0)) for v in new])   # (CarParameters have none)
-        first = new[0]._index
         e.add_agents(s0[:, : e.ns], vd)
-        # vehicle.traj rows of the bulk history (grown geometrically; every vehicle of an engine shares t_s)
-        T = int(30 / new[0].params.t_s)                        # vehicle.py:159
-        n = len(self.vehicles)
-        if self._traj is None or self._traj.shape[1] < n:
-            grown = np.zeros((T, max(n, 2 * (0 if self._traj is None else self._traj.shape[1])), ns))
-            if self._traj is not None:
-                grown[:, : self._traj.shape[1]] = self._traj
-            self._traj = grown
-            for v in self.vehicles:
-                if v._live and not getattr(v, "uncontrolled", False):
-                    v.traj = self._traj[:, v._index, : type(v).N_STATES].T
-        scripted = [v for v in new if getattr(v, "uncontrolled", False)]
-        if scripted:                                          # their prescribed trajectories -> the engine (csf_set_script)
-            rows = [v._script if v._script is not None else np.zeros((0, 4)) for v in scripted]
-            e.set_script([v._index for v in scripted], np.cumsum([0] + [r.shape[0] for r in rows]), np.vstack(rows))
-            for v in scripted:                                # (what the engine holds: writes to car.traj are noticed, _push_mutations)
-                v._script_sent = np.ascontiguousarray(v.traj.T).copy()
-            self._scripted.extend(scripted)
-        for v in new:
-            if v.traj.shape[1] != T and not getattr(v, "uncontrolled", False):
-                raise NotImplementedError("all road users of one intersection share t_s (one engine per intersection)")
+        scripted = [v for v in new if v.uncontrolled]
         if scripted:
-            for k, v in enumerate(new):
-                if not getattr(v, "uncontrolled", False):
-                    self._traj[:, first + k, : type(v).N_STATES] = v.traj.T
-        elif all(type(v).N_STATES == ns for v in new):
-            for c in range(0, len(new), 512):        # adopt the vehicles' own histories, a slab of rows at a time
-                blk = new[c:c + 512]
-                self._traj[:, first + c:first + c + len(blk), :] = np.stack([v.traj for v in blk]).transpose(2, 0, 1)
-        else:
-            for k, v in enumerate(new):
-                self._traj[:, first + k, : type(v).N_STATES] = v.traj.T
-        for k, v in enumerate(new):
-            r = first + k
-            self._S[r] = s0[k]
-            self._shadow[r] = s0[k]
-            self._vd[r] = vd[k]
-            self._zn[r] = v.znav
-            st = (v.i, v.destpointer, v.force)
-            v._live = True
-            v.i, v.destpointer, v.force = st
-            self._bind(v)
-            self._dirty_queues[v] = -1
-        self._drawn_stale = True
-        self._cls[first:first + len(new)] = 0        # (the engine starts a road user in parameter set 0)
+            self._send_scripts(e, scripted)
+            self._scripted.extend(scripted)
+        T = int(30 / new[0].params.t_s)                        # vehicle.py:159
+        for v in new:
+            if v.traj.shape[1] != T and not v.uncontrolled:
+                raise NotImplementedError("all road users of one intersection share t_s (one engine per intersection)")
+        m.adopt(new, s0, vd, T)
+        self._dirty_queues.update(dict.fromkeys(new, QUEUE_REPLACED))
         self._sync_param_rows(cls)
 
-    def _widen(self, ns):
-        """rows of the bulk mirror as wide as the widest vehicle class of the population"""
-        for name in ("_S", "_shadow"):
-            old = getattr(self, name)
-            new = np.zeros((old.shape[0], ns))
-            new[:, : old.shape[1]] = old
-            setattr(self, name, new)
-        if self._traj is not None:
-            grown = np.zeros(self._traj.shape[:2] + (ns,))
-            grown[:, :, : self._traj.shape[2]] = self._traj
-            self._traj = grown
-        for v in self.vehicles:
-            if v._live:
-                st = (v.i, v.destpointer, v.force)
-                self._bind(v)
-                v.i, v.destpointer, v.force = st
-
-    def _mark_queue_dirty(self, v, how=None):
-        """how: None rows appended, -1 queue replaced (pointer rewinds), -2 rows edited in place (pointer kept)"""
-        prev = self._dirty_queues.get(v, 0)          # 0: clean
-        if how == -1 or prev == -1:
-            self._dirty_queues[v] = -1
-        elif how == -2 or prev == -2:
-            self._dirty_queues[v] = -2
-        else:
-            self._dirty_queues[v] = None
+    def _mark_queue_dirty(self, v, how):
+        """how: QUEUE_APPENDED, QUEUE_REPLACED (the pointer rewinds) or QUEUE_EDITED (in place, the pointer is kept)"""
+        prev = self._dirty_queues.get(v, QUEUE_APPENDED)
+        self._dirty_queues[v] = how if QUEUE_RANK[how] >= QUEUE_RANK[prev] else prev
 
     def _push_mutations(self):
         """Everything the user may have changed on the Python side since the last tick."""
-        e = self._engine_ready()
-        n = len(self.vehicles)
-        # UncontrolledVehicle: the reference reads car.traj[:, i] on every step (vehicle.py:964-979), so a trajectory written
-        # after the car joined - external control - has to reach the engine: compare with what was sent, send again on a change
+        e = self._engine
+        if e is None or self._pending or not self.vehicles:
+            e = self._engine_ready()
+        if self._scripted:                       # (each step behind the test that says whether it has anything to look at: a tick of
+            self._push_scripts(e)                #  a population nobody touched makes none of these calls)
+        if self._dirty_queues:
+            self._push_queues(e)
+        if self._mirror.watched:
+            self._push_states(e)
+        if self._track_params and parameters.mutation_count() != self._params_seen:
+            self._push_params(e)
+        if self.priority_rule != self._rule_on_device:
+            self._push_rule(e)
+        if tuple(id(el) for el in self.road_elements) != self._road_sig:
+            self._push_road(e)
+        return e
+
+    # UncontrolledVehicle: the reference reads car.traj[:, i] on every step (vehicle.py:964-979), so a trajectory written
+    # after the car joined - external control - has to reach the engine: compare with what was sent, send again on a change
+    def _push_scripts(self, e):
         changed = []
         for v in self._scripted:
-            if v._live and getattr(v, "_script_sent", None) is not None:
+            if v._mirror is not None and getattr(v, "_script_sent", None) is not None:
                 cur = np.ascontiguousarray(v.traj.T)
                 if cur.shape != v._script_sent.shape or not np.array_equal(cur, v._script_sent):
                     v._script = cur
-                    v._script_sent = cur.copy()
                     changed.append(v)
         if changed:
-            e.set_script([v._index for v in changed], np.cumsum([0] + [v._script.shape[0] for v in changed]),
-                         np.vstack([v._script for v in changed]))
-        # destination queues (only vehicles whose setDestinations / stop / go ran since the last push):
-        # replaced queues go up with reset=1, rows edited in place with reset=2, appended rows with reset=0
-        if self._dirty_queues:
-            groups = {1: ([], [], [0]), 2: ([], [], [0]), 0: ([], [], [0])}
-            for v, how in self._dirty_queues.items():
-                q = v.destqueue
-                if how == -1 or v._queue_synced < 0:
-                    mode, rows = 1, q
-                elif how == -2:
-                    mode, rows = 2, q
-                elif v._queue_synced < q.shape[0]:
-                    mode, rows = 0, q[v._queue_synced:]
-                else:
-                    continue
-                agents, blocks, off = groups[mode]
-                agents.append(v._index); blocks.append(rows); off.append(off[-1] + rows.shape[0])
-                v._queue_synced = q.shape[0]
-                v._queue_dirty = False
-            self._dirty_queues = {}
-            for mode in (1, 2, 0):
-                agents, blocks, off = groups[mode]
-                if agents:
-                    e.set_dest_queue(agents, off, np.vstack(blocks), reset=mode)
-        # vehicle.s edited in place (calibration.py:455-460): looked for once a vehicle.s has been handed out (Vehicle.s)
-        if self._s_watched and (self._S[:n] != self._shadow[:n]).any():
-            changed = np.where(np.any(self._S[:n] != self._shadow[:n], axis=1))[0]
-            e.push_state(changed, self._S[changed][:, : e.ns])
-            self._shadow[changed] = self._S[changed]
-        if self._track_params:
-            # params.v_desired_default is the per-agent parameter (demoCSFstandalone.py:104-113); the population is
-            # rescanned only after some parameter object was assigned to
-            if parameters.mutation_count() != self._params_seen:
-                self._params_seen = parameters.mutation_count()
-                vd = np.array([float(getattr(v.params, "v_desired_default", 0.0)) for v in self.vehicles])
-                ch = np.where(vd != self._vd[:n])[0]
-                if ch.size:
-                    e.set_v_desired(ch, vd[ch])
-                    self._vd[ch] = vd[ch]
-                self._sync_param_classes()
-        if self.priority_rule != self._rule_on_device:
-            if self.priority_rule not in PRIORITY_RULES:
-                raise ValueError(f"priority_rule must be one of {tuple(PRIORITY_RULES)}")
-            e.set_priority_rule(PRIORITY_RULES[self.priority_rule])
-            self._rule_on_device = self.priority_rule
-        sig = tuple(id(el) for el in self.road_elements)
-        if sig != self._road_sig:
-            off, verts, F0, sg = flatten_road_elements(self.road_elements)
-            e.set_road(off, verts, F0, sg)
-            self._road_sig = sig
-        return e
+            self._send_scripts(e, changed)
 
-    def _live(self):
-        """the bulk mirror's rows of the live road users (state, destination pointers, navigation state, Fx, Fy): one contiguous
-        block of each, what a read-back straight into the mirror writes"""
-        n = len(self.vehicles)
-        return self._S[:n], self._ptr[:n], self._zn[:n], self._fx[:n], self._fy[:n]
+    def _send_scripts(self, e, cars):
+        """prescribed trajectories -> the engine (csf_set_script), and what it holds now is remembered: later writes to car.traj are noticed"""
+        rows = [v._script if v._script is not None else np.zeros((0, 4)) for v in cars]
+        e.set_script([v._index for v in cars], np.cumsum([0] + [r.shape[0] for r in rows]), np.vstack(rows))
+        for v in cars:
+            v._script_sent = np.ascontiguousarray(v.traj.T).copy()
+
+    # destination queues (only vehicles whose setDestinations / stop / go ran since the last push): replaced queues go up
+    # first, then the ones edited in place, then appended rows
+    def _push_queues(self, e):
+        groups = {mode: ([], [], [0]) for mode in (QUEUE_REPLACED, QUEUE_EDITED, QUEUE_APPENDED)}
+        for v, how in self._dirty_queues.items():
+            rows = v.destqueue
+            mode = QUEUE_REPLACED if v._queue_synced < 0 else how
+            if mode == QUEUE_APPENDED:
+                if v._queue_synced >= rows.shape[0]:
+                    continue
+                rows = rows[v._queue_synced:]
+            agents, blocks, off = groups[mode]
+            agents.append(v._index); blocks.append(rows); off.append(off[-1] + rows.shape[0])
+            v._queue_synced = v.destqueue.shape[0]
+            v._queue_dirty = False
+        self._dirty_queues = {}
+        for mode, (agents, blocks, off) in groups.items():
+            if agents:
+                e.set_dest_queue(agents, off, np.vstack(blocks), reset=mode)
+
+    # vehicle.s edited in place (calibration.py:455-460): looked for once a vehicle.s has been handed out (Vehicle.s)
+    def _push_states(self, e):
+        changed = self._mirror.changed_rows()
+        if changed.size:
+            e.push_state(changed, self._mirror.states(changed, e.ns))
+            self._mirror.sync_shadow(changed)
+
+    # params.v_desired_default is the per-agent parameter (demoCSFstandalone.py:104-113); the population is rescanned
+    # only after some parameter object was assigned to
+    def _push_params(self, e):
+        self._params_seen = parameters.mutation_count()
+        vd = np.array([float(getattr(v.params, "v_desired_default", 0.0)) for v in self.vehicles])
+        ch = self._mirror.update_v_desired(vd)
+        if ch.size:
+            e.set_v_desired(ch, vd[ch])
+        self._sync_param_classes()
+
+    def _push_rule(self, e):
+        if self.priority_rule not in PRIORITY_RULES:
+            raise ValueError(f"priority_rule must be one of {tuple(PRIORITY_RULES)}")
+        e.set_priority_rule(PRIORITY_RULES[self.priority_rule])
+        self._rule_on_device = self.priority_rule
+
+    def _push_road(self, e):
+        e.set_road(*flatten_road_elements(self.road_elements))
+        self._road_sig = tuple(id(el) for el in self.road_elements)
 
     def _pull(self, forces=True, advance=1, step=0):
         """One read-back of the device's view into the bulk mirror (vehicle.s, znav, traj are views of it); step: that many
         ticks first, in the same call (csf_step_get_tick)."""
-        e = self._engine
-        n = len(self.vehicles)
-        if step and self._S.shape[1] == e.ns:
-            S, ptr, zn, fx, fy = self._live()
+        e, m = self._engine, self._mirror
+        if step and m.ns == e.ns:
+            S, ptr, zn, fx, fy = m.live()
             if not forces:
                 fx = fy = None
             e.step_into(step, S, ptr, zn, fx, fy)
-            return self._booked_pull(fx, fy, forces, advance)
         else:
             s, ptr, zn, fx, fy, _ = e.step_snapshot(step, forces=forces, reuse=True) if step else e.tick_snapshot(forces=forces)
-            self._S[:n, : s.shape[1]] = s
-            if self._s_watched:
-                self._shadow[:n, : s.shape[1]] = s
-            self._ptr[:n] = ptr
-            self._zn[:n] = zn
-            if forces:
-                self._fx[:n] = fx                                     # intersection.py:860-862
-                self._fy[:n] = fy
-        return self._book_pull(fx, fy, forces, advance)
+            m.store(s, ptr, zn, fx if forces else None, fy)
+        return self._book_tick(fx, fy, forces, advance)
 
-    def _booked_pull(self, fx, fy, forces, advance):
-        """_book_pull behind a read-back that went straight into the live rows (_pull, step_together): the watched shadow first"""
-        if self._s_watched:
-            n = len(self.vehicles)
-            self._shadow[:n] = self._S[:n]
-        return self._book_pull(fx, fy, forces, advance)
-
-    def _drawn_now(self):
-        """the vehicles with a drawing or saveForces (the only per-tick Python loop), listed anew when the population changed"""
-        if self._drawn_stale:
-            self._drawn = [v for v in self.vehicles if v.drawing is not None or v.saveForces]
-            self._drawn_stale = False
-        return self._drawn
-
-    def _book_pull(self, fx, fy, forces, advance):
-        """the host's per-tick bookkeeping behind a read-back into the bulk mirror (_pull; step_together): trajectory ring,
-        force logs, drawings, SUMO positions"""
-        n = len(self.vehicles)
-        if forces:
-            self._have_force = True
-        if advance:
-            if forces:
-                self._log_forces(fx, fy)
-            T = self._traj.shape[0]
-            ti = self._ti[:n] = (self._ti[:n] + advance) % T          # vehicle.py:1279-1282 (see DESIGN D5)
-            if n and (ti == ti[0]).all():
-                self._traj[ti[0], :n] = self._S[:n]                   # the usual case: everyone joined at tick 0
-            else:
-                self._traj[ti, np.arange(n)] = self._S[:n]
-            for v in self._drawn_now():
-                k = v._index
-                Fx, Fy = (fx[k], fy[k]) if forces else (0.0, 0.0)
-                if v.saveForces:
-                    v.trajF[0, self._ti[k]] = Fx
-                    v.trajF[1, self._ti[k]] = Fy
-                v.update_drawing(Fres=(Fx, Fy))
+    def _book_tick(self, fx, fy, forces, advance):
+        """the host's per-tick bookkeeping behind a read-back into the bulk mirror (_pull; step_together): the mirror's books,
+        and SUMO is told every tick (else the positions are refreshed when somebody reads them)"""
+        self._mirror.book_tick(fx, fy, forces, advance)
         if self.activate_sumo_cosimulation:
-            self.update_road_user_positions()                         # (SUMO is told every tick; else: when somebody reads them)
-        else:
-            self._pos_stale = True
+            self.update_road_user_positions()
         return fx, fy
 
     def _book_block(self, S, F):
-        """_book_pull(fx, fy, True, 1) behind each of K consecutive ticks at once, from their recorded states S [K, n, n_states] and
-        total forces F [K, n, 2] (Engine.recorded / batch_recorded): the trajectory ring, trajF, the force log and vehicle.i move
-        as K read-backs would have moved them.  K may exceed the ring: only the last rows survive, as with K single ticks.  (The
-        bulk mirror itself - _S, _ptr, _zn, _fx, _fy - holds the last tick's values already; drawings and SUMO want every tick on
-        the host and do not come here: _dense_engine.)"""
-        n = len(self.vehicles)
-        K = int(S.shape[0])
-        if K == 0:
-            return
-        self._have_force = True
-        mag = F[:, :, 0] * F[:, :, 0]                                 # (_log_forces, tick by tick: the same two roundings and the root)
-        mag += F[:, :, 1] * F[:, :, 1]
-        np.sqrt(mag, out=mag)
-        for k in range(K):
-            self._flog.append(mag[k])
-            if len(self._flog) >= 4096:
-                self._fold_all_force_logs()
-        T = self._traj.shape[0]
-        k0 = max(0, K - T)                                            # (ticks before it are overwritten by later ones)
-        ti0 = self._ti[:n].copy()
-        steps = np.arange(k0 + 1, K + 1)
-        w = S.shape[2]
-        if n and (ti0 == ti0[0]).all():
-            self._traj[(ti0[0] + steps) % T, :n, :w] = S[k0:]         # the usual case: everyone joined at tick 0
-        elif n:
-            self._traj[(ti0[None, :] + steps[:, None]) % T, np.arange(n)[None, :], :w] = S[k0:]
-        self._ti[:n] = (ti0 + K) % T                                  # vehicle.py:1279-1282 (see DESIGN D5)
-        for v in self._drawn_now():
-            if v.saveForces:
-                k = v._index
-                cols = (ti0[k] + steps) % T
-                v.trajF[0, cols] = F[k0:, k, 0]
-                v.trajF[1, cols] = F[k0:, k, 1]
-        self._pos_stale = True
-
-    def _booked_block(self, S, F):
         """behind a chunk of recorded ticks whose last read-back went straight into the live rows (step_n(dense=True),
-        advance_together): what that many calls of step() leave on the host"""
+        advance_together): what that many calls of step() leave on the host (drawings and SUMO want every tick on the host and
+        do not come here: _dense_engine)"""
         self.is_first_step = False
-        if self._s_watched:
-            n = len(self.vehicles)
-            self._shadow[:n] = self._S[:n]
-        self._book_block(S, F)
+        self._mirror.book_block(S, F)
         self.hist_n_vecs.extend([self.n_bikes] * int(S.shape[0]))
-
-    # vehicle.F: the per-tick magnitudes are logged as arrays and folded into a vehicle's list when it is read
-    def _log_forces(self, fx, fy):
-        mag = fx * fx                                                 # (np.hypot is three times the time of this at N = 16 384)
-        mag += fy * fy
-        self._flog.append(np.sqrt(mag, out=mag))
-        if len(self._flog) >= 4096:
-            self._fold_all_force_logs()
-
-    def _fold_force_log(self, v):
-        start = v._f_seen - self._flog_base
-        if start < len(self._flog):
-            k = v._index
-            v._F.extend(float(a[k]) for a in self._flog[start:])
-            v._f_seen = self._flog_base + len(self._flog)
-
-    def _fold_all_force_logs(self):
-        if self._flog:
-            for v in self.vehicles:
-                self._fold_force_log(v)
-        self._flog_base += len(self._flog)
-        self._flog = []
-        for v in self.vehicles:
-            v._f_seen = self._flog_base
-
-    def _state_handed_out(self):
-        """a vehicle.s view goes to the caller, who may write through it: from now on the mirror is compared with what the
-        device holds (the shadow) before every tick"""
-        if not self._s_watched and self._S is not None:
-            self._shadow[:] = self._S                                 # (nobody has written yet: the getter runs before the write)
-            self._s_watched = True
 
     # vehicleX / vehicleY / vehicleTheta (intersection.py:660-677) are refreshed when they are read: three column copies of the
     # mirror per tick are a tenth of the tick's host time at N = 16 384, and most ticks nobody looks
     def _positions(self):
-        if self._pos_stale:
+        if self._mirror.pos_stale:
             self.update_road_user_positions()
         return self._vx, self._vy, self._vth
 
@@ -782,13 +568,11 @@ class SocialForceIntersection:
     def update_road_user_positions(self):
         """intersection.py:660-677"""
         n = len(self.vehicles)
-        self._pos_stale = False
+        self._mirror.pos_stale = False
         if self._vx.shape[0] != n:
             self._vx, self._vy, self._vth = np.zeros((n, 1)), np.zeros((n, 1)), np.zeros((n, 1))
-        if n and self._S is not None and not self._pending:
-            self._vx[:, 0] = self._S[:n, 0]
-            self._vy[:, 0] = self._S[:n, 1]
-            self._vth[:, 0] = self._S[:n, 2]
+        if n and len(self._mirror.vehicles) == n:                  # (everyone is bound)
+            self._vx[:, 0], self._vy[:, 0], self._vth[:, 0] = self._mirror.positions()
         else:
             for k, v in enumerate(self.vehicles):
                 self._vx[k, 0], self._vy[k, 0], self._vth[k, 0] = v._s[0], v._s[1], v._s[2]
@@ -812,14 +596,11 @@ class SocialForceIntersection:
         e = self._push_mutations()
         if self._hooked and self.n_bikes > 0:
             fx, fy = self._hooked_forces(e)
-            n = len(self.vehicles)
-            self._fx[:n], self._fy[:n] = fx, fy
-            self._have_force = True
-            self._log_forces(fx, fy)
-            return fx, fy
-        fx, fy = e.calc_forces()
-        self._pull(forces=True, advance=0)
-        self._log_forces(fx, fy)
+            self._mirror.store_forces(fx, fy)
+        else:
+            fx, fy = e.calc_forces()
+            self._pull(forces=True, advance=0)
+        self._mirror.log_forces(fx, fy)
         return fx, fy
 
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
@@ -837,15 +618,13 @@ class SocialForceIntersection:
         has moved 0.8333 m/s since the last draw.  In vehicle order: the draws come off one generator.  The tick is split for
         this - forces, draws, then the integration with the forces (csf_calc_forces / csf_apply_forces) - so that a rider steps
         with the poles the reference would have given it in THAT tick."""
-        n = len(self.vehicles)
-        v_now = self._S[:n, 3]
         for r in riders:
-            i, p = r._index, r.params
+            i, p, v_now = r._index, r.params, r._s[3]
             vd = np.sqrt(fx[i] ** 2 + fy[i] ** 2)
-            a = min(max(p.k_p_v * (vd - v_now[i]), p.a_max[0]), p.a_max[1])
-            v_new = min(max(v_now[i] + p.t_s * a, p.v_max_riding[0]), p.v_max_riding[1])
-            if v_new != v_now[i]:
-                p.update_control_params((v_new + v_now[i]) / 2)
+            a = min(max(p.k_p_v * (vd - v_now), p.a_max[0]), p.a_max[1])
+            v_new = min(max(v_now + p.t_s * a, p.v_max_riding[0]), p.v_max_riding[1])
+            if v_new != v_now:
+                p.update_control_params((v_new + v_now) / 2)
 
     # ------------------------------------------------------------------ custom per-vehicle force hooks (vehicle.py:194-204, 250-299)
     def _field_engine(self, v):
@@ -855,8 +634,6 @@ class SocialForceIntersection:
         key = bytes(pod)
         eng = self._field_engines.get(key)
         if eng is None:
-            from .engine import Engine
-
             eng = self._field_engines[key] = Engine(pod, 1)
         return eng
 
@@ -872,8 +649,7 @@ class SocialForceIntersection:
         n = self.n_bikes
         fdx, fdy = e.dest_force()                                  # :799 for every class force; advances the queues as the reference does
         self._pull(forces=False, advance=0)                        # vehicle.s / dest / destpointer as the hooks expect to find them
-        S = self._S[:n]
-        X, Y, PSI = S[:, 0].copy(), S[:, 1].copy(), S[:, 2].copy()
+        X, Y, PSI = self._mirror.positions()
         for i, v in enumerate(self.vehicles):
             if v.dest_force_func is not None:                      # vehicle.py:295-297 (updateDestination has run: csf_dest_force)
                 fdx[i], fdy[i] = v.dest_force_func(v)
@@ -890,7 +666,7 @@ class SocialForceIntersection:
                 elif getattr(v.params, "f_0", 1.0) == 0.0 and v.MODEL != 0:
                     continue                                       # vehicle.py:1592-1593
                 else:
-                    fxi, fyi = self._field_engine(v).pair_force(np.r_[S[i, :3], S[i, 3]], X[trk], Y[trk], PSI[trk])
+                    fxi, fyi = self._field_engine(v).pair_force(v._s[:4].copy(), X[trk], Y[trk], PSI[trk])
                 Fx[i, trk], Fy[i, trk] = fxi, fyi                  # :822-823
             frx, fry = limitMagnitude(Fx.sum(axis=0), Fy.sum(axis=0), np.sqrt(fdx ** 2 + fdy ** 2))   # :841-845
             fx, fy = frx + fdx, fry + fdy
@@ -907,35 +683,51 @@ class SocialForceIntersection:
                 if v.drawing is None:
                     v.add_drawing(self.ax, animated=True, **self.bicycle_drawing_kwargs)
         self.is_first_step = False
-        stochastic = self.n_bikes > 0 and self._stochastic_riders()
-        if self.n_bikes > 0 and (self._hooked or stochastic):
+        why = self._host_reason()
+        if why in (HOOKS, POLES):
             e = self._push_mutations()
             if self._hooked:
                 fx, fy = self._hooked_forces(e)                    # intersection.py:889
             else:
                 fx, fy = e.calc_forces()
+            stochastic = self._stochastic_riders()
             if stochastic:
                 self._resample_poles(stochastic, fx, fy)
                 e = self._push_mutations()                         # (a new draw is a new parameter set of its rider)
             e.apply_forces(fx, fy)                                 # :891-892: every vehicle.step(Fx[i], Fy[i])
             self._pull(forces=True, advance=1)                     # :894
-        elif self.n_bikes > 0:
+        elif why is None:
             self._push_mutations()
             self._pull(forces=True, advance=1, step=1)
         self.hist_n_vecs.append(self.n_bikes)
 
+    def _host_reason(self, drawn=False, first_drawings=False):
+        """Why every tick of this intersection has to pass the host, or None.  An empty intersection, custom force hooks and
+        drawn poles bind every route; what a route cannot serve besides is its argument: `drawn` - the dense routes book a block
+        of ticks afterwards, so no `animate`, no SUMO co-simulation, no drawing at all -, `first_drawings` - the batched route
+        hands out no drawings, which `animate` wants on the first tick."""
+        if self.n_bikes <= 0:
+            return EMPTY
+        if self._hooked:
+            return HOOKS
+        if self._stochastic_riders():
+            return POLES
+        if drawn and (self.animate or self.activate_sumo_cosimulation or any(v.drawing is not None for v in self.vehicles)):
+            return DRAWN
+        if first_drawings and self.animate and self.is_first_step:
+            return FIRST_DRAWINGS
+        return None
+
     def _dense_engine(self):
         """the engine, recording (Engine.record: it keeps the one-wave tick and the batched launch), when n ticks of this
-        intersection can run in one call and be booked from the record afterwards; None when every tick has to pass the host:
-        empty, custom force hooks, drawn poles, drawings or `animate`, SUMO co-simulation, a mirror wider than the engine's state"""
-        if self.n_bikes <= 0 or self._hooked or self.animate or self.activate_sumo_cosimulation or self._stochastic_riders():
-            return None
-        if any(v.drawing is not None for v in self.vehicles):
+        intersection can run in one call and be booked from the record afterwards; None when every tick has to pass the host
+        (_host_reason) or the mirror's rows are wider than the engine's state"""
+        if self._host_reason(drawn=True) is not None:
             return None
         e = self._push_mutations()
-        if self._S.shape[1] != e.ns:
+        if self._mirror.ns != e.ns:
             return None
-        if getattr(e, "_dense_for", None) != e.n:                     # (a new engine, or road users came or went: a ring of this layout)
+        if e._dense_for != e.n:                                       # (a new engine, or road users came or went: a ring of this layout)
             e.record(stride=1, capacity=DENSE_CHUNK, forces=True)
             e._dense_for = e.n
         return e
@@ -953,15 +745,16 @@ class SocialForceIntersection:
                     left -= 1
                     continue
                 k = min(left, DENSE_CHUNK)
-                tick = e.step_into(k, *self._live())
-                self._booked_block(*e.recorded(tick - k, k))
+                tick = e.step_into(k, *self._mirror.live())
+                self._book_block(*e.recorded(tick - k, k))
                 left -= k
             return
-        if self.n_bikes > 0 and (self._hooked or self._stochastic_riders()):   # (custom force hooks, drawn poles: every tick passes the host)
+        why = self._host_reason()
+        if why in (HOOKS, POLES):                                     # (every tick passes the host)
             for _ in range(int(n_ticks)):
                 self.step()
             return
-        if self.n_bikes > 0 and n_ticks > 0:
+        if why is None and n_ticks > 0:
             e = self._push_mutations()
             e.step(int(n_ticks))
             if pull:
@@ -970,13 +763,11 @@ class SocialForceIntersection:
 
     def _batch_outputs(self):
         """(engine, the bulk mirror's arrays for csf_step_batch_get_tick) when this intersection's tick can join a batched step,
-        else None: empty, custom force hooks, drawn poles or drawings on the first tick, a mirror narrower than the engine's state"""
-        if self.n_bikes <= 0 or self._hooked or (self.animate and self.is_first_step) or self._stochastic_riders():
+        else None: _host_reason, or rows wider than the engine's state"""
+        if self._host_reason(first_drawings=True) is not None:
             return None
         e = self._push_mutations()
-        if self._S.shape[1] != e.ns:
-            return None
-        return e, self._live()
+        return (e, self._mirror.live()) if self._mirror.ns == e.ns else None
 
     def set_small_classes(self, on=True):
         """Engine.small_classes for this intersection's engine, now or when it is made: up to 32 road users with their own `params=`, of
@@ -1001,10 +792,10 @@ def _batch_of(engines):
     """the engines as ONE batch (Engine.batch_join), joined again when the set of engines changed - an intersection creates its
     engine lazily, or a new one when its population's vehicle classes change"""
     key = [id(e) for e in engines]
-    if getattr(engines[0], "_together", None) is not None and [id(e) for e in engines[0]._together] == key:
+    if engines[0]._together is not None and [id(e) for e in engines[0]._together] == key:
         return
     for e in engines:
-        old = getattr(e, "_together", None)
+        old = e._together
         if old is None:
             continue
         try:
@@ -1018,14 +809,11 @@ def _batch_of(engines):
         e._together = list(engines)
 
 
-DENSE_CHUNK = 512        # ticks per call of the dense paths = samples of the engines' rings (DESIGN 4.6c: the bytes per member)
-
-
 def advance_together(intersections, n_ticks):
     """step_together(intersections, n_ticks) - the same vehicle.s, traj, trajF, F, znav, destpointer, hist_n_vecs - with the
     ticks in calls of up to DENSE_CHUNK: the engines record every tick on the device (Engine.record), a chunk is one
     csf_step_batch_get_tick (one launch per vehicle class) and one csf_batch_get_record (one gather, one transfer, one wait), and
-    the host books the whole block at once (_book_block) - instead of a call, a wait and the host's bookkeeping per tick.
+    the host books the whole block at once (PopulationMirror.book_block) - instead of a call, a wait and the host's bookkeeping per tick.
     Intersections that need the host every tick (custom force hooks, stochastic riders, drawings or `animate`, SUMO
     co-simulation) and empty ones take step_together's route inside the same call."""
     intersections = list(intersections)
@@ -1044,9 +832,9 @@ def advance_together(intersections, n_ticks):
         if dense:
             engines = [e for _, e in dense]
             _batch_of(engines)
-            Engine.step_batch_into(engines, k, [ins._live() for ins, _ in dense])
+            Engine.step_batch_into(engines, k, [ins._mirror.live() for ins, _ in dense])
             for (ins, _), (S, F, _) in zip(dense, Engine.batch_recorded(engines, k)):
-                ins._booked_block(S, F)
+                ins._book_block(S, F)
         left -= k
 
 
@@ -1072,5 +860,5 @@ def step_together(intersections, n_ticks=1):
         Engine.step_batch_into(engines, 1, [o for _, _, o in joined])
         for ins, _, (_, _, _, fx, fy) in joined:
             ins.is_first_step = False
-            ins._booked_pull(fx, fy, True, 1)
+            ins._book_tick(fx, fy, True, 1)
             ins.hist_n_vecs.append(ins.n_bikes)

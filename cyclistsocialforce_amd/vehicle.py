@@ -20,6 +20,11 @@ from .parameters import (BalancingRiderBicycleParameters, BicycleParameters, Car
                          PlanarBicycleParameters, PlanarPointBicycleParameters, VehicleParameters)
 from .utils import limitAngle
 
+# what happened to a destination queue since it was last sent = the reset modes of csf_set_dest_queue; a later change of a
+# higher rank wins: replaced (the pointer rewinds) beats edited in place (the pointer is kept) beats rows appended
+QUEUE_APPENDED, QUEUE_REPLACED, QUEUE_EDITED = 0, 1, 2
+QUEUE_RANK = {QUEUE_APPENDED: 0, QUEUE_EDITED: 1, QUEUE_REPLACED: 2}
+
 
 class Vehicle:
     """Parent class — vehicle.py:49-917.  Abstract here: a concrete class selects the rider model."""
@@ -35,7 +40,7 @@ class Vehicle:
         # on the GPU.  A custom callable is the caller's Python code: honoured by the single-vehicle methods below, and inside
         # a SocialForceIntersection by a tick that forms the forces on the host from the engine's pieces (intersection.py of
         # this package: _hooked_forces) - meant for the handful of road users such scenarios have.
-        self._owner = None
+        self._owner = None        # SocialForceIntersection that holds this vehicle, or None
         self.dest_force_func = dest_force_func
         self.rep_force_func = rep_force_func
         if self.MODEL is None:
@@ -47,9 +52,8 @@ class Vehicle:
                 raise TypeError(f"Params must be a '{self.PARAMS_TYPE.__name__}' object. "
                                 f"Instead it was '{type(params).__name__}'.")
             self.params = params
-        self._owner = None        # SocialForceIntersection that holds this vehicle, or None
         self._index = -1
-        self._live = False        # True once the intersection's engine holds this vehicle (bulk mirror active)
+        self._mirror = None       # the owner's PopulationMirror once its engine holds this vehicle (set by bind, cleared by detach)
         self.i = 0                                                     # vehicle.py:146
         if len(s0) < self.N_STATES:                                    # vehicle.py:149-152
             raise ValueError(f"The initial state s0 has to be size {self.N_STATES} with states "
@@ -105,7 +109,7 @@ class Vehicle:
             self._owner._hooked = True
 
     # ------------------------------------------------------------------ mirrored scalars
-    # Inside a SocialForceIntersection these live in the intersection's bulk arrays (one device read-back per tick
+    # Inside a SocialForceIntersection these live in the intersection's PopulationMirror (one device read-back per tick
     # refreshes every vehicle at once); on its own the vehicle keeps them itself.
     @property
     def s(self):
@@ -113,16 +117,16 @@ class Vehicle:
         holds it may write through it (calibration.py:455-460 edits vehicle.s in place): the intersection is told, and
         compares its mirror with what the device holds before the next tick - only from then on, not on every tick of a
         population nobody looks at"""
-        if self._live:
-            self._owner._state_handed_out()
+        if self._mirror is not None:
+            self._mirror.watch()
         return self._s
 
     @s.setter
     def s(self, value):
-        if self._live:                                                 # rebinding vehicle.s: the mirror's row takes the values
+        if self._mirror is not None:                                   # rebinding vehicle.s: the mirror's row takes the values
             row = self._s
             if value is not row:
-                self._owner._state_handed_out()
+                self._mirror.watch()
                 row[:] = np.asarray(value, dtype=float)[: row.size]
         else:
             self._s = value
@@ -130,23 +134,23 @@ class Vehicle:
     @property
     def i(self):
         """column of `traj` written last (vehicle.py:146, 1279-1282)"""
-        return int(self._owner._ti[self._index]) if self._live else self._i
+        return self._mirror.i_of(self) if self._mirror is not None else self._i
 
     @i.setter
     def i(self, value):
         self._i = int(value)
-        if self._live:
-            self._owner._ti[self._index] = int(value)
+        if self._mirror is not None:
+            self._mirror.set_i(self, int(value))
 
     @property
     def destpointer(self):
-        return int(self._owner._ptr[self._index]) if self._live else self._destpointer
+        return self._mirror.pointer_of(self) if self._mirror is not None else self._destpointer
 
     @destpointer.setter
     def destpointer(self, value):
         self._destpointer = int(value)
-        if self._live:
-            self._owner._ptr[self._index] = int(value)
+        if self._mirror is not None:
+            self._mirror.set_pointer(self, int(value))
 
     @property
     def dest(self):
@@ -160,15 +164,13 @@ class Vehicle:
     @property
     def force(self):
         """total force of the last evaluated tick (intersection.py:860-861)"""
-        if self._live and self._owner._have_force:
-            return (float(self._owner._fx[self._index]), float(self._owner._fy[self._index]))
-        return self._force
+        return (self._mirror.force_of(self) if self._mirror is not None else None) or self._force
 
     @force.setter
     def force(self, value):
         self._force = (float(value[0]), float(value[1]))
-        if self._live:
-            self._owner._fx[self._index], self._owner._fy[self._index] = self._force
+        if self._mirror is not None:
+            self._mirror.set_force(self, self._force)
 
     @property
     def drawing(self):
@@ -177,14 +179,14 @@ class Vehicle:
     @drawing.setter
     def drawing(self, value):
         self._drawing = value
-        if self._owner is not None:
-            self._owner._drawn_stale = True
+        if self._mirror is not None:
+            self._mirror.drawn_stale = True
 
     @property
     def F(self):
         """magnitudes of the total force, one entry per evaluated tick (intersection.py:862)"""
-        if self._owner is not None:
-            self._owner._fold_force_log(self)
+        if self._mirror is not None:
+            self._mirror.fold(self)
         return self._F
 
     @F.setter
@@ -208,7 +210,7 @@ class Vehicle:
         e = self._solo
         if self._queue_dirty:
             keep = getattr(self, "_queue_keep_ptr", False) and self._solo_synced
-            e.set_dest_queue([0], [0, self.destqueue.shape[0]], self.destqueue, reset=2 if keep else 1)
+            e.set_dest_queue([0], [0, self.destqueue.shape[0]], self.destqueue, reset=QUEUE_EDITED if keep else QUEUE_REPLACED)
             self._queue_dirty = False
             self._queue_keep_ptr = False
             self._solo_synced = True
@@ -323,7 +325,7 @@ class Vehicle:
             self.destqueue = np.vstack((self.destqueue, np.c_[x, y, stop]))
         self._queue_dirty = True
         if self._owner is not None:
-            self._owner._mark_queue_dirty(self, -1 if reset else None)
+            self._owner._mark_queue_dirty(self, QUEUE_REPLACED if reset else QUEUE_APPENDED)
 
     def stop(self, stoptype=0, stopdest=None):
         """vehicle.py:459-503.  Type 0 sets the stop flag of the current destination (the reference does it through
@@ -363,7 +365,7 @@ class Vehicle:
         self._queue_dirty = True
         self._queue_keep_ptr = True
         if self._owner is not None:
-            self._owner._mark_queue_dirty(self, -2)
+            self._owner._mark_queue_dirty(self, QUEUE_EDITED)
 
     def setSplineDestinations(self, x, y, npoints, stop=False, reset=False):
         """vehicle.py:649-693 (host-side convenience; uses scipy like the reference)."""

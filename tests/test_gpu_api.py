@@ -135,9 +135,9 @@ def test_vehicle_state_written_through_a_view_a_rebinding_or_an_old_reference(go
     ins = SocialForceIntersection(vs)
     for _ in range(3):
         ins.step()
-    assert not ins._s_watched                                  # nobody has looked: no compare, no shadow copy per tick
+    assert not ins._mirror.watched                                  # nobody has looked: no compare, no shadow copy per tick
     old_ref = vs[7].s                                          # handed out now ...
-    assert ins._s_watched
+    assert ins._mirror.watched
     for _ in range(3):
         ins.step()
     x_before = float(ins.vehicleX[7, 0])
@@ -154,6 +154,45 @@ def test_vehicle_state_written_through_a_view_a_rebinding_or_an_old_reference(go
     np.testing.assert_array_equal(dev, np.array([v.s for v in ins.vehicles]))      # mirror == device after the pull
     np.testing.assert_array_equal(ins.vehicleX[:, 0], dev[:, 0])                   # refreshed when read
     np.testing.assert_array_equal(ins.vehicleTheta[:, 0], dev[:, 2])
+
+
+def test_dense_ticks_after_a_wider_class_joined_a_state_was_edited_and_a_road_user_left():
+    """Two intersections built alike: three TwoDBicycles and three ticks, an InvPendulumBicycle joins (wider rows), one vehicle.s
+    is read again and written through, one road user leaves by index.  Then five step() on the one and step_n(5, dense=True)
+    on the other leave every vehicle and the intersection the same, bit for bit."""
+    def run(dense):
+        rng = np.random.default_rng(21)
+        vs = []
+        for k in range(4):
+            x, y, psi = rng.uniform(0, 12), rng.uniform(0, 12), rng.uniform(-np.pi, np.pi)
+            cls = TwoDBicycle if k < 3 else InvPendulumBicycle
+            v = cls((x, y, psi, 4.0, 0.0, 0.0), id=f"v{k}", saveForces=(k % 2 == 0))
+            v.setDestinations(x + np.array([30, 60]) * np.cos(psi), y + np.array([30, 60]) * np.sin(psi))
+            vs.append(v)
+        ins = SocialForceIntersection(vs[:3])
+        for _ in range(3):
+            ins.step()
+        ins.add_road_user(vs[3])                                    # (the rows widen under the three that are bound)
+        vs[2].s[0] += 1.5
+        ins.remove_road_user(1)
+        if dense:
+            ins.step_n(5, dense=True)
+        else:
+            for _ in range(5):
+                ins.step()
+        return ins, vs
+
+    (a, va), (b, vb) = run(False), run(True)
+    assert [v.id for v in a.vehicles] == [v.id for v in b.vehicles] == ["v0", "v2", "v3"]
+    assert a.hist_n_vecs == b.hist_n_vecs == [3] * 8
+    for u, w in zip(va, vb):
+        for name in ("s", "traj", "znav"):
+            np.testing.assert_array_equal(getattr(u, name), getattr(w, name), err_msg=f"{u.id}.{name}")
+        assert (u.i, u.destpointer, u.force, u.F) == (w.i, w.destpointer, w.force, w.F), u.id
+        if u.saveForces:
+            np.testing.assert_array_equal(u.trajF, w.trajF, err_msg=u.id)
+    assert va[0].i == 8 and va[3].i == 5 and va[1].i == 3 and va[1]._owner is None and len(va[0].F) == 8
+    assert va[2].s.shape == (5,) and va[3].s.shape == (6,) and np.isfinite(va[3].s).all()
 
 
 def test_vehicle_hooks_against_golden(golden):

@@ -1,6 +1,6 @@
 """Recording, host side (no GPU): csf_record_out has the same layout in the header and in the ctypes binding, the new entry points
-are declared and exported, and the bookkeeping of a block of K recorded ticks (SocialForceIntersection._book_block) leaves the
-trajectory ring, trajF, the force log and vehicle.i exactly as K single read-backs (_book_pull) do."""
+are declared and exported, and the bookkeeping of a block of K recorded ticks (PopulationMirror.book_block) leaves the
+trajectory ring, trajF, the force log and vehicle.i exactly as K single read-backs (book_tick) do."""
 import ctypes as C
 import os
 import re
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from cyclistsocialforce_amd import _ffi
-from cyclistsocialforce_amd.intersection import SocialForceIntersection
+from cyclistsocialforce_amd.mirror import PopulationMirror
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("csf_record", "csf_get_record", "csf_batch_get_record")
@@ -50,35 +50,36 @@ int main(void) {
 
 class _V:
     """what the bookkeeping touches of a vehicle"""
+    N_STATES = 5
+    uncontrolled = False
 
-    def __init__(self, k, T, save):
+    def __init__(self, k, T, save, i):
         self._index, self.saveForces, self.drawing = k, save, None
+        self._s, self.znav, self.traj = np.zeros(self.N_STATES), np.array([True, False, False]), np.zeros((self.N_STATES, T))
+        self.i, self.destpointer, self.force = int(i), 0, (0.0, 0.0)
         self.trajF = np.zeros((2, T))
-        self._F, self._f_seen = [], 0
+        self._F = []
 
     def update_drawing(self, Fres=None):
         pass
 
 
+def _columns(m):
+    return [m.i_of(v) for v in m.vehicles]
+
+
 def _mirror(n, T, ns, ti, save):
-    """a SocialForceIntersection as far as _book_pull / _book_block go: the bulk mirror of n road users, no engine"""
-    ins = object.__new__(SocialForceIntersection)
-    ins.vehicles = [_V(k, T, save[k]) for k in range(n)]
-    ins._traj = np.zeros((T, n + 2, ns))
-    ins._S = np.zeros((n + 2, ns))
-    ins._ti = np.r_[np.asarray(ti, dtype=np.int64), 0, 0]
-    ins._fx, ins._fy = np.zeros(n + 2), np.zeros(n + 2)
-    ins._flog, ins._flog_base = [], 0
-    ins._drawn, ins._drawn_stale = [], True
-    ins._have_force, ins._pos_stale = False, False
-    ins.activate_sumo_cosimulation = False
-    return ins
+    """the bulk mirror of n road users at the ring columns ti, with room for two more; no engine"""
+    m = PopulationMirror()
+    m.allocate(n + 2, ns)
+    m.adopt([_V(k, T, save[k], ti[k]) for k in range(n)], np.zeros((n, ns)), np.zeros(n), T)
+    return m
 
 
 @pytest.mark.parametrize("n,T,K,ti", [(3, 50, 20, [0, 0, 0]), (3, 50, 50, [7, 7, 7]), (3, 50, 137, [49, 49, 49]), (4, 30, 12, [0, 5, 29, 17]),
                                       (4, 30, 95, [3, 0, 11, 29]), (1, 8, 8, [2]), (5, 16, 1, [1, 1, 1, 1, 2]), (2, 10, 5000, [0, 4])])
 def test_a_block_of_ticks_is_booked_as_the_single_ticks_are(n, T, K, ti):
-    """K ticks booked at once against K calls of _book_pull: road users that joined at the same tick and at different ones
+    """K ticks booked at once against K calls of book_tick: road users that joined at the same tick and at different ones
     (unequal vehicle.i), K below, at and beyond the length of traj, and beyond the 4 096 entries the force log folds at"""
     rng = np.random.default_rng(n * 1000 + K)
     ns = 5
@@ -86,17 +87,20 @@ def test_a_block_of_ticks_is_booked_as_the_single_ticks_are(n, T, K, ti):
     F = rng.normal(size=(K, n, 2)) * 3.0
     save = [k % 2 == 0 for k in range(n)]
     a, b = _mirror(n, T, ns, ti, save), _mirror(n, T, ns, ti, save)
+    assert _columns(a) == list(ti) and not a.pos_stale
     for k in range(K):
-        a._S[:n] = S[k]
-        a._fx[:n], a._fy[:n] = F[k, :, 0], F[k, :, 1]
-        a._book_pull(a._fx[:n], a._fy[:n], True, 1)
-    b._S[:n] = S[-1]
-    b._fx[:n], b._fy[:n] = F[-1, :, 0], F[-1, :, 1]
-    b._book_block(S, F)
-    assert np.array_equal(a._traj, b._traj)
-    assert np.array_equal(a._ti, b._ti)
-    assert a._have_force and b._have_force and b._pos_stale
+        s, _, _, fx, fy = a.live()
+        s[:] = S[k]
+        fx[:], fy[:] = F[k, :, 0], F[k, :, 1]
+        a.book_tick(fx, fy, True, 1)
+    s, _, _, fx, fy = b.live()
+    s[:] = S[-1]
+    fx[:], fy[:] = F[-1, :, 0], F[-1, :, 1]
+    b.book_block(S, F)
+    assert np.array_equal(a.ring, b.ring)
+    assert _columns(a) == _columns(b)
+    assert a.have_force and b.have_force and b.pos_stale
     for u, w in zip(a.vehicles, b.vehicles):
         assert np.array_equal(u.trajF, w.trajF)
-        a._fold_force_log(u); b._fold_force_log(w)
+        a.fold(u); b.fold(w)
         assert u._F == w._F and len(u._F) == K

@@ -24,7 +24,9 @@ def mirror_path(n, box, ticks):
         v.setDestinations(dq[4 * k + 1:4 * k + 4, 0], dq[4 * k + 1:4 * k + 4, 1])
         vs.append(v)
     ins = SocialForceIntersection(vs, capacity=n)
-    ins.step()
+    t0 = time.perf_counter()
+    ins.step()                                  # (the engine is made and the population adopted into the mirror: _flush_pending)
+    print(f"SocialForceIntersection first step()        N={n:6d}: {(time.perf_counter() - t0) * 1e3:8.3f} ms")
     t0 = time.perf_counter()
     for _ in range(ticks):
         ins.step()
