@@ -47,9 +47,11 @@ SYMBOLS = (
     "csf_handout_ranks",
     "csf_wg_order_ranks", "csf_wg_order_tables",
     "csf_pair_shape_of", "csf_pair_shape_words",
+    "csf_field_map", "csf_field_map_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
+FIELD_CROWD, FIELD_ROAD, FIELD_FOV = 1, 2, 4
 
 
 class Params(C.Structure):
@@ -194,6 +196,8 @@ def load():
         L.csf_pair_shape_words.argtypes = [vp, C.POINTER(i32)]
     L.csf_comm_stream_order.argtypes = [vp, C.POINTER(i32), dp]
     L.csf_small_ticks.argtypes = [vp, C.POINTER(i64)]
+    L.csf_field_map.argtypes = [vp, i64, dp, dp, dp, C.c_uint32, i32, dp, dp]
+    L.csf_field_map_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -445,6 +445,20 @@ void launch_nav_kat(const Dev &d, const int32_t *idx, int64_t m, int what, const
                     double *ddest_out, hipStream_t st);
 void launch_pair_kat(const Dev &d, const float4 *src, const float2 *src2, const float4 *recv, int64_t m,
                      int apply_fov, float2 *out, hipStream_t st);
+// csf_fieldmap.hip (csf_field_map): the force field at m probe points, one probe per lane, one launch per term
+struct FieldMapArgs {
+    const double *x, *y, *psi;   // [m] the probes (psi: the crowd term only)
+    double *Fx, *Fy;             // [m]
+    int64_t m;
+    int32_t skip;                // road user of the population order that is no source, or -1
+    int32_t fov;                 // the probe is a receiver of heading psi: intersection.py:690-745
+    int32_t accumulate;          // road term: added to what Fx, Fy hold (the crowd term)
+    // the rounding bands of a pair whose (dx, dy) is an fp64 difference rounded once (engine/abi_fieldmap.inc: field_map_bands), as
+    // tracked_m and side_undecided read them from a PairConsts
+    float fovA, fovB, sideA, sideB, sideP0, sideP1;
+};
+void launch_field_map_crowd(const Dev &d, const FieldMapArgs &a, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+void launch_field_map_road(const Dev &d, const FieldMapArgs &a, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

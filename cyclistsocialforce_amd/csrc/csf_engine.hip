@@ -14,7 +14,8 @@
 #include "engine/abi_population.inc"   // C ABI: road users arriving and leaving, queues, roads, parameter sets, pushed states
 #include "engine/tick.inc"   // one tick enqueued: two launches in turn, one launch (mid-size), side by side (large), one wave (a handful); csf_step, csf_sync
 #include "engine/abi_forces_readback.inc"   // C ABI: forces on their own, replay, read-backs, the single-function entry points
-#include "engine/abi_sharding.inc"   // C ABI: communicators, loopback groups
+#include "engine/abi_fieldmap.inc"   // C ABI: the force field at arbitrary probe points (csf_fieldmap.hip)
+#include "engine/abi_sharding.inc"  // C ABI: communicators, loopback groups
 #include "engine/abi_batch.inc"   // C ABI: batches of independent scenes (one launch per vehicle class for all one-wave members)
 #include "engine/abi_calib.inc"   // C ABI: calibration - a resident data set, many parameter sets evaluated per launch (csf_calib.hip)
 #include "engine/abi_scene.inc"   // C ABI: calibration on closed-loop scenes - workgroup = (parameter set, scene), the error summed in the launch (csf_scene.hip)

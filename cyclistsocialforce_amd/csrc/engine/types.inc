@@ -509,6 +509,7 @@ struct csf_engine {
     HostBuf<double, false> bound_pin;   // where the positions land when that bound is measured again (set_fov_band)
     int64_t moves = 0;
     int64_t small_ticks = 0;         // ticks run by the one-wave kernel (csf_small_ticks)
+    int64_t field_map_launches = 0;  // launches of csf_field_map: one per requested term (csf_field_map_launches)
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     int64_t slab_rewrites = 0;       // compact_slab calls (upload_queues sizes the slab by them)
     bool bound_stale = false;        // positions moved without a speed clamp (csf_replay_forces with fix_speed): measure them

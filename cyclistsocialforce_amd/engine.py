@@ -687,6 +687,43 @@ class Engine:
         self._ck(self._lib.csf_pair_force(self._h, _ptr(src), x.size, _ptr(x), _ptr(y), _ptr(psi), int(apply_fov), _ptr(fx), _ptr(fy)))
         return fx, fy
 
+    def field_map(self, x, y, psi=None, crowd=True, road=True, fov=False, skip=-1):
+        """the force field at arbitrary probe points (csf.h: csf_field_map; scenarios/curve-scenario.py:90-125): x, y (and psi, the
+        heading a road user would have there) of any common shape -> (Fx, Fy) of that shape.  crowd: the sum of the live road users'
+        fields, each its class's field with its own parameter set, unclamped; road: the road-edge term; fov: the probe is a receiver
+        of heading psi - the mask of intersection.py:690-745 with the priority rule; skip: a road user (population order) left out as a
+        source.  psi may be a scalar; it may be None only without the crowd term.  One launch per term, every pair evaluated."""
+        x = np.asarray(x, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if x.shape != y.shape:
+            raise ValueError(f"field_map: x {x.shape} and y {y.shape} differ in shape")
+        if not crowd and not road:
+            raise ValueError("field_map: neither the crowd term nor the road term is asked for")
+        if fov and not crowd:
+            raise ValueError("field_map: fov masks the crowd term - it needs crowd=True")
+        if psi is None:
+            if crowd:
+                raise ValueError("field_map: the crowd term needs the probes' headings psi")
+        else:
+            psi = np.asarray(psi, dtype=np.float64)
+            if psi.ndim == 0:
+                psi = np.full(x.shape, float(psi))
+            elif psi.shape != x.shape:
+                raise ValueError(f"field_map: psi {psi.shape} and x {x.shape} differ in shape")
+            psi = _f64(psi)
+        shape = x.shape
+        x, y = _f64(x), _f64(y)
+        fx, fy = np.zeros(x.size), np.zeros(x.size)
+        what = (_ffi.FIELD_CROWD if crowd else 0) | (_ffi.FIELD_ROAD if road else 0) | (_ffi.FIELD_FOV if fov else 0)
+        self._ck(self._lib.csf_field_map(self._h, x.size, _ptr(x), _ptr(y), None if psi is None else _ptr(psi), what, int(skip), _ptr(fx), _ptr(fy)))
+        return fx.reshape(shape), fy.reshape(shape)
+
+    def field_map_launches(self):
+        """launches of field_map so far: one per requested term and call (csf.h: csf_field_map_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_field_map_launches(self._h, C.byref(n)))
+        return n.value
+
     def untracked(self):
         """get_untracked_foes() (intersection.py:690-745): bool [n, n], row = source, column = receiver"""
         n = self.n

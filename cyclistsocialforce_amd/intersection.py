@@ -48,6 +48,40 @@ class RoadEdge:
     def edges(self):
         return [self]
 
+    def calcRepulsiveForce(self, x, y):
+        """intersection.py:226-242: the force of this edge's vertices at the points (x, y), any common shape -> (Fx, Fy) of that shape.
+        Evaluated on the device (Engine.field_map, road term) by a private engine that holds nothing but this edge; the engine
+        is kept until the vertices or the parameters change.  A point exactly on a vertex gets nothing from that vertex."""
+        x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+        verts = np.ascontiguousarray(self.vertices, dtype=float)
+        sig = (verts.shape, verts.tobytes(), float(self.params.F_0), float(self.params.sigma))
+        cache = self.__dict__.get("_field_cache")
+        if cache is None or cache[0] != sig:
+            if cache is not None:
+                cache[1].close()
+            eng = Engine(_road_probe_pod(), 1)
+            eng.set_road(*flatten_road_elements([self]))
+            cache = self._field_cache = (sig, eng)
+        return cache[1].field_map(x, y, crowd=False, road=True)
+
+
+def _road_probe_pod():
+    """the parameter set of an engine that holds a road and no road user (RoadEdge.calcRepulsiveForce): any vehicle class's defaults"""
+    return parameters.BicycleParameters().to_pod(_ffi.TWOD)
+
+
+def _sum_repulsive_force(parts, x, y):
+    """intersection.py:36-48, 81-94: the parts' forces at the flattened points, added up part by part, in the shape of x"""
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    shape = x.shape
+    x, y = x.flatten(), y.flatten()
+    Fx, Fy = np.zeros_like(x), np.zeros_like(y)
+    for part in parts:
+        fx, fy = part.calcRepulsiveForce(x, y)
+        Fx += fx
+        Fy += fy
+    return np.reshape(Fx, shape), np.reshape(Fy, shape)
+
 
 class RoadSegment:
     """intersection.py:72-115: two edges at +-width/2 around a centre line starting at x0 = (x, y, heading).
@@ -63,6 +97,10 @@ class RoadSegment:
 
     def edges(self):
         return list(self.edge_list)
+
+    def calcRepulsiveForce(self, x, y):
+        """intersection.py:81-94: the sum of the two edges' forces"""
+        return _sum_repulsive_force(self.edge_list, x, y)
 
     @staticmethod
     def _place(local_xy, origin, heading):
@@ -117,6 +155,10 @@ class RoadSegmentCollection:
 
     def edges(self):
         return [e for seg in self.segs for e in seg.edges()]
+
+    def calcRepulsiveForce(self, x, y):
+        """intersection.py:36-48: the sum of the segments' forces (scenarios/curve-scenario.py:90-125 maps it on a meshgrid)"""
+        return _sum_repulsive_force(self.segs, x, y)
 
     def get_destinations_from_segments(self):
         return [seg.x1[0] for seg in self.segs], [seg.x1[1] for seg in self.segs]
@@ -602,6 +644,32 @@ class SocialForceIntersection:
             self._pull(forces=True, advance=0)
         self._mirror.log_forces(fx, fy)
         return fx, fy
+
+    def force_field(self, X, Y, psi=0.0, crowd=True, road=True, fov=False, exclude=None):
+        """The force field of the live population and of `road_elements` at the probe points (X, Y), any common shape -> (Fx, Fy)
+        of that shape: what a road user of heading psi (a scalar, or an array of that shape) would feel there - the sum of every
+        road user's calcRepulsiveForce (its class's field, its own parameter set; unclamped: limitMagnitude needs a destination
+        force, which a probe has not) and the road-edge term.  fov: the probe ignores the road users a receiver there would ignore
+        (get_untracked_foes, the priority rule included).  exclude: a vehicle of this intersection, or its id, left out as a source -
+        what THAT rider would feel elsewhere.  One launch per term on the population's own engine (Engine.field_map)."""
+        X, Y = np.asarray(X, dtype=float), np.asarray(Y, dtype=float)
+        if crowd and any(v.rep_force_func is not None for v in self.vehicles):
+            raise NotImplementedError("force_field: a vehicle carries a custom rep_force_func - that field lives in Python")
+        left_out = None
+        if exclude is not None:
+            hit = [v for v in self.vehicles if v is exclude or (not isinstance(exclude, Vehicle) and v.id == exclude)]
+            if not hit:
+                raise ValueError(f"force_field: {exclude!r} is no road user of this intersection")
+            left_out = hit[0]
+        if not self.vehicles:                                      # nobody there: the road elements' own engines
+            if X.shape != Y.shape:
+                raise ValueError(f"force_field: X {X.shape} and Y {Y.shape} differ in shape")
+            if road:
+                return _sum_repulsive_force(self.road_elements, X, Y)
+            return np.zeros(X.shape), np.zeros(X.shape)
+        e = self._push_mutations()
+        skip = -1 if left_out is None else left_out._index        # (its place in the population order, once arrivals are on the device)
+        return e.field_map(X, Y, psi, crowd=crowd, road=road, fov=fov, skip=skip)
 
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):

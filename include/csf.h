@@ -247,6 +247,25 @@ int csf_get_history(csf_engine *e, int64_t first_sample, int64_t n_samples, doub
 int csf_record(csf_engine *e, int32_t stride, int32_t capacity, uint32_t what);
 int csf_get_record(csf_engine *e, int64_t first_sample, int64_t n_samples, double *s_out, double *F_out);
 
+/* ---- force-field maps ----------------------------------------------------------------------------- */
+
+/* The force field at m arbitrary probe points (x, y, psi [m]; scenarios/curve-scenario.py:90-125): what a road user would
+ * feel there.  `what` names the terms; with both, Fx, Fy = crowd + road, added in fp64.  Every pair is evaluated - no
+ * far-field cull.  psi may be NULL only without CSF_FIELD_CROWD (it enters the TwoD field itself, vehicle.py:1595).  skip: -1,
+ * or a road user (population order) that is left out as a source - what THAT road user would feel elsewhere.  One launch per
+ * requested term whatever m is (csf_field_map_launches counts them); pending uploads are brought in, the engine's work is
+ * waited for, and the engine is left exactly as it was.  An empty population / no road gives zeros; a probe with a
+ * non-finite coordinate gets NaN, the others are not affected.  Refused (CSF_E_ARG / CSF_E_STATE, nothing changed): NULL
+ * arrays, m < 0, what == 0 or unknown bits, FOV without CROWD, skip out of range, a rank of a sharded run or a member of a
+ * loopback group, an engine that holds a calibration data set.  While csf_profile_enable is on, the crowd launch is timed as
+ * kernel 0 and the road launch as kernel 1 of csf_profile_kernels / csf_profile_samples_of. */
+#define CSF_FIELD_CROWD 1u   /* sum of the live road users' fields (each its class's field, its own parameter set), unclamped */
+#define CSF_FIELD_ROAD  2u   /* road-edge term of csf_set_road_vertices */
+#define CSF_FIELD_FOV   4u   /* with CROWD: the probe is a receiver of heading psi - field-of-view mask and priority rule applied */
+int csf_field_map(csf_engine *e, int64_t m, const double *x, const double *y, const double *psi,
+                  uint32_t what, int32_t skip, double *Fx, double *Fy);
+int csf_field_map_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
