@@ -339,8 +339,10 @@ void launch_small_batch(int model, const Dev *table, int count, int max_nv_pad, 
 void launch_small_classes(const Dev &d, int n_ticks, hipStream_t st);
 void launch_small_classes_batch(const Dev *table, int count, int max_nv_pad, int n_ticks, bool pack, hipStream_t st);
 // csf_mid.hip: one tick of a mid-size population (plain pair sums + per-agent tick) in one launch; d.rec_w / recg_w / rec2_w /
-// src64_w point at the halves of the double buffers this tick does not read, d.mid_group = slots per workgroup
-bool launch_mid_tick(const Dev &d, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// src64_w point at the halves of the double buffers this tick does not read, d.mid_group = slots per workgroup; road: the instance
+// that sums the road term of d.rv itself (no launch_road in front; at most MID_ROAD_MAX padded vertices, no lattice)
+constexpr int MID_ROAD_MAX = SMALL_ROAD_MAX;   // (what the one-wave tick stages; DESIGN.md 4.7b has the measurement behind it)
+bool launch_mid_tick(const Dev &d, bool road, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // csf_step_batch, mid-size members (csf_mid.hip: mid_batch_kernel): what changes in a member's Dev from tick to tick, 48 bytes
 // where the Dev is 1.3 KB.  The batch's table holds the rest - the halves of the double buffers by name, rec / recg / rec2 / src64 the
 // engine's first halves and rec_w / recg_w / rec2_w / src64_w its second - and the kernels compose the tick's Dev from the two.
@@ -364,8 +366,9 @@ __host__ __device__ __forceinline__ void mid_compose(Dev &d, const MidTick &t) {
     d.pc.fovA = t.fovA, d.pc.fovB = t.fovB, d.pc.sideA = t.sideA, d.pc.sideB = t.sideB, d.pc.fovT0 = t.fovT0, d.pc.fovT1 = t.fovT1;
 }
 bool mid_shape_ok(const Dev &d);   // launch_mid_tick / mid_batch_kernel take this population in groups of d.mid_group
-// one tick of the `n_groups` groups listed in `groups` (table slot, group within the member), all of vehicle class `model` and one priority rule
-void launch_mid_batch(int model, bool p2r, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st);
+// one tick of the `n_groups` groups listed in `groups` (table slot, group within the member), all of vehicle class `model` and one priority
+// rule, all with a road the launch sums itself (road) or all without
+void launch_mid_batch(int model, bool p2r, bool road, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st);
 // the periodic work of the members whose MidTick says so, one launch each whatever their number (grid y = table slot; the x
 // extents are the largest member's): the plain order and every record re-expressed (launch_identity_perm + launch_rebase: two
 // launches), the other halves made equal (launch_chase_sync without the binned copy)

@@ -13,7 +13,9 @@
 //   wave 0        the destination-force phase of the group's road users - queue, navigation state, planner: it needs no sums -
 //                 (csf_agent_dev.h: agent_body, lane = road user) ...
 //   the others    ... while they form the group's repulsive sums, item by item from an LDS counter, sources in the lanes, straight
-//                 from the records in memory, asked for one item ahead.  TwoD field: an item is ONE receiver (wave-uniform, in
+//                 from the records in memory, asked for one item ahead.  (ROAD instances, below: behind the pair items the same
+//                 queue hands out the group's road term, four receivers against all vertices of a small road per item -
+//                 csf_road_dev.h)  The pair items, TwoD field: an item is ONE receiver (wave-uniform, in
 //                 scalar registers) against four batches of 64 sources, cull first as in csf_pair.hip - two batches at a time
 //                 through the field-of-view test on packed arithmetic, the tracked sources to a queue in LDS, the packed field on
 //                 what the queue holds, the rare pairs (near, marginal, on the line ahead of a source) one per lane on the precise
@@ -34,6 +36,7 @@
 // the per-agent phase renews for the next tick in the other half as well.
 #include "csf_agent_dev.h"
 #include "csf_pair_dev.h"
+#include "csf_road_dev.h"
 
 namespace csf {
 
@@ -45,7 +48,10 @@ constexpr int MID_GROUP_MAX = 32;             // road users (slots) of a group a
 constexpr int MID_ITEMS_MAX = 384;            // (receiver set, source batch) items of a group at most: 12 KB of partial sums
 constexpr int MID_SB = 4;                     // TwoD field: source batches of an item (one receiver against 256 sources)
 
-template <int MODEL, bool P2R>
+// ROAD: the pair waves also sum the road term of the group's road users, as items of the same queue behind the pair
+// items, where the launch would otherwise follow road_kernel's; everything of it sits under if constexpr (ROAD) in the body, and the
+// host picks the instance (tick.inc: mid_road_ok) - Dev is the same.
+template <int MODEL, bool P2R, bool ROAD>
 __global__ __launch_bounds__(mid_waves(MODEL) * WAVE) void mid_tick_kernel(const Dev d) {
 #define MID_GROUP_INDEX blockIdx.x
 #define MID_KERNARG_LINES kernarg_touch<(int)sizeof(Dev) + 4>()
@@ -59,7 +65,7 @@ __global__ __launch_bounds__(mid_waves(MODEL) * WAVE) void mid_tick_kernel(const
 // different scenes share a grid as they are.  The table holds every member's Dev in a form that does not change from tick to
 // tick - the halves of the double buffers by name (rec: the engine's first half, rec_w: its second), tick, stamp and rounding
 // bands zero -; what does change is the member's MidTick of this tick, and the kernel composes its Dev from the two.
-template <int MODEL, bool P2R>
+template <int MODEL, bool P2R, bool ROAD>
 __global__ __launch_bounds__(mid_waves(MODEL) * WAVE) void mid_batch_kernel(const Dev *__restrict__ table, const MidTick *__restrict__ ticks,
                                                                             const int2 *__restrict__ groups, const int n_groups) {
     if ((int)blockIdx.x >= n_groups) return;                     // (before any load)
@@ -81,12 +87,18 @@ bool mid_shape_ok(const Dev &d) {
     return (d.mid_group / RPW) * ((d.n_src - d.src_beg) >> 6) <= MID_ITEMS_MAX;
 }
 
-void launch_mid_batch(int model, bool p2r, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st) {
+void launch_mid_batch(int model, bool p2r, bool road, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st) {
     if (n_groups <= 0) return;
     const dim3 g((unsigned)n_groups);
-#define CSF_MIDB(MODEL)                                                                                                               \
-    if (p2r) hipLaunchKernelGGL((mid_batch_kernel<MODEL, true>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, table, ticks, groups, n_groups); \
-    else hipLaunchKernelGGL((mid_batch_kernel<MODEL, false>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, table, ticks, groups, n_groups)
+#define CSF_MIDB2(MODEL, ROAD)                                                                                                               \
+    if (p2r) hipLaunchKernelGGL((mid_batch_kernel<MODEL, true, ROAD>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, table, ticks, groups, n_groups); \
+    else hipLaunchKernelGGL((mid_batch_kernel<MODEL, false, ROAD>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, table, ticks, groups, n_groups)
+#define CSF_MIDB(MODEL)                 \
+    if (road) {                         \
+        CSF_MIDB2(MODEL, true);         \
+    } else {                            \
+        CSF_MIDB2(MODEL, false);        \
+    }
     switch (model) {
     case CSF_BICYCLE: CSF_MIDB(CSF_BICYCLE); break;
     case CSF_TWOD: CSF_MIDB(CSF_TWOD); break;
@@ -95,16 +107,24 @@ void launch_mid_batch(int model, bool p2r, const Dev *table, const MidTick *tick
     default: CSF_MIDB(CSF_PLANARPOINT); break;
     }
 #undef CSF_MIDB
+#undef CSF_MIDB2
 }
 
 // false: nothing was launched (a shape this kernel is not built for) - the caller must not count the tick as taken
-bool launch_mid_tick(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+// road: the ROAD instance - the launch sums the road term itself and no launch_road goes in front of it (the caller has asked mid_road_ok)
+bool launch_mid_tick(const Dev &d, bool road, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
     if (!mid_shape_ok(d)) return false;
     const dim3 g((unsigned)((d.hi - d.lo + d.mid_group - 1) / d.mid_group));
     const bool p2r = d.p.priority_rule == CSF_P2R;
-#define CSF_MID(MODEL)                                                                                            \
-    if (p2r) hipExtLaunchKernelGGL((mid_tick_kernel<MODEL, true>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, t0, t1, 0, d);       \
-    else hipExtLaunchKernelGGL((mid_tick_kernel<MODEL, false>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, t0, t1, 0, d)
+#define CSF_MID2(MODEL, ROAD)                                                                                            \
+    if (p2r) hipExtLaunchKernelGGL((mid_tick_kernel<MODEL, true, ROAD>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, t0, t1, 0, d);       \
+    else hipExtLaunchKernelGGL((mid_tick_kernel<MODEL, false, ROAD>), g, dim3(mid_waves(MODEL) * WAVE), 0, st, t0, t1, 0, d)
+#define CSF_MID(MODEL)                 \
+    if (road) {                        \
+        CSF_MID2(MODEL, true);         \
+    } else {                           \
+        CSF_MID2(MODEL, false);        \
+    }
     switch (d.p.model) {
     case CSF_BICYCLE: CSF_MID(CSF_BICYCLE); break;
     case CSF_TWOD: CSF_MID(CSF_TWOD); break;
@@ -113,6 +133,7 @@ bool launch_mid_tick(const Dev &d, hipStream_t st, hipEvent_t t0, hipEvent_t t1)
     default: CSF_MID(CSF_PLANARPOINT); break;
     }
 #undef CSF_MID
+#undef CSF_MID2
     return true;
 }
 

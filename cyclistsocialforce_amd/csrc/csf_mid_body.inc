@@ -1,7 +1,7 @@
 // csf_mid_body.inc - the body of the one-launch tick, TEXTUALLY shared by mid_tick_kernel and mid_batch_kernel (csf_mid.hip includes
 // it in both; not a translation unit, not a header).  A function would do for the batch kernel, but the single-scene kernel's
 // registers must stay what they were, and the compiler allocates an inlined body differently from a body in place.  In scope:
-// MODEL, P2R, `d` (the scene's Dev); MID_GROUP_INDEX (the group's number within the scene), MID_KERNARG_LINES (kernarg_touch's
+// MODEL, P2R, ROAD, `d` (the scene's Dev); MID_GROUP_INDEX (the group's number within the scene), MID_KERNARG_LINES (kernarg_touch's
 // result, or 0u where d does not live in the kernarg segment).
     constexpr int MID_WAVES = mid_waves(MODEL);
     constexpr int FIELD = MODEL == CSF_BICYCLE ? 1 : 0;
@@ -43,6 +43,48 @@
         gorg[lane] = d.rorg[j];
     }
     __syncthreads();
+    // ROAD (DESIGN.md 4.7b): the group's road term (intersection.py:226-242, 854-857) as further items of the queue, BEHIND the pair
+    // items - item `items + s` is receiver set s (RPW slots) against all d.nv_pad vertices, so the pair items' numbers and psum are
+    // what they are without a road.  The arithmetic and the order inside a lane are road_kernel's (csf_road_dev.h): d.froad gets the
+    // very float that launch would have left.  d.road_np is uniform: a switch inside the item, not further kernel instances.  Lane 0's
+    // store is an ordinary one: it has landed before this wave's s_waitcnt vmcnt(0) in front of the workgroup's barrier, wave 0 asks for
+    // d.froad[a] again behind that barrier (agent_body, second call), and a workgroup's waves share one CU's write-through L1.
+    // (generic: instantiated only where it is called, under if constexpr (ROAD) - the other instances do not contain it)
+    [[maybe_unused]] auto road_items = [&](int item, auto &claim) {
+        while (item < items + sets) {
+            const int s = item - items;
+            const int64_t j0 = g0 + (int64_t)s * RPW;
+            float rh[RPW][2], rl[RPW][2];
+#pragma unroll
+            for (int u = 0; u < RPW; u++) {
+                float4 q;
+                float2 o;
+                if constexpr (BICYCLE) {                              // (this field keeps no grec)
+                    const int64_t j = j0 + u < d.hi ? j0 + u : d.hi - 1;   // clamp: results of the duplicates are not stored
+                    q = d.rec[j];
+                    o = d.rorg[j];
+                } else {
+                    q = grec[s * RPW + u];                            // (clamped where it was loaded)
+                    o = gorg[s * RPW + u];
+                }
+                two_sum(o.x, q.x, rh[u][0], rl[u][0]);
+                two_sum(o.y, q.y, rh[u][1], rl[u][1]);
+            }
+            float2 f[RPW];
+            switch (d.road_np) {
+            case 2: road_sum_from_memory<2>(d, lane, rh, rl, f); break;
+            case 3: road_sum_from_memory<3>(d, lane, rh, rl, f); break;
+            case 4: road_sum_from_memory<4>(d, lane, rh, rl, f); break;
+            case 5: road_sum_from_memory<5>(d, lane, rh, rl, f); break;
+            case 6: road_sum_from_memory<6>(d, lane, rh, rl, f); break;
+            default: road_sum_from_memory<0>(d, lane, rh, rl, f); break;
+            }
+#pragma unroll
+            for (int u = 0; u < RPW; u++)
+                if (lane == 0 && j0 + u < d.hi) d.froad[j0 + u] = f[u];
+            item = claim();
+        }
+    };
     if (wave == 0) {
         stamp(0);
         if (lane < G) agent_body<MODEL, false, false, 1>(d, PH_DEST, a, nullptr, ka_lines, 0.0, 0.0);
@@ -215,6 +257,7 @@
             if ((lane & 31) == 0) (&psum[0][0])[2 * item + (lane >> 5)] = v;
             item = nxt;
         }
+        if constexpr (ROAD) road_items(item, claim);            // (the claim that ended the loop above may be a road item)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (wave == 1) stamp(6);
         if (wave == MID_WAVES - 1) stamp(7);
@@ -276,7 +319,8 @@
             o = on;
             qb = qbn;
         }
-        // (what this wave left in memory for wave 0 - status bits, hand-over entries - has landed before the barrier)
+        if constexpr (ROAD) road_items(item, claim);
+        // (what this wave left in memory for wave 0 - status bits, hand-over entries, with ROAD the road term - has landed before the barrier)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (wave == 1) stamp(6);
         if (wave == MID_WAVES - 1) stamp(7);

@@ -49,6 +49,7 @@
 // The math is trig-free: every angle of the reference enters only through sin/cos, which are dot and cross
 // products of unit vectors here.
 #include "csf_pair_dev.h"
+#include "csf_road_dev.h"
 
 namespace csf {
 
@@ -1042,36 +1043,13 @@ __global__ __launch_bounds__(BLOCK) void road_kernel(const Dev d) {
             pf.y = two ? pf.y : 0.0f;
             v2f pw{0.f, 0.f};
             if (!NP) pw = lds_pair(vw, t, t2);
-#pragma unroll
-            for (int u = 0; u < RPW; u++) {
-                const v2f ex = px - r[u].x, ey = py - r[u].y;       // :235-236 (numerators)
-                const v2f r2 = ex * ex + ey * ey;                   // :231-234
-                v2f m;
-                if (NP) {
-                    v2f inv = rsq2(r2);
-                    inv = __builtin_elementwise_min(inv, v2f{1e6f, 1e6f});   // r = 0: finite, times ex = ey = 0
-                    const v2f i2 = inv * inv;
-                    m = NP == 2 ? i2 : NP == 3 ? i2 * inv : NP == 4 ? i2 * i2 : NP == 5 ? i2 * i2 * inv : i2 * i2 * i2;
-                } else {
-                    v2f lg = pw * v2f{fast_log2(r2.x), fast_log2(r2.y)};
-                    lg = __builtin_elementwise_min(lg, v2f{120.f, 120.f});   // r = 0: finite, times ex = ey = 0
-                    m = v2f{fast_exp2(lg.x), fast_exp2(lg.y)};
-                }
-                m = m * pf;                                         // -F0 r^-(sigma+1)    :238
-                ax[u] = m * ex + ax[u];                             // :239-240
-                ay[u] = m * ey + ay[u];
-            }
+            road_pair_x2<NP>(px, py, pf, pw, r, ax, ay);       // (csf_road_dev.h: the one-launch tick's road items run the same)
         }
     }
 #pragma unroll
     for (int u = 0; u < RPW; u++) {
-        float sx = ax[u].x + ax[u].y, sy = ay[u].x + ay[u].y;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            sx += __shfl_xor(sx, o, WAVE);
-            sy += __shfl_xor(sy, o, WAVE);
-        }
-        if (lane == 0 && j0 + u < d.hi) d.froad[j0 + u] = make_float2(sx, sy);
+        const float2 f = road_wave_sum(ax[u], ay[u]);
+        if (lane == 0 && j0 + u < d.hi) d.froad[j0 + u] = f;
     }
 }
 

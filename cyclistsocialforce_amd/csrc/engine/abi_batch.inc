@@ -12,9 +12,10 @@
 // (Dev::rec_tick) that the launch reads and moves on itself.  The host knows what the word holds (csf_engine::rec_tick_dev) and
 // writes it in stream order only where the engine has ticked outside the batched launch since.
 //
-// Mid-size members - those the one-launch tick takes (tick.inc: mid_fused_ok), without a road (the road term is a launch of its
-// own per tick: such members stay in turn), without wave traces, with nothing pending, and at least two of them - are stepped
-// together too: tick by tick, one launch of mid_batch_kernel (csf_mid.hip) per vehicle class and priority rule present.  Their
+// Mid-size members - those the one-launch tick takes (tick.inc: mid_fused_ok), without a road or with one that the launch sums itself
+// (tick.inc: mid_road_ok - csf_mid_road on, no lattice, at most MID_ROAD_MAX vertices; any other road is a launch of its own per tick:
+// such members stay in turn), without wave traces, with nothing pending, and at least two of them - are stepped together too: tick by
+// tick, one launch of mid_batch_kernel (csf_mid.hip) per vehicle class, priority rule and with / without road present.  Their
 // Dev differs on every tick (the halves of the double buffers trade places, tick, stamp, rounding bands), so a second table holds
 // each member's Dev in a form that does not (mid_canon), renewed like the first one, and the kernel composes the tick's Dev from
 // it and the member's MidTick (csf_dev.h: 48 bytes).  The host knows these records in advance: it writes them for a STRETCH of
@@ -57,7 +58,7 @@ struct BatchState {
     DevBuf<int2> mgroups;
     HostBuf<int2, false> mgroups_stage;
     std::vector<int2> mgroups_now, mgroups_dev;  // what this call wants / what the device holds
-    struct MidLaunch { int model, p2r, beg, end; };
+    struct MidLaunch { int model, p2r, road, beg, end; };    // (road: the ROAD instance - members without a road keep their kernel)
     std::vector<MidLaunch> mlaunch;
     DevBuf<MidTick> mticks;                      // [MID_STRETCH][members]
     HostBuf<MidTick, false> mticks_stage;        // two of them, used in turn
@@ -167,7 +168,7 @@ static int batch_table(BatchState &b, hipStream_t st) {
 // ---- mid-size members ---------------------------------------------------------------------------------------------------------
 // could the batched one-launch tick take this member (behind upload_all and the calibration)?
 static bool batch_mid_ok(const csf_engine *e) {
-    return e->knobs.batch_mid != 0 && mid_fused_ok(e) && e->d.nv == 0 && e->d.atrace == nullptr && e->pend.empty() && !e->dirty;
+    return e->knobs.batch_mid != 0 && mid_fused_ok(e) && (e->d.nv == 0 || mid_road_ok(e)) && e->d.atrace == nullptr && e->pend.empty() && !e->dirty;
 }
 
 // A member's Dev as the table holds it: what enqueue_mid_tick's launch sees, but for what changes from tick to tick - the halves
@@ -238,9 +239,9 @@ static int mid_groups(BatchState &b, csf_engine *const *engines, hipStream_t st)
     for (size_t j = 0; j < b.mid.size(); j++) {
         if (b.mid_out[j]) continue;
         const csf_engine *e = engines[b.mid[j]];
-        const int model = e->d.p.model, p2r = e->d.p.priority_rule == CSF_P2R ? 1 : 0;
-        if (b.mlaunch.empty() || b.mlaunch.back().model != model || b.mlaunch.back().p2r != p2r)
-            b.mlaunch.push_back({model, p2r, (int)b.mgroups_now.size(), (int)b.mgroups_now.size()});
+        const int model = e->d.p.model, p2r = e->d.p.priority_rule == CSF_P2R ? 1 : 0, road = e->d.nv > 0 ? 1 : 0;
+        if (b.mlaunch.empty() || b.mlaunch.back().model != model || b.mlaunch.back().p2r != p2r || b.mlaunch.back().road != road)
+            b.mlaunch.push_back({model, p2r, road, (int)b.mgroups_now.size(), (int)b.mgroups_now.size()});
         const int G = mid_group_for(e), groups = (int)((e->d.hi - e->d.lo + G - 1) / G);
         for (int g = 0; g < groups; g++) b.mgroups_now.push_back(make_int2((int)j, g));
         b.mlaunch.back().end = (int)b.mgroups_now.size();
@@ -301,11 +302,13 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
         if ((rc = chase_join(e))) return rc;
         if ((rc = alt_alloc(e))) return rc;
     }
-    // by launch: vehicle class, then priority rule; join order within
+    // by launch: vehicle class, then priority rule, then without / with a road (batch_mid_ok: a road here is one the launch sums);
+    // join order within
     std::stable_sort(b.mid.begin(), b.mid.end(), [&](int32_t x, int32_t y) {
         const Dev &dx = engines[x]->d, &dy = engines[y]->d;
         const int px = dx.p.priority_rule == CSF_P2R, py = dy.p.priority_rule == CSF_P2R;
-        return dx.p.model != dy.p.model ? dx.p.model < dy.p.model : px < py;
+        const int rx = dx.nv > 0, ry = dy.nv > 0;
+        return dx.p.model != dy.p.model ? dx.p.model < dy.p.model : px != py ? px < py : rx < ry;
     });
     b.mid_out.assign(k, 0);
     struct Defer {   // (the members go back to enqueueing their own periodic launches on every way out)
@@ -371,7 +374,7 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
                 max_sync = std::max(max_sync, std::max<int64_t>(e->d.n_pad, 3 * e->d.cap));
                 e->mid_deferred = 0;
             }
-            mid_ticked(e, other_halves(e), true);
+            mid_ticked(e, other_halves(e), true, e->d.nv > 0);
             e->device_ahead = true;
             return CSF_OK;
         };
@@ -416,7 +419,7 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
         }
         for (int64_t r = 0; r < T; r++)
             for (const BatchState::MidLaunch &l : b.mlaunch) {
-                launch_mid_batch(l.model, l.p2r != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
+                launch_mid_batch(l.model, l.p2r != 0, l.road != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
                 b.launches++;
             }
         HIPCHK(e0, hipGetLastError());

@@ -193,6 +193,14 @@ static bool mid_fused_ok(const csf_engine *e) {
            d.src_beg == 0 && d.n_src / 64 * 8 <= 384;                  // (csf_mid.hip: MID_ITEMS_MAX items of the largest group)
 }
 
+// ... and does its launch sum the road term too (csf_mid.hip: the ROAD instances; DESIGN.md 4.7b)?  The switch of csf_mid_road on, a
+// road, no lattice (csf_road.hip sums a lattice its own way), and no more padded vertices than MID_ROAD_MAX.  False: launch_road goes
+// in front of the plain instance, as before there was a switch - and inside a batch the member is stepped in turn.
+static bool mid_road_ok(const csf_engine *e) {
+    const Dev &d = e->d;
+    return e->mid_road && d.nv > 0 && d.rg_nx == 0 && d.nv_pad <= MID_ROAD_MAX;
+}
+
 // the second halves of the double buffers (allocations synchronise: never inside something that is being timed)
 static int alt_alloc(csf_engine *e) {
     const size_t nrec = e->rec.n;
@@ -298,11 +306,12 @@ static int mid_group_for(const csf_engine *e) {
 }
 
 // behind the launch: the halves trade places, the counters move on
-static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched) {
+static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched, bool road) {
     trade_halves(e, o, false);
     bounds_after_pair(e, true);
     e->moves++;
     e->mid_ticks++;
+    if (road) e->mid_road_ticks++;
     if (batched) e->batch_mid_ticks++;
     e->d.tick++;
 }
@@ -310,15 +319,16 @@ static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched) {
 // (behind mid_prelude)
 static int enqueue_mid_tick(csf_engine *e) {
     Dev &d = e->d;
-    if (d.nv > 0) launch_road(d, e->main);
+    const bool road = mid_road_ok(e);                             // (the launch below sums the road term itself)
+    if (d.nv > 0 && !road) launch_road(d, e->main);
     const OtherHalves o = other_halves(e);
     Dev dd = d;
     write_other_halves(dd, o, false);                             // (this tick writes no binned copy)
     dd.mid_group = mid_group_for(e);
     // (nothing has traded places yet: a refused launch leaves the engine where it was)
-    if (!launch_mid_tick(dd, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, dd.mid_group);
+    if (!launch_mid_tick(dd, road, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, dd.mid_group);
     HIPCHK(e, hipGetLastError());
-    mid_ticked(e, o, false);
+    mid_ticked(e, o, false, road);
     return CSF_OK;
 }
 

@@ -942,6 +942,18 @@ class Engine:
         tick and the batched launch too (csf.h: csf_small_classes; off by default, or what CSF_SMALL_CLASSES said at creation)"""
         self._ck(self._lib.csf_small_classes(self._h, 1 if on else 0))
 
+    def mid_road(self, on=True):
+        """the one-launch tick of a mid-size population sums the road term of a small road (no lattice, at most 2 048 padded vertices)
+        itself, alone and as a batch member, instead of a road launch in front of every tick (csf.h: csf_mid_road; off by default, or
+        what CSF_MID_ROAD said at creation)"""
+        self._ck(self._lib.csf_mid_road(self._h, 1 if on else 0))
+
+    def mid_road_ticks(self):
+        """ticks whose road term was summed inside the one-launch tick (csf.h: csf_mid_road_ticks; mid_ticks counts them too)"""
+        v = C.c_int64()
+        self._ck(self._lib.csf_mid_road_ticks(self._h, C.byref(v)))
+        return v.value
+
     def mid_ticks(self):
         """ticks run as one launch each (csf_mid.hip: mid-size populations)"""
         v = C.c_int64()

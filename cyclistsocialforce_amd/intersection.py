@@ -214,6 +214,7 @@ class SocialForceIntersection:
         self._track_params = track_params
         self._engine = None
         self._small_classes = None   # set_small_classes: what the engine is told once it exists (None: the engine's own default)
+        self._mid_road = None        # set_mid_road: the same
         self._mirror = PopulationMirror()   # the bulk host arrays of the per-vehicle attributes the device produces, and their books
         self._scripted = []       # live UncontrolledVehicles (their traj may be rewritten while they run)
         self._rule_on_device = None
@@ -438,6 +439,8 @@ class SocialForceIntersection:
             self._engine = Engine(pod, cap, device=self._device)
             if self._small_classes is not None:
                 self._engine.small_classes(self._small_classes)
+            if self._mid_road is not None:
+                self._engine.mid_road(self._mid_road)
             self._capacity = cap
             self._mirror.allocate(cap, max(type(v).N_STATES for v in self.vehicles))
             self._rule_on_device = self.priority_rule
@@ -844,6 +847,14 @@ class SocialForceIntersection:
         self._small_classes = bool(on)
         if self._engine is not None:
             self._engine.small_classes(self._small_classes)
+
+    def set_mid_road(self, on=True):
+        """Engine.mid_road for this intersection's engine, now or when it is made: 33 ... 2 175 road users between road edges of at most
+        2 048 vertices take ONE launch per tick, road term included - through step, step_n, step_together and advance_together
+        (off by default)"""
+        self._mid_road = bool(on)
+        if self._engine is not None:
+            self._engine.mid_road(self._mid_road)
 
     def set_animated(self, animated):
         """intersection.py:899-915: switch every drawing between blitted (animated) and ordinary artists."""

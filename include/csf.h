@@ -327,9 +327,11 @@ int csf_step_group(csf_engine *const *engines, int32_t world, int64_t n_ticks);
  * whatever their classes (a small member of several sets or of the UncontrolledVehicle's class is stepped in turn otherwise);
  * the members the one-launch tick takes (see csf_mid_ticks: 33 ... 2 175 road users of one
  * parameter set), where the batch has at least two of them, run tick by tick in ONE launch per vehicle class and priority rule
- * present; every other member is stepped by csf_step in turn - among them a mid-size member with road edges (its road term is
- * a launch of its own per tick), with several parameter sets, a BalancingRider or UncontrolledVehicle population above 32 road
- * users, and a single mid-size member.  CSF_BATCH_MID=0 steps the mid-size members in turn as well.  Bit for bit what csf_step on
+ * and with / without road edges present - a member's road is summed inside that launch where csf_mid_road is on, the road is on no
+ * lattice and has at most 2 048 padded vertices; every other member is stepped by csf_step in turn - among them a mid-size member
+ * with road edges while csf_mid_road is off (the default), above that cap or on a lattice (its road term is a launch of its own per
+ * tick), one with several parameter sets, a BalancingRider or UncontrolledVehicle population above 32 road users, and a single
+ * mid-size member.  CSF_BATCH_MID=0 steps the mid-size members in turn as well.  Bit for bit what csf_step on
  * each member would give.  `engines` must be the batch in join order.  csf_batch_leave dissolves the batch, and so does
  * csf_destroy of a member: the others go on as single engines, and csf_step_batch on them fails with CSF_E_STATE. */
 int csf_batch_join(csf_engine *const *engines, int32_t count);
@@ -465,6 +467,19 @@ int csf_small_classes(csf_engine *e, int32_t on);
  * sums, and behind the workgroup's barrier the same wave carries on with the group's road users; the
  * next tick's records go to the other half of a double buffer.  CSF_FUSED_MID=0, a pinned CSF_PAIR_VARIANT or per-kernel profiling keep the two launches. */
 int csf_mid_ticks(const csf_engine *e, int64_t *n_ticks);
+/* The ROAD TERM INSIDE the one-launch tick (no change of CSF_ABI_VERSION or csf_params: bind it where the library
+ * exports it).  A population that csf_mid_ticks' tick takes and that has road edges (csf_set_road_vertices) runs road_kernel in front of
+ * every tick: two launches again, and inside a batch such a member is stepped in turn.  on = 1: where the road is on no lattice
+ * (CSF_ROAD_GRID) and has at most 2 048 padded vertices, the pair waves of the one launch sum the road term too (intersection.py:226-242)
+ * - as further items of their queue, the vertices straight from memory, the arithmetic and its order those of road_kernel - and
+ * csf_step_batch takes such members into its batched launch, one launch per vehicle class, priority rule and with / without road.  Bit
+ * for bit what the two launches give.  Any other road keeps the launch of its own.  on = 0 (the default; CSF_MID_ROAD=1 in the environment
+ * of csf_create turns it on from the start): every call takes the kernels it took before there was a switch.  CSF_E_ARG for e == NULL or
+ * on outside 0 / 1; refused like csf_step while a calibration data set is held; a refused call changes nothing.
+ * csf_mid_road_ticks: the ticks whose road term was summed inside the one-launch tick (csf_mid_ticks and, in a batch, csf_batch_mid_ticks
+ * count them too). */
+int csf_mid_road(csf_engine *e, int32_t on);
+int csf_mid_road_ticks(const csf_engine *e, int64_t *n_ticks);
 /* Ticks whose per-agent launch ran BESIDE the pair launch that feeds it (ABI 9).  From a few thousand road users
  * of one TwoD-field class on one device, a tick of csf_step(e, n >= 4) is a pair launch on one of the engine's two streams and the
  * per-agent kernel on the other: every wave runs its destination-force phase (vehicle.py:1416-1558) at once and takes up the column
