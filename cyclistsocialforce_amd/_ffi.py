@@ -45,6 +45,7 @@ SYMBOLS = (
     "csf_scene_calib_lane_classes",
     "csf_small_classes",
     "csf_mid_road", "csf_mid_road_ticks",
+    "csf_mid_classes", "csf_mid_classes_ticks",
     "csf_handout_ranks",
     "csf_wg_order_ranks", "csf_wg_order_tables",
     "csf_pair_shape_of", "csf_pair_shape_words",
@@ -253,6 +254,9 @@ def load():
     if hasattr(L, "csf_mid_road"):                  # (the same)
         L.csf_mid_road.argtypes = [vp, i32]
         L.csf_mid_road_ticks.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_mid_classes"):               # (the same)
+        L.csf_mid_classes.argtypes = [vp, i32]
+        L.csf_mid_classes_ticks.argtypes = [vp, C.POINTER(i64)]
     if L.csf_abi_version() != ABI_VERSION:
         raise EngineError(f"libcsf_hip.so has ABI {L.csf_abi_version()}, expected {ABI_VERSION}")
     if L.csf_params_size() != C.sizeof(Params):

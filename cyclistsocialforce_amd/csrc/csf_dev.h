@@ -374,6 +374,11 @@ void launch_mid_batch(int model, bool p2r, bool road, const Dev *table, const Mi
 // launches), the other halves made equal (launch_chase_sync without the binned copy)
 void launch_mid_batch_rebin(const Dev *table, const MidTick *ticks, int slots, int64_t max_n_pad, hipStream_t st);
 void launch_mid_batch_sync(const Dev *table, const MidTick *ticks, int slots, int64_t max_elems, hipStream_t st);
+// csf_mid_classes.hip: the one-launch tick and its batched twin for a mid-size population of several parameter sets or
+// vehicle classes, the UncontrolledVehicle's among them (no BalancingRider) - d.ptab / pctab / pbtab / cls are read, otherwise what
+// launch_mid_tick / launch_mid_batch take; one batched launch serves members of any classes.  false: nothing was launched
+bool launch_mid_classes(const Dev &d, bool road, hipStream_t st);
+void launch_mid_classes_batch(bool p2r, bool road, const Dev *table, const MidTick *ticks, const int2 *groups, int n_groups, hipStream_t st);
 const char *pair_kernel_name(const Dev &d);           // the kernel launch_pair() takes for this engine
 void launch_records(const Dev &d, hipStream_t st);  // rebuild fp32 records from the fp64 state
 // csf_get_tick: row-major state [n, ns], Fx [n], Fy [n] (doubles), destination pointers [n] (int32), navigation state

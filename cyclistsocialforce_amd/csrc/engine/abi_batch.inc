@@ -171,6 +171,11 @@ static bool batch_mid_ok(const csf_engine *e) {
     return e->knobs.batch_mid != 0 && mid_fused_ok(e) && (e->d.nv == 0 || mid_road_ok(e)) && e->d.atrace == nullptr && e->pend.empty() && !e->dirty;
 }
 
+// The launch a member belongs to, beside its priority rule and with / without road: its vehicle class, or 7 - "classes kernel" - for
+// a member of several sets or classes (mid_classes_batch_kernel: ONE launch whatever the members' classes, as the one-wave members'
+// small_takes_classes ? 7 : model below).
+static int mid_launch_key(const csf_engine *e) { return mid_takes_classes(e) ? 7 : e->d.p.model; }
+
 // A member's Dev as the table holds it: what enqueue_mid_tick's launch sees, but for what changes from tick to tick - the halves
 // by name, not by role; tick, stamp and bands zero (csf_dev.h: mid_compose puts them in) - and the flags that say which halves
 // this tick reads.
@@ -239,7 +244,7 @@ static int mid_groups(BatchState &b, csf_engine *const *engines, hipStream_t st)
     for (size_t j = 0; j < b.mid.size(); j++) {
         if (b.mid_out[j]) continue;
         const csf_engine *e = engines[b.mid[j]];
-        const int model = e->d.p.model, p2r = e->d.p.priority_rule == CSF_P2R ? 1 : 0, road = e->d.nv > 0 ? 1 : 0;
+        const int model = mid_launch_key(e), p2r = e->d.p.priority_rule == CSF_P2R ? 1 : 0, road = e->d.nv > 0 ? 1 : 0;
         if (b.mlaunch.empty() || b.mlaunch.back().model != model || b.mlaunch.back().p2r != p2r || b.mlaunch.back().road != road)
             b.mlaunch.push_back({model, p2r, road, (int)b.mgroups_now.size(), (int)b.mgroups_now.size()});
         const int G = mid_group_for(e), groups = (int)((e->d.hi - e->d.lo + G - 1) / G);
@@ -308,7 +313,8 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
         const Dev &dx = engines[x]->d, &dy = engines[y]->d;
         const int px = dx.p.priority_rule == CSF_P2R, py = dy.p.priority_rule == CSF_P2R;
         const int rx = dx.nv > 0, ry = dy.nv > 0;
-        return dx.p.model != dy.p.model ? dx.p.model < dy.p.model : px != py ? px < py : rx < ry;
+        const int kx = mid_launch_key(engines[x]), ky = mid_launch_key(engines[y]);
+        return kx != ky ? kx < ky : px != py ? px < py : rx < ry;
     });
     b.mid_out.assign(k, 0);
     struct Defer {   // (the members go back to enqueueing their own periodic launches on every way out)
@@ -374,7 +380,7 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
                 max_sync = std::max(max_sync, std::max<int64_t>(e->d.n_pad, 3 * e->d.cap));
                 e->mid_deferred = 0;
             }
-            mid_ticked(e, other_halves(e), true, e->d.nv > 0);
+            mid_ticked(e, other_halves(e), true, e->d.nv > 0, mid_takes_classes(e));
             e->device_ahead = true;
             return CSF_OK;
         };
@@ -419,7 +425,8 @@ static int step_batch_mid(BatchState &b, csf_engine *const *engines, int64_t n_t
         }
         for (int64_t r = 0; r < T; r++)
             for (const BatchState::MidLaunch &l : b.mlaunch) {
-                launch_mid_batch(l.model, l.p2r != 0, l.road != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
+                if (l.model == 7) launch_mid_classes_batch(l.p2r != 0, l.road != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
+                else launch_mid_batch(l.model, l.p2r != 0, l.road != 0, b.mtable.p, b.mticks.p + (size_t)r * k, b.mgroups.p + l.beg, l.end - l.beg, st);
                 b.launches++;
             }
         HIPCHK(e0, hipGetLastError());

@@ -46,6 +46,7 @@ csf_engine *csf_create(const csf_params *params, int64_t n_capacity, int32_t dev
     e->knobs.read();
     e->small_classes = e->knobs.small_classes != 0;
     e->mid_road = e->knobs.mid_road != 0;
+    e->mid_classes = e->knobs.mid_classes != 0;
     e->time_pop = getenv("CSF_TIME_POP") != nullptr;
     e->d.p = *params;
     derive_consts(e);

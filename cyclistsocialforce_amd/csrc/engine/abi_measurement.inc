@@ -224,6 +224,20 @@ int csf_mid_road_ticks(const csf_engine *e, int64_t *n_ticks) try {
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 
+// (refused like csf_small_classes; the next tick asks mid_takes_classes, and a batch asks it at the start of every call)
+int csf_mid_classes(csf_engine *e, int32_t on) try {
+    if (!e || (on != 0 && on != 1)) return CSF_E_ARG;
+    if (int crc = calib_refuses(e, "csf_mid_classes")) return crc;
+    e->mid_classes = on == 1;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
+int csf_mid_classes_ticks(const csf_engine *e, int64_t *n_ticks) try {
+    if (!e || !n_ticks) return CSF_E_ARG;
+    *n_ticks = e->mid_classes_ticks;
+    return CSF_OK;
+} catch (...) { return csf_caught(e); }
+
 int csf_mid_ticks(const csf_engine *e, int64_t *n_ticks) try {
     if (!e || !n_ticks) return CSF_E_ARG;
     *n_ticks = e->mid_ticks;

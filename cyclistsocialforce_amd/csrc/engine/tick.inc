@@ -180,17 +180,53 @@ int calibrate_comm_stream(csf_engine *e) {
 // two): the classes with twelve waves per workgroup and the cull-first pair sums win up to ~2 100 road users (2 048: TwoD 20.9 /
 // 22.0, PlanarPoint 20.6 / 21.7), the InvPendulum (eight waves) and the Bicycle field (four receivers per item, no cull) only
 // to ~1 300 (1 024: 18.2 / 19.2 and 13.7 / 14.0; 2 048: 29.2 / 26.0 and 20.0 / 17.5).
+
+// A population of several parameter sets (any classes), or of the UncontrolledVehicle's class: mid_tick_kernel does not take it.
+static bool mid_is_classes(const csf_engine *e) { return e->classes.size() > 1 || e->d.p.model == CSF_UNCONTROLLED; }
+
+// mid_classes_kernel (csf_mid_classes.hip) has plain items and eight waves.  Where it was measured faster than the general path
+// (tools/mid_classes_rate.py, profiles/mid_classes_rate.jsonl; DESIGN.md 4.7c has the table; the median of five windows below the general
+// path's minimum): every composition up to 1 024 road users - at 1 279 the populations of one class lose (two TwoD sets 22.7 against 21.4 us,
+// 32 sets 23.1 against 22.4) -, but for a population of ONE vehicle class whose road term is not summed inside the launch, which wins by
+// 6 ... 11 % up to 256 road users (one pass of the per-agent phases: the launch saved is all there is to gain), loses at 600 (two sets 14.7
+// against 14.2) and wins again at 1 024 (15.9 against 18.5): between the two it keeps the general path.
+constexpr int64_t MID_CLASSES_BELOW = 1025;
+constexpr int64_t MID_CLASSES_ONE_CLASS_UPTO = 256, MID_CLASSES_ONE_CLASS_FROM = 1024;
 static int64_t mid_below_for(const csf_engine *e) {
     if (e->knobs.mid_below > 0) return e->knobs.mid_below;
+    if (mid_is_classes(e)) return MID_CLASSES_BELOW;
     return e->d.p.model == CSF_INVPEND || e->d.p.model == CSF_BICYCLE ? 1280 : 2176;
 }
 
-static bool mid_fused_ok(const csf_engine *e) {
+// what the one-launch tick asks whatever its kernel
+static bool mid_common_ok(const csf_engine *e) {
     const Dev &d = e->d;
-    return e->knobs.fused_mid != 0 && e->knobs.pair_variant < 0 && d.pair_variant == 1 && d.n_live > 1 && d.n_live < mid_below_for(e) && e->classes.size() == 1 &&
-           d.p.model != CSF_UNCONTROLLED && d.p.model != CSF_BALANCINGRIDER && e->world == 1 && !e->nccl && !e->loopback && e->knobs.fake_world <= 1 && e->profile <= 0 &&
+    return e->knobs.fused_mid != 0 && e->knobs.pair_variant < 0 && d.pair_variant == 1 && d.n_live > 1 && d.n_live < mid_below_for(e) &&
+           e->world == 1 && !e->nccl && !e->loopback && e->knobs.fake_world <= 1 && e->profile <= 0 &&
            d.trace == nullptr && d.pair_count == nullptr && d.lo == 0 && d.hi == d.n && e->segs.empty() && e->state_all_current &&
            d.src_beg == 0 && d.n_src / 64 * 8 <= 384;                  // (csf_mid.hip: MID_ITEMS_MAX items of the largest group)
+}
+
+// ... and does mid_classes_kernel take this population?  The switch of csf_mid_classes on, several sets or the UncontrolledVehicle's
+// class, no set of a BalancingRiderBicycle (its one-launch tick was measured slower than two launches: csf_mid.hip), the table within
+// what the kernel stages - and everything mid_tick_kernel asks.  A single set of a rider class keeps mid_tick_kernel, switch or no switch.
+static bool mid_road_ok(const csf_engine *e);
+static bool mid_takes_classes(const csf_engine *e) {
+    if (!e->mid_classes || !mid_is_classes(e) || (e->d.model_mask & (1 << CSF_BALANCINGRIDER)) != 0 || e->classes.size() > 256) return false;
+    const int64_t n = e->d.n_live;
+    // (no trace of the workgroups' phases - tools/mid_timeline.py reads mid_tick_kernel's stamps, this kernel leaves none -, and more road
+    // users than the one-wave tick's range: the smallest measured cell is 64, and 33 is where the one-launch tick begins)
+    if (e->d.atrace != nullptr || n <= SMALL_MAX) return false;
+    // (Dev::model_mask is formed from the TABLE of sets, derive_consts: a table that lists a second class no road user belongs to counts as
+    // several classes here - it is admitted between 257 and 1 023 road users too, and wave 0 runs an empty pass per phase for that class)
+    const bool one_class = (e->d.model_mask & (e->d.model_mask - 1)) == 0;
+    if (one_class && !mid_road_ok(e) && n > MID_CLASSES_ONE_CLASS_UPTO && n < MID_CLASSES_ONE_CLASS_FROM) return false;   // (measured slower: above)
+    return mid_common_ok(e);
+}
+
+static bool mid_fused_ok(const csf_engine *e) {
+    if (mid_is_classes(e)) return mid_takes_classes(e);
+    return mid_common_ok(e) && e->d.p.model != CSF_BALANCINGRIDER;
 }
 
 // ... and does its launch sum the road term too (csf_mid.hip: the ROAD instances; DESIGN.md 4.7b)?  The switch of csf_mid_road on, a
@@ -306,12 +342,13 @@ static int mid_group_for(const csf_engine *e) {
 }
 
 // behind the launch: the halves trade places, the counters move on
-static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched, bool road) {
+static void mid_ticked(csf_engine *e, const OtherHalves &o, bool batched, bool road, bool classes) {
     trade_halves(e, o, false);
     bounds_after_pair(e, true);
     e->moves++;
     e->mid_ticks++;
     if (road) e->mid_road_ticks++;
+    if (classes) e->mid_classes_ticks++;
     if (batched) e->batch_mid_ticks++;
     e->d.tick++;
 }
@@ -326,9 +363,11 @@ static int enqueue_mid_tick(csf_engine *e) {
     write_other_halves(dd, o, false);                             // (this tick writes no binned copy)
     dd.mid_group = mid_group_for(e);
     // (nothing has traded places yet: a refused launch leaves the engine where it was)
-    if (!launch_mid_tick(dd, road, e->main)) return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, dd.mid_group);
+    const bool classes = mid_takes_classes(e);                    // (several sets or classes: csf_mid_classes.hip in place of the pair launch and the launches per class)
+    if (!(classes ? launch_mid_classes(dd, road, e->main) : launch_mid_tick(dd, road, e->main)))
+        return fail(e, CSF_E_STATE, "the one-launch tick does not take this population (%lld sources, groups of %d)", (long long)d.n_src, dd.mid_group);
     HIPCHK(e, hipGetLastError());
-    mid_ticked(e, o, false, road);
+    mid_ticked(e, o, false, road, classes);
     return CSF_OK;
 }
 

@@ -200,6 +200,7 @@ struct Knobs {
     int chase_gate_pct = 85;                  // CSF_CHASE_GATE: per cent of the pair workgroups through before the per-agent kernel is let go
     int fused_small = 1;                      // CSF_FUSED_SMALL=0: a handful of road users take the general path too (csf_agent.hip: small_tick_kernel)
     int small_classes = 0;                    // CSF_SMALL_CLASSES=1: csf_small_classes is on from csf_create (csf_small_classes.hip; DESIGN.md 4.6e)
+    int mid_classes = 0;                      // CSF_MID_CLASSES=1: csf_mid_classes is on from csf_create (csf_mid_classes.hip; DESIGN.md 4.7c)
     int mid_road = 0;                         // CSF_MID_ROAD=1: csf_mid_road is on from csf_create (csf_mid.hip: the ROAD instances; DESIGN.md 4.7b)
     int segments = -1;                        // CSF_SEGMENTS
     int handout_index = 0;                    // CSF_HANDOUT=index: the pair kernel's workgroups hand their receivers out in index order (0, default: heaviest first, csf_handout.h)
@@ -249,6 +250,7 @@ struct Knobs {
         fused_small = geti("CSF_FUSED_SMALL", 1);
         small_classes = geti("CSF_SMALL_CLASSES", 0) == 1 ? 1 : 0;
         mid_road = geti("CSF_MID_ROAD", 0) == 1 ? 1 : 0;
+        mid_classes = geti("CSF_MID_CLASSES", 0) == 1 ? 1 : 0;
         fused_mid = geti("CSF_FUSED_MID", 1);
         mid_below = geti("CSF_MID_BELOW", 0);
         batch_mid = geti("CSF_BATCH_MID", 1);
@@ -515,6 +517,8 @@ struct csf_engine {
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)
+    bool mid_classes = false;        // csf_mid_classes: several parameter sets / an UncontrolledVehicle population take the one-launch tick too (tick.inc: mid_takes_classes)
+    int64_t mid_classes_ticks = 0;   // ... and the ticks mid_classes_kernel took (csf_mid_classes_ticks; mid_ticks / batch_mid_ticks / mid_road_ticks count them too)
     int64_t slab_rewrites = 0;       // compact_slab calls (upload_queues sizes the slab by them)
     bool bound_stale = false;        // positions moved without a speed clamp (csf_replay_forces with fix_speed): measure them
     uint32_t edge_stamp = 0;

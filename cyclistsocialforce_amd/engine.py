@@ -954,6 +954,18 @@ class Engine:
         self._ck(self._lib.csf_mid_road_ticks(self._h, C.byref(v)))
         return v.value
 
+    def mid_classes(self, on=True):
+        """a mid-size population (33 ... 1 024 road users) of several parameter sets, of several vehicle classes or holding
+        UncontrolledVehicles - no BalancingRiderBicycle - takes ONE launch per tick, alone and as a batch member, instead of a pair launch
+        and a per-agent launch per class (csf.h: csf_mid_classes; off by default, or what CSF_MID_CLASSES said at creation)"""
+        self._ck(self._lib.csf_mid_classes(self._h, 1 if on else 0))
+
+    def mid_classes_ticks(self):
+        """ticks taken by the one-launch tick of mixed populations (csf.h: csf_mid_classes_ticks; mid_ticks counts them too)"""
+        v = C.c_int64()
+        self._ck(self._lib.csf_mid_classes_ticks(self._h, C.byref(v)))
+        return v.value
+
     def mid_ticks(self):
         """ticks run as one launch each (csf_mid.hip: mid-size populations)"""
         v = C.c_int64()

@@ -480,6 +480,24 @@ int csf_mid_ticks(const csf_engine *e, int64_t *n_ticks);
  * count them too). */
 int csf_mid_road(csf_engine *e, int32_t on);
 int csf_mid_road_ticks(const csf_engine *e, int64_t *n_ticks);
+/* The one-launch tick for mid-size populations of SEVERAL PARAMETER SETS AND VEHICLE CLASSES (no change of
+ * CSF_ABI_VERSION or csf_params: bind it where the library exports it).  A population that meets every other condition of csf_mid_ticks
+ * but has more than one parameter set (csf_set_param_classes) or is of class CSF_UNCONTROLLED takes the general path: a pair launch and
+ * one per-agent launch PER VEHICLE CLASS every tick, and inside a batch it is stepped in turn.  on = 1: such a population of at most
+ * 1 024 road users without a CSF_BALANCINGRIDER set (257 ... 1 023 road users of ONE vehicle class whose road term is not summed inside the
+ * launch keep the general path: measured slower) is ticked by mid_classes_kernel (csf_mid_classes.hip) - ONE launch per tick, the
+ * workgroup of csf_mid_ticks, every source evaluated with the constants and the field of view of ITS set (staged in LDS), one pass of the
+ * per-agent phases per vehicle class present, an UncontrolledVehicle following its script - and csf_step_batch steps all such members of
+ * one priority rule and with / without road in ONE launch per tick whatever their classes.  With csf_mid_road on as well the launch sums
+ * the road term of a small road itself (bit for bit what road_kernel leaves).  csf_mid_ticks, csf_batch_mid_ticks and csf_mid_road_ticks
+ * count these ticks as they count the other one-launch ticks; csf_mid_classes_ticks counts them alone.  A single set of a rider class keeps
+ * mid_tick_kernel bit for bit, switch or no switch; a population with a BalancingRider set keeps the general path.  on = 0 (the default;
+ * CSF_MID_CLASSES=1 in the environment of csf_create turns it on from the start): every call takes the kernels it took before there was a
+ * switch.  The results agree with the general path's within the rounding of the pair sum (its partial sums are formed per batch of 64
+ * sources and added in fp64), not bit for bit.  CSF_E_ARG for e == NULL or on outside 0 / 1; refused like csf_step while a calibration
+ * data set is held; a refused call changes nothing. */
+int csf_mid_classes(csf_engine *e, int32_t on);
+int csf_mid_classes_ticks(const csf_engine *e, int64_t *n_ticks);
 /* Ticks whose per-agent launch ran BESIDE the pair launch that feeds it (ABI 9).  From a few thousand road users
  * of one TwoD-field class on one device, a tick of csf_step(e, n >= 4) is a pair launch on one of the engine's two streams and the
  * per-agent kernel on the other: every wave runs its destination-force phase (vehicle.py:1416-1558) at once and takes up the column
