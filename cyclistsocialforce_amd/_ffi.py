@@ -50,6 +50,7 @@ SYMBOLS = (
     "csf_wg_order_ranks", "csf_wg_order_tables",
     "csf_pair_shape_of", "csf_pair_shape_words",
     "csf_field_map", "csf_field_map_launches",
+    "csf_encounters", "csf_batch_encounters", "csf_encounter_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -89,6 +90,21 @@ class RecordOut(C.Structure):
     """csf_record_out of include/csf.h: where the last samples of one member of a batch go (s and F NULL: the member is left out)."""
 
     _fields_ = [("s", C.c_void_p), ("F", C.c_void_p), ("first_sample", C.POINTER(C.c_int64))]
+
+
+class EncounterEvent(C.Structure):
+    """csf_encounter_event of include/csf.h: a (sample, i < j) under a threshold"""
+
+    _fields_ = [("sample", C.c_int64), ("i", C.c_int32), ("j", C.c_int32), ("d", C.c_double), ("ttc", C.c_double)]
+
+
+class EncounterOut(C.Structure):
+    """csf_encounter_out of include/csf.h: where the encounter measures of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("d_min", C.c_void_p), ("d_with", C.c_void_p), ("ttc_min", C.c_void_p), ("ttc_with", C.c_void_p),
+                ("run_d_min", C.c_void_p), ("run_d_with", C.c_void_p), ("run_d_sample", C.c_void_p),
+                ("run_ttc_min", C.c_void_p), ("run_ttc_with", C.c_void_p), ("run_ttc_sample", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -200,6 +216,11 @@ def load():
     L.csf_small_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_field_map.argtypes = [vp, i64, dp, dp, dp, C.c_uint32, i32, dp, dp]
     L.csf_field_map_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_encounters"):             # (CSF_LIB may name an older build for an A/B measurement: it lacks these three)
+        f64 = C.c_double
+        L.csf_encounters.argtypes = [vp, i64, i64, f64, f64, f64, C.POINTER(EncounterOut)]
+        L.csf_batch_encounters.argtypes = [C.POINTER(vp), i32, i64, f64, f64, f64, C.POINTER(EncounterOut)]
+        L.csf_encounter_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -467,6 +467,40 @@ struct FieldMapArgs {
 };
 void launch_field_map_crowd(const Dev &d, const FieldMapArgs &a, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 void launch_field_map_road(const Dev &d, const FieldMapArgs &a, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_encounter.hip (csf_encounters, csf_batch_encounters): closest approach and time to collision of every (sample, road user), one
+// receiver per lane.  One descriptor per engine, read by the kernels from mapped host memory as RecDesc is: a wrapped ring needs no copy.
+// A member's results are one block of the packed output, in this order (cells = count * n; every array starts on a multiple of 8 bytes):
+//   double d_min [cells], ttc_min [cells], run_d_min [n], run_ttc_min [n]; int64 run_d_sample [n], run_ttc_sample [n];
+//   int32 d_with [cells], ttc_with [cells], run_d_with [n], run_ttc_with [n]
+constexpr int ENC_SMALL = 32;   // populations up to this size pack the cells (sample, rider) of a member into the lanes of a workgroup
+struct EncDesc {
+    const double *s;         // ring: the state ring [cap][n][ns]; else the state array, row r of slot a at s[r * stride + a]
+    const int32_t *order;    // the current state: road user of the population order -> slot (NULL: the slot itself)
+    int64_t stride;          // the current state: Dev::cap
+    int64_t first_abs;       // index of the first sample as csf_get_record numbers them; -1: the current state
+    int64_t out_off;         // where the member's block starts in the packed output, in bytes (a multiple of 32)
+    int64_t ev_off, ev_cap;  // ... and its events, csf_encounter_event [ev_cap]
+    int32_t n, ns, cap;      // road users, states of each, samples the ring holds
+    int32_t first, count;    // ring slot of the first sample asked for, samples asked for
+    int32_t ring;
+    // n > ENC_SMALL: the sources of a sample are walked by `split` workgroups per receiver tile, chunk_tiles tiles of 256 each; with
+    // split > 1 every chunk leaves its minima at part_off (bytes; device scratch behind what is transferred): double d [split][cells],
+    // ttc [split][cells]; int32 d_with [split][cells], ttc_with [split][cells] - and the second pass forms the per-sample arrays
+    int32_t split, chunk_tiles;
+    int64_t part_off;
+};
+struct EncArgs {
+    const EncDesc *desc;           // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] events found, cleared in front of the launch
+    double R2;                     // (2 radius)^2
+    double d_event, ttc_event;     // thresholds (<= 0: off)
+    double de2_hi;                 // d_event^2 widened by 1e-15: a pair whose ww is not under it has d >= d_event
+};
+inline size_t enc_block_bytes(size_t cells, size_t n) { return (24 * cells + 40 * n + 31) & ~(size_t)31; }
+// the grid of the first launch: x, y the largest member's (n > ENC_SMALL: tiles of 256 receivers, samples; the packed members take
+// the plane x * y), z = members; then the window pass over max_n riders of every member.  Two launches whatever the members are.
+void launch_encounters(const EncArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

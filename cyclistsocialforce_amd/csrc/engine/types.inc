@@ -293,6 +293,15 @@ struct RecGather {
     }
 };
 
+// What csf_encounters / csf_batch_encounters keep across calls (one per engine; a batch uses its first member's): the descriptors the
+// kernels read (mapped host memory), the packed output on the device - event counters, then every member's block and events - and
+// the pinned buffer its one copy lands in.
+struct EncScratch {
+    HostBuf<EncDesc> desc;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -514,6 +523,8 @@ struct csf_engine {
     int64_t moves = 0;
     int64_t small_ticks = 0;         // ticks run by the one-wave kernel (csf_small_ticks)
     int64_t field_map_launches = 0;  // launches of csf_field_map: one per requested term (csf_field_map_launches)
+    int64_t encounter_launches = 0;  // launches of csf_encounters / csf_batch_encounters: two per call (csf_encounter_launches)
+    EncScratch enc;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

@@ -25,6 +25,92 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+EVENT_DTYPE = np.dtype([("sample", np.int64), ("i", np.int32), ("j", np.int32), ("d", np.float64), ("ttc", np.float64)])   # csf_encounter_event
+
+
+class Encounters:
+    """What Engine.encounters returns for one engine: `first` the index of the first sample covered (-1: the current state), per
+    sample d_min, d_with, ttc_min, ttc_with [count, n] (None when per_sample was off), over the window run_d_min, run_d_with,
+    run_d_sample, run_ttc_min, run_ttc_with, run_ttc_sample [n], and events (EVENT_DTYPE, sorted by sample, i, j; None when no
+    threshold was given) with n_events their number."""
+
+    __slots__ = ("first", "radius", "d_min", "d_with", "ttc_min", "ttc_with", "run_d_min", "run_d_with", "run_d_sample",
+                 "run_ttc_min", "run_ttc_with", "run_ttc_sample", "events", "n_events",
+                 "ids", "d_with_id", "ttc_with_id", "run_d_with_id", "run_ttc_with_id")   # (SocialForceIntersection.encounters fills these)
+
+
+def _events_wanted(d_event, ttc_event):
+    return (d_event is not None and d_event > 0) or (ttc_event is not None and ttc_event > 0)
+
+
+def _encounter_args(who, first, count, radius, d_event, ttc_event):
+    """the checks of Engine.encounters / batch_encounters, before any device call: (first, count) as the C ABI takes them"""
+    if not np.isscalar(radius) or not np.isfinite(radius) or radius < 0:
+        raise ValueError(f"{who}: radius must be a finite number >= 0 (got {radius!r})")
+    for name, v in (("d_event", d_event), ("ttc_event", ttc_event)):
+        if v is not None and (not np.isscalar(v) or np.isnan(v)):
+            raise ValueError(f"{who}: {name} must be None or a number (got {v!r})")
+    if first is None:
+        if count not in (None, 1):
+            raise ValueError(f"{who}: the current state (first=None) is one sample, count={count!r}")
+        return -1, 1
+    if count is None:
+        raise ValueError(f"{who}: count is needed with first")
+    if int(first) != first or int(count) != count or first < 0 or count < 0:
+        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
+    if count > 65535:
+        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
+    return int(first), int(count)
+
+
+class _EncounterPack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
+    csf_encounter_out records that point into them"""
+
+    def __init__(self, shapes, per_sample, caps):
+        m = len(shapes)
+        cells = np.array([n * c for n, c in shapes], dtype=np.int64)
+        ns = np.array([n for n, _ in shapes], dtype=np.int64)
+        self.shapes, self.caps = shapes, caps
+        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (cells, ns, np.asarray(caps, dtype=np.int64)))
+        nc, nn = (int(self.c0[-1]), int(self.n0[-1]))
+        self.per = None
+        if per_sample:
+            self.per = (np.empty(nc), np.empty(nc, np.int32), np.empty(nc), np.empty(nc, np.int32))
+        # (an empty window leaves them as they are: a minimum of +inf with nobody, at no sample)
+        self.run = (np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64),
+                    np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64))
+        self.events = np.empty(int(self.e0[-1]), EVENT_DTYPE)
+        # the records as one int64 table (every member of csf_encounter_out is 8 bytes), filled column by column: a batch of 1 024
+        # members is written in a dozen array operations instead of 12 288 attribute stores
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.EncounterOut) // 8), dtype=np.int64)
+        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
+        if self.per is not None:
+            for col, (a, size) in enumerate(zip(self.per, (8, 4, 8, 4))):
+                tab[:, col] = a.ctypes.data + size * c0
+        for col, (a, size) in zip(range(4, 10), zip(self.run, (8, 4, 8, 8, 4, 8))):
+            tab[:, col] = a.ctypes.data + size * n0
+        caps = np.asarray(caps, dtype=np.int64)
+        tab[:, 10] = np.where(caps > 0, self.events.ctypes.data + EVENT_DTYPE.itemsize * e0, 0)
+        tab[:, 11] = caps
+        self.outs = (_ffi.EncounterOut * m).from_buffer(tab)
+
+    def result(self, i, radius, want_events):
+        n, count = self.shapes[i]
+        o = self.outs[i]
+        r = Encounters()
+        r.first, r.radius, r.n_events = int(o.first_sample), float(radius), int(o.n_events)
+        r.ids = r.d_with_id = r.ttc_with_id = r.run_d_with_id = r.run_ttc_with_id = None
+        c, u = int(self.c0[i]), int(self.n0[i])
+        if self.per is None:
+            r.d_min = r.d_with = r.ttc_min = r.ttc_with = None
+        else:
+            r.d_min, r.d_with, r.ttc_min, r.ttc_with = (a[c:c + n * count].reshape(count, n) for a in self.per)
+        (r.run_d_min, r.run_d_with, r.run_d_sample, r.run_ttc_min, r.run_ttc_with, r.run_ttc_sample) = (a[u:u + n] for a in self.run)
+        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        return r
+
+
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
 
@@ -722,6 +808,48 @@ class Engine:
         """launches of field_map so far: one per requested term and call (csf.h: csf_field_map_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_field_map_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- encounters: closest approach and time to collision (include/csf.h: csf_encounters) ----------------------------------
+    def encounters(self, first=None, count=None, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
+        """closest approach and time to collision of every road user (csf.h: csf_encounters; every road user a disc of `radius`):
+        samples [first, first + count) of the recording (record / enable_history), or - first=None - the current state.  Returns
+        an Encounters: d_min, d_with, ttc_min, ttc_with [count, n] (None without per_sample), run_* [n] over the window with the
+        sample of each, and - with d_event or ttc_event - events, the pairs (sample, i < j) under a threshold, sorted.  Events
+        are fetched with a guessed capacity; when more were found, one second call with the exact capacity."""
+        first, count = _encounter_args("encounters", first, count, radius, d_event, ttc_event)
+        n = self.n
+        want = _events_wanted(d_event, ttc_event)
+        cap = min(max(64, count * n), 1 << 16) if want else 0
+        while True:
+            pack = _EncounterPack([(n, count)], per_sample, [cap])
+            self._ck(self._lib.csf_encounters(self._h, first, count, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), pack.outs))
+            if pack.outs[0].n_events <= cap:
+                return pack.result(0, radius, want)
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_encounters(engines, n_last, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
+        """encounters() over the last n_last samples of every recording member of a batch (the engines in join order), all members
+        in the same two launches with one transfer and one wait (csf.h: csf_batch_encounters): a list with an Encounters per
+        member, None for members that do not record"""
+        n_last = _encounter_args("batch_encounters", 0, n_last, radius, d_event, ttc_event)[1]
+        engines, arr = Engine._batch_array(engines, "batch_encounters")
+        want = _events_wanted(d_event, ttc_event)
+        shapes = [(e.n, n_last) for e in engines]
+        caps = [min(max(64, n_last * n), 1 << 16) if want else 0 for n, _ in shapes]
+        while True:
+            pack = _EncounterPack(shapes, per_sample, caps)
+            Engine._group_call("csf_batch_encounters", engines, arr, n_last, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, radius, want) for i in range(len(engines))]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def encounter_launches(self):
+        """launches of encounters / batch_encounters so far: two per call (csf.h: csf_encounter_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_encounter_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

@@ -677,6 +677,15 @@ class SocialForceIntersection:
         skip = -1 if left_out is None else left_out._index        # (its place in the population order, once arrivals are on the device)
         return e.field_map(X, Y, psi, crowd=crowd, road=road, fov=fov, skip=skip)
 
+    def encounters(self, first=None, count=None, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
+        """Engine.encounters on the population's own engine: closest approach and time to collision of every road user, each a disc
+        of `radius`, over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together
+        record every tick in a ring of DENSE_CHUNK samples) or - first=None - now.  The result carries the partners also as the road
+        users' ids: `ids`, d_with_id, ttc_with_id [count, n] and run_d_with_id, run_ttc_with_id [n] (None where there is no partner)."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        return _encounter_ids(self._push_mutations().encounters(first, count, radius, d_event, ttc_event, per_sample), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -926,6 +935,31 @@ def advance_together(intersections, n_ticks):
             for (ins, _), (S, F, _) in zip(dense, Engine.batch_recorded(engines, k)):
                 ins._book_block(S, F)
         left -= k
+
+
+def _encounter_ids(res, ids):
+    """an Encounters with the partners' places in the population order also given as the road users' ids"""
+    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
+    res.ids = list(ids)
+    res.d_with_id = None if res.d_with is None else names[res.d_with]
+    res.ttc_with_id = None if res.ttc_with is None else names[res.ttc_with]
+    res.run_d_with_id, res.run_ttc_with_id = names[res.run_d_with], names[res.run_ttc_with]
+    return res
+
+
+def encounters_together(intersections, n_last, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
+    """SocialForceIntersection.encounters over the last n_last recorded samples of many intersections - those advance_together
+    has just ticked - with all their engines in the same two launches, one transfer and one wait (Engine.batch_encounters): a list
+    with a result per intersection, None for an empty one and for one whose engine does not record."""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, Engine.batch_encounters(engines, n_last, radius, d_event, ttc_event, per_sample)):
+            got[id(ins)] = None if res is None else _encounter_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
 
 
 def step_together(intersections, n_ticks=1):

@@ -266,6 +266,89 @@ int csf_field_map(csf_engine *e, int64_t m, const double *x, const double *y, co
                   uint32_t what, int32_t skip, double *Fx, double *Fy);
 int csf_field_map_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- encounters: proximity and time to collision of a recording ---------------------------------- */
+
+/* How close the road users came, to whom and when, and how many seconds from a collision they were - formed on the device from
+ * the state ring that csf_record / csf_enable_history keep, or from the current state.
+ *
+ * For one sample and road user i, take its position p_i = (x, y), heading psi and speed v from rows 0-3 of its state, as
+ * csf_get_state returns them. Its velocity is u_i = v_i (cos psi_i, sin psi_i). Every road user is a disc of the call's `radius`,
+ * and R = 2 radius.
+ *
+ * For j != i, let w = p_j - p_i and c = u_j - u_i. Let a = c.c, b = w.c and q = w.w - R^2.
+ *
+ * - d_ij = sqrt(w.w).
+ * - ttc_ij is the time to collision at constant velocity. It takes four cases:
+ *   - If q <= 0 the discs overlap now, and ttc_ij is 0.
+ *   - Otherwise, if b >= 0 or a == 0 or b^2 - a q < 0, the discs never meet, and ttc_ij is +inf.
+ *   - Otherwise ttc_ij is q / (-b + sqrt(b^2 - a q)). This is the root written without cancellation. Use this form, not
+ *     (-b - sqrt)/a.
+ * - Per (sample, i), report four values:
+ *   - d_min = min_j d_ij.
+ *   - d_with = the j that gives it.
+ *   - ttc_min = min_j ttc_ij.
+ *   - ttc_with = the j that gives it, or -1 when ttc_min is +inf.
+ * - Ties go to the lowest j. A strict < in population order gives this.
+ * - All of this is computed in fp64 from the fp64 ring. It is a diagnostic with exact yes/no cases, and CDNA4 runs vector fp64
+ *   at half the fp32 rate. The implementation uses no fp32 and no fast-math functions.
+ * - d_ij and ttc_ij are bitwise symmetric in (i, j), because negating w and c is exact. Rely on that for the events below.
+ * - A road user with a non-finite x, y, psi or v in a sample is neither receiver nor partner in that sample.
+ *   - Its own row is NaN / -1.
+ *   - Nobody else's row is affected.
+ * - A population of one gives +inf / -1.
+ *
+ * Over the window of a call, per road user, report the minimum d_min and the minimum ttc_min. With each go its partner and the
+ * absolute sample index at which it occurred. On ties the earliest sample wins.  (A minimum of +inf - nobody else in any sample,
+ * or no course that meets - has partner -1 and sample -1; the current state counts as sample -1.)
+ *
+ * Events are optional. An event is a (sample, i < j) with d_ij < d_event or ttc_ij < ttc_event. It is stored as
+ * {int64 sample; int32 i, j; double d, ttc;}. Either threshold may be <= 0 to switch it off.
+ *
+ * The caller gives a capacity. The call always returns the total number found. It stores at most `capacity` events. When
+ * total <= capacity it returns them sorted by (sample, i, j), so the result is deterministic although slots are handed out by
+ * atomics. When total > capacity the stored subset is unspecified. */
+typedef struct csf_encounter_event {
+    int64_t sample;
+    int32_t i, j;
+    double d, ttc;
+} csf_encounter_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned).  n = the road users, n_samples the
+ * samples the call covers.  event_capacity = 0 with events NULL counts the events without storing any. */
+typedef struct csf_encounter_out {
+    double *d_min;            /* [n_samples, n] */
+    int32_t *d_with;          /* [n_samples, n] */
+    double *ttc_min;          /* [n_samples, n] */
+    int32_t *ttc_with;        /* [n_samples, n] */
+    double *run_d_min;        /* [n] the window's minima ... */
+    int32_t *run_d_with;      /* [n] ... the partner ... */
+    int64_t *run_d_sample;    /* [n] ... and the sample of each */
+    double *run_ttc_min;      /* [n] */
+    int32_t *run_ttc_with;    /* [n] */
+    int64_t *run_ttc_sample;  /* [n] */
+    csf_encounter_event *events;  /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the events found, stored or not */
+    int64_t first_sample;     /* written: the index of the first sample covered (-1: the current state) */
+} csf_encounter_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
+ * them; with first_sample == -1 and n_samples == 1 the current state (no ring needed, population order).  Pending uploads are
+ * brought in, both streams are waited for as the read-backs do, and the engine is left exactly as it was.  Two launches whatever
+ * the sizes are - every pair of every sample, then the window's minima over the per-sample arrays - with one transfer and one wait
+ * (the launch counter below grows by 2 per call that covers anything).  An empty population or n_samples == 0
+ * succeeds with n_events = 0.  Refused without side effects (CSF_E_ARG / CSF_E_STATE, with a message): a NULL out; a negative or
+ * non-finite radius; n_samples < 0 or above 65535; samples that are not in the ring; no ring when a window is asked for; a
+ * negative event capacity, or a capacity with a NULL buffer; a rank of a sharded run or a member of a loopback group; an engine
+ * that holds a calibration data set.  While csf_profile_enable is on, the first launch is timed as kernel 0. */
+int csf_encounters(csf_engine *e, int64_t first_sample, int64_t n_samples, double radius, double d_event, double ttc_event,
+                   csf_encounter_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, all members in the same two launches, with one
+ * transfer and one wait; outs [count].  A member without a ring is skipped: its n_events becomes 0 and its first_sample -2.  A
+ * recording member with fewer than n_last samples in its ring makes the call a refusal before anything is written. */
+int csf_batch_encounters(csf_engine *const *engines, int32_t count, int64_t n_last, double radius, double d_event, double ttc_event,
+                         csf_encounter_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_encounter_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
