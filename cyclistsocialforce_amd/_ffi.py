@@ -51,6 +51,7 @@ SYMBOLS = (
     "csf_pair_shape_of", "csf_pair_shape_words",
     "csf_field_map", "csf_field_map_launches",
     "csf_encounters", "csf_batch_encounters", "csf_encounter_launches",
+    "csf_post_encroachment", "csf_batch_post_encroachment", "csf_pet_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -104,6 +105,22 @@ class EncounterOut(C.Structure):
     _fields_ = [("d_min", C.c_void_p), ("d_with", C.c_void_p), ("ttc_min", C.c_void_p), ("ttc_with", C.c_void_p),
                 ("run_d_min", C.c_void_p), ("run_d_with", C.c_void_p), ("run_d_sample", C.c_void_p),
                 ("run_ttc_min", C.c_void_p), ("run_ttc_with", C.c_void_p), ("run_ttc_sample", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
+
+
+class PetEvent(C.Structure):
+    """csf_pet_event of include/csf.h: a crossing of the paths of i < j under the threshold, as i reports it"""
+
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("k", C.c_int32), ("l", C.c_int32),
+                ("t_i", C.c_double), ("t_j", C.c_double), ("x", C.c_double), ("y", C.c_double)]
+
+
+class PetOut(C.Structure):
+    """csf_pet_out of include/csf.h: where the path crossings of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("seg_pet", C.c_void_p), ("seg_with", C.c_void_p), ("seg_t_own", C.c_void_p), ("seg_t_with", C.c_void_p),
+                ("run_pet", C.c_void_p), ("run_with", C.c_void_p), ("run_t_own", C.c_void_p), ("run_t_with", C.c_void_p),
+                ("run_x", C.c_void_p), ("run_y", C.c_void_p), ("run_count", C.c_void_p),
                 ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
 
 
@@ -221,6 +238,10 @@ def load():
         L.csf_encounters.argtypes = [vp, i64, i64, f64, f64, f64, C.POINTER(EncounterOut)]
         L.csf_batch_encounters.argtypes = [C.POINTER(vp), i32, i64, f64, f64, f64, C.POINTER(EncounterOut)]
         L.csf_encounter_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_post_encroachment"):      # (likewise)
+        L.csf_post_encroachment.argtypes = [vp, i64, i64, C.c_double, C.POINTER(PetOut)]
+        L.csf_batch_post_encroachment.argtypes = [C.POINTER(vp), i32, i64, C.c_double, C.POINTER(PetOut)]
+        L.csf_pet_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -501,6 +501,37 @@ inline size_t enc_block_bytes(size_t cells, size_t n) { return (24 * cells + 40 
 // the grid of the first launch: x, y the largest member's (n > ENC_SMALL: tiles of 256 receivers, samples; the packed members take
 // the plane x * y), z = members; then the window pass over max_n riders of every member.  Two launches whatever the members are.
 void launch_encounters(const EncArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_pet.hip (csf_post_encroachment, csf_batch_post_encroachment): path crossings of a recording and their post-encroachment time, one
+// own segment per lane.  One descriptor per engine in mapped host memory, as EncDesc.  segs = (count - 1) * n own segments, cell (k, i) at
+// k * n + i.  A member's results are one block of the packed output, in this order (every array starts on a multiple of 8 bytes):
+//   double seg_pet [segs], seg_t_own [segs], seg_t_with [segs], run_pet [n], run_t_own [n], run_t_with [n], run_x [n], run_y [n];
+//   int32 seg_with [segs], run_with [n], run_count [n]
+constexpr int PET_TILE = 256;   // own segments per workgroup, and partner segments per LDS tile
+struct PetDesc {
+    const double *s;         // the state ring [cap][n][ns]
+    int64_t out_off;         // where the member's block starts in the packed output, in bytes (a multiple of 32)
+    int64_t ev_off, ev_cap;  // ... and its events, csf_pet_event [ev_cap]
+    // The partner segments, numbered p = j * (count - 1) + l - the (j, l) order of the tie rule -, are walked by `split` workgroups per
+    // tile of own segments, chunk_tiles tiles of 256 each.  Every chunk leaves what ITS partners gave at part_off (bytes; device scratch
+    // behind what is transferred): double pet, t_own, t_with, x, y [split][segs]; int32 with, count [split][segs] - and the window
+    // pass takes the chunks in order with a strict `<` and forms seg_* and run_*.
+    int64_t part_off;
+    int32_t n, ns, cap;      // road users, states of each, samples the ring holds
+    int32_t first, count;    // ring slot of the first sample asked for, samples asked for (>= 2)
+    int32_t split, chunk_tiles;
+};
+struct PetArgs {
+    const PetDesc *desc;           // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] events found, cleared in front of the launch
+    double pet_event;              // threshold in samples (<= 0: off; +inf: every crossing)
+};
+inline size_t pet_block_bytes(size_t segs, size_t n) { return (28 * segs + 48 * n + 31) & ~(size_t)31; }
+inline size_t pet_part_bytes(size_t segs, size_t split) { return 48 * segs * split; }
+constexpr int PET_LAUNCHES = 2;
+// grid (x = the largest member's tiles of own segments, y = the largest split, z = members), then the window pass over max_n riders of
+// every member: PET_LAUNCHES launches whatever the members are.
+void launch_pet(const PetArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

@@ -302,6 +302,13 @@ struct EncScratch {
     HostBuf<unsigned char, false> host;
 };
 
+// ... and csf_post_encroachment / csf_batch_post_encroachment: the same three, the chunks' partial results behind the packed output
+struct PetScratch {
+    HostBuf<PetDesc> desc;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -525,6 +532,8 @@ struct csf_engine {
     int64_t field_map_launches = 0;  // launches of csf_field_map: one per requested term (csf_field_map_launches)
     int64_t encounter_launches = 0;  // launches of csf_encounters / csf_batch_encounters: two per call (csf_encounter_launches)
     EncScratch enc;
+    int64_t pet_launches = 0;        // launches of csf_post_encroachment / csf_batch_post_encroachment: two per call (csf_pet_launches)
+    PetScratch pet;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

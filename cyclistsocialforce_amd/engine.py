@@ -111,8 +111,112 @@ class _EncounterPack:
         return r
 
 
+PET_EVENT_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("k", np.int32), ("l", np.int32),
+                            ("t_i", np.float64), ("t_j", np.float64), ("x", np.float64), ("y", np.float64)])   # csf_pet_event
+
+_PET_TIMES = ("seg_pet", "seg_t_own", "seg_t_with", "run_pet", "run_t_own", "run_t_with")
+
+
+class PostEncroachment:
+    """What Engine.post_encroachment returns for one engine (csf.h: csf_post_encroachment): `first` the index of the first sample
+    covered, per own segment seg_pet, seg_with, seg_t_own, seg_t_with [count - 1, n] (None when per_segment was off), per road user
+    run_pet, run_with, run_t_own, run_t_with, run_x, run_y, run_count [n], and events (PET_EVENT_DTYPE, sorted by i, j, k, l; None when
+    no threshold was given) with n_events their number.  Times and pet are in samples from `first`; `period` is the seconds per
+    sample (stride x t_s of the recording), and in_seconds() returns the same result with them scaled by it."""
+
+    __slots__ = ("first", "period", "seconds", "seg_pet", "seg_with", "seg_t_own", "seg_t_with", "run_pet", "run_with", "run_t_own",
+                 "run_t_with", "run_x", "run_y", "run_count", "events", "n_events",
+                 "ids", "seg_with_id", "run_with_id", "event_i_id", "event_j_id")   # (SocialForceIntersection.post_encroachment fills these)
+
+    def in_seconds(self):
+        """a copy whose times - seg_t_*, run_t_*, the events' t_i, t_j - and pet are seconds (from the sample `first`) instead of samples"""
+        if self.seconds:
+            return self
+        if self.period is None:
+            raise ValueError("in_seconds: the period of the recording is not known (record / enable_history were not called through this Engine)")
+        r = PostEncroachment()
+        for f in self.__slots__:
+            setattr(r, f, getattr(self, f))
+        for f in _PET_TIMES:
+            if getattr(self, f) is not None:
+                setattr(r, f, getattr(self, f) * self.period)
+        if self.events is not None:
+            r.events = self.events.copy()
+            r.events["t_i"] *= self.period
+            r.events["t_j"] *= self.period
+        r.seconds = True
+        return r
+
+
+def _pet_args(who, first, count, pet_event):
+    """the checks of Engine.post_encroachment / batch_post_encroachment, before any device call"""
+    if pet_event is not None and (isinstance(pet_event, bool) or not np.isscalar(pet_event) or not isinstance(pet_event, (int, float, np.integer, np.floating))
+                                  or np.isnan(pet_event) or pet_event == -np.inf):
+        raise ValueError(f"{who}: pet_event must be None or a number, +inf for every crossing (got {pet_event!r})")
+    if first is None or count is None:
+        raise ValueError(f"{who}: first and count are needed - a path is a window of the recording, the current state has none")
+    if isinstance(first, bool) or isinstance(count, bool) or int(first) != first or int(count) != count or first < 0 or count < 0:
+        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
+    if count > 65535:
+        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
+    return int(first), int(count)
+
+
+def _pet_capacity_guess(segs):
+    """room for events in the first call: crossings are far fewer than segments in every population looked at"""
+    return min(max(64, segs), 1 << 16)
+
+
+class _PetPack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
+    csf_pet_out records that point into them (shapes: (n, count) per member)"""
+
+    SEG = (("seg_pet", np.float64), ("seg_with", np.int32), ("seg_t_own", np.float64), ("seg_t_with", np.float64))
+    RUN = (("run_pet", np.float64), ("run_with", np.int32), ("run_t_own", np.float64), ("run_t_with", np.float64),
+           ("run_x", np.float64), ("run_y", np.float64), ("run_count", np.int32))
+
+    def __init__(self, shapes, per_segment, caps):
+        m = len(shapes)
+        segs = np.array([n * max(c - 1, 0) for n, c in shapes], dtype=np.int64)
+        ns = np.array([n for n, _ in shapes], dtype=np.int64)
+        caps = np.asarray(caps, dtype=np.int64)
+        self.shapes = shapes
+        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (segs, ns, caps))
+        nc, nn = int(self.c0[-1]), int(self.n0[-1])
+        self.seg = [np.empty(nc, dt) for _, dt in self.SEG] if per_segment else None
+        self.run = [np.empty(nn, dt) for _, dt in self.RUN]
+        self.events = np.empty(int(self.e0[-1]), PET_EVENT_DTYPE)
+        # the records as one int64 table (every member of csf_pet_out is 8 bytes), filled column by column
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.PetOut) // 8), dtype=np.int64)
+        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
+        if self.seg is not None:
+            for col, a in enumerate(self.seg):
+                tab[:, col] = a.ctypes.data + a.itemsize * c0
+        for col, a in enumerate(self.run, start=4):
+            tab[:, col] = a.ctypes.data + a.itemsize * n0
+        tab[:, 11] = np.where(caps > 0, self.events.ctypes.data + PET_EVENT_DTYPE.itemsize * e0, 0)
+        tab[:, 12] = caps
+        self.outs = (_ffi.PetOut * m).from_buffer(tab)
+
+    def result(self, i, want_events, period):
+        n, count = self.shapes[i]
+        o = self.outs[i]
+        r = PostEncroachment()
+        r.first, r.n_events, r.period, r.seconds = int(o.first_sample), int(o.n_events), period, False
+        r.ids = r.seg_with_id = r.run_with_id = r.event_i_id = r.event_j_id = None
+        c, u, rows = int(self.c0[i]), int(self.n0[i]), max(count - 1, 0)
+        for k, (name, _) in enumerate(self.SEG):
+            setattr(r, name, None if self.seg is None else self.seg[k][c:c + n * rows].reshape(rows, n))
+        for k, (name, _) in enumerate(self.RUN):
+            setattr(r, name, self.run[k][u:u + n])
+        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        return r
+
+
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
+
+    _rec_stride = None    # the stride of the state ring, as record / enable_history were last called (PostEncroachment.period)
 
     # what intersection.py keeps on an engine.  Declared on the class, not assigned in __init__: two more entries in every instance's
     # dictionary cost the batched calls over 256 engines 8 % of their host time (profiles/mirror_refactor_ab.txt)
@@ -710,6 +814,7 @@ class Engine:
 
     def enable_history(self, stride=1, capacity=3000):
         self._ck(self._lib.csf_enable_history(self._h, int(stride), int(capacity)))
+        self._rec_stride = int(stride)
 
     def history(self, first, count):
         out = np.zeros((count, self.n, self.ns))
@@ -722,6 +827,7 @@ class Engine:
         what = _ffi.REC_STATE | (_ffi.REC_FORCE if forces else 0)
         self._ck(self._lib.csf_record(self._h, int(stride), int(capacity), what))
         self._rec_forces = bool(forces)
+        self._rec_stride = int(stride)
 
     def recorded(self, first, count):
         """samples [first, first + count) of the recording: (S [count, n, n_states], F [count, n, 2] or None) - sample k is the
@@ -850,6 +956,52 @@ class Engine:
         """launches of encounters / batch_encounters so far: two per call (csf.h: csf_encounter_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_encounter_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- post-encroachment time: path crossings of a recording (include/csf.h: csf_post_encroachment) -------------------------
+    def _period(self):
+        return None if self._rec_stride is None else self._rec_stride * float(self.params.t_s)
+
+    def post_encroachment(self, first, count, pet_event=None, per_segment=True):
+        """who crossed whose path, where, and how long after the other had passed (csf.h: csf_post_encroachment): the paths of
+        all road users over samples [first, first + count) of the recording (record / enable_history).  Returns a
+        PostEncroachment: seg_pet, seg_with, seg_t_own, seg_t_with [count - 1, n] (None without per_segment), run_* [n], and - with
+        pet_event, in samples, +inf for every crossing - events, the crossings (i < j) under it, sorted by (i, j, k, l).  Times are
+        in samples from `first`; in_seconds() scales them.  Events are fetched with a guessed capacity; when more were found,
+        one second call with the exact capacity."""
+        first, count = _pet_args("post_encroachment", first, count, pet_event)
+        n = self.n
+        want = pet_event is not None and pet_event > 0
+        cap = _pet_capacity_guess(max(count - 1, 0) * n) if want else 0
+        while True:
+            pack = _PetPack([(n, count)], per_segment, [cap])
+            self._ck(self._lib.csf_post_encroachment(self._h, first, count, float(pet_event or 0.0), pack.outs))
+            if pack.outs[0].n_events <= cap:
+                return pack.result(0, want, self._period())
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_post_encroachment(engines, n_last, pet_event=None, per_segment=True):
+        """post_encroachment() over the last n_last samples of every recording member of a batch (the engines in join order), all
+        members in the same two launches with one transfer and one wait (csf.h: csf_batch_post_encroachment): a list with a
+        PostEncroachment per member, None for members that do not record"""
+        n_last = _pet_args("batch_post_encroachment", 0, n_last, pet_event)[1]
+        engines, arr = Engine._batch_array(engines, "batch_post_encroachment")
+        want = pet_event is not None and pet_event > 0
+        shapes = [(e.n, n_last) for e in engines]
+        caps = [_pet_capacity_guess(max(n_last - 1, 0) * n) if want else 0 for n, _ in shapes]
+        while True:
+            pack = _PetPack(shapes, per_segment, caps)
+            Engine._group_call("csf_batch_post_encroachment", engines, arr, n_last, float(pet_event or 0.0), pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, want, e._period()) for i, e in enumerate(engines)]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def pet_launches(self):
+        """launches of post_encroachment / batch_post_encroachment so far: two per call (csf.h: csf_pet_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_pet_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

@@ -686,6 +686,15 @@ class SocialForceIntersection:
             raise RuntimeError("the intersection is empty")
         return _encounter_ids(self._push_mutations().encounters(first, count, radius, d_event, ttc_event, per_sample), self.get_road_user_ids())
 
+    def post_encroachment(self, first, count, pet_event=None, per_segment=True):
+        """Engine.post_encroachment on the population's own engine: who crossed whose path, where, and how long after the other had
+        passed, over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record
+        every tick in a ring of DENSE_CHUNK samples).  The result carries the partners also as the road users' ids: `ids`,
+        seg_with_id [count - 1, n], run_with_id [n] (None where there is no partner) and event_i_id, event_j_id beside the events."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        return _pet_ids(self._push_mutations().post_encroachment(first, count, pet_event, per_segment), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -959,6 +968,33 @@ def encounters_together(intersections, n_last, radius=0.5, d_event=None, ttc_eve
         _batch_of(engines)
         for ins, res in zip(live, Engine.batch_encounters(engines, n_last, radius, d_event, ttc_event, per_sample)):
             got[id(ins)] = None if res is None else _encounter_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
+def _pet_ids(res, ids):
+    """a PostEncroachment with the partners' places in the population order also given as the road users' ids"""
+    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
+    res.ids = list(ids)
+    res.seg_with_id = None if res.seg_with is None else names[res.seg_with]
+    res.run_with_id = names[res.run_with]
+    if res.events is not None:
+        res.event_i_id, res.event_j_id = names[res.events["i"]], names[res.events["j"]]
+    return res
+
+
+def post_encroachment_together(intersections, n_last, pet_event=None, per_segment=True):
+    """SocialForceIntersection.post_encroachment over the last n_last recorded samples of many intersections - those
+    advance_together has just ticked - with all their engines in the same two launches, one transfer and one wait
+    (Engine.batch_post_encroachment): a list with a result per intersection, None for an empty one and for one whose engine does
+    not record."""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, Engine.batch_post_encroachment(engines, n_last, pet_event, per_segment)):
+            got[id(ins)] = None if res is None else _pet_ids(res, ins.get_road_user_ids())
     return [got.get(id(ins)) for ins in intersections]
 
 

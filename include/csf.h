@@ -349,6 +349,114 @@ int csf_batch_encounters(csf_engine *const *engines, int32_t count, int64_t n_la
 /* launches of the two calls above so far (a batch counts on its first member) */
 int csf_encounter_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- post-encroachment time: path crossings of a recording --------------------------------------- */
+
+/* Who crossed whose path, where, and how long after the other had passed - formed on the device from the state ring that
+ * csf_record / csf_enable_history keep.
+ *
+ * A call covers samples [first_sample, first_sample + c) of the state ring. Number them k = 0 ... c-1 inside the call, and let
+ * m = c - 1.
+ *
+ * Segments.
+ * - P_i(k) = (x, y) is rows 0 and 1 of road user i's state in sample k, the fp64 bits of the ring.
+ * - Segment (i, k), for k = 0 ... m-1, runs from A = P_i(k) to B = P_i(k+1), with r = B - A.
+ * - A segment exists if all four coordinates are finite.
+ * - psi and v are not read.
+ *
+ * Terms of one pair. Take own segment (i, k) with A, r and partner segment (j, l), j != i, with C = P_j(l), s = P_j(l+1) - C.
+ * Both must exist. Let w = C - A.
+ * - den = r.x*s.y - r.y*s.x
+ * - ns = w.x*s.y - w.y*s.x
+ * - nt = w.x*r.y - w.y*r.x
+ * - Each term is two products and one subtraction in fp64. None is contracted to an FMA (#pragma clang fp contract(off), as in
+ *   csf_encounter.hip). No fp32 and no fast-math functions are used.
+ *
+ * Box test. The closed bounding boxes of the two segments overlap. Each box is the min and max of its two endpoints, compared
+ * with >= / <= in x and in y.
+ *
+ * inside(num).
+ * - If den > 0, it is 0 <= num && num < den.
+ * - If den < 0, it is den < num && num <= 0.
+ * - If den == 0 (parallel, collinear, or a stationary road user), it is false.
+ *
+ * Crossing. The paths cross on this pair iff the boxes overlap and inside(ns) and inside(nt).
+ * - The decision is made from num and den, never from a quotient.
+ * - The intervals are half open, so a crossing through a shared vertex counts on exactly one segment of each path.
+ * - The box test is part of the definition. Any coarser cull by boxes over these boxes is therefore exact.
+ *
+ * Values of a crossing.
+ * - s_own = ns / den and s_with = nt / den. Either may round to 1.0.
+ * - t_own = (double)k + s_own and t_with = (double)l + s_with, in samples from the first sample of the call.
+ * - pet = fabs(t_with - t_own).
+ * - x = A.x + s_own * r.x and y = A.y + s_own * r.y, each a product and then a sum.
+ *
+ * Symmetry. Seen from (j, l), den, ns and nt are the exact negatives with the roles swapped. So the decision, both times and
+ * pet are bitwise symmetric in (i, j). The point is taken on the own segment of whoever reports it, and may differ in the last
+ * bit.
+ *
+ * Per own segment (k, i).
+ * - seg_pet is the minimum pet over all (j, l).
+ * - With it go seg_with (the j), seg_t_own and seg_t_with.
+ * - Ties go to the lowest j, then the lowest l. A strict < in that loop order gives this.
+ * - No crossing gives +inf / -1 / NaN / NaN.
+ * - An own segment that does not exist gives NaN / -1 / NaN / NaN and is nobody's partner. Nobody else's row changes.
+ *
+ * Per road user over the call.
+ * - run_pet is the minimum seg_pet over k, the earliest k on ties.
+ * - With it go run_with, run_t_own, run_t_with, run_x, run_y.
+ * - run_count (int32) is the number of crossings (k, j, l) on the road user's path.
+ * - No crossing gives +inf / -1 / NaN ... / 0.
+ *
+ * Events.
+ * - Events are optional (pet_event > 0; +inf is allowed and means every crossing).
+ * - An event is a crossing with i < j and pet < pet_event.
+ * - It is stored as {int32 i, j, k, l; double t_i, t_j, x, y;}: 48 bytes, point and times as i reports them, k and l counted
+ *   from the call's first sample.
+ * - Capacity, total count, "sorted by (i, j, k, l) when total <= capacity, unspecified subset otherwise" are exactly as for
+ *   csf_encounter_event.
+ *
+ * Small calls. n_samples < 2, or a population of one, succeeds with nothing found. */
+typedef struct csf_pet_event {
+    int32_t i, j, k, l;
+    double t_i, t_j, x, y;
+} csf_pet_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned).  n = the road users, n_samples the
+ * samples the call covers.  event_capacity = 0 with events NULL counts the events without storing any.  With n_samples < 2 the
+ * seg_* arrays have no rows and run_* are written as "no crossing". */
+typedef struct csf_pet_out {
+    double *seg_pet;          /* [n_samples-1, n] */
+    int32_t *seg_with;        /* [n_samples-1, n] */
+    double *seg_t_own;        /* [n_samples-1, n] */
+    double *seg_t_with;       /* [n_samples-1, n] */
+    double *run_pet;          /* [n] the smallest seg_pet ... */
+    int32_t *run_with;        /* [n] ... whose path was crossed ... */
+    double *run_t_own;        /* [n] ... when the road user was there ... */
+    double *run_t_with;       /* [n] ... when the other was ... */
+    double *run_x;            /* [n] ... and where */
+    double *run_y;            /* [n] */
+    int32_t *run_count;       /* [n] crossings on the road user's path */
+    csf_pet_event *events;    /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the events found, stored or not */
+    int64_t first_sample;     /* written: the index of the first sample covered */
+} csf_pet_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
+ * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every pair of segments, then
+ * the per-segment and per-road-user minima - with one hipMemsetAsync of the event counters, one transfer and one wait (the launch
+ * counter below grows by 2 per call that covers a segment).  Refused without side effects (CSF_E_ARG / CSF_E_STATE, with a
+ * message, launch counter unchanged): a NULL out; first_sample == -1 (the current state has no path) or no ring; n_samples < 0 or
+ * above 65535; samples that are not in the ring; a NaN or -inf pet_event; a negative event capacity, or a capacity with a NULL
+ * buffer; a rank of a sharded run or a member of a loopback group; an engine that holds a calibration data set.  While
+ * csf_profile_enable is on, the first launch is timed as kernel 0. */
+int csf_post_encroachment(csf_engine *e, int64_t first_sample, int64_t n_samples, double pet_event, csf_pet_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, all members in the same two launches, with one
+ * transfer and one wait; outs [count].  A member without a ring is skipped: its n_events becomes 0 and its first_sample -2.  A
+ * recording member with fewer than n_last samples in its ring makes the call a refusal before anything is written. */
+int csf_batch_post_encroachment(csf_engine *const *engines, int32_t count, int64_t n_last, double pet_event, csf_pet_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_pet_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
