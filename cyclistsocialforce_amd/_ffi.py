@@ -52,6 +52,7 @@ SYMBOLS = (
     "csf_field_map", "csf_field_map_launches",
     "csf_encounters", "csf_batch_encounters", "csf_encounter_launches",
     "csf_post_encroachment", "csf_batch_post_encroachment", "csf_pet_launches",
+    "csf_passing", "csf_batch_passing", "csf_passing_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -121,6 +122,27 @@ class PetOut(C.Structure):
     _fields_ = [("seg_pet", C.c_void_p), ("seg_with", C.c_void_p), ("seg_t_own", C.c_void_p), ("seg_t_with", C.c_void_p),
                 ("run_pet", C.c_void_p), ("run_with", C.c_void_p), ("run_t_own", C.c_void_p), ("run_t_with", C.c_void_p),
                 ("run_x", C.c_void_p), ("run_y", C.c_void_p), ("run_count", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
+
+
+class PassingEvent(C.Structure):
+    """csf_passing_event of include/csf.h: i passes j in interval k under the threshold, as i reports it"""
+
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("k", C.c_int32), ("kind", C.c_int32),
+                ("t", C.c_double), ("lat", C.c_double), ("closing", C.c_double), ("cosine", C.c_double)]
+
+
+class PassingOut(C.Structure):
+    """csf_passing_out of include/csf.h: where the gaps and passings of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("gap", C.c_void_p), ("gap_with", C.c_void_p), ("thw", C.c_void_p),
+                ("made_lat", C.c_void_p), ("made_with", C.c_void_p), ("made_t", C.c_void_p), ("made_kind", C.c_void_p),
+                ("by_lat", C.c_void_p), ("by_with", C.c_void_p), ("by_t", C.c_void_p), ("by_kind", C.c_void_p),
+                ("run_gap", C.c_void_p), ("run_gap_with", C.c_void_p), ("run_gap_k", C.c_void_p),
+                ("run_thw", C.c_void_p), ("run_thw_with", C.c_void_p), ("run_thw_k", C.c_void_p),
+                ("run_made_lat", C.c_void_p), ("run_made_with", C.c_void_p), ("run_made_t", C.c_void_p), ("run_made_kind", C.c_void_p),
+                ("run_by_lat", C.c_void_p), ("run_by_with", C.c_void_p), ("run_by_t", C.c_void_p), ("run_by_kind", C.c_void_p),
+                ("run_made", C.c_void_p), ("run_by", C.c_void_p),
                 ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
 
 
@@ -242,6 +264,10 @@ def load():
         L.csf_post_encroachment.argtypes = [vp, i64, i64, C.c_double, C.POINTER(PetOut)]
         L.csf_batch_post_encroachment.argtypes = [C.POINTER(vp), i32, i64, C.c_double, C.POINTER(PetOut)]
         L.csf_pet_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_passing"):                # (likewise)
+        L.csf_passing.argtypes = [vp, i64, i64, C.c_double, C.c_double, C.c_double, C.POINTER(PassingOut)]
+        L.csf_batch_passing.argtypes = [C.POINTER(vp), i32, i64, C.c_double, C.c_double, C.c_double, C.POINTER(PassingOut)]
+        L.csf_passing_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -532,6 +532,47 @@ constexpr int PET_LAUNCHES = 2;
 // grid (x = the largest member's tiles of own segments, y = the largest split, z = members), then the window pass over max_n riders of
 // every member: PET_LAUNCHES launches whatever the members are.
 void launch_pet(const PetArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_passing.hip (csf_passing, csf_batch_passing): gaps to the leader, overtakings and meetings of a recording, one own station (k, i)
+// per lane.  One descriptor per engine in mapped host memory, as EncDesc.  S = (count - 1) * n stations, cell (k, i) at k * n + i;
+// I = (count - 2) * n intervals (0 with two samples), the same cells without the last row.  A member's results are one block of the
+// packed output, in this order (every array starts on a multiple of 8 bytes: the int32 arrays follow the doubles):
+//   double gap [S], thw [S], made_lat [I], made_t [I], by_lat [I], by_t [I], run_gap, run_thw, run_made_lat, run_made_t, run_by_lat, run_by_t [n];
+//   int32 gap_with [S], made_with, made_kind, by_with, by_kind [I], run_gap_with, run_gap_k, run_thw_with, run_thw_k, run_made_with,
+//         run_made_kind, run_by_with, run_by_kind [n], run_made [n][3], run_by [n][3]
+struct PassDesc {
+    const double *s;         // the state ring [cap][n][ns]
+    int64_t out_off;         // where the member's block starts in the packed output, in bytes (a multiple of 32)
+    int64_t ev_off, ev_cap;  // ... and its events, csf_passing_event [ev_cap]
+    // n > ENC_SMALL: the partners of a station are walked by `split` workgroups per tile of own stations, chunk_tiles tiles of 256
+    // each (1: one workgroup walks them all; always 1 for the packed members).  Every chunk leaves what ITS partners gave at part_off
+    // (bytes; device scratch behind what is transferred) as one PassPart per cell, [split][S] - and the window pass takes the chunks in
+    // order with a strict `<`, writes the per-station and per-interval arrays, and forms run_*.
+    int64_t part_off;
+    int32_t n, ns, cap;      // road users, states of each, samples the ring holds
+    int32_t first, count;    // ring slot of the first sample asked for, samples asked for (>= 2)
+    int32_t split, chunk_tiles;
+};
+struct PassArgs {
+    const PassDesc *desc;          // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] events found, cleared in front of the launch
+    double band, lat_max;          // metres
+    double lat_event;              // threshold in metres (<= 0: off; +inf: every passing)
+};
+// what one chunk of partners gave one station
+struct PassPart {
+    double g, gap, thw;               // the leader's g (+inf: none; NaN: the station does not exist), and what is reported of it
+    double m_lat, m_t, b_lat, b_t;    // the passing made / received with the smallest fabs(lat)
+    int32_t gj, m_with, m_kind, b_with, b_kind;
+    int32_t mc[3], bc[3];             // passings made / received: overtakings, meetings, others
+    int32_t pad;
+};
+inline size_t pass_block_bytes(size_t S, size_t I, size_t n) { return (20 * S + 48 * I + 104 * n + 31) & ~(size_t)31; }
+inline size_t pass_part_bytes(size_t S, size_t split) { return sizeof(PassPart) * S * split; }
+constexpr int PASS_LAUNCHES = 2;
+// the grid of the first launch as launch_encounters has it, with stations in the place of samples; then the window pass over max_n
+// riders of every member: PASS_LAUNCHES launches whatever the members are.
+void launch_passing(const PassArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

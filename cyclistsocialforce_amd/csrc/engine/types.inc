@@ -309,6 +309,13 @@ struct PetScratch {
     HostBuf<unsigned char, false> host;
 };
 
+// ... and csf_passing / csf_batch_passing: the same three
+struct PassScratch {
+    HostBuf<PassDesc> desc;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -534,6 +541,8 @@ struct csf_engine {
     EncScratch enc;
     int64_t pet_launches = 0;        // launches of csf_post_encroachment / csf_batch_post_encroachment: two per call (csf_pet_launches)
     PetScratch pet;
+    int64_t passing_launches = 0;    // launches of csf_passing / csf_batch_passing: two per call (csf_passing_launches)
+    PassScratch passing;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

@@ -213,6 +213,133 @@ class _PetPack:
         return r
 
 
+PASSING_EVENT_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("k", np.int32), ("kind", np.int32),
+                                ("t", np.float64), ("lat", np.float64), ("closing", np.float64), ("cosine", np.float64)])   # csf_passing_event
+
+_PASSING_TIMES = ("thw", "made_t", "by_t", "run_thw", "run_made_t", "run_by_t")
+
+
+class Passing:
+    """What Engine.passing returns for one engine (csf.h: csf_passing): `first` the index of the first sample covered; per station
+    gap, gap_with, thw [count - 1, n] and per interval made_lat, made_with, made_t, made_kind, by_lat, by_with, by_t, by_kind
+    [count - 2, n] (None when per_station was off); per road user run_gap, run_gap_with, run_gap_k, run_thw, run_thw_with, run_thw_k,
+    run_made_lat, run_made_with, run_made_t, run_made_kind, run_by_lat, run_by_with, run_by_t, run_by_kind [n] and the counts run_made,
+    run_by [n, 3] (overtakings, meetings, others); events (PASSING_EVENT_DTYPE, sorted by i, j, k; None when no threshold was given)
+    with n_events their number.  t and thw are in samples (t from `first`), closing in metres per sample; `period` is the seconds
+    per sample (stride x t_s of the recording), and in_seconds() returns the same result with them scaled by it."""
+
+    STATION = (("gap", np.float64), ("gap_with", np.int32), ("thw", np.float64))
+    INTERVAL = (("made_lat", np.float64), ("made_with", np.int32), ("made_t", np.float64), ("made_kind", np.int32),
+                ("by_lat", np.float64), ("by_with", np.int32), ("by_t", np.float64), ("by_kind", np.int32))
+    RUN = (("run_gap", np.float64), ("run_gap_with", np.int32), ("run_gap_k", np.int32),
+           ("run_thw", np.float64), ("run_thw_with", np.int32), ("run_thw_k", np.int32),
+           ("run_made_lat", np.float64), ("run_made_with", np.int32), ("run_made_t", np.float64), ("run_made_kind", np.int32),
+           ("run_by_lat", np.float64), ("run_by_with", np.int32), ("run_by_t", np.float64), ("run_by_kind", np.int32))
+    COUNT = (("run_made", np.int32), ("run_by", np.int32))
+
+    __slots__ = (("first", "period", "seconds", "events", "n_events") + tuple(f for f, _ in STATION + INTERVAL + RUN + COUNT)
+                 + ("ids", "gap_with_id", "made_with_id", "by_with_id", "run_gap_with_id", "run_thw_with_id", "run_made_with_id",
+                    "run_by_with_id", "event_i_id", "event_j_id"))   # (SocialForceIntersection.passing fills these)
+
+    def in_seconds(self):
+        """a copy whose times - thw, made_t, by_t, their run_* and the events' t - are seconds (t from the sample `first`) and whose
+        closing speeds are metres per second"""
+        if self.seconds:
+            return self
+        if self.period is None:
+            raise ValueError("in_seconds: the period of the recording is not known (record / enable_history were not called through this Engine)")
+        r = Passing()
+        for f in self.__slots__:
+            setattr(r, f, getattr(self, f))
+        for f in _PASSING_TIMES:
+            if getattr(self, f) is not None:
+                setattr(r, f, getattr(self, f) * self.period)
+        if self.events is not None:
+            r.events = self.events.copy()
+            r.events["t"] *= self.period
+            r.events["closing"] /= self.period
+        r.seconds = True
+        return r
+
+
+def _is_number(v):
+    return not isinstance(v, bool) and np.isscalar(v) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _passing_args(who, first, count, band, lat_max, lat_event):
+    """the checks of Engine.passing / batch_passing, before any device call"""
+    if not _is_number(band) or not band >= 0:
+        raise ValueError(f"{who}: band must be a number >= 0, +inf for every road user ahead (got {band!r})")
+    if not _is_number(lat_max) or not lat_max > 0:
+        raise ValueError(f"{who}: lat_max must be a number > 0, +inf for every passing (got {lat_max!r})")
+    if lat_event is not None and (not _is_number(lat_event) or np.isnan(lat_event) or lat_event == -np.inf):
+        raise ValueError(f"{who}: lat_event must be None or a number, +inf for every passing (got {lat_event!r})")
+    if first is None or count is None:
+        raise ValueError(f"{who}: first and count are needed - a direction of travel is a window of the recording, the current state has none")
+    if isinstance(first, bool) or isinstance(count, bool) or int(first) != first or int(count) != count or first < 0 or count < 0:
+        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
+    if count > 65535:
+        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
+    return int(first), int(count)
+
+
+def _passing_capacity_guess(cells):
+    """room for events in the first call: passings are fewer than stations in every population looked at"""
+    return min(max(64, cells), 1 << 16)
+
+
+class _PassingPack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
+    csf_passing_out records that point into them (shapes: (n, count) per member)"""
+
+    def __init__(self, shapes, per_station, caps):
+        m = len(shapes)
+        st = np.array([n * max(c - 1, 0) for n, c in shapes], dtype=np.int64)
+        iv = np.array([n * max(c - 2, 0) for n, c in shapes], dtype=np.int64)
+        ns = np.array([n for n, _ in shapes], dtype=np.int64)
+        caps = np.asarray(caps, dtype=np.int64)
+        self.shapes = shapes
+        self.s0, self.i0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (st, iv, ns, caps))
+        self.station = [np.empty(int(self.s0[-1]), dt) for _, dt in Passing.STATION] if per_station else None
+        self.interval = [np.empty(int(self.i0[-1]), dt) for _, dt in Passing.INTERVAL] if per_station else None
+        self.run = [np.empty(int(self.n0[-1]), dt) for _, dt in Passing.RUN]
+        self.count = [np.empty(3 * int(self.n0[-1]), dt) for _, dt in Passing.COUNT]
+        self.events = np.empty(int(self.e0[-1]), PASSING_EVENT_DTYPE)
+        # the records as one int64 table (every member of csf_passing_out is 8 bytes), filled column by column in header order
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.PassingOut) // 8), dtype=np.int64)
+        col = 0
+        for names, arrays, start, width in ((Passing.STATION, self.station, self.s0, 1), (Passing.INTERVAL, self.interval, self.i0, 1),
+                                            (Passing.RUN, self.run, self.n0, 1), (Passing.COUNT, self.count, self.n0, 3)):
+            if arrays is not None:
+                for k, a in enumerate(arrays):
+                    tab[:, col + k] = a.ctypes.data + a.itemsize * width * start[:-1]
+            col += len(names)
+        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + PASSING_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
+        tab[:, col + 1] = caps
+        self.outs = (_ffi.PassingOut * m).from_buffer(tab)
+
+    def result(self, i, want_events, period):
+        n, count = self.shapes[i]
+        o = self.outs[i]
+        r = Passing()
+        for f in Passing.__slots__:
+            setattr(r, f, None)
+        r.first, r.n_events, r.period, r.seconds = int(o.first_sample), int(o.n_events), period, False
+        s, v, u = int(self.s0[i]), int(self.i0[i]), int(self.n0[i])
+        rows_s, rows_i = max(count - 1, 0), max(count - 2, 0)
+        if self.station is not None:
+            for k, (name, _) in enumerate(Passing.STATION):
+                setattr(r, name, self.station[k][s:s + n * rows_s].reshape(rows_s, n))
+            for k, (name, _) in enumerate(Passing.INTERVAL):
+                setattr(r, name, self.interval[k][v:v + n * rows_i].reshape(rows_i, n))
+        for k, (name, _) in enumerate(Passing.RUN):
+            setattr(r, name, self.run[k][u:u + n])
+        for k, (name, _) in enumerate(Passing.COUNT):
+            setattr(r, name, self.count[k][3 * u:3 * (u + n)].reshape(n, 3))
+        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        return r
+
+
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
 
@@ -1002,6 +1129,50 @@ class Engine:
         """launches of post_encroachment / batch_post_encroachment so far: two per call (csf.h: csf_pet_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_pet_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- following and passing: gaps, overtakings and meetings of a recording (include/csf.h: csf_passing) --------------------
+    def passing(self, first, count, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
+        """who rode behind whom, at what gap and headway, and who overtook or met whom, when and at what lateral clearance (csf.h:
+        csf_passing), over samples [first, first + count) of the recording (record / enable_history).  band: half the width in metres
+        of the corridor ahead in which a leader is looked for; lat_max: the largest clearance at which a passing counts.  Returns
+        a Passing: per station gap, gap_with, thw [count - 1, n], per interval made_* and by_* [count - 2, n] (None without
+        per_station), run_* [n], and - with lat_event, in metres, +inf for every passing - events, the ordered passings (i passes
+        j) under it, sorted by (i, j, k).  Times are in samples; in_seconds() scales them.  Events are fetched with a guessed
+        capacity; when more were found, one second call with the exact capacity."""
+        first, count = _passing_args("passing", first, count, band, lat_max, lat_event)
+        n = self.n
+        want = lat_event is not None and lat_event > 0
+        cap = _passing_capacity_guess(max(count - 1, 0) * n) if want else 0
+        while True:
+            pack = _PassingPack([(n, count)], per_station, [cap])
+            self._ck(self._lib.csf_passing(self._h, first, count, float(band), float(lat_max), float(lat_event or 0.0), pack.outs))
+            if pack.outs[0].n_events <= cap:
+                return pack.result(0, want, self._period())
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_passing(engines, n_last, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
+        """passing() over the last n_last samples of every recording member of a batch (the engines in join order), all members in
+        the same two launches with one transfer and one wait (csf.h: csf_batch_passing): a list with a Passing per member, None
+        for members that do not record"""
+        n_last = _passing_args("batch_passing", 0, n_last, band, lat_max, lat_event)[1]
+        engines, arr = Engine._batch_array(engines, "batch_passing")
+        want = lat_event is not None and lat_event > 0
+        shapes = [(e.n, n_last) for e in engines]
+        caps = [_passing_capacity_guess(max(n_last - 1, 0) * n) if want else 0 for n, _ in shapes]
+        while True:
+            pack = _PassingPack(shapes, per_station, caps)
+            Engine._group_call("csf_batch_passing", engines, arr, n_last, float(band), float(lat_max), float(lat_event or 0.0), pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, want, e._period()) for i, e in enumerate(engines)]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def passing_launches(self):
+        """launches of passing / batch_passing so far: two per call (csf.h: csf_passing_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_passing_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

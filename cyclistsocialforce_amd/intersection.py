@@ -695,6 +695,17 @@ class SocialForceIntersection:
             raise RuntimeError("the intersection is empty")
         return _pet_ids(self._push_mutations().post_encroachment(first, count, pet_event, per_segment), self.get_road_user_ids())
 
+    def passing(self, first, count, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
+        """Engine.passing on the population's own engine: who rode behind whom, at what gap and headway, and who overtook or met
+        whom, when and at what lateral clearance, over samples [first, first + count) of the engine's recording (step_n(...,
+        dense=True) and advance_together record every tick in a ring of DENSE_CHUNK samples).  The result carries the partners also
+        as the road users' ids: `ids`, gap_with_id [count - 1, n], made_with_id, by_with_id [count - 2, n], run_gap_with_id,
+        run_thw_with_id, run_made_with_id, run_by_with_id [n] (None where there is no partner) and event_i_id, event_j_id beside the
+        events."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        return _passing_ids(self._push_mutations().passing(first, count, band, lat_max, lat_event, per_station), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -995,6 +1006,32 @@ def post_encroachment_together(intersections, n_last, pet_event=None, per_segmen
         _batch_of(engines)
         for ins, res in zip(live, Engine.batch_post_encroachment(engines, n_last, pet_event, per_segment)):
             got[id(ins)] = None if res is None else _pet_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
+def _passing_ids(res, ids):
+    """a Passing with the partners' places in the population order also given as the road users' ids"""
+    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
+    res.ids = list(ids)
+    for f in ("gap_with", "made_with", "by_with", "run_gap_with", "run_thw_with", "run_made_with", "run_by_with"):
+        setattr(res, f + "_id", None if getattr(res, f) is None else names[getattr(res, f)])
+    if res.events is not None:
+        res.event_i_id, res.event_j_id = names[res.events["i"]], names[res.events["j"]]
+    return res
+
+
+def passing_together(intersections, n_last, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
+    """SocialForceIntersection.passing over the last n_last recorded samples of many intersections - those advance_together has
+    just ticked - with all their engines in the same two launches, one transfer and one wait (Engine.batch_passing): a list with
+    a result per intersection, None for an empty one and for one whose engine does not record."""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, Engine.batch_passing(engines, n_last, band, lat_max, lat_event, per_station)):
+            got[id(ins)] = None if res is None else _passing_ids(res, ins.get_road_user_ids())
     return [got.get(id(ins)) for ins in intersections]
 
 

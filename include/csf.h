@@ -457,6 +457,148 @@ int csf_batch_post_encroachment(csf_engine *const *engines, int32_t count, int64
 /* launches of the two calls above so far (a batch counts on its first member) */
 int csf_pet_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- following and passing: gaps, overtakings and meetings of a recording ------------------------ */
+
+/* Who rode behind whom, at what gap and time headway, and who overtook or met whom, when, and with how much lateral clearance -
+ * formed on the device from the state ring that csf_record / csf_enable_history keep.
+ *
+ * A call covers samples [first_sample, first_sample + c) of the state ring, numbered k = 0 ... c-1 inside the call. P_i(k) = (x, y)
+ * are the fp64 bits of the ring.
+ *
+ * Stations.
+ * - Station (i, k), for k = 0 ... c-2, has the direction of travel h_i(k) = P_i(k+1) - P_i(k).
+ * - It also has hh = h.x*h.x + h.y*h.y and len = sqrt(hh).
+ * - A station exists if all four coordinates are finite.
+ * - A station moves if it exists and hh > 0.
+ *
+ * Terms of an ordered pair (i, j), j != i, at station k.
+ * - Both stations must exist and (i, k) must move.
+ * - Always subtract, never negate: w = P_j(k) - P_i(k).
+ * - With h = h_i(k):
+ *   - g = w.x*h.x + w.y*h.y is how far j is ahead of i, in m * m/sample.
+ *   - cr = h.x*w.y - h.y*w.x is positive when j is on i's left.
+ *   - dot = h.x*h_j(k).x + h.y*h_j(k).y.
+ * - Each term is two products and one sum or difference in fp64. None is contracted to an FMA (#pragma clang fp contract(off)).
+ *   No fp32 and no fast-math functions are used.
+ * - a = g / len and lat = cr / len, in metres.
+ *
+ * Following, per station (k, i).
+ * - j is a candidate leader iff the terms exist, g > 0, fabs(lat) <= band and dot >= 0.
+ * - dot >= 0 means a stationary j ahead counts and an oncoming j does not.
+ * - The leader is the candidate with the smallest g. Ties go to the lowest j (a strict < in population order).
+ * - Report three values:
+ *   - gap = g / len, in metres.
+ *   - gap_with = j.
+ *   - thw = gap / len, in samples.
+ * - If there is no candidate, or (i, k) exists but does not move, the row is +inf / -1 / +inf.
+ * - If (i, k) does not exist, the row is NaN / -1 / NaN, and (i, k) is nobody's partner.
+ *
+ * Passing, per interval k = 0 ... c-3.
+ * - "i passes j in interval k" holds iff all of the following hold:
+ *   - Stations (i, k) and (i, k+1) move.
+ *   - Stations (j, k) and (j, k+1) exist.
+ *   - g(k) > 0 && g(k+1) <= 0, each with its own station's h.
+ *   - fabs(lat_at) <= lat_max, with lat_at as below.
+ * - The interval is half open. A partner exactly abeam at a sample counts in the interval that ends there and nowhere else.
+ * - The values are:
+ *   - s = a0 / (a0 - a1).
+ *   - t = (double)k + s.
+ *   - lat_at = lat0 + s * (lat1 - lat0).
+ *   - closing = a0 - a1, in m/sample.
+ *   - kind is +1 (overtaking) if dot(k) > 0, -1 (meeting) if < 0, and 0 otherwise. Kind 0 covers a stationary partner or an
+ *     exactly perpendicular one.
+ *   - cosine = dot(k) / (len_i(k) * len_j(k)). It is NaN for a stationary partner.
+ * - Comparisons are made as written, so a NaN fails them.
+ *
+ * Made and received.
+ * - Per interval (k, i), made_* is the passing by i with the smallest fabs(lat_at), lowest j on ties: made_lat (signed),
+ *   made_with, made_t, made_kind.
+ * - by_* is the passing OF i by some j with the smallest fabs(lat_at), lowest j on ties. Here lat_at, t and kind are as the passer
+ *   j reports them.
+ * - The lane of i evaluates "j passes i" itself, in j's frame, with the same operations in the same order as j's lane:
+ *   w' = P_i - P_j, and so on. IEEE gives a - b == -(b - a), so both lanes form the same bits. The results therefore need no
+ *   atomics, and a row does not depend on what else is in the launch.
+ * - Rows with no passing are +inf / -1 / NaN / 0.
+ * - Row made_*[k, i] is NaN / -1 / NaN / 0 if station (i, k) does not exist.
+ *
+ * Per road user over the call.
+ * - run_gap and run_thw are each the minimum over the stations. Each comes with its partner and its k, the earliest k on ties.
+ * - run_made_* and run_by_* are each the minimum fabs(lat) over the intervals, earliest k on ties. Each comes with lat, with, t
+ *   and kind.
+ * - run_made[n][3] and run_by[n][3] (int32) count passings as (overtaking, meeting, other).
+ *
+ * Events.
+ * - Events are optional. They are on when lat_event > 0; +inf means every passing.
+ * - An event is an ORDERED passing (i passes j) with fabs(lat_at) < lat_event.
+ * - It is stored by the passer's lane as {int32 i, j, k, kind; double t, lat, closing, cosine;}, 48 bytes.
+ * - Capacity, total count, "sorted by (i, j, k) when total <= capacity" and "unspecified subset otherwise" are exactly as for
+ *   csf_pet_event.
+ *
+ * Small calls.
+ * - c < 2 gives no stations.
+ * - c < 3 gives no intervals.
+ * - A population of one finds nothing.
+ * - All of these succeed. */
+typedef struct csf_passing_event {
+    int32_t i, j, k, kind;
+    double t, lat, closing, cosine;
+} csf_passing_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned).  n = the road users, c = n_samples.
+ * event_capacity = 0 with events NULL counts the events without storing any.  With c < 2 the per-station arrays have no rows,
+ * with c < 3 the per-interval arrays have none, and run_* are written as "nothing found" (+inf / -1 / NaN / 0, k = -1).  t and
+ * the k of run_gap_k / run_thw_k count from the call's first sample. */
+typedef struct csf_passing_out {
+    double *gap;              /* [c-1, n] metres to the leader */
+    int32_t *gap_with;        /* [c-1, n] the leader */
+    double *thw;              /* [c-1, n] time headway, in samples */
+    double *made_lat;         /* [c-2, n] signed clearance of the passing i made with the smallest fabs ... */
+    int32_t *made_with;       /* [c-2, n] ... whom it passed ... */
+    double *made_t;           /* [c-2, n] ... when ... */
+    int32_t *made_kind;       /* [c-2, n] ... and +1 overtaking, -1 meeting, 0 other */
+    double *by_lat;           /* [c-2, n] the passing OF i with the smallest fabs(lat_at), as the passer reports it */
+    int32_t *by_with;         /* [c-2, n] the passer */
+    double *by_t;             /* [c-2, n] */
+    int32_t *by_kind;         /* [c-2, n] */
+    double *run_gap;          /* [n] the smallest gap ... */
+    int32_t *run_gap_with;    /* [n] ... to whom ... */
+    int32_t *run_gap_k;       /* [n] ... at which station */
+    double *run_thw;          /* [n] the smallest headway, likewise */
+    int32_t *run_thw_with;    /* [n] */
+    int32_t *run_thw_k;       /* [n] */
+    double *run_made_lat;     /* [n] the passing made with the smallest fabs(lat) */
+    int32_t *run_made_with;   /* [n] */
+    double *run_made_t;       /* [n] */
+    int32_t *run_made_kind;   /* [n] */
+    double *run_by_lat;       /* [n] the passing received with the smallest fabs(lat) */
+    int32_t *run_by_with;     /* [n] */
+    double *run_by_t;         /* [n] */
+    int32_t *run_by_kind;     /* [n] */
+    int32_t *run_made;        /* [n, 3] passings made: overtakings, meetings, others */
+    int32_t *run_by;          /* [n, 3] passings received */
+    csf_passing_event *events;   /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the events found, stored or not */
+    int64_t first_sample;     /* written: the index of the first sample covered */
+} csf_passing_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
+ * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every ordered pair at every
+ * station, then the window pass - with one hipMemsetAsync of the event counters, one transfer and one wait (the launch counter
+ * below grows by 2 per call that covers a station).  Refused without side effects (CSF_E_ARG / CSF_E_STATE, with a message,
+ * launch counter unchanged): a NULL out; first_sample == -1 (the current state has no direction of travel) or no ring;
+ * n_samples < 0 or above 65535; samples that are not in the ring; band NaN or negative (+inf is allowed); lat_max NaN or <= 0
+ * (+inf is allowed); lat_event NaN or -inf; a negative event capacity, or a capacity with a NULL buffer; a rank of a sharded run
+ * or a member of a loopback group; an engine that holds a calibration data set.  While csf_profile_enable is on, the first
+ * launch is timed as kernel 0. */
+int csf_passing(csf_engine *e, int64_t first_sample, int64_t n_samples, double band, double lat_max, double lat_event, csf_passing_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, all members in the same two launches, with one
+ * transfer and one wait; outs [count].  A member without a ring is skipped: its n_events becomes 0 and its first_sample -2.  A
+ * recording member with fewer than n_last samples in its ring makes the call a refusal before anything is written. */
+int csf_batch_passing(csf_engine *const *engines, int32_t count, int64_t n_last, double band, double lat_max, double lat_event,
+                      csf_passing_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_passing_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
