@@ -53,6 +53,7 @@ SYMBOLS = (
     "csf_encounters", "csf_batch_encounters", "csf_encounter_launches",
     "csf_post_encroachment", "csf_batch_post_encroachment", "csf_pet_launches",
     "csf_passing", "csf_batch_passing", "csf_passing_launches",
+    "csf_flow", "csf_batch_flow", "csf_flow_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -144,6 +145,30 @@ class PassingOut(C.Structure):
                 ("run_by_lat", C.c_void_p), ("run_by_with", C.c_void_p), ("run_by_t", C.c_void_p), ("run_by_kind", C.c_void_p),
                 ("run_made", C.c_void_p), ("run_by", C.c_void_p),
                 ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
+
+
+class FlowLayout(C.Structure):
+    """csf_flow_layout of include/csf.h: the counting lines, areas and grid every member of a call is measured at"""
+
+    _fields_ = [("lines", C.c_void_p), ("areas", C.c_void_p), ("n_lines", C.c_int32), ("n_areas", C.c_int32),
+                ("x0", C.c_double), ("y0", C.c_double), ("h", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32)]
+
+
+class FlowEvent(C.Structure):
+    """csf_flow_event of include/csf.h: road user i crosses line l in interval k"""
+
+    _fields_ = [("i", C.c_int32), ("l", C.c_int32), ("k", C.c_int32), ("dir", C.c_int32),
+                ("t", C.c_double), ("u", C.c_double), ("speed", C.c_double)]
+
+
+class FlowOut(C.Structure):
+    """csf_flow_out of include/csf.h: where the crossings and occupancies of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("line_count", C.c_void_p), ("cross_n", C.c_void_p),
+                ("first_t", C.c_void_p), ("first_u", C.c_void_p), ("first_speed", C.c_void_p), ("first_dir", C.c_void_p),
+                ("occupancy", C.c_void_p), ("in_samples", C.c_void_p), ("in_first", C.c_void_p), ("in_last", C.c_void_p), ("in_dist", C.c_void_p),
+                ("grid_count", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("n_outside", C.c_int64), ("first_sample", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -268,6 +293,10 @@ def load():
         L.csf_passing.argtypes = [vp, i64, i64, C.c_double, C.c_double, C.c_double, C.POINTER(PassingOut)]
         L.csf_batch_passing.argtypes = [C.POINTER(vp), i32, i64, C.c_double, C.c_double, C.c_double, C.POINTER(PassingOut)]
         L.csf_passing_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_flow"):                   # (likewise)
+        L.csf_flow.argtypes = [vp, i64, i64, C.POINTER(FlowLayout), C.POINTER(FlowOut)]
+        L.csf_batch_flow.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(FlowLayout), C.POINTER(FlowOut)]
+        L.csf_flow_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

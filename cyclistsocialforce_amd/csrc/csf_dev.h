@@ -573,6 +573,48 @@ constexpr int PASS_LAUNCHES = 2;
 // the grid of the first launch as launch_encounters has it, with stations in the place of samples; then the window pass over max_n
 // riders of every member: PASS_LAUNCHES launches whatever the members are.
 void launch_passing(const PassArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_flow.hip (csf_flow, csf_batch_flow): crossings of counting lines, occupancy of areas and of a grid, one (sample, road user) cell
+// per lane.  One descriptor per engine in mapped host memory, as EncDesc; the layout (FlowArgs) is shared by the members.  With
+// c = count, L lines, R areas and G = nx * ny cells, a member's results are two blocks of the packed output:
+//   the counts the first launch ADDS to, cleared together with the counters in front of it (acc_off; every member's lie together):
+//     int32 line_count [c-1][L][2], occupancy [c][R], grid_count [G]
+//   what the second launch writes (out_off; the int32 arrays follow the doubles):
+//     double first_t, first_u, first_speed [n][L], in_dist [n][R];
+//     int32 cross_n [n][L][2], first_dir [n][L], in_samples, in_first, in_last [n][R]
+// and behind what is transferred, one FlowCell per (sample, road user) cell (cell_off): what the second launch walks along k.
+constexpr int FLOW_MAX = 64;    // lines, and areas, of a layout: one bit each of a cell's masks
+struct FlowDesc {
+    const double *s;         // the state ring [cap][n][ns]
+    int64_t acc_off;         // the member's added counts in the packed output, in bytes (a multiple of 32)
+    int64_t out_off;         // ... its per-road-user block ...
+    int64_t ev_off, ev_cap;  // ... and its events, csf_flow_event [ev_cap]
+    int64_t cell_off;        // FlowCell [count][n] (device scratch behind what is transferred)
+    int32_t n, ns, cap;      // road users, states of each, samples the ring holds
+    int32_t first, count;    // ring slot of the first sample asked for, samples asked for (>= 1)
+    int32_t pad;
+};
+struct FlowArgs {
+    const FlowDesc *desc;          // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] crossings found, then [members] existing samples outside the grid: cleared in front of the launch
+    const double *lines, *areas;   // the layout as the caller gave it: [L][4], [R][5] (mapped host memory)
+    double x0, y0, h;
+    int32_t L, R, nx, ny;
+    int32_t members;
+};
+// what the first launch leaves of a cell (k, i)
+struct FlowCell {
+    unsigned long long inside;     // bit r: sample (i, k) is inside area r
+    unsigned long long cross;      // bit l: station (i, k) crosses line l ...
+    unsigned long long left;       // ... from the left (dir = +1)
+    double len;                    // len_i(k); NaN: the station does not exist
+};
+inline size_t flow_acc_bytes(size_t c, size_t L, size_t R, size_t G) { return (4 * ((c ? c - 1 : 0) * L * 2 + c * R + G) + 31) & ~(size_t)31; }
+inline size_t flow_block_bytes(size_t n, size_t L, size_t R) { return (n * (36 * L + 20 * R) + 31) & ~(size_t)31; }
+constexpr int FLOW_LAUNCHES = 2;
+// the grid of the first launch as launch_encounters has it (n > ENC_SMALL: tiles of 256 road users x samples; the packed members take
+// the plane x * y), z = members; then the walk over max_n * (L + R) lanes of every member: FLOW_LAUNCHES launches whatever the members are.
+void launch_flow(const FlowArgs &a, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

@@ -316,6 +316,14 @@ struct PassScratch {
     HostBuf<unsigned char, false> host;
 };
 
+// ... and csf_flow / csf_batch_flow: the same three, and the layout as the kernels read it (mapped host memory)
+struct FlowScratch {
+    HostBuf<FlowDesc> desc;
+    HostBuf<double> layout;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -543,6 +551,8 @@ struct csf_engine {
     PetScratch pet;
     int64_t passing_launches = 0;    // launches of csf_passing / csf_batch_passing: two per call (csf_passing_launches)
     PassScratch passing;
+    int64_t flow_launches = 0;       // launches of csf_flow / csf_batch_flow: two per call (csf_flow_launches)
+    FlowScratch flow;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

@@ -4,6 +4,7 @@
 directly with NumPy arrays.  Every number it returns was computed by the HIP kernels.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -337,6 +338,191 @@ class _PassingPack:
         for k, (name, _) in enumerate(Passing.COUNT):
             setattr(r, name, self.count[k][3 * u:3 * (u + n)].reshape(n, 3))
         r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        return r
+
+
+FLOW_EVENT_DTYPE = np.dtype([("i", np.int32), ("l", np.int32), ("k", np.int32), ("dir", np.int32),
+                             ("t", np.float64), ("u", np.float64), ("speed", np.float64)])   # csf_flow_event
+
+FLOW_MAX = 64             # lines, and areas, of a layout
+FLOW_MAX_GRID = 1 << 20   # cells of a grid
+
+
+class Flow:
+    """What Engine.flow returns for one engine (csf.h: csf_flow): `first` the index of the first sample covered; line_count
+    [c - 1, L, 2] the crossings of every interval by direction (index 0: left to right of A -> B, 1: right to left), cross_n [n, L, 2]
+    those of every road user, first_t, first_u, first_speed, first_dir [n, L] a road user's first crossing of a line (+inf / NaN / NaN /
+    0 without one); occupancy [c, R] the road users inside every area at every sample, in_samples, in_first, in_last, in_dist [n, R]
+    every road user's samples inside, the first and last of them (-1: never) and the metres ridden inside; grid_count [ny, nx] the
+    samples in every cell (None without a grid) and n_outside those outside the grid; events (FLOW_EVENT_DTYPE, every crossing, sorted
+    by i, l, k; None when they were not asked for) with n_events their number.  lines [L, 4], areas [R, 5] and grid (x0, y0, h, nx, ny
+    or None) are the layout the call was made with.  t is in samples from `first`, speed in metres per sample; `period` is the
+    seconds per sample of the recording (None when it is not known), and the helpers take the dt to scale by."""
+
+    ARRAYS = (("line_count", np.int32), ("cross_n", np.int32), ("first_t", np.float64), ("first_u", np.float64),
+              ("first_speed", np.float64), ("first_dir", np.int32), ("occupancy", np.int32), ("in_samples", np.int32),
+              ("in_first", np.int32), ("in_last", np.int32), ("in_dist", np.float64), ("grid_count", np.int32))
+
+    __slots__ = (("first", "period", "events", "n_events", "n_outside", "lines", "areas", "grid") + tuple(f for f, _ in ARRAYS)
+                 + ("ids", "event_i_id"))                     # (SocialForceIntersection.flow fills these)
+
+    def _events_of(self, l, who):
+        if self.events is None:
+            raise ValueError(f"{who}: the events were not asked for (events=True)")
+        return self.events[self.events["l"] == l]
+
+    def flow(self, l, dt):
+        """crossings of line l per second over the call, by direction: [2]"""
+        rows = self.line_count.shape[0]
+        total = self.line_count[:, l, :].sum(axis=0).astype(np.float64)
+        return total / (rows * dt) if rows else np.full(2, np.nan)
+
+    def cumulative(self, l):
+        """line_count summed along k, by direction [c - 1, 2]: with a second line's, the N-curves of a stretch"""
+        return np.cumsum(self.line_count[:, l, :], axis=0, dtype=np.int64)
+
+    def travel_time(self, l_from, l_to, dt):
+        """seconds from every road user's first crossing of line l_from to its first of l_to [n]; NaN where either is missing"""
+        a, b = self.first_t[:, l_from], self.first_t[:, l_to]
+        both = np.isfinite(a) & np.isfinite(b)
+        out = np.full(a.shape, np.nan)
+        out[both] = (b[both] - a[both]) * dt
+        return out
+
+    def speeds(self, l, dt):
+        """(time-mean, harmonic = space-mean) speed in m/s of the crossings of line l, from the events; NaN without a crossing"""
+        v = self._events_of(l, "speeds")["speed"] / dt
+        if v.size == 0:
+            return float("nan"), float("nan")
+        with np.errstate(divide="ignore"):
+            return math.fsum(v) / v.size, v.size / math.fsum(1.0 / v)
+
+    def headways(self, l, dt):
+        """seconds between successive crossings of line l, in either direction, from the events"""
+        return np.diff(np.sort(self._events_of(l, "headways")["t"])) * dt
+
+    def _area(self, r):
+        ax, ay, bx, by, hw = (float(v) for v in self.areas[r])
+        return 2.0 * hw * math.sqrt((bx - ax) * (bx - ax) + (by - ay) * (by - ay))
+
+    def density(self, r):
+        """road users per square metre inside area r at every sample [c]: occupancy / (2 * half_width * ld)"""
+        return self.occupancy[:, r] / self._area(r)
+
+    def edie(self, r, dt):
+        """Edie's generalised (q, k, v) of area r over the call: the metres ridden inside and the seconds spent inside, both over
+        area x T with T = the call's samples x dt - q in 1/(m s), k in 1/m^2 - and their ratio, the space-mean speed in m/s (NaN when
+        nobody was inside).  Summed with math.fsum."""
+        dist, time = math.fsum(self.in_dist[:, r]), math.fsum(self.in_samples[:, r] * float(dt))
+        over = self._area(r) * self.occupancy.shape[0] * dt
+        return dist / over, time / over, (dist / time if time > 0 else float("nan"))
+
+
+def _flow_layout(who, lines, areas, grid):
+    """the checks of the layout of Engine.flow / batch_flow, before any device call: (lines [L, 4], areas [R, 5], grid or None)"""
+    def table(v, width, what):
+        if v is None:
+            return np.zeros((0, width))
+        a = np.array(v, dtype=np.float64, ndmin=2) if np.size(v) else np.zeros((0, width))
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError(f"{who}: {what} must be [k, {width}] (got shape {a.shape})")
+        if a.shape[0] > FLOW_MAX:
+            raise ValueError(f"{who}: at most {FLOW_MAX} {what} (got {a.shape[0]})")
+        if not np.isfinite(a[:, :4]).all():
+            raise ValueError(f"{who}: {what} with a non-finite coordinate")
+        dx, dy = a[:, 2] - a[:, 0], a[:, 3] - a[:, 1]
+        if not (dx * dx + dy * dy > 0).all():
+            raise ValueError(f"{who}: {what} of no length (A == B)")
+        return np.ascontiguousarray(a)
+    lines, areas = table(lines, 4, "lines"), table(areas, 5, "areas")
+    hw = areas[:, 4]
+    if not (np.isfinite(hw) & (hw >= 0)).all():
+        raise ValueError(f"{who}: the half widths of the areas must be finite and >= 0 (got {hw.tolist()})")
+    if grid is not None:
+        if len(grid) != 5:
+            raise ValueError(f"{who}: grid must be (x0, y0, h, nx, ny) or None (got {grid!r})")
+        x0, y0, h, nx, ny = grid
+        if not all(_is_number(v) for v in (x0, y0, h, nx, ny)) or int(nx) != nx or int(ny) != ny:
+            raise ValueError(f"{who}: grid must be (x0, y0, h, nx, ny) with whole nx, ny (got {grid!r})")
+        if not (np.isfinite(x0) and np.isfinite(y0) and np.isfinite(h) and h > 0):
+            raise ValueError(f"{who}: the grid's origin must be finite and h finite and > 0 (got {grid!r})")
+        if nx < 1 or ny < 1 or nx * ny > FLOW_MAX_GRID:
+            raise ValueError(f"{who}: the grid must have 1 ... 2^20 cells (got {nx} x {ny})")
+        grid = (float(x0), float(y0), float(h), int(nx), int(ny))
+    return lines, areas, grid
+
+
+def _flow_args(who, first, count):
+    if first is None or count is None:
+        raise ValueError(f"{who}: first and count are needed - an interval is a window of the recording, the current state has none")
+    if isinstance(first, bool) or isinstance(count, bool) or not _is_number(first) or not _is_number(count) \
+            or int(first) != first or int(count) != count or first < 0 or count < 0:
+        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
+    if count > 65535:
+        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
+    return int(first), int(count)
+
+
+def _flow_capacity_guess(cells, lines):
+    """room for events in the first call: on straight paths a few percent of the stations cross any one line"""
+    return min(max(64, cells * min(lines, 4) // 4), 1 << 16)
+
+
+class _FlowPack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, the
+    csf_flow_out records that point into them (shapes: (n, count) per member) and the csf_flow_layout they share"""
+
+    def __init__(self, shapes, lines, areas, grid, caps):
+        m = len(shapes)
+        L, R = lines.shape[0], areas.shape[0]
+        G = grid[3] * grid[4] if grid else 0
+        self.shapes, self.lines, self.areas, self.grid = shapes, lines, areas, grid
+        n = np.array([n for n, _ in shapes], dtype=np.int64)
+        c = np.array([c for _, c in shapes], dtype=np.int64)
+        caps = np.asarray(caps, dtype=np.int64)
+        sizes = {"line_count": np.maximum(c - 1, 0) * L * 2, "cross_n": n * L * 2, "first_t": n * L, "first_u": n * L, "first_speed": n * L,
+                 "first_dir": n * L, "occupancy": c * R, "in_samples": n * R, "in_first": n * R, "in_last": n * R, "in_dist": n * R,
+                 "grid_count": np.full(m, G, dtype=np.int64)}
+        self.start = {f: np.r_[0, np.cumsum(v)] for f, v in sizes.items()}
+        self.e0 = np.r_[0, np.cumsum(caps)]
+        self.arrays = {f: np.empty(int(self.start[f][-1]), dt) for f, dt in Flow.ARRAYS}
+        self.events = np.empty(int(self.e0[-1]), FLOW_EVENT_DTYPE)
+        # the records as one int64 table (every member of csf_flow_out is 8 bytes), filled column by column in header order
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.FlowOut) // 8), dtype=np.int64)
+        for col, (f, _) in enumerate(Flow.ARRAYS):
+            a = self.arrays[f]
+            tab[:, col] = a.ctypes.data + a.itemsize * self.start[f][:-1]
+        col = len(Flow.ARRAYS)
+        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + FLOW_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
+        tab[:, col + 1] = caps
+        self.outs = (_ffi.FlowOut * m).from_buffer(tab)
+        self._read = None                                        # what the call wrote into the records, read once (result)
+        y = self.layout = _ffi.FlowLayout()
+        y.lines, y.areas, y.n_lines, y.n_areas = (lines.ctypes.data if L else None), (areas.ctypes.data if R else None), L, R
+        y.x0, y.y0, y.h, y.nx, y.ny = grid if grid else (0.0, 0.0, 1.0, 0, 0)
+
+    def result(self, i, want_events, period):
+        """member i's Flow, after the call (plain Python numbers throughout: a batch builds a thousand of these)"""
+        if self._read is None:
+            col = len(Flow.ARRAYS)
+            self._read = (self._tab[:, col + 2:col + 5].tolist(), {f: v.tolist() for f, v in self.start.items()}, self.e0.tolist())
+        (n_events, n_outside, first), start, e0 = self._read[0][i], self._read[1], self._read[2]
+        n, c = self.shapes[i]
+        L, R = self.lines.shape[0], self.areas.shape[0]
+        r = Flow()
+        for f in Flow.__slots__:
+            setattr(r, f, None)
+        r.first, r.n_events, r.n_outside, r.period = first, n_events, n_outside, period
+        r.lines, r.areas, r.grid = self.lines, self.areas, self.grid
+        for f, shape in (("line_count", (max(c - 1, 0), L, 2)), ("cross_n", (n, L, 2)), ("first_t", (n, L)), ("first_u", (n, L)),
+                         ("first_speed", (n, L)), ("first_dir", (n, L)), ("occupancy", (c, R)), ("in_samples", (n, R)), ("in_first", (n, R)),
+                         ("in_last", (n, R)), ("in_dist", (n, R))):
+            at = start[f][i]
+            setattr(r, f, self.arrays[f][at:at + math.prod(shape)].reshape(shape))
+        if self.grid:
+            at = start["grid_count"][i]
+            r.grid_count = self.arrays["grid_count"][at:at + self.grid[3] * self.grid[4]].reshape(self.grid[4], self.grid[3])
+        r.events = self.events[e0[i]:e0[i] + n_events] if want_events else None
         return r
 
 
@@ -1173,6 +1359,51 @@ class Engine:
         """launches of passing / batch_passing so far: two per call (csf.h: csf_passing_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_passing_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- flow: crossings of counting lines, occupancy of areas and of a grid (include/csf.h: csf_flow) ------------------------
+    def flow(self, first, count, lines=None, areas=None, grid=None, events=False):
+        """how many road users crossed which counting line, in which direction and at what speed, how many were inside which
+        area at every sample and how far they rode there, and where on a grid they spent their samples (csf.h: csf_flow), over
+        samples [first, first + count) of the recording (record / enable_history).  lines [L, 4] = ax, ay, bx, by; areas [R, 5] =
+        ax, ay, bx, by, half_width (an oriented rectangle around the centre line A -> B); grid = (x0, y0, h, nx, ny).  Returns a
+        Flow; with events=True it carries every crossing, sorted by (i, l, k).  Events are fetched with a guessed capacity; when
+        more were found, one second call with the exact capacity."""
+        first, count = _flow_args("flow", first, count)
+        lines, areas, grid = _flow_layout("flow", lines, areas, grid)
+        n = self.n
+        cap = _flow_capacity_guess(max(count - 1, 0) * n, lines.shape[0]) if events else 0
+        while True:
+            pack = _FlowPack([(n, count)], lines, areas, grid, [cap])
+            self._ck(self._lib.csf_flow(self._h, first, count, C.byref(pack.layout), pack.outs))
+            if not events or pack.outs[0].n_events <= cap:
+                return pack.result(0, bool(events), self._period())
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_flow(engines, n_last, lines=None, areas=None, grid=None, events=False):
+        """flow() over the last n_last samples of every recording member of a batch (the engines in join order), all members in
+        the same two launches with one transfer and one wait (csf.h: csf_batch_flow): a list with a Flow per member, None for
+        members that do not record"""
+        n_last = _flow_args("batch_flow", 0, n_last)[1]
+        lines, areas, grid = _flow_layout("batch_flow", lines, areas, grid)
+        engines, arr = Engine._batch_array(engines, "batch_flow")
+        if grid and len(engines) * grid[3] * grid[4] > 1 << 24:
+            raise ValueError(f"batch_flow: {len(engines)} members x {grid[3]} x {grid[4]} grid cells (at most 2^24)")
+        shapes = [(e.n, n_last) for e in engines]
+        caps = [_flow_capacity_guess(max(n_last - 1, 0) * n, lines.shape[0]) if events else 0 for n, _ in shapes]
+        while True:
+            pack = _FlowPack(shapes, lines, areas, grid, caps)
+            Engine._group_call("csf_batch_flow", engines, arr, n_last, C.byref(pack.layout), pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if not events or all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, bool(events), e._period()) for i, e in enumerate(engines)]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def flow_launches(self):
+        """launches of flow / batch_flow so far: two per call (csf.h: csf_flow_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_flow_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

@@ -706,6 +706,15 @@ class SocialForceIntersection:
             raise RuntimeError("the intersection is empty")
         return _passing_ids(self._push_mutations().passing(first, count, band, lat_max, lat_event, per_station), self.get_road_user_ids())
 
+    def flow(self, first, count, lines=None, areas=None, grid=None, events=False):
+        """Engine.flow on the population's own engine: the crossings of counting lines, the occupancy of areas and of a grid, over
+        samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record every tick in
+        a ring of DENSE_CHUNK samples).  The result carries the road users' ids: `ids` - row i of cross_n, first_* and in_* is
+        ids[i] - and event_i_id beside the events."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        return _flow_ids(self._push_mutations().flow(first, count, lines, areas, grid, events), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -1032,6 +1041,29 @@ def passing_together(intersections, n_last, band=0.75, lat_max=3.0, lat_event=No
         _batch_of(engines)
         for ins, res in zip(live, Engine.batch_passing(engines, n_last, band, lat_max, lat_event, per_station)):
             got[id(ins)] = None if res is None else _passing_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
+def _flow_ids(res, ids):
+    """a Flow with the road users' ids beside their places in the population order"""
+    res.ids = list(ids)
+    if res.events is not None:
+        res.event_i_id = np.array(list(ids) + [None], dtype=object)[res.events["i"]]
+    return res
+
+
+def flow_together(intersections, n_last, lines=None, areas=None, grid=None, events=False):
+    """SocialForceIntersection.flow over the last n_last recorded samples of many intersections - those advance_together has
+    just ticked - at one layout, with all their engines in the same two launches, one transfer and one wait (Engine.batch_flow):
+    a list with a result per intersection, None for an empty one and for one whose engine does not record."""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, Engine.batch_flow(engines, n_last, lines, areas, grid, events)):
+            got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
     return [got.get(id(ins)) for ins in intersections]
 
 

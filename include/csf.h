@@ -599,6 +599,130 @@ int csf_batch_passing(csf_engine *const *engines, int32_t count, int64_t n_last,
 /* launches of the two calls above so far (a batch counts on its first member) */
 int csf_passing_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- flow: crossings of counting lines, occupancy of areas and of a grid, of a recording --------- */
+
+/* How many road users crossed a cross-section, in which direction and at what speed, how many were inside a stretch of path at each
+ * sample and how far they rode there, and where on the plane they spent their time - formed on the device from the state ring that
+ * csf_record / csf_enable_history keep.
+ *
+ * A call covers samples [first_sample, first_sample + c) of the state ring, numbered k = 0 ... c-1 inside the call. P_i(k) = (x, y)
+ * are the fp64 bits of the ring.
+ *
+ * General rules.
+ * - Every term below is at most two products and one sum or difference in fp64, formed as written.
+ * - Nothing is contracted to an FMA (#pragma clang fp contract(off)). No fp32 and no fast-math functions are used.
+ * - sqrt and / are the correctly rounded ones.
+ * - Comparisons are made as written, so a NaN fails them.
+ * - Always subtract, never negate.
+ *
+ * Samples and stations.
+ * - Sample (i, k) exists iff both coordinates are finite.
+ * - Station (i, k), for k <= c-2, exists iff samples k and k+1 exist.
+ * - At a station h = P(k+1) - P(k), hh = h.x*h.x + h.y*h.y and len = sqrt(hh). len is in metres per sample.
+ *
+ * Layout. csf_flow_layout is shared by all members of a batch. It holds:
+ * - lines [L, 4] = ax, ay, bx, by, with L <= 64;
+ * - areas [R, 5] = ax, ay, bx, by, half_width, with R <= 64;
+ * - a grid x0, y0, h, nx, ny, where nx == 0 means no grid and nx*ny <= 2^20.
+ * For a line or an area, d = B - A, dd = d.x*d.x + d.y*d.y and ld = sqrt(dd).
+ *
+ * Lines, per station (i, k) and line l.
+ * - Side values: s(P) = d.x*(P.y - A.y) - d.y*(P.x - A.x), which is positive on the left of A -> B. s0 = s(P(k)) and
+ *   s1 = s(P(k+1)).
+ * - A sign change is (s0 > 0) != (s1 > 0). A point exactly on the line counts as on the right. A path that touches the line and
+ *   turns back therefore crosses twice, once in each direction.
+ * - t = s0 / (s0 - s1).
+ * - The crossing point is X = (P(k).x + t*h.x, P(k).y + t*h.y).
+ * - u = ((X.x - A.x)*d.x + (X.y - A.y)*d.y) / dd.
+ * - A crossing is a sign change with u >= 0 && u <= 1.
+ * - dir is +1 if s0 > 0 (left to right) and -1 otherwise.
+ * - time = (double)k + t.
+ * - speed = len.
+ *
+ * Areas are oriented rectangles around a centre line, as for a stretch of cycle path. Per sample (i, k) that exists and area r:
+ * - w = P - A.
+ * - g = w.x*d.x + w.y*d.y.
+ * - cr = d.x*w.y - d.y*w.x.
+ * - The sample is inside iff g >= 0 && g <= dd && fabs(cr) <= half_width*ld.
+ *
+ * Grid, per sample that exists.
+ * - cx = floor((P.x - x0)/h) and cy likewise.
+ * - The sample is inside iff cx >= 0 && cx < nx && cy >= 0 && cy < ny. The test is made on the doubles before any conversion.
+ *
+ * Results.
+ * - Each (road user, interval, line) has at most one crossing, so the results carry no reduction order except the stated
+ *   sequential sum over k of in_dist. All other aggregates are integers.
+ * - in_dist starts from +0.0 and is the sum over k = 0 ... c-2, in this order, of len_i(k) for the existing stations whose sample k
+ *   is inside.
+ *
+ * Events.
+ * - An event is a crossing, stored by the lane that found it as {int32 i, l, k, dir; double t, u, speed;}, 40 bytes.
+ * - n_events counts every crossing found, stored or not, and is always written.
+ * - When n_events <= event_capacity the events are sorted by (i, l, k). Otherwise an unspecified subset is stored, exactly as for
+ *   csf_passing_event.
+ *
+ * Small calls.
+ * - c < 2 gives no intervals.
+ * - n = 0, L = R = nx = 0 and a population of one are all fine.
+ * - All of these succeed. */
+typedef struct csf_flow_layout {
+    const double *lines;      /* [n_lines, 4] ax, ay, bx, by */
+    const double *areas;      /* [n_areas, 5] ax, ay, bx, by, half_width */
+    int32_t n_lines;          /* L: 0 ... 64 */
+    int32_t n_areas;          /* R: 0 ... 64 */
+    double x0;                /* the grid's origin ... */
+    double y0;
+    double h;                 /* ... the side of a cell, in metres ... */
+    int32_t nx;               /* ... and the cells along x and y; nx == 0 && ny == 0: no grid */
+    int32_t ny;
+} csf_flow_layout;
+typedef struct csf_flow_event {
+    int32_t i, l, k, dir;
+    double t, u, speed;
+} csf_flow_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned), and the arrays of an absent part of
+ * the layout have no rows.  n = the road users, c = n_samples, L, R, nx, ny the layout's.  event_capacity = 0 with events NULL
+ * counts the events without storing any.  t counts from the call's first sample. */
+typedef struct csf_flow_out {
+    int32_t *line_count;      /* [c-1, L, 2] crossings in interval k by direction (index 0: +1, 1: -1) */
+    int32_t *cross_n;         /* [n, L, 2] crossings of each road user over the call */
+    double *first_t;          /* [n, L] a road user's first crossing of a line (the lowest k): when; +inf if none ... */
+    double *first_u;          /* [n, L] ... where along the line; NaN if none ... */
+    double *first_speed;      /* [n, L] ... at what speed; NaN if none ... */
+    int32_t *first_dir;       /* [n, L] ... and in which direction; 0 if none */
+    int32_t *occupancy;       /* [c, R] road users inside at sample k */
+    int32_t *in_samples;      /* [n, R] samples inside */
+    int32_t *in_first;        /* [n, R] first sample inside, -1 if never */
+    int32_t *in_last;         /* [n, R] last sample inside, -1 if never */
+    double *in_dist;          /* [n, R] metres ridden inside */
+    int32_t *grid_count;      /* [ny, nx] samples in each cell over the call */
+    csf_flow_event *events;   /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the crossings found, stored or not */
+    int64_t n_outside;        /* written: the existing samples outside the grid (0 without a grid) */
+    int64_t first_sample;     /* written: the index of the first sample covered */
+} csf_flow_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
+ * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every (sample, road user) cell
+ * against the layout, then the walk along k of every (road user, line or area) - with one hipMemsetAsync of the counters, one
+ * transfer and one wait (the launch counter below grows by 2 per call that covers a sample of a road user).  Refused without side
+ * effects (CSF_E_ARG / CSF_E_STATE, with a message, launch counter unchanged): a NULL out or layout; n_lines or n_areas outside
+ * 0 ... 64, or a count above 0 with a NULL array; a line or area with a non-finite coordinate or dd == 0; half_width NaN, negative
+ * or +inf; with a grid, h not finite or <= 0, x0 or y0 not finite; nx or ny negative, exactly one of them 0, or nx*ny > 2^20;
+ * first_sample < 0 (the current state has no interval) or no ring; n_samples < 0 or above 65535; samples that are not in the
+ * ring; more than 2^31 (sample, road user) cells; a negative event capacity, or a capacity with a NULL buffer; a rank of a sharded
+ * run or a member of a loopback group; an engine that holds a calibration data set.  While csf_profile_enable is on, the first
+ * launch is timed as kernel 0. */
+int csf_flow(csf_engine *e, int64_t first_sample, int64_t n_samples, const csf_flow_layout *layout, csf_flow_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, all members in the same two launches, with one
+ * transfer and one wait; outs [count].  A member without a ring is skipped: its n_events becomes 0 and its first_sample -2.  A
+ * recording member with fewer than n_last samples in its ring makes the call a refusal before anything is written, and so do
+ * members x grid cells above 2^24. */
+int csf_batch_flow(csf_engine *const *engines, int32_t count, int64_t n_last, const csf_flow_layout *layout, csf_flow_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_flow_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
