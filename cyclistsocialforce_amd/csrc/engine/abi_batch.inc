@@ -603,11 +603,9 @@ int csf_batch_get_record(csf_engine *const *engines, int32_t count, int64_t n_la
         if (!o.s && !o.F) continue;
         if (!e->d.hist) return fail(e, CSF_E_STATE, "member %d: history is not enabled (csf_record)", (int)i);
         if (o.F && !e->d.hist_F) return fail(e, CSF_E_STATE, "member %d: forces are not recorded (csf_record with CSF_REC_FORCE)", (int)i);
-        const int64_t have = e->d.tick / e->d.hist_stride;
-        if (n_last > have || n_last > e->d.hist_cap)
-            return fail(e, CSF_E_ARG, "member %d: the last %lld samples are not in the ring (have %lld, capacity %d)", (int)i, (long long)n_last,
-                        (long long)have, e->d.hist_cap);
-        b.asks.push_back(RecAsk{e, have - n_last, n_last, o.s, o.F});
+        int64_t first = 0;
+        if (int rrc = record_last(e, i, n_last, &first)) return rrc;
+        b.asks.push_back(RecAsk{e, first, n_last, o.s, o.F});
     }
     HIPCHK(e0, hipSetDevice(e0->device));
     // (the members share one stream, and a member stepped in turn has joined its second stream back into it: stream order is enough)

@@ -200,12 +200,10 @@ int csf_batch_encounters(csf_engine *const *engines, int32_t count, int64_t n_la
         if ((rc = encounter_args_ok(e, "csf_batch_encounters", radius, &outs[i]))) return rc;
         if ((rc = encounter_engine_ok(e, "csf_batch_encounters"))) return rc;
         if (!e->d.hist) continue;
-        const int64_t have = e->d.tick / e->d.hist_stride;
-        if (n_last > have || n_last > e->d.hist_cap)
-            return fail(e, CSF_E_ARG, "member %d: the last %lld samples are not in the ring (have %lld, capacity %d)", (int)i, (long long)n_last,
-                        (long long)have, e->d.hist_cap);
+        int64_t first = 0;
+        if (int rrc = record_last(e, i, n_last, &first)) return rrc;
         if (e->d.n * n_last > ENC_MAX_CELLS) return fail(e, CSF_E_ARG, "member %d: more than 2^31 (sample, road user) cells in one call", (int)i);
-        asks.push_back(EncAsk{e, have - n_last, n_last, &outs[i]});
+        asks.push_back(EncAsk{e, first, n_last, &outs[i]});
     }
     for (int32_t i = 0; i < count; i++) outs[i].n_events = 0, outs[i].first_sample = -2;
     for (const EncAsk &a : asks) a.out->first_sample = a.first;

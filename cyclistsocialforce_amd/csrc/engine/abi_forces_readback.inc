@@ -276,6 +276,7 @@ static int rings_setup(csf_engine *e, int32_t stride, int32_t capacity, bool for
     e->d.hist_stride = stride;
     e->d.hist_cap = capacity;
     e->rec_tick_dev = -1;
+    e->rec_k0 = e->d.tick / stride;                       // sample k is the state after tick (k + 1) * stride: k >= tick / stride are this ring's
     e->rec_fast = fast;
     return CSF_OK;
 }
@@ -303,12 +304,24 @@ struct RecAsk {
     double *s_out, *F_out;
 };
 
-// samples [first, first + count) are in the ring: the message of csf_get_history
+// samples [first, first + count) are in the ring, and written since it was started or the roster last changed (rec_k0): the
+// message of csf_get_history
 static int record_range(csf_engine *e, int64_t first, int64_t count) {
     const int64_t have = e->d.tick / e->d.hist_stride;
-    if (first < 0 || count < 0 || first + count > have || have - first > e->d.hist_cap)
-        return fail(e, CSF_E_ARG, "samples [%lld, %lld) are not in the ring (have %lld, capacity %d)",
-                    (long long)first, (long long)(first + count), (long long)have, e->d.hist_cap);
+    if (first < 0 || count < 0 || first + count > have || have - first > e->d.hist_cap || first < e->rec_k0)
+        return fail(e, CSF_E_ARG, "samples [%lld, %lld) are not in the ring (have %lld, capacity %d, first readable sample %lld)",
+                    (long long)first, (long long)(first + count), (long long)have, e->d.hist_cap,
+                    (long long)std::max(e->rec_k0, have - e->d.hist_cap));
+    return CSF_OK;
+}
+
+// the same for the last n_last samples of member i of a batch (n_last >= 0): *first is the first of them
+static int record_last(csf_engine *e, int32_t i, int64_t n_last, int64_t *first) {
+    const int64_t have = e->d.tick / e->d.hist_stride;
+    if (n_last > have || n_last > e->d.hist_cap || n_last > have - e->rec_k0)
+        return fail(e, CSF_E_ARG, "member %d: the last %lld samples are not in the ring (have %lld, capacity %d, first readable sample %lld)",
+                    (int)i, (long long)n_last, (long long)have, e->d.hist_cap, (long long)std::max(e->rec_k0, have - e->d.hist_cap));
+    *first = have - n_last;
     return CSF_OK;
 }
 

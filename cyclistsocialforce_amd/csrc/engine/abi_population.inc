@@ -28,6 +28,14 @@ static void side_state(csf_engine *e, size_t a, const csf_params &p) {
     e->h_ppsi[a] = s[2 * cap];                                   // dynamics.py:828, 987-993
 }
 
+// The roster has changed (arrivals, departures - a replacement is both): a state ring begins a new stretch here, its samples of
+// before are gone (include/csf.h, "the lifetime of a recording").  The ring is laid out [sample][road user] with the population
+// of the tick that wrote the sample, and row i of it is road user i of THAT roster: neither survives the change.  With a ring
+// the change goes through the host mirror (can_patch_device), which leaves slots == population order again (compact_host).
+static void roster_changed(csf_engine *e) {
+    if (e->d.hist != nullptr) e->rec_k0 = e->d.tick / e->d.hist_stride;
+}
+
 // q_off / q_rows: NULL (every new road user gets the one-row queue of vehicle.py:183-185) or the destination queues the arrivals
 // START with, CSR - what csf_add_agents followed by csf_set_dest_queue(reset = 1) on the new road users leaves, in one pass
 // over them (csf_replace_agents)
@@ -181,6 +189,7 @@ static int add_agents_impl(csf_engine *e, int64_t n, const double *s0, const dou
             set_chunks(e);
         }
     }
+    roster_changed(e);
     return CSF_OK;
 }
 
@@ -285,6 +294,7 @@ int csf_remove_agents(csf_engine *e, int64_t n, const int32_t *idx) try {
         compact_host(e);
         set_shard(e);
     }
+    roster_changed(e);
     return CSF_OK;
 } catch (...) { return csf_caught(e); }
 

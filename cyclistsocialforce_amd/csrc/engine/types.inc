@@ -447,6 +447,9 @@ struct csf_engine {
     DevBuf<double> hist_F;
     DevBuf<int64_t> rec_tick;
     int64_t rec_tick_dev = -1;
+    // the ring's first valid sample (include/csf.h, "The lifetime of a recording"): tick / stride when the ring was started
+    // (rings_setup) or the roster last changed (roster_changed); every reader refuses what lies before it (record_range)
+    int64_t rec_k0 = 0;
     bool rec_fast = false;
     RecGather rgather;
     DevBuf<int64_t> qbeg;

@@ -534,7 +534,7 @@ class Engine:
     # what intersection.py keeps on an engine.  Declared on the class, not assigned in __init__: two more entries in every instance's
     # dictionary cost the batched calls over 256 engines 8 % of their host time (profiles/mirror_refactor_ab.txt)
     _together = None      # the engines of the batch this one was last joined to (_batch_of)
-    _dense_for = None     # the population size its dense record ring was made for (SocialForceIntersection._dense_engine)
+    _dense_ring = False   # it has the record ring of the dense routes (SocialForceIntersection._dense_engine)
 
     def __init__(self, params, capacity, device=0):
         self._lib = _ffi.load()

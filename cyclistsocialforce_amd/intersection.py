@@ -681,7 +681,9 @@ class SocialForceIntersection:
         """Engine.encounters on the population's own engine: closest approach and time to collision of every road user, each a disc
         of `radius`, over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together
         record every tick in a ring of DENSE_CHUNK samples) or - first=None - now.  The result carries the partners also as the road
-        users' ids: `ids`, d_with_id, ttc_with_id [count, n] and run_d_with_id, run_ttc_with_id [n] (None where there is no partner)."""
+        users' ids: `ids`, d_with_id, ttc_with_id [count, n] and run_d_with_id, run_ttc_with_id [n] (None where there is no partner).  A window that begins before the
+        ring was started, or before road users last came, went or were swapped, is refused: the recording begins a new stretch then
+        (csf.h, "the lifetime of a recording")."""
         if not self.vehicles:
             raise RuntimeError("the intersection is empty")
         return _encounter_ids(self._push_mutations().encounters(first, count, radius, d_event, ttc_event, per_sample), self.get_road_user_ids())
@@ -690,7 +692,9 @@ class SocialForceIntersection:
         """Engine.post_encroachment on the population's own engine: who crossed whose path, where, and how long after the other had
         passed, over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record
         every tick in a ring of DENSE_CHUNK samples).  The result carries the partners also as the road users' ids: `ids`,
-        seg_with_id [count - 1, n], run_with_id [n] (None where there is no partner) and event_i_id, event_j_id beside the events."""
+        seg_with_id [count - 1, n], run_with_id [n] (None where there is no partner) and event_i_id, event_j_id beside the events.  A window that begins before the
+        ring was started, or before road users last came, went or were swapped, is refused: the recording begins a new stretch then
+        (csf.h, "the lifetime of a recording")."""
         if not self.vehicles:
             raise RuntimeError("the intersection is empty")
         return _pet_ids(self._push_mutations().post_encroachment(first, count, pet_event, per_segment), self.get_road_user_ids())
@@ -701,7 +705,9 @@ class SocialForceIntersection:
         dense=True) and advance_together record every tick in a ring of DENSE_CHUNK samples).  The result carries the partners also
         as the road users' ids: `ids`, gap_with_id [count - 1, n], made_with_id, by_with_id [count - 2, n], run_gap_with_id,
         run_thw_with_id, run_made_with_id, run_by_with_id [n] (None where there is no partner) and event_i_id, event_j_id beside the
-        events."""
+        events.  A window that begins before the
+        ring was started, or before road users last came, went or were swapped, is refused: the recording begins a new stretch then
+        (csf.h, "the lifetime of a recording")."""
         if not self.vehicles:
             raise RuntimeError("the intersection is empty")
         return _passing_ids(self._push_mutations().passing(first, count, band, lat_max, lat_event, per_station), self.get_road_user_ids())
@@ -710,7 +716,9 @@ class SocialForceIntersection:
         """Engine.flow on the population's own engine: the crossings of counting lines, the occupancy of areas and of a grid, over
         samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record every tick in
         a ring of DENSE_CHUNK samples).  The result carries the road users' ids: `ids` - row i of cross_n, first_* and in_* is
-        ids[i] - and event_i_id beside the events."""
+        ids[i] - and event_i_id beside the events.  A window that begins before the
+        ring was started, or before road users last came, went or were swapped, is refused: the recording begins a new stretch then
+        (csf.h, "the lifetime of a recording")."""
         if not self.vehicles:
             raise RuntimeError("the intersection is empty")
         return _flow_ids(self._push_mutations().flow(first, count, lines, areas, grid, events), self.get_road_user_ids())
@@ -839,9 +847,12 @@ class SocialForceIntersection:
         e = self._push_mutations()
         if self._mirror.ns != e.ns:
             return None
-        if e._dense_for != e.n:                                       # (a new engine, or road users came or went: a ring of this layout)
+        # A new engine gets its ring; the ring is sized for the engine's capacity and stays when road users come, go or are swapped
+        # one for one: the engine itself begins a new stretch of the recording then (csf.h, "the lifetime of a recording"), and the
+        # samples of the old roster are refused - to this intersection's encounters / post_encroachment / passing / flow as well.
+        if not e._dense_ring:
             e.record(stride=1, capacity=DENSE_CHUNK, forces=True)
-            e._dense_for = e.n
+            e._dense_ring = True
         return e
 
     def step_n(self, n_ticks, pull=True, dense=False):

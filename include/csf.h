@@ -240,6 +240,20 @@ int csf_get_history(csf_engine *e, int64_t first_sample, int64_t n_samples, doub
  * force (Fx, Fy as csf_get_forces returns them after the sampled tick) - written by whatever kernel ticks the engine, the
  * one-wave kernel and the batched launch of csf_step_batch included (see csf_small_ticks).  The state ring is always kept.
  * Calling either again starts a new ring; the later call decides which path the engine takes.
+ *
+ * The lifetime of a recording.  A state ring has a FIRST VALID SAMPLE k0, and every reader of the ring refuses what lies before it:
+ *  - csf_record / csf_enable_history called at tick T with stride s set k0 = T / s (integer division): sample k is the state after
+ *    tick (k + 1) * s, so k >= T / s are exactly the samples written into this ring.  A ring begun at tick 0 has k0 = 0.
+ *  - Every call that changes the roster sets k0 = tick / stride at that moment: csf_add_agents with n > 0, csf_remove_agents with
+ *    n > 0, csf_replace_agents with anybody leaving or arriving (also one for one: row i of a sample is road user i of the roster
+ *    of ITS tick).  A change of the roster starts a new stretch of the recording; the samples of the stretch before are gone - the
+ *    ring is not re-allocated, and sample numbers go on counting from tick 0.  A refused population call changes nothing, k0 included.
+ *  - csf_push_state, parameter, parameter-set, queue, script and desired-speed calls leave k0 alone.
+ *  - Readers are csf_get_history, csf_get_record, csf_batch_get_record, csf_encounters (with a window), csf_post_encroachment,
+ *    csf_passing, csf_flow and their csf_batch_* forms.  first_sample < k0 - for the batch forms n_last > tick / stride - k0 of a
+ *    member - is CSF_E_ARG, "samples [a, b) are not in the ring (have h, capacity c, first readable sample r)", like a sample the
+ *    ring has overwritten or not yet taken (r = max(k0, h - c)), and before anything is written, launched or counted.
+ *
  * csf_get_record: samples [first_sample, first_sample + n_samples) as s_out [n_samples, n_agents, n_states] and F_out
  * [n_samples, n_agents, 2]; one of the two may be NULL.  One gather launch and one wait, whatever n_samples is. */
 #define CSF_REC_STATE 1u
@@ -331,7 +345,7 @@ typedef struct csf_encounter_out {
     int64_t first_sample;     /* written: the index of the first sample covered (-1: the current state) */
 } csf_encounter_out;
 /* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
- * them; with first_sample == -1 and n_samples == 1 the current state (no ring needed, population order).  Pending uploads are
+ * them (not before the ring's first valid sample: "the lifetime of a recording" at csf_record); with first_sample == -1 and n_samples == 1 the current state (no ring needed, population order).  Pending uploads are
  * brought in, both streams are waited for as the read-backs do, and the engine is left exactly as it was.  Two launches whatever
  * the sizes are - every pair of every sample, then the window's minima over the per-sample arrays - with one transfer and one wait
  * (the launch counter below grows by 2 per call that covers anything).  An empty population or n_samples == 0
@@ -441,7 +455,7 @@ typedef struct csf_pet_out {
     int64_t first_sample;     /* written: the index of the first sample covered */
 } csf_pet_out;
 /* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
- * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * them (not before the ring's first valid sample: "the lifetime of a recording" at csf_record), on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
  * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every pair of segments, then
  * the per-segment and per-road-user minima - with one hipMemsetAsync of the event counters, one transfer and one wait (the launch
  * counter below grows by 2 per call that covers a segment).  Refused without side effects (CSF_E_ARG / CSF_E_STATE, with a
@@ -581,7 +595,7 @@ typedef struct csf_passing_out {
     int64_t first_sample;     /* written: the index of the first sample covered */
 } csf_passing_out;
 /* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
- * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * them (not before the ring's first valid sample: "the lifetime of a recording" at csf_record), on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
  * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every ordered pair at every
  * station, then the window pass - with one hipMemsetAsync of the event counters, one transfer and one wait (the launch counter
  * below grows by 2 per call that covers a station).  Refused without side effects (CSF_E_ARG / CSF_E_STATE, with a message,
@@ -703,7 +717,7 @@ typedef struct csf_flow_out {
     int64_t first_sample;     /* written: the index of the first sample covered */
 } csf_flow_out;
 /* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_get_record has
- * them, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
+ * them (not before the ring's first valid sample: "the lifetime of a recording" at csf_record), on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for as the
  * read-backs do, and the engine is left exactly as it was.  TWO launches whatever the sizes are - every (sample, road user) cell
  * against the layout, then the walk along k of every (road user, line or area) - with one hipMemsetAsync of the counters, one
  * transfer and one wait (the launch counter below grows by 2 per call that covers a sample of a road user).  Refused without side
