@@ -54,6 +54,7 @@ SYMBOLS = (
     "csf_post_encroachment", "csf_batch_post_encroachment", "csf_pet_launches",
     "csf_passing", "csf_batch_passing", "csf_passing_launches",
     "csf_flow", "csf_batch_flow", "csf_flow_launches",
+    "csf_clearance", "csf_batch_clearance", "csf_clearance_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -169,6 +170,31 @@ class FlowOut(C.Structure):
                 ("occupancy", C.c_void_p), ("in_samples", C.c_void_p), ("in_first", C.c_void_p), ("in_last", C.c_void_p), ("in_dist", C.c_void_p),
                 ("grid_count", C.c_void_p),
                 ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("n_outside", C.c_int64), ("first_sample", C.c_int64)]
+
+
+class ClearanceRoad(C.Structure):
+    """csf_clearance_road of include/csf.h: the polylines every member of a call is measured against"""
+
+    _fields_ = [("offsets", C.c_void_p), ("xy", C.c_void_p), ("n_edges", C.c_int32)]
+
+
+class ClearanceEvent(C.Structure):
+    """csf_clearance_event of include/csf.h: road user i crosses segment (edge, seg) at station k"""
+
+    _fields_ = [("i", C.c_int32), ("k", C.c_int32), ("edge", C.c_int32), ("seg", C.c_int32), ("dir", C.c_int32),
+                ("t", C.c_double), ("u", C.c_double)]
+
+
+class ClearanceOut(C.Structure):
+    """csf_clearance_out of include/csf.h: where the edge distances and crossings of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("d", C.c_void_p), ("edge", C.c_void_p), ("seg", C.c_void_p), ("t", C.c_void_p),
+                ("left", C.c_void_p), ("right", C.c_void_p), ("left_edge", C.c_void_p), ("right_edge", C.c_void_p), ("cross", C.c_void_p),
+                ("d_min", C.c_void_p), ("d_min_k", C.c_void_p), ("d_min_edge", C.c_void_p), ("d_min_seg", C.c_void_p),
+                ("left_min", C.c_void_p), ("left_min_k", C.c_void_p), ("right_min", C.c_void_p), ("right_min_k", C.c_void_p),
+                ("near_samples", C.c_void_p), ("near_first", C.c_void_p), ("near_last", C.c_void_p), ("cross_n", C.c_void_p),
+                ("near_count", C.c_void_p), ("cross_count", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -297,6 +323,10 @@ def load():
         L.csf_flow.argtypes = [vp, i64, i64, C.POINTER(FlowLayout), C.POINTER(FlowOut)]
         L.csf_batch_flow.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(FlowLayout), C.POINTER(FlowOut)]
         L.csf_flow_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_clearance"):              # (likewise)
+        L.csf_clearance.argtypes = [vp, i64, i64, C.POINTER(ClearanceRoad), C.c_double, C.POINTER(ClearanceOut)]
+        L.csf_batch_clearance.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(ClearanceRoad), C.c_double, C.POINTER(ClearanceOut)]
+        L.csf_clearance_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -615,6 +615,51 @@ constexpr int FLOW_LAUNCHES = 2;
 // the grid of the first launch as launch_encounters has it (n > ENC_SMALL: tiles of 256 road users x samples; the packed members take
 // the plane x * y), z = members; then the walk over max_n * (L + R) lanes of every member: FLOW_LAUNCHES launches whatever the members are.
 void launch_flow(const FlowArgs &a, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_clearance.hip (csf_clearance, csf_batch_clearance): distances to, sides of and crossings of the segments of a road given to the
+// call, one (sample, road user) cell per lane against one chunk of CLR_CHUNK segments per workgroup.  One descriptor per engine in
+// mapped host memory, as EncDesc; the road (ClrArgs) is shared by the members and lies in device memory: double seg [S][4] = ax, ay,
+// bx, by, then int32 edge_of [S], first_g [n_edges].  With c = count and cells = c * n, cell (k, i) at k * n + i, a member's results are
+//   the counts the second launch ADDS to, cleared together with the counters in front of the first (acc_off): int32 near_count [c],
+//     cross_count [c]   (the last row of cross_count stays 0: the host copies c - 1)
+//   what the third launch writes (out_off): double d_min, left_min, right_min [n]; int32 d_min_k, d_min_edge, d_min_seg, left_min_k,
+//     right_min_k, near_samples, near_first, near_last, cross_n [n]
+//   what the second launch writes (cell_off; behind every member's blocks and events, so that a call that asks for no per-cell array
+//     transfers none): double d, t, left, right [cells]; int32 edge, seg, left_edge, right_edge, cross [cells]   (stations: the
+//     rows k < c - 1)
+// and behind what is transferred, one ClrPart per (chunk, cell) (part_off): what the first launch leaves for the second.
+constexpr int CLR_CHUNK = 512;                // segments per workgroup: 40 B each in LDS
+constexpr int64_t CLR_MAX_SEGS = 1ll << 20;
+struct ClrDesc {
+    const double *s;         // the state ring [cap][n][ns]
+    int64_t acc_off, out_off, cell_off, part_off;   // bytes into the packed output, multiples of 32
+    int64_t ev_off, ev_cap;  // the member's events, csf_clearance_event [ev_cap]
+    int32_t n, ns, cap;      // road users, states of each, samples the ring holds
+    int32_t first, count;    // ring slot of the first sample asked for, samples asked for (>= 1)
+    int32_t pad;
+};
+struct ClrArgs {
+    const ClrDesc *desc;           // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] crossings found, cleared in front of the first launch
+    const double *seg;             // [S][4]
+    const int32_t *edge_of;        // [S] the polyline of segment g
+    const int32_t *first_g;        // [n_edges] the first segment of a polyline
+    double d_event;
+    int32_t S, chunks;             // segments, and chunks of CLR_CHUNK of them
+    int32_t members;
+};
+// what one chunk of segments gave one cell: the nearest of all, on the left and on the right (d2 +inf, g -1: none), the crossings
+struct ClrPart {
+    double d2, l2, r2;
+    int32_t g, lg, rg, cross;
+};
+inline size_t clr_acc_bytes(size_t c) { return (8 * c + 31) & ~(size_t)31; }
+inline size_t clr_block_bytes(size_t n) { return (60 * n + 31) & ~(size_t)31; }
+inline size_t clr_cell_bytes(size_t cells) { return (52 * cells + 31) & ~(size_t)31; }
+constexpr int CLEARANCE_LAUNCHES = 3;
+// the grid of the first launch: x, y as launch_flow's, z = members x chunks (member = z / chunks); then a lane per cell of every member
+// (max_cells the largest member's), then a lane per road user: CLEARANCE_LAUNCHES launches whatever the members are.
+void launch_clearance(const ClrArgs &a, dim3 grid, int members, int64_t max_cells, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

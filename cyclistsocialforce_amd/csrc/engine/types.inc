@@ -324,6 +324,16 @@ struct FlowScratch {
     HostBuf<unsigned char, false> host;
 };
 
+// ... and csf_clearance / csf_batch_clearance: the same three, and the road as the kernels read it - staged in pinned memory, copied
+// to the device once per call
+struct ClrScratch {
+    HostBuf<ClrDesc> desc;
+    HostBuf<unsigned char, false> road_host;
+    DevBuf<unsigned char> road;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -556,6 +566,8 @@ struct csf_engine {
     PassScratch passing;
     int64_t flow_launches = 0;       // launches of csf_flow / csf_batch_flow: two per call (csf_flow_launches)
     FlowScratch flow;
+    int64_t clearance_launches = 0;  // launches of csf_clearance / csf_batch_clearance: three per call (csf_clearance_launches)
+    ClrScratch clearance;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

@@ -526,6 +526,180 @@ class _FlowPack:
         return r
 
 
+CLEARANCE_EVENT_DTYPE = np.dtype({"names": ["i", "k", "edge", "seg", "dir", "t", "u"],
+                                  "formats": [np.int32] * 5 + [np.float64] * 2,
+                                  "offsets": [0, 4, 8, 12, 16, 24, 32], "itemsize": 40})        # csf_clearance_event
+
+CLEARANCE_CHUNK = 512             # segments a workgroup runs against (csf_dev.h: CLR_CHUNK)
+CLEARANCE_LAUNCHES = 3
+CLEARANCE_MAX_SEGMENTS = 1 << 20
+
+
+class Clearance:
+    """What Engine.clearance returns for one engine (csf.h: csf_clearance): `first` the index of the first sample covered; per
+    sample and road user [c, n] d the distance to the nearest segment of the road (NaN where the road user has no finite position),
+    edge and seg which one (-1), t the clamped place along it; per station [c - 1, n] left and right the nearest segment on either
+    side of the direction of travel (+inf: none, NaN: no station) with left_edge, right_edge, and cross the segments crossed; per road
+    user [n] d_min with d_min_k, d_min_edge, d_min_seg, left_min, left_min_k, right_min, right_min_k, near_samples, near_first,
+    near_last (the samples with d < d_event) and cross_n; per sample near_count [c] and cross_count [c - 1]; events
+    (CLEARANCE_EVENT_DTYPE, every crossing, sorted by i, k, edge, seg; None when they were not asked for) with n_events their number.
+    The per-sample and per-station arrays are None with per_sample=False.  offsets [n_edges + 1] are the road's; t of an event is in
+    samples from `first`, `period` the seconds per sample of the recording (None when it is not known)."""
+
+    CELL = (("d", np.float64), ("edge", np.int32), ("seg", np.int32), ("t", np.float64))
+    STATION = (("left", np.float64), ("right", np.float64), ("left_edge", np.int32), ("right_edge", np.int32), ("cross", np.int32))
+    USER = (("d_min", np.float64), ("d_min_k", np.int32), ("d_min_edge", np.int32), ("d_min_seg", np.int32),
+            ("left_min", np.float64), ("left_min_k", np.int32), ("right_min", np.float64), ("right_min_k", np.int32),
+            ("near_samples", np.int32), ("near_first", np.int32), ("near_last", np.int32), ("cross_n", np.int32))
+    SAMPLE = (("near_count", np.int32), ("cross_count", np.int32))
+    ARRAYS = CELL + STATION + USER + SAMPLE
+
+    __slots__ = (("first", "period", "events", "n_events", "offsets", "d_event") + tuple(f for f, _ in ARRAYS)
+                 + ("ids", "event_i_id"))                     # (SocialForceIntersection.clearance fills these)
+
+    def _stations(self, who):
+        if self.left is None:
+            raise ValueError(f"{who}: the per-station arrays were not asked for (per_sample=True)")
+
+    def lateral_position(self):
+        """where across the path every station lies, [c - 1, n]: right / (left + right) - 0 on the right edge, 1 on the left one -,
+        NaN where either side is not finite"""
+        self._stations("lateral_position")
+        both = np.isfinite(self.left) & np.isfinite(self.right)
+        out = np.full(self.left.shape, np.nan)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[both] = (self.right / (self.left + self.right))[both]
+        return out
+
+    def width(self):
+        """left + right per station [c - 1, n]: the width of the path as the road user met it"""
+        self._stations("width")
+        return self.left + self.right
+
+    def off_road(self):
+        """[c - 1, n] bool: an odd number of crossings has been made by the end of station k - the road user that started on the
+        road is off it"""
+        self._stations("off_road")
+        return (np.cumsum(self.cross, axis=0, dtype=np.int64) & 1).astype(bool)
+
+    def nearest_edge_share(self):
+        """the share of the existing samples whose nearest segment belongs to each edge [n_edges]; NaN without a sample"""
+        if self.edge is None:
+            raise ValueError("nearest_edge_share: the per-sample arrays were not asked for (per_sample=True)")
+        n_edges = len(self.offsets) - 1
+        e = self.edge[self.edge >= 0]
+        return np.bincount(e, minlength=n_edges)[:n_edges] / e.size if e.size else np.full(n_edges, np.nan)
+
+
+def _clearance_road(who, road):
+    """the checks of the road of Engine.clearance / batch_clearance, before any device call: (offsets [n_edges + 1] int64,
+    xy [V, 2] float64) from a list of road elements (objects with edges(), whose edges have vertices) or an (offsets, xy) pair"""
+    if road is None:
+        raise ValueError(f"{who}: a road is needed (a list of road elements or an (offsets, xy) pair)")
+    if isinstance(road, (tuple, list)) and len(road) == 2 and not hasattr(road[0], "edges"):
+        off, xy = np.asarray(road[0]), np.array(road[1], dtype=np.float64, ndmin=2)
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError(f"{who}: offsets must be whole numbers [n_edges + 1]")
+        off = off.astype(np.int64)
+    else:
+        if hasattr(road, "edges"):
+            road = [road]
+        try:
+            edges = [e for el in road for e in el.edges()]
+            verts = [np.array(e.vertices, dtype=np.float64, ndmin=2) for e in edges]
+        except (TypeError, AttributeError):
+            raise ValueError(f"{who}: road must be a list of road elements or an (offsets, xy) pair") from None
+        if any(v.ndim != 2 or v.shape[1] != 2 for v in verts):
+            raise ValueError(f"{who}: the vertices of an edge must be [k, 2]")
+        off = np.r_[0, np.cumsum([v.shape[0] for v in verts])].astype(np.int64)
+        xy = np.vstack(verts) if verts else np.zeros((0, 2))
+    if off.size < 2:
+        raise ValueError(f"{who}: the road has no edge")
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError(f"{who}: xy must be [V, 2] (got shape {xy.shape})")
+    if off[0] != 0 or off[-1] != xy.shape[0] or (np.diff(off) < 2).any():
+        raise ValueError(f"{who}: offsets must start at 0, end at the {xy.shape[0]} vertices, and give every edge at least 2 (got {off.tolist()[:8]} ...)")
+    if xy.shape[0] - (off.size - 1) > CLEARANCE_MAX_SEGMENTS:
+        raise ValueError(f"{who}: at most 2^20 segments")
+    if not np.isfinite(xy).all():
+        raise ValueError(f"{who}: the road has a non-finite coordinate")
+    inner = np.ones(xy.shape[0] - 1, bool)
+    inner[off[1:-1] - 1] = False                                 # (the step from one polyline's end to the next one's start is no segment)
+    dx, dy = np.diff(xy[:, 0])[inner], np.diff(xy[:, 1])[inner]
+    with np.errstate(over="ignore"):
+        dd = dx * dx + dy * dy
+    if not ((dd > 0) & np.isfinite(dd)).all():
+        raise ValueError(f"{who}: segment {int(np.argmin((dd > 0) & np.isfinite(dd)))} of the road has no length or a non-finite one")
+    return np.ascontiguousarray(off), np.ascontiguousarray(xy)
+
+
+def _clearance_d_event(who, d_event):
+    if isinstance(d_event, bool) or not _is_number(d_event) or not np.isfinite(d_event) or d_event < 0:
+        raise ValueError(f"{who}: d_event must be finite and >= 0 (got {d_event!r})")
+    return float(d_event)
+
+
+def _clearance_capacity_guess(stations):
+    """room for events in the first call: a road user that keeps to its path crosses no edge"""
+    return min(max(64, stations // 8), 1 << 16)
+
+
+class _ClearancePack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, the
+    csf_clearance_out records that point into them (shapes: (n, count) per member) and the csf_clearance_road they share"""
+
+    def __init__(self, shapes, off, xy, caps, per_sample):
+        m = len(shapes)
+        self.shapes, self.off, self.xy, self.per_sample = shapes, off, xy, per_sample
+        n = np.array([n for n, _ in shapes], dtype=np.int64)
+        c = np.array([c for _, c in shapes], dtype=np.int64)
+        caps = np.asarray(caps, dtype=np.int64)
+        rows = {}
+        rows.update({f: c * n for f, _ in Clearance.CELL})
+        rows.update({f: np.maximum(c - 1, 0) * n for f, _ in Clearance.STATION})
+        rows.update({f: n for f, _ in Clearance.USER})
+        rows.update(near_count=c, cross_count=np.maximum(c - 1, 0))
+        wide = {f for f, _ in Clearance.CELL + Clearance.STATION}
+        self.start = {f: np.r_[0, np.cumsum(v)] for f, v in rows.items()}
+        self.e0 = np.r_[0, np.cumsum(caps)]
+        self.arrays = {f: (np.empty(int(self.start[f][-1]), dt) if per_sample or f not in wide else None) for f, dt in Clearance.ARRAYS}
+        self.events = np.empty(int(self.e0[-1]), CLEARANCE_EVENT_DTYPE)
+        # the records as one int64 table (every member of csf_clearance_out is 8 bytes), filled column by column in header order
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.ClearanceOut) // 8), dtype=np.int64)
+        for col, (f, _) in enumerate(Clearance.ARRAYS):
+            a = self.arrays[f]
+            if a is not None:
+                tab[:, col] = a.ctypes.data + a.itemsize * self.start[f][:-1]
+        col = len(Clearance.ARRAYS)
+        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + CLEARANCE_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
+        tab[:, col + 1] = caps
+        self.outs = (_ffi.ClearanceOut * m).from_buffer(tab)
+        self._read = None                                        # what the call wrote into the records, read once (result)
+        y = self.road = _ffi.ClearanceRoad()
+        y.offsets, y.xy, y.n_edges = off.ctypes.data, xy.ctypes.data, off.size - 1
+
+    def result(self, i, want_events, period, d_event):
+        """member i's Clearance, after the call"""
+        if self._read is None:
+            col = len(Clearance.ARRAYS)
+            self._read = (self._tab[:, col + 2:col + 4].tolist(), {f: v.tolist() for f, v in self.start.items()}, self.e0.tolist())
+        (n_events, first), start, e0 = self._read[0][i], self._read[1], self._read[2]
+        n, c = self.shapes[i]
+        r = Clearance()
+        for f in Clearance.__slots__:
+            setattr(r, f, None)
+        r.first, r.n_events, r.period, r.offsets, r.d_event = first, n_events, period, self.off, d_event
+        shapes = [(Clearance.CELL, (c, n)), (Clearance.STATION, (max(c - 1, 0), n)), (Clearance.USER, (n,)),
+                  (Clearance.SAMPLE[:1], (c,)), (Clearance.SAMPLE[1:], (max(c - 1, 0),))]
+        for kind, shape in shapes:
+            for f, _ in kind:
+                if self.arrays[f] is not None:
+                    at = start[f][i]
+                    setattr(r, f, self.arrays[f][at:at + math.prod(shape)].reshape(shape))
+        r.events = self.events[e0[i]:e0[i] + n_events] if want_events else None
+        return r
+
+
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
 
@@ -1404,6 +1578,51 @@ class Engine:
         """launches of flow / batch_flow so far: two per call (csf.h: csf_flow_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_flow_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- road clearance: edge distances and edge crossings of a recording (include/csf.h: csf_clearance) ----------------------
+    def clearance(self, first, count, road, d_event=0.0, events=False, per_sample=True):
+        """how close to the edges of a road every road user came, where across the width of the path it rode and which edges it
+        crossed (csf.h: csf_clearance), over samples [first, first + count) of the recording (record / enable_history).  road is a
+        list of RoadEdge / RoadSegment / RoadSegmentCollection objects or an (offsets, xy) pair as set_road takes it - given to
+        the call in fp64, not taken from the engine's own road.  d_event: a sample with d below it counts as near.  Returns a
+        Clearance; with events=True it carries every crossing, sorted by (i, k, edge, seg).  Events are fetched with a guessed
+        capacity; when more were found, one second call with the exact capacity."""
+        first, count = _flow_args("clearance", first, count)
+        off, xy = _clearance_road("clearance", road)
+        d_event = _clearance_d_event("clearance", d_event)
+        n = self.n
+        cap = _clearance_capacity_guess(max(count - 1, 0) * n) if events else 0
+        while True:
+            pack = _ClearancePack([(n, count)], off, xy, [cap], bool(per_sample))
+            self._ck(self._lib.csf_clearance(self._h, first, count, C.byref(pack.road), d_event, pack.outs))
+            if not events or pack.outs[0].n_events <= cap:
+                return pack.result(0, bool(events), self._period(), d_event)
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_clearance(engines, n_last, road, d_event=0.0, events=False, per_sample=True):
+        """clearance() over the last n_last samples of every recording member of a batch (the engines in join order) at one road,
+        all members in the same three launches with one transfer and one wait (csf.h: csf_batch_clearance): a list with a
+        Clearance per member, None for members that do not record"""
+        n_last = _flow_args("batch_clearance", 0, n_last)[1]
+        off, xy = _clearance_road("batch_clearance", road)
+        d_event = _clearance_d_event("batch_clearance", d_event)
+        engines, arr = Engine._batch_array(engines, "batch_clearance")
+        shapes = [(e.n, n_last) for e in engines]
+        caps = [_clearance_capacity_guess(max(n_last - 1, 0) * n) if events else 0 for n, _ in shapes]
+        while True:
+            pack = _ClearancePack(shapes, off, xy, caps, bool(per_sample))
+            Engine._group_call("csf_batch_clearance", engines, arr, n_last, C.byref(pack.road), d_event, pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if not events or all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, bool(events), e._period(), d_event) for i, e in enumerate(engines)]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def clearance_launches(self):
+        """launches of clearance / batch_clearance so far: three per call (csf.h: csf_clearance_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_clearance_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

@@ -723,6 +723,21 @@ class SocialForceIntersection:
             raise RuntimeError("the intersection is empty")
         return _flow_ids(self._push_mutations().flow(first, count, lines, areas, grid, events), self.get_road_user_ids())
 
+    def clearance(self, first, count, road=None, d_event=0.0, events=False, per_sample=True):
+        """Engine.clearance on the population's own engine: the distances to, the sides of and the crossings of the edges of a road,
+        over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record every
+        tick in a ring of DENSE_CHUNK samples).  road=None: the intersection's own road_elements (a ValueError if it has none).  The
+        result carries the road users' ids: `ids` - row i of the per-road-user arrays is ids[i] - and event_i_id beside the events.
+        A window that begins before the ring was started, or before road users last came, went or were swapped, is refused: the
+        recording begins a new stretch then (csf.h, "the lifetime of a recording")."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        if road is None:
+            if not self.road_elements:
+                raise ValueError("clearance: the intersection has no road_elements, and no road was given")
+            road = list(self.road_elements)
+        return _flow_ids(self._push_mutations().clearance(first, count, road, d_event, events, per_sample), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -1074,6 +1089,21 @@ def flow_together(intersections, n_last, lines=None, areas=None, grid=None, even
         engines = [ins._push_mutations() for ins in live]
         _batch_of(engines)
         for ins, res in zip(live, Engine.batch_flow(engines, n_last, lines, areas, grid, events)):
+            got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
+def clearance_together(intersections, n_last, road, d_event=0.0, events=False, per_sample=True):
+    """SocialForceIntersection.clearance over the last n_last recorded samples of many intersections - those advance_together has
+    just ticked - at one road, with all their engines in the same three launches, one transfer and one wait
+    (Engine.batch_clearance): a list with a result per intersection, None for an empty one and for one whose engine does not record."""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, Engine.batch_clearance(engines, n_last, road, d_event, events, per_sample)):
             got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
     return [got.get(id(ins)) for ins in intersections]
 

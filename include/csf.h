@@ -737,6 +737,124 @@ int csf_batch_flow(csf_engine *const *engines, int32_t count, int64_t n_last, co
 /* launches of the two calls above so far (a batch counts on its first member) */
 int csf_flow_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- road clearance: edge distances and edge crossings of a recording ---------------------------- */
+
+/* How close to the road's edges every road user came, where across the width of the path it rode, and whether it left the road -
+ * formed on the device from the state ring that csf_record / csf_enable_history keep.
+ *
+ * A call covers samples [first_sample, first_sample + c) of the state ring, numbered k = 0 ... c-1 inside the call. P_i(k) = (x, y)
+ * are the fp64 bits of rows 0 and 1 of the ring. The general rules are those of the flow section above: every term is at most two
+ * products and one sum or difference in fp64, formed as written and never contracted; sqrt and / are the correctly rounded ones;
+ * comparisons are made as written, so a NaN fails them.
+ *
+ * The road is given to the call (csf_clearance_road); it is NOT the engine's packed fp32 vertices. It is n_edges polylines as
+ * csf_set_road_vertices takes them: offsets [n_edges + 1] into xy [V][2], every polyline with at least 2 vertices. Its
+ * S = V - n_edges segments A -> B (consecutive vertices of a polyline) are numbered g = 0 ... S-1 in the order of the polylines; a
+ * result names a segment as (edge, seg), seg counted within the polyline. For a segment dx = bx - ax, dy = by - ay,
+ * dd = dx*dx + dy*dy.
+ *
+ * Samples and stations.
+ * - Cell (k, i) exists iff both coordinates of P_i(k) are finite.
+ * - Station (k, i), for k <= c-2, exists iff cells k and k+1 exist. At a station w = P(k+1) - P(k): the direction of travel.
+ *
+ * Distance, per cell P = (px, py) and segment.
+ * - rx = px - ax, ry = py - ay.
+ * - gg = rx*dx + ry*dy.
+ * - t = gg / dd, then t = t > 0 ? t : 0.0, then t = t > 1 ? 1.0 : t.
+ * - qx = ax + t*dx, qy = ay + t*dy.
+ * - ex = qx - px, ey = qy - py.
+ * - d2 = ex*ex + ey*ey.
+ * The nearest segment is the lowest g with the smallest d2 (a strict < from +inf). d = sqrt(d2); t is that segment's.
+ *
+ * Left and right, per station and segment, with the ex, ey of sample k.
+ * - z = wx*ey - wy*ex.
+ * - A segment with z > 0 is on the left of the direction of travel, one with z < 0 on its right; z == 0 (straight ahead, behind,
+ *   or not moving) is neither.
+ * - left / right are the square roots of the smallest d2 among each, the lowest g on ties; +inf where there is none.
+ *
+ * Crossing, per station and segment: the flow section's test with the segment as the line.
+ * - s(P) = dx*(P.y - ay) - dy*(P.x - ax); s0 = s(P(k)), s1 = s(P(k+1)).
+ * - A sign change is (s0 > 0) != (s1 > 0).
+ * - tt = s0 / (s0 - s1).
+ * - The crossing point is C = (P(k).x + tt*wx, P(k).y + tt*wy).
+ * - u = ((C.x - ax)*dx + (C.y - ay)*dy) / dd.
+ * - A crossing is a sign change with u >= 0 && u <= 1. dir is +1 if s0 > 0 and -1 otherwise.
+ * - A path through a vertex shared by two consecutive segments may count on both (u == 1 of one, u == 0 of the next).
+ *
+ * Per road user.
+ * - d_min is the smallest d over k (strict <, so the lowest k on ties) with its k, edge and seg; +inf and -1 if never present.
+ * - left_min and right_min likewise over the stations; +inf and -1 where no station has a segment on that side.
+ * - near_samples counts the samples with d < d_event, near_first and near_last are the first and last of them (-1: none).
+ *   d_event == 0 finds none.
+ * - cross_n is the number of crossings.
+ *
+ * Events.
+ * - An event is a crossing, stored by the lane that found it as {int32 i, k, edge, seg, dir; double t, u;} with t = k + tt: 40 bytes.
+ * - n_events counts every crossing found, stored or not, and is always written.
+ * - When n_events <= event_capacity the events are sorted by (i, k, edge, seg). Otherwise an unspecified subset is stored.
+ *
+ * Small calls. c == 0 or no road users succeeds without a launch and writes "nothing found"; c == 1 has samples and no station. */
+typedef struct csf_clearance_road {
+    const int64_t *offsets;   /* [n_edges + 1] first vertex of every polyline, and V */
+    const double *xy;         /* [V, 2] */
+    int32_t n_edges;
+} csf_clearance_road;
+typedef struct csf_clearance_event {
+    int32_t i, k, edge, seg, dir;
+    double t, u;
+} csf_clearance_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned).  n = the road users, c = n_samples.
+ * event_capacity = 0 with events NULL counts the events without storing any. */
+typedef struct csf_clearance_out {
+    double *d;                /* [c, n] distance to the nearest segment; NaN without a cell */
+    int32_t *edge;            /* [c, n] ... its polyline; -1 */
+    int32_t *seg;             /* [c, n] ... its place in the polyline; -1 */
+    double *t;                /* [c, n] ... the clamped place along it; NaN */
+    double *left;             /* [c-1, n] nearest on the left; +inf: none; NaN: no station */
+    double *right;            /* [c-1, n] nearest on the right */
+    int32_t *left_edge;       /* [c-1, n] -1 */
+    int32_t *right_edge;      /* [c-1, n] -1 */
+    int32_t *cross;           /* [c-1, n] segments crossed at the station */
+    double *d_min;            /* [n] */
+    int32_t *d_min_k;         /* [n] */
+    int32_t *d_min_edge;      /* [n] */
+    int32_t *d_min_seg;       /* [n] */
+    double *left_min;         /* [n] */
+    int32_t *left_min_k;      /* [n] */
+    double *right_min;        /* [n] */
+    int32_t *right_min_k;     /* [n] */
+    int32_t *near_samples;    /* [n] */
+    int32_t *near_first;      /* [n] */
+    int32_t *near_last;       /* [n] */
+    int32_t *cross_n;         /* [n] */
+    int32_t *near_count;      /* [c] road users with d < d_event at sample k */
+    int32_t *cross_count;     /* [c-1] crossings at the stations k */
+    csf_clearance_event *events;   /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the crossings found, stored or not */
+    int64_t first_sample;     /* written: the index of the first sample covered */
+} csf_clearance_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as for the flow call
+ * above, on rings of csf_record and csf_enable_history alike.  Pending uploads are brought in, both streams are waited for, and the
+ * engine is left exactly as it was.  THREE launches whatever the sizes are - every cell against every chunk of 512 segments (the
+ * grid's third extent), the chunks put together in the order of their index with the same strict < (the result does not depend on
+ * the chunk size), then the walk along k of every road user - with one upload of the road, one hipMemsetAsync of the counters, one
+ * transfer and one wait (the launch counter below grows by 3 per call that covers a sample of a road user).  Refused without side
+ * effects (CSF_E_ARG / CSF_E_STATE, with a message, launch counter unchanged): a NULL out or road; n_edges < 1, NULL offsets or xy;
+ * offsets that do not start at 0 or a polyline with fewer than 2 vertices (which covers offsets that are not monotone); more than
+ * 2^20 segments; a non-finite coordinate; a segment with dd == 0 or non-finite dd (the message names edge and segment); d_event
+ * negative or not finite; everything the flow call refuses for its window and engine; (sample, road user) cells x segments above
+ * 2^40; a negative event capacity, or a capacity with a NULL buffer.  While csf_profile_enable is on, the first launch is timed as
+ * kernel 0. */
+int csf_clearance(csf_engine *e, int64_t first_sample, int64_t n_samples, const csf_clearance_road *road, double d_event, csf_clearance_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, at ONE road shared by all members, in the same
+ * three launches, with one transfer and one wait; outs [count].  A member without a ring is skipped: its n_events becomes 0 and
+ * its first_sample -2.  A recording member with fewer than n_last samples in its ring makes the call a refusal before anything is
+ * written, and so do members x chunks of segments above 65535 and the cells of all members x segments above 2^40. */
+int csf_batch_clearance(csf_engine *const *engines, int32_t count, int64_t n_last, const csf_clearance_road *road, double d_event, csf_clearance_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_clearance_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
