@@ -55,6 +55,7 @@ SYMBOLS = (
     "csf_passing", "csf_batch_passing", "csf_passing_launches",
     "csf_flow", "csf_batch_flow", "csf_flow_launches",
     "csf_clearance", "csf_batch_clearance", "csf_clearance_launches",
+    "csf_body_encounters", "csf_batch_body_encounters", "csf_body_encounter_launches",
 )
 ABI_VERSION = 9
 REC_STATE, REC_FORCE = 1, 2
@@ -197,6 +198,21 @@ class ClearanceOut(C.Structure):
                 ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
 
 
+class BodyEvent(C.Structure):
+    """csf_body_event of include/csf.h: a (sample, i < j) whose outlines are under a threshold"""
+
+    _fields_ = [("sample", C.c_int64), ("i", C.c_int32), ("j", C.c_int32), ("gap", C.c_double), ("ttc", C.c_double)]
+
+
+class BodyOut(C.Structure):
+    """csf_body_out of include/csf.h: where the body encounters of one engine go (any pointer may be NULL)"""
+
+    _fields_ = [("gap_min", C.c_void_p), ("gap_with", C.c_void_p), ("ttc_min", C.c_void_p), ("ttc_with", C.c_void_p),
+                ("run_gap_min", C.c_void_p), ("run_gap_with", C.c_void_p), ("run_gap_sample", C.c_void_p),
+                ("run_ttc_min", C.c_void_p), ("run_ttc_with", C.c_void_p), ("run_ttc_sample", C.c_void_p), ("overlap_n", C.c_void_p),
+                ("events", C.c_void_p), ("event_capacity", C.c_int64), ("n_events", C.c_int64), ("first_sample", C.c_int64)]
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -327,6 +343,11 @@ def load():
         L.csf_clearance.argtypes = [vp, i64, i64, C.POINTER(ClearanceRoad), C.c_double, C.POINTER(ClearanceOut)]
         L.csf_batch_clearance.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(ClearanceRoad), C.c_double, C.POINTER(ClearanceOut)]
         L.csf_clearance_launches.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(L, "csf_body_encounters"):        # (likewise)
+        f64 = C.c_double
+        L.csf_body_encounters.argtypes = [vp, i64, i64, vp, f64, f64, C.POINTER(BodyOut)]
+        L.csf_batch_body_encounters.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(vp), f64, f64, C.POINTER(BodyOut)]
+        L.csf_body_encounter_launches.argtypes = [vp, C.POINTER(i64)]
     L.csf_step_get_tick.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.csf_mid_ticks.argtypes = [vp, C.POINTER(i64)]
     L.csf_holes_taken.argtypes = [vp, C.POINTER(i64)]

@@ -660,6 +660,26 @@ constexpr int CLEARANCE_LAUNCHES = 3;
 // the grid of the first launch: x, y as launch_flow's, z = members x chunks (member = z / chunks); then a lane per cell of every member
 // (max_cells the largest member's), then a lane per road user: CLEARANCE_LAUNCHES launches whatever the members are.
 void launch_clearance(const ClrArgs &a, dim3 grid, int members, int64_t max_cells, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+// csf_body.hip (csf_body_encounters, csf_batch_body_encounters): free gap and time to contact between the road users' outlines, every
+// road user an oriented rectangle of its own extents.  The mapping, the grid and the descriptor are csf_encounter.hip's (`m`: where the
+// samples are, the source split, where the results go); `ext` are the member's extents on the device, double [n][3] = (front, rear,
+// half width) in population order.  A member's block of the packed output, in this order (cells = count * n):
+//   double gap_min [cells], ttc_min [cells], run_gap_min [n], run_ttc_min [n]; int64 run_gap_sample [n], run_ttc_sample [n], overlap_n [n];
+//   int32 gap_with [cells], ttc_with [cells], run_gap_with [n], run_ttc_with [n]
+// and with m.split > 1 the chunks' minima at m.part_off exactly as EncDesc has them.
+struct BodyDesc {
+    EncDesc m;
+    const double *ext;
+};
+struct BodyArgs {
+    const BodyDesc *desc;          // [members]
+    unsigned char *out;            // the packed output (device memory)
+    unsigned long long *count;     // [members] events found, cleared in front of the launch
+    double gap_event, ttc_event;   // thresholds (gap_event < 0: off; ttc_event <= 0: off)
+};
+inline size_t body_block_bytes(size_t cells, size_t n) { return (24 * cells + 48 * n + 31) & ~(size_t)31; }
+// the grid as launch_encounters has it; then the window pass over max_n riders of every member.  Two launches whatever the members are.
+void launch_body(const BodyArgs &a, bool events, dim3 grid, int members, int max_n, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 
 // The kernel's arguments (csf_dev.h: Dev, 1.3 KB with the parameter set) live in the kernarg segment, which the host has just
 // written: the first scalar load from each of its 64-byte lines goes to memory (~0.4 us), and the compiler loads a member where

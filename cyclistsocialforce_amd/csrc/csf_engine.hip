@@ -22,6 +22,7 @@
 #include "engine/abi_passing.inc"   // C ABI: gaps to the leader, overtakings and meetings of a recording (csf_passing.hip)
 #include "engine/abi_flow.inc"      // C ABI: crossings of counting lines, occupancy of areas and of a grid (csf_flow.hip)
 #include "engine/abi_clearance.inc" // C ABI: distances to, sides of and crossings of the edges of a road (csf_clearance.hip)
+#include "engine/abi_body.inc"   // C ABI: gaps and time to contact between the road users' outlines (csf_body.hip; after abi_encounter.inc, whose checks it shares)
 #include "engine/abi_calib.inc"   // C ABI: calibration - a resident data set, many parameter sets evaluated per launch (csf_calib.hip)
 #include "engine/abi_scene.inc"   // C ABI: calibration on closed-loop scenes - workgroup = (parameter set, scene), the error summed in the launch (csf_scene.hip)
 #include "engine/abi_measurement.inc"   // C ABI: far-field radius, time stamps, counters

@@ -334,6 +334,16 @@ struct ClrScratch {
     HostBuf<unsigned char, false> host;
 };
 
+// ... and csf_body_encounters / csf_batch_body_encounters: the same three, and the extents as the kernels read them - staged in pinned
+// memory, copied to the device once per call
+struct BodyScratch {
+    HostBuf<BodyDesc> desc;
+    HostBuf<double, false> ext_host;
+    DevBuf<double> ext;
+    DevBuf<unsigned char> dev;
+    HostBuf<unsigned char, false> host;
+};
+
 struct csf_engine {
     Dev d{};
     Knobs knobs;
@@ -568,6 +578,8 @@ struct csf_engine {
     FlowScratch flow;
     int64_t clearance_launches = 0;  // launches of csf_clearance / csf_batch_clearance: three per call (csf_clearance_launches)
     ClrScratch clearance;
+    int64_t body_launches = 0;       // launches of csf_body_encounters / csf_batch_body_encounters: two per call (csf_body_encounter_launches)
+    BodyScratch body;
     bool small_classes = false;      // csf_small_classes: several parameter sets / an UncontrolledVehicle population take the one-wave tick too
     bool mid_road = false;           // csf_mid_road: the one-launch tick sums the road term of a small road itself (tick.inc: mid_road_ok)
     int64_t mid_road_ticks = 0;      // ... and the ticks on which it did (csf_mid_road_ticks; mid_ticks / batch_mid_ticks count them too)

@@ -700,6 +700,132 @@ class _ClearancePack:
         return r
 
 
+BODY_EVENT_DTYPE = np.dtype([("sample", np.int64), ("i", np.int32), ("j", np.int32), ("gap", np.float64), ("ttc", np.float64)])   # csf_body_event
+
+
+class BodyEncounters:
+    """What Engine.body_encounters returns for one engine: `first` the index of the first sample covered (-1: the current state),
+    `extents` [n, 3] as the call had them, per sample gap_min, gap_with, ttc_min, ttc_with [count, n] (None when per_sample was off),
+    over the window run_gap_min, run_gap_with, run_gap_sample, run_ttc_min, run_ttc_with, run_ttc_sample and overlap_n [n], and
+    events (BODY_EVENT_DTYPE, sorted by sample, i, j; None when no threshold was given) with n_events their number."""
+
+    __slots__ = ("first", "extents", "gap_min", "gap_with", "ttc_min", "ttc_with", "run_gap_min", "run_gap_with", "run_gap_sample",
+                 "run_ttc_min", "run_ttc_with", "run_ttc_sample", "overlap_n", "events", "n_events",
+                 "ids", "gap_with_id", "ttc_with_id", "run_gap_with_id", "run_ttc_with_id")   # (SocialForceIntersection.body_encounters fills these)
+
+    def collisions(self):
+        """the events whose outlines overlap (gap 0), or None when the call fetched no events"""
+        return None if self.events is None else self.events[self.events["gap"] == 0.0]
+
+
+def _body_events_wanted(gap_event, ttc_event):
+    return (gap_event is not None and gap_event >= 0) or (ttc_event is not None and ttc_event > 0)
+
+
+def _body_thresholds(who, gap_event, ttc_event):
+    """(gap_event, ttc_event) as the C ABI takes them: None is a threshold that is off"""
+    for name, v in (("gap_event", gap_event), ("ttc_event", ttc_event)):
+        if v is not None and (not _is_number(v) or not np.isfinite(v)):
+            raise ValueError(f"{who}: {name} must be None or a finite number (got {v!r})")
+    return (-1.0 if gap_event is None else float(gap_event)), (0.0 if ttc_event is None else float(ttc_event))
+
+
+def _body_extents_shape(who, extents, n, member=None):
+    """extents - one (front, rear, half_width) for everybody or an [n, 3] array - as a contiguous fp64 [n, 3]; values unchecked"""
+    where = who if member is None else f"{who}: member {member}"
+    if extents is None:
+        raise ValueError(f"{where}: extents are needed: one (front, rear, half_width) or an [n, 3] array")
+    try:
+        a = np.asarray(extents, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: extents must be numbers: one (front, rear, half_width) or an [n, 3] array") from None
+    if a.shape == (3,):
+        a = np.broadcast_to(a, (n, 3))
+    if a.shape != (n, 3):
+        raise ValueError(f"{where}: extents must be one (front, rear, half_width) or an [{n}, 3] array (got shape {a.shape})")
+    return np.ascontiguousarray(a)
+
+
+def _body_extents_bad(a):
+    """the first row of extents [k, 3] that the C ABI would refuse, or -1"""
+    bad = ~np.isfinite(a).all(axis=1) | (a[:, 0] < 0) | (a[:, 1] < 0) | ~(a[:, 0] + a[:, 1] > 0) | ~(a[:, 2] > 0)
+    return int(np.flatnonzero(bad)[0]) if bad.any() else -1
+
+
+_BODY_EXTENTS_RULE = "finite, front >= 0, rear >= 0, front + rear > 0, half_width > 0"
+
+
+def _body_extents(who, extents, n):
+    a = _body_extents_shape(who, extents, n)
+    u = _body_extents_bad(a)
+    if u >= 0:
+        raise ValueError(f"{who}: road user {u} has the extents {tuple(float(v) for v in a[u])}: {_BODY_EXTENTS_RULE}")
+    return a
+
+
+def _batch_body_extents(who, extents, ns):
+    """one (front, rear, half_width) for every member, or a list with a triple or an [n, 3] array per member: an [n, 3] array each
+    (the values of all members are checked in one pass: a batch has a thousand members)"""
+    if extents is None:
+        raise ValueError(f"{who}: extents are needed: one (front, rear, half_width) or a list with one entry per member")
+    single = hasattr(extents, "__len__") and len(extents) == 3 and all(_is_number(v) for v in extents)
+    if not single and (isinstance(extents, np.ndarray) or not hasattr(extents, "__len__") or len(extents) != len(ns)):
+        raise ValueError(f"{who}: extents must be one (front, rear, half_width) or a list with one entry for each of the {len(ns)} members")
+    out = [_body_extents_shape(who, extents if single else extents[i], n, i) for i, n in enumerate(ns)]
+    row = _body_extents_bad(np.concatenate(out)) if out else -1
+    if row >= 0:
+        i = int(np.searchsorted(np.cumsum(ns), row, side="right"))
+        u = row - int(np.sum(ns[:i]))
+        raise ValueError(f"{who}: member {i}: road user {u} has the extents {tuple(float(v) for v in out[i][u])}: {_BODY_EXTENTS_RULE}")
+    return out
+
+
+class _BodyPack:
+    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
+    csf_body_out records that point into them (as _EncounterPack)"""
+
+    def __init__(self, shapes, per_sample, caps):
+        m = len(shapes)
+        cells = np.array([n * c for n, c in shapes], dtype=np.int64)
+        ns = np.array([n for n, _ in shapes], dtype=np.int64)
+        self.shapes, self.caps = shapes, caps
+        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (cells, ns, np.asarray(caps, dtype=np.int64)))
+        nc, nn = (int(self.c0[-1]), int(self.n0[-1]))
+        self.per = None
+        if per_sample:
+            self.per = (np.empty(nc), np.empty(nc, np.int32), np.empty(nc), np.empty(nc, np.int32))
+        # (an empty window leaves them as they are: a minimum of +inf with nobody, at no sample, and no overlap)
+        self.run = (np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64),
+                    np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64), np.zeros(nn, np.int64))
+        self.events = np.empty(int(self.e0[-1]), BODY_EVENT_DTYPE)
+        tab = self._tab = np.zeros((m, C.sizeof(_ffi.BodyOut) // 8), dtype=np.int64)   # (every member of csf_body_out is 8 bytes)
+        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
+        if self.per is not None:
+            for col, (a, size) in enumerate(zip(self.per, (8, 4, 8, 4))):
+                tab[:, col] = a.ctypes.data + size * c0
+        for col, (a, size) in zip(range(4, 11), zip(self.run, (8, 4, 8, 8, 4, 8, 8))):
+            tab[:, col] = a.ctypes.data + size * n0
+        caps = np.asarray(caps, dtype=np.int64)
+        tab[:, 11] = np.where(caps > 0, self.events.ctypes.data + BODY_EVENT_DTYPE.itemsize * e0, 0)
+        tab[:, 12] = caps
+        self.outs = (_ffi.BodyOut * m).from_buffer(tab)
+
+    def result(self, i, extents, want_events):
+        n, count = self.shapes[i]
+        o = self.outs[i]
+        r = BodyEncounters()
+        r.first, r.extents, r.n_events = int(o.first_sample), extents, int(o.n_events)
+        r.ids = r.gap_with_id = r.ttc_with_id = r.run_gap_with_id = r.run_ttc_with_id = None
+        c, u = int(self.c0[i]), int(self.n0[i])
+        if self.per is None:
+            r.gap_min = r.gap_with = r.ttc_min = r.ttc_with = None
+        else:
+            r.gap_min, r.gap_with, r.ttc_min, r.ttc_with = (a[c:c + n * count].reshape(count, n) for a in self.per)
+        (r.run_gap_min, r.run_gap_with, r.run_gap_sample, r.run_ttc_min, r.run_ttc_with, r.run_ttc_sample, r.overlap_n) = (a[u:u + n] for a in self.run)
+        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        return r
+
+
 class Engine:
     """One population of one vehicle class on one MI355X (csf_engine)."""
 
@@ -1623,6 +1749,56 @@ class Engine:
         """launches of clearance / batch_clearance so far: three per call (csf.h: csf_clearance_launches)"""
         n = C.c_int64(0)
         self._ck(self._lib.csf_clearance_launches(self._h, C.byref(n)))
+        return n.value
+
+    # -- body encounters: gaps and time to contact between the outlines (include/csf.h: csf_body_encounters) ------------------
+    def body_encounters(self, first=None, count=None, extents=None, gap_event=None, ttc_event=None, per_sample=True):
+        """the free gap and the time to contact between the road users' outlines (csf.h: csf_body_encounters; every road user an
+        oriented rectangle, `extents` one (front, rear, half_width) for everybody or an [n, 3] array): samples [first, first +
+        count) of the recording (record / enable_history), or - first=None - the current state.  Returns a BodyEncounters:
+        gap_min, gap_with, ttc_min, ttc_with [count, n] (None without per_sample), run_* [n] over the window with the sample of
+        each, overlap_n [n], and - with gap_event (>= 0; 0 lists exactly the collisions) or ttc_event - events, the pairs (sample,
+        i < j) with gap <= gap_event or ttc < ttc_event, sorted.  Events are fetched with a guessed capacity; when more were
+        found, one second call with the exact capacity."""
+        first, count = _encounter_args("body_encounters", first, count, 0.0, None, None)
+        ge, te = _body_thresholds("body_encounters", gap_event, ttc_event)
+        n = self.n
+        ext = _body_extents("body_encounters", extents, n)
+        want = _body_events_wanted(gap_event, ttc_event)
+        cap = min(max(64, count * n), 1 << 16) if want else 0
+        while True:
+            pack = _BodyPack([(n, count)], per_sample, [cap])
+            self._ck(self._lib.csf_body_encounters(self._h, first, count, _ptr(ext), ge, te, pack.outs))
+            if pack.outs[0].n_events <= cap:
+                return pack.result(0, ext, want)
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def batch_body_encounters(engines, n_last, extents=None, gap_event=None, ttc_event=None, per_sample=True):
+        """body_encounters() over the last n_last samples of every recording member of a batch (the engines in join order), all
+        members in the same two launches with one transfer and one wait (csf.h: csf_batch_body_encounters).  extents: one (front,
+        rear, half_width) for everybody, or a list with a triple or an [n, 3] array per member.  A list with a BodyEncounters per
+        member, None for members that do not record"""
+        n_last = _encounter_args("batch_body_encounters", 0, n_last, 0.0, None, None)[1]
+        ge, te = _body_thresholds("batch_body_encounters", gap_event, ttc_event)
+        engines, arr = Engine._batch_array(engines, "batch_body_encounters")
+        shapes = [(e.n, n_last) for e in engines]
+        exts = _batch_body_extents("batch_body_encounters", extents, [n for n, _ in shapes])
+        ptrs = (C.c_void_p * len(engines))(*[a.ctypes.data for a in exts])
+        want = _body_events_wanted(gap_event, ttc_event)
+        caps = [min(max(64, n_last * n), 1 << 16) if want else 0 for n, _ in shapes]
+        while True:
+            pack = _BodyPack(shapes, per_sample, caps)
+            Engine._group_call("csf_batch_body_encounters", engines, arr, n_last, ptrs, ge, te, pack.outs)
+            found = [int(o.n_events) for o in pack.outs]
+            if all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else pack.result(i, exts[i], want) for i in range(len(engines))]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def body_encounter_launches(self):
+        """launches of body_encounters / batch_body_encounters so far: two per call (csf.h: csf_body_encounter_launches)"""
+        n = C.c_int64(0)
+        self._ck(self._lib.csf_body_encounter_launches(self._h, C.byref(n)))
         return n.value
 
     def untracked(self):

@@ -28,7 +28,7 @@ from .engine import Engine
 from .mirror import PopulationMirror
 from .parameters import RoadElementParameters
 from .utils import angleSFMtoSUMO, generateSplinePrototype
-from .vehicle import QUEUE_APPENDED, QUEUE_EDITED, QUEUE_RANK, QUEUE_REPLACED, Vehicle
+from .vehicle import QUEUE_APPENDED, QUEUE_EDITED, QUEUE_RANK, QUEUE_REPLACED, Vehicle, vehicle_extents
 
 PRIORITY_RULES = {"unregulated": _ffi.UNREGULATED, "p2r": _ffi.P2R}
 DENSE_CHUNK = 512        # ticks per call of the dense paths = samples of the engines' rings (the bytes per member)
@@ -738,6 +738,19 @@ class SocialForceIntersection:
             road = list(self.road_elements)
         return _flow_ids(self._push_mutations().clearance(first, count, road, d_event, events, per_sample), self.get_road_user_ids())
 
+    def body_encounters(self, first=None, count=None, extents=None, gap_event=None, ttc_event=None, per_sample=True):
+        """Engine.body_encounters on the population's own engine: the free gap and the time to contact between the road users'
+        outlines over samples [first, first + count) of the engine's recording (step_n(..., dense=True) and advance_together record
+        every tick in a ring of DENSE_CHUNK samples) or - first=None - now.  extents=None: every vehicle's own (vehicle_extents);
+        else one (front, rear, half_width) for everybody or an [n, 3] array.  The result carries the partners also as the road
+        users' ids: `ids`, gap_with_id, ttc_with_id [count, n] and run_gap_with_id, run_ttc_with_id [n] (None where there is no
+        partner)."""
+        if not self.vehicles:
+            raise RuntimeError("the intersection is empty")
+        if extents is None:
+            extents = np.array([vehicle_extents(v) for v in self.vehicles], dtype=np.float64)
+        return _body_ids(self._push_mutations().body_encounters(first, count, extents, gap_event, ttc_event, per_sample), self.get_road_user_ids())
+
     # ------------------------------------------------------------------ riders whose poles are drawn anew as their speed changes
     def _stochastic_riders(self):
         """the BalancingRiderBicycles with `stochastic_control_behavior=True` (parameters.py:1380-1396); cached until the population changes"""
@@ -1105,6 +1118,41 @@ def clearance_together(intersections, n_last, road, d_event=0.0, events=False, p
         _batch_of(engines)
         for ins, res in zip(live, Engine.batch_clearance(engines, n_last, road, d_event, events, per_sample)):
             got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
+def _body_ids(res, ids):
+    """a BodyEncounters with the partners' places in the population order also given as the road users' ids"""
+    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
+    res.ids = list(ids)
+    res.gap_with_id = None if res.gap_with is None else names[res.gap_with]
+    res.ttc_with_id = None if res.ttc_with is None else names[res.ttc_with]
+    res.run_gap_with_id, res.run_ttc_with_id = names[res.run_gap_with], names[res.run_ttc_with]
+    return res
+
+
+def body_encounters_together(intersections, n_last, extents=None, gap_event=None, ttc_event=None, per_sample=True):
+    """SocialForceIntersection.body_encounters over the last n_last recorded samples of many intersections - those advance_together
+    has just ticked - with all their engines in the same two launches, one transfer and one wait (Engine.batch_body_encounters).
+    extents=None: every vehicle's own; else one (front, rear, half_width) for everybody or a list with an entry per intersection
+    (None entries of empty ones are skipped).  A list with a result per intersection, None for an empty one and for one whose
+    engine does not record."""
+    intersections = list(intersections)
+    live = [(k, ins) for k, ins in enumerate(intersections) if ins.vehicles]
+    got = {}
+    if live:
+        if extents is None:
+            ext = [np.array([vehicle_extents(v) for v in ins.vehicles], dtype=np.float64) for _, ins in live]
+        elif hasattr(extents, "__len__") and len(extents) == 3 and all(np.isscalar(v) for v in extents):
+            ext = extents
+        else:
+            if len(extents) != len(intersections):
+                raise ValueError(f"body_encounters_together: {len(extents)} extents for {len(intersections)} intersections")
+            ext = [extents[k] for k, _ in live]
+        engines = [ins._push_mutations() for _, ins in live]
+        _batch_of(engines)
+        for (_, ins), res in zip(live, Engine.batch_body_encounters(engines, n_last, ext, gap_event, ttc_event, per_sample)):
+            got[id(ins)] = None if res is None else _body_ids(res, ins.get_road_user_ids())
     return [got.get(id(ins)) for ins in intersections]
 
 

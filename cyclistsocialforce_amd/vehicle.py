@@ -26,6 +26,24 @@ QUEUE_APPENDED, QUEUE_REPLACED, QUEUE_EDITED = 0, 1, 2
 QUEUE_RANK = {QUEUE_APPENDED: 0, QUEUE_EDITED: 1, QUEUE_REPLACED: 2}
 
 
+WHEEL_RADIUS = 0.325          # the wheels the reference draws are 0.65 m across (vizualisation.py:732-735)
+HANDLEBAR_HALF_WIDTH = 0.225  # ... and the handlebar 0.45 m wide (vizualisation.py:706)
+
+
+def vehicle_extents(vehicle):
+    """(front, rear, half_width) of a vehicle's outline in metres from the point (x, y) of its state, as Engine.body_encounters
+    takes them - the outline the reference draws: params with `length` and `width` (CarParameters, vizualisation.py:523-529) are a
+    box around the point; params with `l_1` and `l_2` are a bicycle whose frame runs from -l_1 to l_2 (vizualisation.py:768-771)
+    with a wheel at either end and the handlebar as its width."""
+    p = getattr(vehicle, "params", None)
+    if hasattr(p, "length") and hasattr(p, "width"):
+        return (0.5 * float(p.length), 0.5 * float(p.length), 0.5 * float(p.width))
+    if hasattr(p, "l_1") and hasattr(p, "l_2"):
+        return (float(p.l_2) + WHEEL_RADIUS, float(p.l_1) + WHEEL_RADIUS, HANDLEBAR_HALF_WIDTH)
+    raise ValueError(f"vehicle_extents: a {type(vehicle).__name__} has neither length and width nor l_1 and l_2 in its params "
+                     f"({type(p).__name__}): give its extents to the call")
+
+
 class Vehicle:
     """Parent class — vehicle.py:49-917.  Abstract here: a concrete class selects the rider model."""
 

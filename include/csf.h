@@ -855,6 +855,120 @@ int csf_batch_clearance(csf_engine *const *engines, int32_t count, int64_t n_las
 /* launches of the two calls above so far (a batch counts on its first member) */
 int csf_clearance_launches(const csf_engine *e, int64_t *n_launches);
 
+/* ---- body encounters: gaps and time to contact between vehicle outlines of a recording ----------- */
+
+/* csf_encounters makes every road user a disc of one radius.  Here every road user is an oriented rectangle of its own size, and
+ * the call reports the free gap between the outlines and the constant-velocity time to contact of the outlines (DESIGN.md
+ * section 4.17).
+ *
+ * Outline.
+ * - Road user i has ext[i] = (front, rear, half_width). These are the metres from the point (x, y) of its state to the front end
+ *   and to the rear end along the heading, and the half width. A call carries one triple per road user.
+ * - Take x, y, psi, v from rows 0 - 3 of the state, as csf_encounters does.
+ * - cs = cos psi, sn = sin psi.
+ * - L = 0.5 (front + rear), W = half_width, o = 0.5 (front - rear).
+ * - The centre is m = (x + o cs, y + o sn). The velocity is u = (v cs, v sn).
+ *
+ * Pair (i, j), j != i.
+ * - w = m_j - m_i, c = u_j - u_i.
+ * - cr = cs_i cs_j + sn_i sn_j, sr = cs_i sn_j - sn_i cs_j.
+ * - Four axes in the order h_i, n_i, h_j, n_j, with h = (cs, sn) and n = (-sn, cs). For each axis:
+ *   - the place s_k = w . e_k;
+ *   - the rate g_k = c . e_k;
+ *   - the reach r_k.
+ * - The products are written wx*cs + wy*sn and wy*cs - wx*sn.
+ * - The reaches are:
+ *   - r_0 = L_i + (L_j |cr| + W_j |sr|)
+ *   - r_1 = W_i + (L_j |sr| + W_j |cr|)
+ *   - r_2 = L_j + (L_i |cr| + W_i |sr|)
+ *   - r_3 = W_j + (L_i |sr| + W_i |cr|)
+ * - sep = max_k (|s_k| - r_k). The bodies overlap iff sep <= 0. Touching counts as overlap.
+ *
+ * Gap.
+ * - The gap is 0 if the bodies overlap.
+ * - Otherwise it is sqrt(min d2) over eight corner-to-box distances.
+ * - For the four corners (a, b) in {+1, -1}^2 of j in the frame of i:
+ *   - X = s_0 + (a L_j cr - b W_j sr)
+ *   - Y = s_1 + (a L_j sr + b W_j cr)
+ *   - dx = max(|X| - L_i, 0), dy = max(|Y| - W_i, 0)
+ *   - d2 = dx dx + dy dy
+ * - Do the same for the corners of i in the frame of j, with -s_2, -s_3, cr, -sr and the roles of i and j exchanged.
+ * - Take the minimum with a strict < from +inf.
+ *
+ * Time to contact. Headings and velocities are held constant.
+ * - ttc = 0 if the bodies overlap.
+ * - Otherwise go per axis:
+ *   - If g_k == 0 and |s_k| > r_k, the pair never meets.
+ *   - If g_k == 0 otherwise, the axis constrains nothing.
+ *   - If g_k != 0, ta = (-r_k - s_k) / g_k, tb = (r_k - s_k) / g_k, enter_k = min(ta, tb), leave_k = max(ta, tb).
+ * - T_in = max_k enter_k, T_out = min_k leave_k.
+ * - ttc = +inf if the pair never meets, or T_in > T_out, or T_in < 0. Otherwise ttc = T_in.
+ *
+ * Arithmetic.
+ * - No term is contracted to an FMA.
+ * - / and sqrt are the correctly rounded ones.
+ * - There is no fp32 and no fast math.
+ * - gap_ij and ttc_ij are bitwise symmetric in (i, j).
+ *
+ * Per (sample, i).
+ * - gap_min, gap_with, ttc_min, ttc_with.
+ * - The lowest j wins on ties.
+ * - The partner is -1 where the minimum is +inf.
+ * - A road user with a non-finite x, y, psi, v is neither receiver nor partner. Its own row is NaN / -1.
+ * - A population of one gives +inf / -1.
+ *
+ * Per road user over the window.
+ * - run_gap_min, run_ttc_min, each with its partner and its absolute sample. The earliest sample wins on ties.
+ * - overlap_n: the number of samples in which its gap_min is 0.
+ * - The current state counts as sample -1.
+ *
+ * Events {int64 sample; int32 i, j; double gap, ttc;} for i < j:
+ * - An event needs gap_ij <= gap_event or ttc_ij < ttc_event.
+ * - gap_event < 0 switches the gap test off.
+ * - gap_event == 0 lists exactly the collisions.
+ * - ttc_event <= 0 switches the ttc test off.
+ * - Capacity, counting and sorting by (sample, i, j) are as for csf_encounter_event. */
+typedef struct csf_body_event {
+    int64_t sample;
+    int32_t i, j;
+    double gap, ttc;
+} csf_body_event;
+/* Where the results of one engine go; any pointer may be NULL (that array is not returned).  n = the road users, n_samples the
+ * samples the call covers.  event_capacity = 0 with events NULL counts the events without storing any. */
+typedef struct csf_body_out {
+    double *gap_min;          /* [n_samples, n] */
+    int32_t *gap_with;        /* [n_samples, n] */
+    double *ttc_min;          /* [n_samples, n] */
+    int32_t *ttc_with;        /* [n_samples, n] */
+    double *run_gap_min;      /* [n] the window's minima ... */
+    int32_t *run_gap_with;    /* [n] ... the partner ... */
+    int64_t *run_gap_sample;  /* [n] ... and the sample of each */
+    double *run_ttc_min;      /* [n] */
+    int32_t *run_ttc_with;    /* [n] */
+    int64_t *run_ttc_sample;  /* [n] */
+    int64_t *overlap_n;       /* [n] samples in which gap_min is 0 */
+    csf_body_event *events;   /* [event_capacity] */
+    int64_t event_capacity;
+    int64_t n_events;         /* written: the events found, stored or not */
+    int64_t first_sample;     /* written: the index of the first sample covered (-1: the current state) */
+} csf_body_out;
+/* Samples [first_sample, first_sample + n_samples) of the engine's state ring, numbered and range-checked as csf_encounters has
+ * them; first_sample == -1 with n_samples == 1 is the current state.  ext [n][3] are the extents (front, rear, half_width) of the
+ * road users in population order.  The engine is left exactly as it was.  Two launches whatever the sizes are, one upload of the
+ * extents, one memset, one transfer and one wait (the launch counter below grows by 2 per call that covers anything).  Refused
+ * without side effects (CSF_E_ARG / CSF_E_STATE, with a message): everything csf_encounters refuses; a NULL ext; a non-finite
+ * extent; front < 0, rear < 0, front + rear <= 0 or half_width <= 0 (the message names the road user); a non-finite threshold.
+ * While csf_profile_enable is on, the first launch is timed as kernel 0. */
+int csf_body_encounters(csf_engine *e, int64_t first_sample, int64_t n_samples, const double *ext, double gap_event, double ttc_event,
+                        csf_body_out *out);
+/* The last n_last samples of every member of a batch (in join order) that records, all members in the same two launches; exts
+ * [count] pointers to every member's extents, outs [count].  A member without a ring is skipped: its n_events becomes 0 and its
+ * first_sample -2 (its exts entry is not read).  Refusals as for csf_batch_encounters and the call above. */
+int csf_batch_body_encounters(csf_engine *const *engines, int32_t count, int64_t n_last, const double *const *exts, double gap_event,
+                              double ttc_event, csf_body_out *outs);
+/* launches of the two calls above so far (a batch counts on its first member) */
+int csf_body_encounter_launches(const csf_engine *e, int64_t *n_launches);
+
 /* ---- single-function entry points for known-answer tests -------------------------------------- */
 
 /* calcRepulsiveForce of one source at m receivers through the device code of the pair kernel
