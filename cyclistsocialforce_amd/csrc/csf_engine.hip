@@ -17,12 +17,13 @@
 #include "engine/abi_fieldmap.inc"   // C ABI: the force field at arbitrary probe points (csf_fieldmap.hip)
 #include "engine/abi_sharding.inc"  // C ABI: communicators, loopback groups
 #include "engine/abi_batch.inc"   // C ABI: batches of independent scenes (one launch per vehicle class for all one-wave members)
+#include "engine/measure.inc"   // what the measures of a recording share: checks, asks, grid, one clear, launches, one copy, one wait, unpacking
 #include "engine/abi_encounter.inc"   // C ABI: closest approach and time to collision of a recording (csf_encounter.hip)
 #include "engine/abi_pet.inc"   // C ABI: path crossings and post-encroachment time of a recording (csf_pet.hip)
 #include "engine/abi_passing.inc"   // C ABI: gaps to the leader, overtakings and meetings of a recording (csf_passing.hip)
 #include "engine/abi_flow.inc"      // C ABI: crossings of counting lines, occupancy of areas and of a grid (csf_flow.hip)
 #include "engine/abi_clearance.inc" // C ABI: distances to, sides of and crossings of the edges of a road (csf_clearance.hip)
-#include "engine/abi_body.inc"   // C ABI: gaps and time to contact between the road users' outlines (csf_body.hip; after abi_encounter.inc, whose checks it shares)
+#include "engine/abi_body.inc"   // C ABI: gaps and time to contact between the road users' outlines (csf_body.hip; after abi_encounter.inc, whose split it shares)
 #include "engine/abi_calib.inc"   // C ABI: calibration - a resident data set, many parameter sets evaluated per launch (csf_calib.hip)
 #include "engine/abi_scene.inc"   // C ABI: calibration on closed-loop scenes - workgroup = (parameter set, scene), the error summed in the launch (csf_scene.hip)
 #include "engine/abi_measurement.inc"   // C ABI: far-field radius, time stamps, counters

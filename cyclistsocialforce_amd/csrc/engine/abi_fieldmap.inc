@@ -67,13 +67,7 @@ int csf_field_map(csf_engine *e, int64_t m, const double *x, const double *y, co
     field_map_bands(e->knobs, a);
     // csf_profile_enable: the launches are timed like a tick's - the crowd launch as kernel 0 (pair), the road launch as kernel 1
     csf_engine::ProfSlot *ps = nullptr;
-    if (e->profile > 0) {
-        if ((rc = prof_make_pool(e))) return rc;
-        if (e->prof_issued - e->prof_resolved >= PROF_SLOTS && (rc = prof_resolve_one(e))) return rc;
-        ps = &e->prof_pool[e->prof_issued % PROF_SLOTS];
-        ps->pair = ps->road = ps->agent = ps->gather = false;
-        e->prof_issued++;
-    }
+    if ((rc = prof_take(e, true, &ps))) return rc;
     if (crowd) {
         launch_field_map_crowd(dd, a, e->main, ps ? ps->ev[0] : nullptr, ps ? ps->ev[1] : nullptr);
         if (ps) ps->pair = true;

@@ -64,15 +64,24 @@ int prof_make_pool(csf_engine *e) {
     return CSF_OK;
 }
 
-// a free slot for this tick (NULL with *rc == 0: profiling is off for it)
-csf_engine::ProfSlot *prof_slot(csf_engine *e, int *rc) {
-    *rc = CSF_OK;
-    if (e->profile <= 0 || e->d.tick % e->profile != 0) return nullptr;
-    if ((*rc = prof_make_pool(e))) return nullptr;
-    if (e->prof_issued - e->prof_resolved >= PROF_SLOTS && (*rc = prof_resolve_one(e))) return nullptr;
-    csf_engine::ProfSlot *sl = &e->prof_pool[e->prof_issued % PROF_SLOTS];
-    sl->pair = sl->road = sl->agent = sl->gather = false;
+// a free slot for a call outside the ticks (csf_profile_enable: its first launch is timed like a tick's pair launch, as kernel 0), if
+// the call launches anything; *sl stays NULL where profiling is off
+int prof_take(csf_engine *e, bool launches, csf_engine::ProfSlot **sl) {
+    *sl = nullptr;
+    if (e->profile <= 0 || !launches) return CSF_OK;
+    if (int rc = prof_make_pool(e)) return rc;
+    if (e->prof_issued - e->prof_resolved >= PROF_SLOTS)
+        if (int rc = prof_resolve_one(e)) return rc;
+    *sl = &e->prof_pool[e->prof_issued % PROF_SLOTS];
+    (*sl)->pair = (*sl)->road = (*sl)->agent = (*sl)->gather = false;
     e->prof_issued++;
+    return CSF_OK;
+}
+
+// ... and for this tick (NULL with *rc == 0: profiling is off for it)
+csf_engine::ProfSlot *prof_slot(csf_engine *e, int *rc) {
+    csf_engine::ProfSlot *sl = nullptr;
+    *rc = prof_take(e, e->profile > 0 && e->d.tick % e->profile == 0, &sl);
     return sl;
 }
 

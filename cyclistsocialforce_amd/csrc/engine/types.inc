@@ -293,55 +293,35 @@ struct RecGather {
     }
 };
 
-// What csf_encounters / csf_batch_encounters keep across calls (one per engine; a batch uses its first member's): the descriptors the
-// kernels read (mapped host memory), the packed output on the device - event counters, then every member's block and events - and
-// the pinned buffer its one copy lands in.
-struct EncScratch {
-    HostBuf<EncDesc> desc;
+// What a measure of a recording keeps across calls (one per engine; a batch uses its first member's): the descriptors the kernels read
+// (mapped host memory), the packed output on the device - event counters, then every member's block and events, and behind what is
+// transferred the chunks' partial results - and the pinned buffer its one copy lands in.
+template <class Desc>
+struct MeasureScratch {
+    HostBuf<Desc> desc;
     DevBuf<unsigned char> dev;
     HostBuf<unsigned char, false> host;
 };
 
-// ... and csf_post_encroachment / csf_batch_post_encroachment: the same three, the chunks' partial results behind the packed output
-struct PetScratch {
-    HostBuf<PetDesc> desc;
-    DevBuf<unsigned char> dev;
-    HostBuf<unsigned char, false> host;
-};
-
-// ... and csf_passing / csf_batch_passing: the same three
-struct PassScratch {
-    HostBuf<PassDesc> desc;
-    DevBuf<unsigned char> dev;
-    HostBuf<unsigned char, false> host;
-};
-
-// ... and csf_flow / csf_batch_flow: the same three, and the layout as the kernels read it (mapped host memory)
+// ... csf_flow / csf_batch_flow: and the layout as the kernels read it (mapped host memory)
 struct FlowScratch {
-    HostBuf<FlowDesc> desc;
+    MeasureScratch<FlowDesc> m;
     HostBuf<double> layout;
-    DevBuf<unsigned char> dev;
-    HostBuf<unsigned char, false> host;
 };
 
-// ... and csf_clearance / csf_batch_clearance: the same three, and the road as the kernels read it - staged in pinned memory, copied
-// to the device once per call
+// ... csf_clearance / csf_batch_clearance: and the road as the kernels read it - staged in pinned memory, copied to the device once per call
 struct ClrScratch {
-    HostBuf<ClrDesc> desc;
+    MeasureScratch<ClrDesc> m;
     HostBuf<unsigned char, false> road_host;
     DevBuf<unsigned char> road;
-    DevBuf<unsigned char> dev;
-    HostBuf<unsigned char, false> host;
 };
 
-// ... and csf_body_encounters / csf_batch_body_encounters: the same three, and the extents as the kernels read them - staged in pinned
-// memory, copied to the device once per call
+// ... csf_body_encounters / csf_batch_body_encounters: and the extents as the kernels read them - staged in pinned memory, copied to the
+// device once per call
 struct BodyScratch {
-    HostBuf<BodyDesc> desc;
+    MeasureScratch<BodyDesc> m;
     HostBuf<double, false> ext_host;
     DevBuf<double> ext;
-    DevBuf<unsigned char> dev;
-    HostBuf<unsigned char, false> host;
 };
 
 struct csf_engine {
@@ -569,11 +549,11 @@ struct csf_engine {
     int64_t small_ticks = 0;         // ticks run by the one-wave kernel (csf_small_ticks)
     int64_t field_map_launches = 0;  // launches of csf_field_map: one per requested term (csf_field_map_launches)
     int64_t encounter_launches = 0;  // launches of csf_encounters / csf_batch_encounters: two per call (csf_encounter_launches)
-    EncScratch enc;
+    MeasureScratch<EncDesc> enc;
     int64_t pet_launches = 0;        // launches of csf_post_encroachment / csf_batch_post_encroachment: two per call (csf_pet_launches)
-    PetScratch pet;
+    MeasureScratch<PetDesc> pet;
     int64_t passing_launches = 0;    // launches of csf_passing / csf_batch_passing: two per call (csf_passing_launches)
-    PassScratch passing;
+    MeasureScratch<PassDesc> passing;
     int64_t flow_launches = 0;       // launches of csf_flow / csf_batch_flow: two per call (csf_flow_launches)
     FlowScratch flow;
     int64_t clearance_launches = 0;  // launches of csf_clearance / csf_batch_clearance: three per call (csf_clearance_launches)

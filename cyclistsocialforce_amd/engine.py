@@ -64,16 +64,54 @@ def _encounter_args(who, first, count, radius, d_event, ttc_event):
     return int(first), int(count)
 
 
-class _EncounterPack:
+def _window_args(who, first, count, what, numbers_only=False):
+    """(first, count) of a measure that needs a window of the recording, checked before any device call; what: the thing a
+    window has and the current state lacks ("a path is")"""
+    if first is None or count is None:
+        raise ValueError(f"{who}: first and count are needed - {what} a window of the recording, the current state has none")
+    if isinstance(first, bool) or isinstance(count, bool) or (numbers_only and not (_is_number(first) and _is_number(count))) \
+            or int(first) != first or int(count) != count or first < 0 or count < 0:
+        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
+    if count > 65535:
+        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
+    return int(first), int(count)
+
+
+def _starts(*sizes):
+    """where every member's part starts in an array that holds all members' parts of the given sizes, and where the last ends"""
+    return tuple(np.r_[0, np.cumsum(v)] for v in sizes)
+
+
+class _Pack:
     """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
-    csf_encounter_out records that point into them"""
+    records of the C ABI that point into them"""
+
+    def _records(self, record, columns, events_col, caps, event_dtype):
+        """self.events for `caps` events per member, and self.outs: the records as ONE int64 table (every member of a csf_*_out
+        is 8 bytes), filled column by column - a batch of 1 024 members is written in a dozen array operations instead of 12 288
+        attribute stores.  columns: (column, array or None, the members' starts in it); events_col: events, event_capacity"""
+        caps = np.asarray(caps, dtype=np.int64)
+        self.e0, = _starts(caps)
+        self.events = np.empty(int(self.e0[-1]), event_dtype)
+        tab = self._tab = np.zeros((len(caps), C.sizeof(record) // 8), dtype=np.int64)
+        for col, a, start in columns:
+            if a is not None:
+                tab[:, col] = a.ctypes.data + a.itemsize * start[:-1]
+        tab[:, events_col] = np.where(caps > 0, self.events.ctypes.data + event_dtype.itemsize * self.e0[:-1], 0)
+        tab[:, events_col + 1] = caps
+        self.outs = (record * len(caps)).from_buffer(tab)
+
+    def _events_of(self, i, n_events, want_events):
+        """member i's events (_FlowPack and _ClearancePack slice theirs from plain Python numbers read once: _read)"""
+        return self.events[int(self.e0[i]):int(self.e0[i]) + n_events] if want_events else None
+
+
+class _EncounterPack(_Pack):
+    """_Pack of csf_encounter_out records (shapes: (n, count) per member)"""
 
     def __init__(self, shapes, per_sample, caps):
-        m = len(shapes)
-        cells = np.array([n * c for n, c in shapes], dtype=np.int64)
-        ns = np.array([n for n, _ in shapes], dtype=np.int64)
         self.shapes, self.caps = shapes, caps
-        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (cells, ns, np.asarray(caps, dtype=np.int64)))
+        self.c0, self.n0 = _starts([n * c for n, c in shapes], [n for n, _ in shapes])
         nc, nn = (int(self.c0[-1]), int(self.n0[-1]))
         self.per = None
         if per_sample:
@@ -81,20 +119,8 @@ class _EncounterPack:
         # (an empty window leaves them as they are: a minimum of +inf with nobody, at no sample)
         self.run = (np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64),
                     np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64))
-        self.events = np.empty(int(self.e0[-1]), EVENT_DTYPE)
-        # the records as one int64 table (every member of csf_encounter_out is 8 bytes), filled column by column: a batch of 1 024
-        # members is written in a dozen array operations instead of 12 288 attribute stores
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.EncounterOut) // 8), dtype=np.int64)
-        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
-        if self.per is not None:
-            for col, (a, size) in enumerate(zip(self.per, (8, 4, 8, 4))):
-                tab[:, col] = a.ctypes.data + size * c0
-        for col, (a, size) in zip(range(4, 10), zip(self.run, (8, 4, 8, 8, 4, 8))):
-            tab[:, col] = a.ctypes.data + size * n0
-        caps = np.asarray(caps, dtype=np.int64)
-        tab[:, 10] = np.where(caps > 0, self.events.ctypes.data + EVENT_DTYPE.itemsize * e0, 0)
-        tab[:, 11] = caps
-        self.outs = (_ffi.EncounterOut * m).from_buffer(tab)
+        columns = [(col, a, self.c0) for col, a in enumerate(self.per or ())] + [(col, a, self.n0) for col, a in enumerate(self.run, start=4)]
+        self._records(_ffi.EncounterOut, columns, 10, caps, EVENT_DTYPE)
 
     def result(self, i, radius, want_events):
         n, count = self.shapes[i]
@@ -108,7 +134,7 @@ class _EncounterPack:
         else:
             r.d_min, r.d_with, r.ttc_min, r.ttc_with = (a[c:c + n * count].reshape(count, n) for a in self.per)
         (r.run_d_min, r.run_d_with, r.run_d_sample, r.run_ttc_min, r.run_ttc_with, r.run_ttc_sample) = (a[u:u + n] for a in self.run)
-        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        r.events = self._events_of(i, r.n_events, want_events)
         return r
 
 
@@ -154,13 +180,7 @@ def _pet_args(who, first, count, pet_event):
     if pet_event is not None and (isinstance(pet_event, bool) or not np.isscalar(pet_event) or not isinstance(pet_event, (int, float, np.integer, np.floating))
                                   or np.isnan(pet_event) or pet_event == -np.inf):
         raise ValueError(f"{who}: pet_event must be None or a number, +inf for every crossing (got {pet_event!r})")
-    if first is None or count is None:
-        raise ValueError(f"{who}: first and count are needed - a path is a window of the recording, the current state has none")
-    if isinstance(first, bool) or isinstance(count, bool) or int(first) != first or int(count) != count or first < 0 or count < 0:
-        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
-    if count > 65535:
-        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
-    return int(first), int(count)
+    return _window_args(who, first, count, "a path is")
 
 
 def _pet_capacity_guess(segs):
@@ -168,36 +188,21 @@ def _pet_capacity_guess(segs):
     return min(max(64, segs), 1 << 16)
 
 
-class _PetPack:
-    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
-    csf_pet_out records that point into them (shapes: (n, count) per member)"""
+class _PetPack(_Pack):
+    """_Pack of csf_pet_out records (shapes: (n, count) per member)"""
 
     SEG = (("seg_pet", np.float64), ("seg_with", np.int32), ("seg_t_own", np.float64), ("seg_t_with", np.float64))
     RUN = (("run_pet", np.float64), ("run_with", np.int32), ("run_t_own", np.float64), ("run_t_with", np.float64),
            ("run_x", np.float64), ("run_y", np.float64), ("run_count", np.int32))
 
     def __init__(self, shapes, per_segment, caps):
-        m = len(shapes)
-        segs = np.array([n * max(c - 1, 0) for n, c in shapes], dtype=np.int64)
-        ns = np.array([n for n, _ in shapes], dtype=np.int64)
-        caps = np.asarray(caps, dtype=np.int64)
         self.shapes = shapes
-        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (segs, ns, caps))
+        self.c0, self.n0 = _starts([n * max(c - 1, 0) for n, c in shapes], [n for n, _ in shapes])
         nc, nn = int(self.c0[-1]), int(self.n0[-1])
         self.seg = [np.empty(nc, dt) for _, dt in self.SEG] if per_segment else None
         self.run = [np.empty(nn, dt) for _, dt in self.RUN]
-        self.events = np.empty(int(self.e0[-1]), PET_EVENT_DTYPE)
-        # the records as one int64 table (every member of csf_pet_out is 8 bytes), filled column by column
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.PetOut) // 8), dtype=np.int64)
-        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
-        if self.seg is not None:
-            for col, a in enumerate(self.seg):
-                tab[:, col] = a.ctypes.data + a.itemsize * c0
-        for col, a in enumerate(self.run, start=4):
-            tab[:, col] = a.ctypes.data + a.itemsize * n0
-        tab[:, 11] = np.where(caps > 0, self.events.ctypes.data + PET_EVENT_DTYPE.itemsize * e0, 0)
-        tab[:, 12] = caps
-        self.outs = (_ffi.PetOut * m).from_buffer(tab)
+        columns = [(col, a, self.c0) for col, a in enumerate(self.seg or ())] + [(col, a, self.n0) for col, a in enumerate(self.run, start=4)]
+        self._records(_ffi.PetOut, columns, 11, caps, PET_EVENT_DTYPE)
 
     def result(self, i, want_events, period):
         n, count = self.shapes[i]
@@ -210,7 +215,7 @@ class _PetPack:
             setattr(r, name, None if self.seg is None else self.seg[k][c:c + n * rows].reshape(rows, n))
         for k, (name, _) in enumerate(self.RUN):
             setattr(r, name, self.run[k][u:u + n])
-        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        r.events = self._events_of(i, r.n_events, want_events)
         return r
 
 
@@ -275,13 +280,7 @@ def _passing_args(who, first, count, band, lat_max, lat_event):
         raise ValueError(f"{who}: lat_max must be a number > 0, +inf for every passing (got {lat_max!r})")
     if lat_event is not None and (not _is_number(lat_event) or np.isnan(lat_event) or lat_event == -np.inf):
         raise ValueError(f"{who}: lat_event must be None or a number, +inf for every passing (got {lat_event!r})")
-    if first is None or count is None:
-        raise ValueError(f"{who}: first and count are needed - a direction of travel is a window of the recording, the current state has none")
-    if isinstance(first, bool) or isinstance(count, bool) or int(first) != first or int(count) != count or first < 0 or count < 0:
-        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
-    if count > 65535:
-        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
-    return int(first), int(count)
+    return _window_args(who, first, count, "a direction of travel is")
 
 
 def _passing_capacity_guess(cells):
@@ -289,35 +288,22 @@ def _passing_capacity_guess(cells):
     return min(max(64, cells), 1 << 16)
 
 
-class _PassingPack:
-    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
-    csf_passing_out records that point into them (shapes: (n, count) per member)"""
+class _PassingPack(_Pack):
+    """_Pack of csf_passing_out records (shapes: (n, count) per member)"""
 
     def __init__(self, shapes, per_station, caps):
-        m = len(shapes)
-        st = np.array([n * max(c - 1, 0) for n, c in shapes], dtype=np.int64)
-        iv = np.array([n * max(c - 2, 0) for n, c in shapes], dtype=np.int64)
-        ns = np.array([n for n, _ in shapes], dtype=np.int64)
-        caps = np.asarray(caps, dtype=np.int64)
         self.shapes = shapes
-        self.s0, self.i0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (st, iv, ns, caps))
+        self.s0, self.i0, self.n0 = _starts([n * max(c - 1, 0) for n, c in shapes], [n * max(c - 2, 0) for n, c in shapes], [n for n, _ in shapes])
         self.station = [np.empty(int(self.s0[-1]), dt) for _, dt in Passing.STATION] if per_station else None
         self.interval = [np.empty(int(self.i0[-1]), dt) for _, dt in Passing.INTERVAL] if per_station else None
         self.run = [np.empty(int(self.n0[-1]), dt) for _, dt in Passing.RUN]
         self.count = [np.empty(3 * int(self.n0[-1]), dt) for _, dt in Passing.COUNT]
-        self.events = np.empty(int(self.e0[-1]), PASSING_EVENT_DTYPE)
-        # the records as one int64 table (every member of csf_passing_out is 8 bytes), filled column by column in header order
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.PassingOut) // 8), dtype=np.int64)
-        col = 0
-        for names, arrays, start, width in ((Passing.STATION, self.station, self.s0, 1), (Passing.INTERVAL, self.interval, self.i0, 1),
-                                            (Passing.RUN, self.run, self.n0, 1), (Passing.COUNT, self.count, self.n0, 3)):
-            if arrays is not None:
-                for k, a in enumerate(arrays):
-                    tab[:, col + k] = a.ctypes.data + a.itemsize * width * start[:-1]
+        columns, col = [], 0                                     # (in header order)
+        for names, arrays, start in ((Passing.STATION, self.station, self.s0), (Passing.INTERVAL, self.interval, self.i0),
+                                     (Passing.RUN, self.run, self.n0), (Passing.COUNT, self.count, 3 * self.n0)):
+            columns += [(col + k, a, start) for k, a in enumerate(arrays or ())]
             col += len(names)
-        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + PASSING_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
-        tab[:, col + 1] = caps
-        self.outs = (_ffi.PassingOut * m).from_buffer(tab)
+        self._records(_ffi.PassingOut, columns, col, caps, PASSING_EVENT_DTYPE)
 
     def result(self, i, want_events, period):
         n, count = self.shapes[i]
@@ -337,7 +323,7 @@ class _PassingPack:
             setattr(r, name, self.run[k][u:u + n])
         for k, (name, _) in enumerate(Passing.COUNT):
             setattr(r, name, self.count[k][3 * u:3 * (u + n)].reshape(n, 3))
-        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        r.events = self._events_of(i, r.n_events, want_events)
         return r
 
 
@@ -453,14 +439,7 @@ def _flow_layout(who, lines, areas, grid):
 
 
 def _flow_args(who, first, count):
-    if first is None or count is None:
-        raise ValueError(f"{who}: first and count are needed - an interval is a window of the recording, the current state has none")
-    if isinstance(first, bool) or isinstance(count, bool) or not _is_number(first) or not _is_number(count) \
-            or int(first) != first or int(count) != count or first < 0 or count < 0:
-        raise ValueError(f"{who}: first and count must be integers >= 0 (got {first!r}, {count!r})")
-    if count > 65535:
-        raise ValueError(f"{who}: at most 65535 samples in one call (got {count})")
-    return int(first), int(count)
+    return _window_args(who, first, count, "an interval is", numbers_only=True)
 
 
 def _flow_capacity_guess(cells, lines):
@@ -468,9 +447,8 @@ def _flow_capacity_guess(cells, lines):
     return min(max(64, cells * min(lines, 4) // 4), 1 << 16)
 
 
-class _FlowPack:
-    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, the
-    csf_flow_out records that point into them (shapes: (n, count) per member) and the csf_flow_layout they share"""
+class _FlowPack(_Pack):
+    """_Pack of csf_flow_out records (shapes: (n, count) per member), and the csf_flow_layout they share"""
 
     def __init__(self, shapes, lines, areas, grid, caps):
         m = len(shapes)
@@ -479,23 +457,13 @@ class _FlowPack:
         self.shapes, self.lines, self.areas, self.grid = shapes, lines, areas, grid
         n = np.array([n for n, _ in shapes], dtype=np.int64)
         c = np.array([c for _, c in shapes], dtype=np.int64)
-        caps = np.asarray(caps, dtype=np.int64)
         sizes = {"line_count": np.maximum(c - 1, 0) * L * 2, "cross_n": n * L * 2, "first_t": n * L, "first_u": n * L, "first_speed": n * L,
                  "first_dir": n * L, "occupancy": c * R, "in_samples": n * R, "in_first": n * R, "in_last": n * R, "in_dist": n * R,
                  "grid_count": np.full(m, G, dtype=np.int64)}
-        self.start = {f: np.r_[0, np.cumsum(v)] for f, v in sizes.items()}
-        self.e0 = np.r_[0, np.cumsum(caps)]
+        self.start = dict(zip(sizes, _starts(*sizes.values())))
         self.arrays = {f: np.empty(int(self.start[f][-1]), dt) for f, dt in Flow.ARRAYS}
-        self.events = np.empty(int(self.e0[-1]), FLOW_EVENT_DTYPE)
-        # the records as one int64 table (every member of csf_flow_out is 8 bytes), filled column by column in header order
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.FlowOut) // 8), dtype=np.int64)
-        for col, (f, _) in enumerate(Flow.ARRAYS):
-            a = self.arrays[f]
-            tab[:, col] = a.ctypes.data + a.itemsize * self.start[f][:-1]
-        col = len(Flow.ARRAYS)
-        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + FLOW_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
-        tab[:, col + 1] = caps
-        self.outs = (_ffi.FlowOut * m).from_buffer(tab)
+        columns = [(col, self.arrays[f], self.start[f]) for col, (f, _) in enumerate(Flow.ARRAYS)]   # (in header order)
+        self._records(_ffi.FlowOut, columns, len(Flow.ARRAYS), caps, FLOW_EVENT_DTYPE)
         self._read = None                                        # what the call wrote into the records, read once (result)
         y = self.layout = _ffi.FlowLayout()
         y.lines, y.areas, y.n_lines, y.n_areas = (lines.ctypes.data if L else None), (areas.ctypes.data if R else None), L, R
@@ -644,36 +612,23 @@ def _clearance_capacity_guess(stations):
     return min(max(64, stations // 8), 1 << 16)
 
 
-class _ClearancePack:
-    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, the
-    csf_clearance_out records that point into them (shapes: (n, count) per member) and the csf_clearance_road they share"""
+class _ClearancePack(_Pack):
+    """_Pack of csf_clearance_out records (shapes: (n, count) per member), and the csf_clearance_road they share"""
 
     def __init__(self, shapes, off, xy, caps, per_sample):
-        m = len(shapes)
         self.shapes, self.off, self.xy, self.per_sample = shapes, off, xy, per_sample
         n = np.array([n for n, _ in shapes], dtype=np.int64)
         c = np.array([c for _, c in shapes], dtype=np.int64)
-        caps = np.asarray(caps, dtype=np.int64)
         rows = {}
         rows.update({f: c * n for f, _ in Clearance.CELL})
         rows.update({f: np.maximum(c - 1, 0) * n for f, _ in Clearance.STATION})
         rows.update({f: n for f, _ in Clearance.USER})
         rows.update(near_count=c, cross_count=np.maximum(c - 1, 0))
         wide = {f for f, _ in Clearance.CELL + Clearance.STATION}
-        self.start = {f: np.r_[0, np.cumsum(v)] for f, v in rows.items()}
-        self.e0 = np.r_[0, np.cumsum(caps)]
+        self.start = dict(zip(rows, _starts(*rows.values())))
         self.arrays = {f: (np.empty(int(self.start[f][-1]), dt) if per_sample or f not in wide else None) for f, dt in Clearance.ARRAYS}
-        self.events = np.empty(int(self.e0[-1]), CLEARANCE_EVENT_DTYPE)
-        # the records as one int64 table (every member of csf_clearance_out is 8 bytes), filled column by column in header order
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.ClearanceOut) // 8), dtype=np.int64)
-        for col, (f, _) in enumerate(Clearance.ARRAYS):
-            a = self.arrays[f]
-            if a is not None:
-                tab[:, col] = a.ctypes.data + a.itemsize * self.start[f][:-1]
-        col = len(Clearance.ARRAYS)
-        tab[:, col] = np.where(caps > 0, self.events.ctypes.data + CLEARANCE_EVENT_DTYPE.itemsize * self.e0[:-1], 0)
-        tab[:, col + 1] = caps
-        self.outs = (_ffi.ClearanceOut * m).from_buffer(tab)
+        columns = [(col, self.arrays[f], self.start[f]) for col, (f, _) in enumerate(Clearance.ARRAYS)]   # (in header order)
+        self._records(_ffi.ClearanceOut, columns, len(Clearance.ARRAYS), caps, CLEARANCE_EVENT_DTYPE)
         self._read = None                                        # what the call wrote into the records, read once (result)
         y = self.road = _ffi.ClearanceRoad()
         y.offsets, y.xy, y.n_edges = off.ctypes.data, xy.ctypes.data, off.size - 1
@@ -780,16 +735,12 @@ def _batch_body_extents(who, extents, ns):
     return out
 
 
-class _BodyPack:
-    """the output arrays of a call for every member, each kind ONE array that the members' arrays are views of, and the
-    csf_body_out records that point into them (as _EncounterPack)"""
+class _BodyPack(_Pack):
+    """_Pack of csf_body_out records (as _EncounterPack)"""
 
     def __init__(self, shapes, per_sample, caps):
-        m = len(shapes)
-        cells = np.array([n * c for n, c in shapes], dtype=np.int64)
-        ns = np.array([n for n, _ in shapes], dtype=np.int64)
         self.shapes, self.caps = shapes, caps
-        self.c0, self.n0, self.e0 = (np.r_[0, np.cumsum(v)] for v in (cells, ns, np.asarray(caps, dtype=np.int64)))
+        self.c0, self.n0 = _starts([n * c for n, c in shapes], [n for n, _ in shapes])
         nc, nn = (int(self.c0[-1]), int(self.n0[-1]))
         self.per = None
         if per_sample:
@@ -797,18 +748,8 @@ class _BodyPack:
         # (an empty window leaves them as they are: a minimum of +inf with nobody, at no sample, and no overlap)
         self.run = (np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64),
                     np.full(nn, np.inf), np.full(nn, -1, np.int32), np.full(nn, -1, np.int64), np.zeros(nn, np.int64))
-        self.events = np.empty(int(self.e0[-1]), BODY_EVENT_DTYPE)
-        tab = self._tab = np.zeros((m, C.sizeof(_ffi.BodyOut) // 8), dtype=np.int64)   # (every member of csf_body_out is 8 bytes)
-        c0, n0, e0 = self.c0[:-1], self.n0[:-1], self.e0[:-1]
-        if self.per is not None:
-            for col, (a, size) in enumerate(zip(self.per, (8, 4, 8, 4))):
-                tab[:, col] = a.ctypes.data + size * c0
-        for col, (a, size) in zip(range(4, 11), zip(self.run, (8, 4, 8, 8, 4, 8, 8))):
-            tab[:, col] = a.ctypes.data + size * n0
-        caps = np.asarray(caps, dtype=np.int64)
-        tab[:, 11] = np.where(caps > 0, self.events.ctypes.data + BODY_EVENT_DTYPE.itemsize * e0, 0)
-        tab[:, 12] = caps
-        self.outs = (_ffi.BodyOut * m).from_buffer(tab)
+        columns = [(col, a, self.c0) for col, a in enumerate(self.per or ())] + [(col, a, self.n0) for col, a in enumerate(self.run, start=4)]
+        self._records(_ffi.BodyOut, columns, 11, caps, BODY_EVENT_DTYPE)
 
     def result(self, i, extents, want_events):
         n, count = self.shapes[i]
@@ -822,7 +763,7 @@ class _BodyPack:
         else:
             r.gap_min, r.gap_with, r.ttc_min, r.ttc_with = (a[c:c + n * count].reshape(count, n) for a in self.per)
         (r.run_gap_min, r.run_gap_with, r.run_gap_sample, r.run_ttc_min, r.run_ttc_with, r.run_ttc_sample, r.overlap_n) = (a[u:u + n] for a in self.run)
-        r.events = self.events[int(self.e0[i]):int(self.e0[i]) + r.n_events] if want_events else None
+        r.events = self._events_of(i, r.n_events, want_events)
         return r
 
 
@@ -1529,6 +1470,35 @@ class Engine:
         self._ck(self._lib.csf_field_map_launches(self._h, C.byref(n)))
         return n.value
 
+    # -- the measures of a recording: one route for a single engine, one for a batch --------------------------
+    def _measure(self, make_pack, call, cap, want):
+        """the pack of a single engine's call: make_pack([cap]) holds the outputs, call(pack) is the C ABI's return code.  Events
+        are fetched with the capacity `cap`; when more were found, one second call with the exact capacity - only where events
+        are wanted: flow and clearance count their crossings whether or not, the other measures count none without a threshold."""
+        while True:
+            pack = make_pack([cap])
+            self._ck(call(pack))
+            if not want or pack.outs[0].n_events <= cap:
+                return pack
+            cap = int(pack.outs[0].n_events)
+
+    @staticmethod
+    def _batch_measure(symbol, engines, arr, make_pack, args, caps, want, result):
+        """the same for a batch: make_pack(caps), then the C ABI's `symbol` with args(pack) behind the engines; a list with
+        result(pack, i, engine) per member, None for members that do not record (first_sample -2)"""
+        while True:
+            pack = make_pack(caps)
+            Engine._group_call(symbol, engines, arr, *args(pack))
+            found = [int(o.n_events) for o in pack.outs]
+            if not want or all(f <= c for f, c in zip(found, caps)):
+                return [None if pack.outs[i].first_sample == -2 else result(pack, i, e) for i, e in enumerate(engines)]
+            caps = [max(f, c) for f, c in zip(found, caps)]
+
+    def _launches(self, symbol):
+        n = C.c_int64(0)
+        self._ck(getattr(self._lib, symbol)(self._h, C.byref(n)))
+        return n.value
+
     # -- encounters: closest approach and time to collision (include/csf.h: csf_encounters) ----------------------------------
     def encounters(self, first=None, count=None, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
         """closest approach and time to collision of every road user (csf.h: csf_encounters; every road user a disc of `radius`):
@@ -1540,12 +1510,10 @@ class Engine:
         n = self.n
         want = _events_wanted(d_event, ttc_event)
         cap = min(max(64, count * n), 1 << 16) if want else 0
-        while True:
-            pack = _EncounterPack([(n, count)], per_sample, [cap])
-            self._ck(self._lib.csf_encounters(self._h, first, count, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), pack.outs))
-            if pack.outs[0].n_events <= cap:
-                return pack.result(0, radius, want)
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _EncounterPack([(n, count)], per_sample, caps),
+                             lambda p: self._lib.csf_encounters(self._h, first, count, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), p.outs),
+                             cap, want)
+        return pack.result(0, radius, want)
 
     @staticmethod
     def batch_encounters(engines, n_last, radius=0.5, d_event=None, ttc_event=None, per_sample=True):
@@ -1557,19 +1525,13 @@ class Engine:
         want = _events_wanted(d_event, ttc_event)
         shapes = [(e.n, n_last) for e in engines]
         caps = [min(max(64, n_last * n), 1 << 16) if want else 0 for n, _ in shapes]
-        while True:
-            pack = _EncounterPack(shapes, per_sample, caps)
-            Engine._group_call("csf_batch_encounters", engines, arr, n_last, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, radius, want) for i in range(len(engines))]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_encounters", engines, arr, lambda caps: _EncounterPack(shapes, per_sample, caps),
+                                     lambda p: (n_last, float(radius), float(d_event or 0.0), float(ttc_event or 0.0), p.outs),
+                                     caps, want, lambda p, i, e: p.result(i, radius, want))
 
     def encounter_launches(self):
         """launches of encounters / batch_encounters so far: two per call (csf.h: csf_encounter_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_encounter_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_encounter_launches")
 
     # -- post-encroachment time: path crossings of a recording (include/csf.h: csf_post_encroachment) -------------------------
     def _period(self):
@@ -1586,12 +1548,9 @@ class Engine:
         n = self.n
         want = pet_event is not None and pet_event > 0
         cap = _pet_capacity_guess(max(count - 1, 0) * n) if want else 0
-        while True:
-            pack = _PetPack([(n, count)], per_segment, [cap])
-            self._ck(self._lib.csf_post_encroachment(self._h, first, count, float(pet_event or 0.0), pack.outs))
-            if pack.outs[0].n_events <= cap:
-                return pack.result(0, want, self._period())
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _PetPack([(n, count)], per_segment, caps),
+                             lambda p: self._lib.csf_post_encroachment(self._h, first, count, float(pet_event or 0.0), p.outs), cap, want)
+        return pack.result(0, want, self._period())
 
     @staticmethod
     def batch_post_encroachment(engines, n_last, pet_event=None, per_segment=True):
@@ -1603,19 +1562,12 @@ class Engine:
         want = pet_event is not None and pet_event > 0
         shapes = [(e.n, n_last) for e in engines]
         caps = [_pet_capacity_guess(max(n_last - 1, 0) * n) if want else 0 for n, _ in shapes]
-        while True:
-            pack = _PetPack(shapes, per_segment, caps)
-            Engine._group_call("csf_batch_post_encroachment", engines, arr, n_last, float(pet_event or 0.0), pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, want, e._period()) for i, e in enumerate(engines)]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_post_encroachment", engines, arr, lambda caps: _PetPack(shapes, per_segment, caps),
+                                     lambda p: (n_last, float(pet_event or 0.0), p.outs), caps, want, lambda p, i, e: p.result(i, want, e._period()))
 
     def pet_launches(self):
         """launches of post_encroachment / batch_post_encroachment so far: two per call (csf.h: csf_pet_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_pet_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_pet_launches")
 
     # -- following and passing: gaps, overtakings and meetings of a recording (include/csf.h: csf_passing) --------------------
     def passing(self, first, count, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
@@ -1630,12 +1582,9 @@ class Engine:
         n = self.n
         want = lat_event is not None and lat_event > 0
         cap = _passing_capacity_guess(max(count - 1, 0) * n) if want else 0
-        while True:
-            pack = _PassingPack([(n, count)], per_station, [cap])
-            self._ck(self._lib.csf_passing(self._h, first, count, float(band), float(lat_max), float(lat_event or 0.0), pack.outs))
-            if pack.outs[0].n_events <= cap:
-                return pack.result(0, want, self._period())
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _PassingPack([(n, count)], per_station, caps),
+                             lambda p: self._lib.csf_passing(self._h, first, count, float(band), float(lat_max), float(lat_event or 0.0), p.outs), cap, want)
+        return pack.result(0, want, self._period())
 
     @staticmethod
     def batch_passing(engines, n_last, band=0.75, lat_max=3.0, lat_event=None, per_station=True):
@@ -1647,19 +1596,13 @@ class Engine:
         want = lat_event is not None and lat_event > 0
         shapes = [(e.n, n_last) for e in engines]
         caps = [_passing_capacity_guess(max(n_last - 1, 0) * n) if want else 0 for n, _ in shapes]
-        while True:
-            pack = _PassingPack(shapes, per_station, caps)
-            Engine._group_call("csf_batch_passing", engines, arr, n_last, float(band), float(lat_max), float(lat_event or 0.0), pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, want, e._period()) for i, e in enumerate(engines)]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_passing", engines, arr, lambda caps: _PassingPack(shapes, per_station, caps),
+                                     lambda p: (n_last, float(band), float(lat_max), float(lat_event or 0.0), p.outs),
+                                     caps, want, lambda p, i, e: p.result(i, want, e._period()))
 
     def passing_launches(self):
         """launches of passing / batch_passing so far: two per call (csf.h: csf_passing_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_passing_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_passing_launches")
 
     # -- flow: crossings of counting lines, occupancy of areas and of a grid (include/csf.h: csf_flow) ------------------------
     def flow(self, first, count, lines=None, areas=None, grid=None, events=False):
@@ -1673,12 +1616,9 @@ class Engine:
         lines, areas, grid = _flow_layout("flow", lines, areas, grid)
         n = self.n
         cap = _flow_capacity_guess(max(count - 1, 0) * n, lines.shape[0]) if events else 0
-        while True:
-            pack = _FlowPack([(n, count)], lines, areas, grid, [cap])
-            self._ck(self._lib.csf_flow(self._h, first, count, C.byref(pack.layout), pack.outs))
-            if not events or pack.outs[0].n_events <= cap:
-                return pack.result(0, bool(events), self._period())
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _FlowPack([(n, count)], lines, areas, grid, caps),
+                             lambda p: self._lib.csf_flow(self._h, first, count, C.byref(p.layout), p.outs), cap, events)
+        return pack.result(0, bool(events), self._period())
 
     @staticmethod
     def batch_flow(engines, n_last, lines=None, areas=None, grid=None, events=False):
@@ -1692,19 +1632,12 @@ class Engine:
             raise ValueError(f"batch_flow: {len(engines)} members x {grid[3]} x {grid[4]} grid cells (at most 2^24)")
         shapes = [(e.n, n_last) for e in engines]
         caps = [_flow_capacity_guess(max(n_last - 1, 0) * n, lines.shape[0]) if events else 0 for n, _ in shapes]
-        while True:
-            pack = _FlowPack(shapes, lines, areas, grid, caps)
-            Engine._group_call("csf_batch_flow", engines, arr, n_last, C.byref(pack.layout), pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if not events or all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, bool(events), e._period()) for i, e in enumerate(engines)]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_flow", engines, arr, lambda caps: _FlowPack(shapes, lines, areas, grid, caps),
+                                     lambda p: (n_last, C.byref(p.layout), p.outs), caps, events, lambda p, i, e: p.result(i, bool(events), e._period()))
 
     def flow_launches(self):
         """launches of flow / batch_flow so far: two per call (csf.h: csf_flow_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_flow_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_flow_launches")
 
     # -- road clearance: edge distances and edge crossings of a recording (include/csf.h: csf_clearance) ----------------------
     def clearance(self, first, count, road, d_event=0.0, events=False, per_sample=True):
@@ -1719,12 +1652,9 @@ class Engine:
         d_event = _clearance_d_event("clearance", d_event)
         n = self.n
         cap = _clearance_capacity_guess(max(count - 1, 0) * n) if events else 0
-        while True:
-            pack = _ClearancePack([(n, count)], off, xy, [cap], bool(per_sample))
-            self._ck(self._lib.csf_clearance(self._h, first, count, C.byref(pack.road), d_event, pack.outs))
-            if not events or pack.outs[0].n_events <= cap:
-                return pack.result(0, bool(events), self._period(), d_event)
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _ClearancePack([(n, count)], off, xy, caps, bool(per_sample)),
+                             lambda p: self._lib.csf_clearance(self._h, first, count, C.byref(p.road), d_event, p.outs), cap, events)
+        return pack.result(0, bool(events), self._period(), d_event)
 
     @staticmethod
     def batch_clearance(engines, n_last, road, d_event=0.0, events=False, per_sample=True):
@@ -1737,19 +1667,13 @@ class Engine:
         engines, arr = Engine._batch_array(engines, "batch_clearance")
         shapes = [(e.n, n_last) for e in engines]
         caps = [_clearance_capacity_guess(max(n_last - 1, 0) * n) if events else 0 for n, _ in shapes]
-        while True:
-            pack = _ClearancePack(shapes, off, xy, caps, bool(per_sample))
-            Engine._group_call("csf_batch_clearance", engines, arr, n_last, C.byref(pack.road), d_event, pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if not events or all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, bool(events), e._period(), d_event) for i, e in enumerate(engines)]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_clearance", engines, arr, lambda caps: _ClearancePack(shapes, off, xy, caps, bool(per_sample)),
+                                     lambda p: (n_last, C.byref(p.road), d_event, p.outs),
+                                     caps, events, lambda p, i, e: p.result(i, bool(events), e._period(), d_event))
 
     def clearance_launches(self):
         """launches of clearance / batch_clearance so far: three per call (csf.h: csf_clearance_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_clearance_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_clearance_launches")
 
     # -- body encounters: gaps and time to contact between the outlines (include/csf.h: csf_body_encounters) ------------------
     def body_encounters(self, first=None, count=None, extents=None, gap_event=None, ttc_event=None, per_sample=True):
@@ -1766,12 +1690,9 @@ class Engine:
         ext = _body_extents("body_encounters", extents, n)
         want = _body_events_wanted(gap_event, ttc_event)
         cap = min(max(64, count * n), 1 << 16) if want else 0
-        while True:
-            pack = _BodyPack([(n, count)], per_sample, [cap])
-            self._ck(self._lib.csf_body_encounters(self._h, first, count, _ptr(ext), ge, te, pack.outs))
-            if pack.outs[0].n_events <= cap:
-                return pack.result(0, ext, want)
-            cap = int(pack.outs[0].n_events)
+        pack = self._measure(lambda caps: _BodyPack([(n, count)], per_sample, caps),
+                             lambda p: self._lib.csf_body_encounters(self._h, first, count, _ptr(ext), ge, te, p.outs), cap, want)
+        return pack.result(0, ext, want)
 
     @staticmethod
     def batch_body_encounters(engines, n_last, extents=None, gap_event=None, ttc_event=None, per_sample=True):
@@ -1787,19 +1708,12 @@ class Engine:
         ptrs = (C.c_void_p * len(engines))(*[a.ctypes.data for a in exts])
         want = _body_events_wanted(gap_event, ttc_event)
         caps = [min(max(64, n_last * n), 1 << 16) if want else 0 for n, _ in shapes]
-        while True:
-            pack = _BodyPack(shapes, per_sample, caps)
-            Engine._group_call("csf_batch_body_encounters", engines, arr, n_last, ptrs, ge, te, pack.outs)
-            found = [int(o.n_events) for o in pack.outs]
-            if all(f <= c for f, c in zip(found, caps)):
-                return [None if pack.outs[i].first_sample == -2 else pack.result(i, exts[i], want) for i in range(len(engines))]
-            caps = [max(f, c) for f, c in zip(found, caps)]
+        return Engine._batch_measure("csf_batch_body_encounters", engines, arr, lambda caps: _BodyPack(shapes, per_sample, caps),
+                                     lambda p: (n_last, ptrs, ge, te, p.outs), caps, want, lambda p, i, e: p.result(i, exts[i], want))
 
     def body_encounter_launches(self):
         """launches of body_encounters / batch_body_encounters so far: two per call (csf.h: csf_body_encounter_launches)"""
-        n = C.c_int64(0)
-        self._ck(self._lib.csf_body_encounter_launches(self._h, C.byref(n)))
-        return n.value
+        return self._launches("csf_body_encounter_launches")
 
     def untracked(self):
         """get_untracked_foes() (intersection.py:690-745): bool [n, n], row = source, column = receiver"""

@@ -1005,13 +1005,39 @@ def advance_together(intersections, n_ticks):
         left -= k
 
 
+def _id_table(ids):
+    """the table that turns a place in the population order into a road user's id"""
+    return np.array(list(ids) + [None], dtype=object)             # (-1, no partner, takes the None at the end)
+
+
+def _partner_ids(res, ids, fields):
+    """a result with the road users' ids, and the partners of `fields` - places in the population order - also given as ids in
+    <field>_id; returns the table"""
+    names = _id_table(ids)
+    res.ids = list(ids)
+    for f in fields:
+        setattr(res, f + "_id", None if getattr(res, f) is None else names[getattr(res, f)])
+    return names
+
+
+def _together(intersections, batch_call, add_ids, *args):
+    """a measure over the last recorded samples of many intersections, all their engines in the same launches (batch_call: the
+    Engine.batch_* of the measure, given the engines and args): a list with a result per intersection - add_ids has put the road
+    users' ids into it -, None for an empty one and for one whose engine does not record"""
+    intersections = list(intersections)
+    live = [ins for ins in intersections if ins.vehicles]
+    got = {}
+    if live:
+        engines = [ins._push_mutations() for ins in live]
+        _batch_of(engines)
+        for ins, res in zip(live, batch_call(engines, *args)):
+            got[id(ins)] = None if res is None else add_ids(res, ins.get_road_user_ids())
+    return [got.get(id(ins)) for ins in intersections]
+
+
 def _encounter_ids(res, ids):
     """an Encounters with the partners' places in the population order also given as the road users' ids"""
-    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
-    res.ids = list(ids)
-    res.d_with_id = None if res.d_with is None else names[res.d_with]
-    res.ttc_with_id = None if res.ttc_with is None else names[res.ttc_with]
-    res.run_d_with_id, res.run_ttc_with_id = names[res.run_d_with], names[res.run_ttc_with]
+    _partner_ids(res, ids, ("d_with", "ttc_with", "run_d_with", "run_ttc_with"))
     return res
 
 
@@ -1019,23 +1045,12 @@ def encounters_together(intersections, n_last, radius=0.5, d_event=None, ttc_eve
     """SocialForceIntersection.encounters over the last n_last recorded samples of many intersections - those advance_together
     has just ticked - with all their engines in the same two launches, one transfer and one wait (Engine.batch_encounters): a list
     with a result per intersection, None for an empty one and for one whose engine does not record."""
-    intersections = list(intersections)
-    live = [ins for ins in intersections if ins.vehicles]
-    got = {}
-    if live:
-        engines = [ins._push_mutations() for ins in live]
-        _batch_of(engines)
-        for ins, res in zip(live, Engine.batch_encounters(engines, n_last, radius, d_event, ttc_event, per_sample)):
-            got[id(ins)] = None if res is None else _encounter_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    return _together(intersections, Engine.batch_encounters, _encounter_ids, n_last, radius, d_event, ttc_event, per_sample)
 
 
 def _pet_ids(res, ids):
     """a PostEncroachment with the partners' places in the population order also given as the road users' ids"""
-    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
-    res.ids = list(ids)
-    res.seg_with_id = None if res.seg_with is None else names[res.seg_with]
-    res.run_with_id = names[res.run_with]
+    names = _partner_ids(res, ids, ("seg_with", "run_with"))
     if res.events is not None:
         res.event_i_id, res.event_j_id = names[res.events["i"]], names[res.events["j"]]
     return res
@@ -1046,23 +1061,12 @@ def post_encroachment_together(intersections, n_last, pet_event=None, per_segmen
     advance_together has just ticked - with all their engines in the same two launches, one transfer and one wait
     (Engine.batch_post_encroachment): a list with a result per intersection, None for an empty one and for one whose engine does
     not record."""
-    intersections = list(intersections)
-    live = [ins for ins in intersections if ins.vehicles]
-    got = {}
-    if live:
-        engines = [ins._push_mutations() for ins in live]
-        _batch_of(engines)
-        for ins, res in zip(live, Engine.batch_post_encroachment(engines, n_last, pet_event, per_segment)):
-            got[id(ins)] = None if res is None else _pet_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    return _together(intersections, Engine.batch_post_encroachment, _pet_ids, n_last, pet_event, per_segment)
 
 
 def _passing_ids(res, ids):
     """a Passing with the partners' places in the population order also given as the road users' ids"""
-    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
-    res.ids = list(ids)
-    for f in ("gap_with", "made_with", "by_with", "run_gap_with", "run_thw_with", "run_made_with", "run_by_with"):
-        setattr(res, f + "_id", None if getattr(res, f) is None else names[getattr(res, f)])
+    names = _partner_ids(res, ids, ("gap_with", "made_with", "by_with", "run_gap_with", "run_thw_with", "run_made_with", "run_by_with"))
     if res.events is not None:
         res.event_i_id, res.event_j_id = names[res.events["i"]], names[res.events["j"]]
     return res
@@ -1072,22 +1076,14 @@ def passing_together(intersections, n_last, band=0.75, lat_max=3.0, lat_event=No
     """SocialForceIntersection.passing over the last n_last recorded samples of many intersections - those advance_together has
     just ticked - with all their engines in the same two launches, one transfer and one wait (Engine.batch_passing): a list with
     a result per intersection, None for an empty one and for one whose engine does not record."""
-    intersections = list(intersections)
-    live = [ins for ins in intersections if ins.vehicles]
-    got = {}
-    if live:
-        engines = [ins._push_mutations() for ins in live]
-        _batch_of(engines)
-        for ins, res in zip(live, Engine.batch_passing(engines, n_last, band, lat_max, lat_event, per_station)):
-            got[id(ins)] = None if res is None else _passing_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    return _together(intersections, Engine.batch_passing, _passing_ids, n_last, band, lat_max, lat_event, per_station)
 
 
 def _flow_ids(res, ids):
     """a Flow with the road users' ids beside their places in the population order"""
     res.ids = list(ids)
-    if res.events is not None:
-        res.event_i_id = np.array(list(ids) + [None], dtype=object)[res.events["i"]]
+    if res.events is not None:                                    # (no table without events: a batch has a thousand members)
+        res.event_i_id = _id_table(ids)[res.events["i"]]
     return res
 
 
@@ -1095,39 +1091,19 @@ def flow_together(intersections, n_last, lines=None, areas=None, grid=None, even
     """SocialForceIntersection.flow over the last n_last recorded samples of many intersections - those advance_together has
     just ticked - at one layout, with all their engines in the same two launches, one transfer and one wait (Engine.batch_flow):
     a list with a result per intersection, None for an empty one and for one whose engine does not record."""
-    intersections = list(intersections)
-    live = [ins for ins in intersections if ins.vehicles]
-    got = {}
-    if live:
-        engines = [ins._push_mutations() for ins in live]
-        _batch_of(engines)
-        for ins, res in zip(live, Engine.batch_flow(engines, n_last, lines, areas, grid, events)):
-            got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    return _together(intersections, Engine.batch_flow, _flow_ids, n_last, lines, areas, grid, events)
 
 
 def clearance_together(intersections, n_last, road, d_event=0.0, events=False, per_sample=True):
     """SocialForceIntersection.clearance over the last n_last recorded samples of many intersections - those advance_together has
     just ticked - at one road, with all their engines in the same three launches, one transfer and one wait
     (Engine.batch_clearance): a list with a result per intersection, None for an empty one and for one whose engine does not record."""
-    intersections = list(intersections)
-    live = [ins for ins in intersections if ins.vehicles]
-    got = {}
-    if live:
-        engines = [ins._push_mutations() for ins in live]
-        _batch_of(engines)
-        for ins, res in zip(live, Engine.batch_clearance(engines, n_last, road, d_event, events, per_sample)):
-            got[id(ins)] = None if res is None else _flow_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    return _together(intersections, Engine.batch_clearance, _flow_ids, n_last, road, d_event, events, per_sample)
 
 
 def _body_ids(res, ids):
     """a BodyEncounters with the partners' places in the population order also given as the road users' ids"""
-    names = np.array(list(ids) + [None], dtype=object)            # (-1, no partner, takes the None at the end)
-    res.ids = list(ids)
-    res.gap_with_id = None if res.gap_with is None else names[res.gap_with]
-    res.ttc_with_id = None if res.ttc_with is None else names[res.ttc_with]
-    res.run_gap_with_id, res.run_ttc_with_id = names[res.run_gap_with], names[res.run_ttc_with]
+    _partner_ids(res, ids, ("gap_with", "ttc_with", "run_gap_with", "run_ttc_with"))
     return res
 
 
@@ -1139,21 +1115,14 @@ def body_encounters_together(intersections, n_last, extents=None, gap_event=None
     engine does not record."""
     intersections = list(intersections)
     live = [(k, ins) for k, ins in enumerate(intersections) if ins.vehicles]
-    got = {}
-    if live:
-        if extents is None:
-            ext = [np.array([vehicle_extents(v) for v in ins.vehicles], dtype=np.float64) for _, ins in live]
-        elif hasattr(extents, "__len__") and len(extents) == 3 and all(np.isscalar(v) for v in extents):
-            ext = extents
-        else:
-            if len(extents) != len(intersections):
-                raise ValueError(f"body_encounters_together: {len(extents)} extents for {len(intersections)} intersections")
-            ext = [extents[k] for k, _ in live]
-        engines = [ins._push_mutations() for _, ins in live]
-        _batch_of(engines)
-        for (_, ins), res in zip(live, Engine.batch_body_encounters(engines, n_last, ext, gap_event, ttc_event, per_sample)):
-            got[id(ins)] = None if res is None else _body_ids(res, ins.get_road_user_ids())
-    return [got.get(id(ins)) for ins in intersections]
+    ext = extents
+    if live and extents is None:
+        ext = [np.array([vehicle_extents(v) for v in ins.vehicles], dtype=np.float64) for _, ins in live]
+    elif live and not (hasattr(extents, "__len__") and len(extents) == 3 and all(np.isscalar(v) for v in extents)):
+        if len(extents) != len(intersections):
+            raise ValueError(f"body_encounters_together: {len(extents)} extents for {len(intersections)} intersections")
+        ext = [extents[k] for k, _ in live]
+    return _together(intersections, Engine.batch_body_encounters, _body_ids, n_last, ext, gap_event, ttc_event, per_sample)
 
 
 def step_together(intersections, n_ticks=1):
